@@ -13,8 +13,15 @@ scaling: each rank owns its own block of 10^6 domain points (independent given t
 recomputes because that is cheaper than a broadcast at n = 1000; `--factor-broadcast` exercises the RCCL broadcast
 path instead).
 
-Extra keys of the line:
+A plain run sets up, warms up, times `--steps` steps and prints the line; `ms_per_step` is the wall time of one timed
+step (slowest rank).  `--dump-outputs DIR` writes what rank 0's last timed step returned (mean.npy, variance.npy,
+status.npy; float64 / float64 / float32) under DIR; beyond 2 * 10^6 points a fixed, seeded sample of the points is
+written, with their positions in index.npy.  The inputs depend on the arguments only, so two builds can be compared
+output for output.
+
+Extra keys of the line, measured only with `--full`:
   roofline      dominant kernel of the step (FP64-MFMA quadratic form), HIP-event timed inside this process
+  parity_max_abs_err_64pts  64 points of the last step against the oracle (the run fails beyond 1e-8)
   cpu_baseline  oracle C restatement, single thread like the reference's loop krig.jl:180, bounded sample (N = 1 only)
   fftgs         second headline metric (BASELINE.json: "+ FFTGS 512^3 realisations/sec at 1/2/4/8"): configs[2],
                 realisations sharded over the ranks ((seed, r)-keyed noise), spectrum computed on rank 0 and broadcast
@@ -36,6 +43,7 @@ for p in (ROOT, os.path.join(ROOT, "geostatssolvers.jl_amd")):
 
 FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X FP64 matrix peak (public spec)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_MAX_POINTS = 2_000_000    # --dump-outputs: 28 B per point with index.npy, under 64 MB in all
 
 
 def parse():
@@ -59,7 +67,14 @@ def parse():
     ap.add_argument("--lugs", type=int, default=128, help="LUGS grid edge, a quarter of the cells carry data "
                                                          "(configs[3]: 128; 0 disables the leg)")
     ap.add_argument("--lugs-reals", type=int, default=100, help="LUGS realisations in total (sharded over the ranks)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure the roofline, the oracle parity check, the CPU "
+                    "baseline and the FFTGS / LUGS legs (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's outputs of the last timed step as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def launch_ranks(a):
@@ -158,8 +173,9 @@ def main():
         torch.cuda.synchronize()
         h.close()
 
-    _lib.profile_reset()
-    _lib.profile_enable(True)
+    if a.full:   # per-launch HIP events around the two hot kernels, for the roofline
+        _lib.profile_reset()
+        _lib.profile_enable(True)
     barrier()
     t0 = time.perf_counter()
     keep = None
@@ -170,14 +186,32 @@ def main():
         keep = (h, out)
     barrier()
     dt = time.perf_counter() - t0
-    _lib.profile_enable(False)
-    q_ms, q_n = _lib.profile_read("krig_quadform")
-    r_ms, r_n = _lib.profile_read("krig_rhs")
+    if a.full:
+        _lib.profile_enable(False)
+        q_ms, q_n = _lib.profile_read("krig_quadform")
+        r_ms, r_n = _lib.profile_read("krig_rhs")
     mu, var, st = keep[1]
     keep[0].close()
 
     dt = max_over_ranks(dt)
     value = world * m * a.steps / dt
+
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, mu, var, st)
+
+    line = {"metric": "kriged domain points/sec (OK, 1000 3-D data, Matern-3/2, global neighbourhood)",
+            "value": round(value, 1), "unit": "points/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "configs[1]: OK, %d 3-D data -> %d domain points per GPU, Matern-3/2 range 30, "
+                                   "global neighbourhood; step = device fit + predict" % (n, m),
+                       "points_per_gpu": m, "ndata": n, "factor": "broadcast" if a.factor_broadcast else "replicated"}}
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline of the dominant kernel (quadratic form: (n+nc)^2 flop per point) ----------
     N1 = n + 1
@@ -201,15 +235,7 @@ def main():
         roofline["traffic"] = tj["hbm_bytes_per_step"] / max(q_n / a.steps, 1)
         roofline["traffic_unit"] = "B per launch (rocprofv3 PMC FETCH_SIZE*2+WRITE_SIZE, profiles/%s)" % os.path.basename(tfile)
         roofline["algorithmic_bytes"] = 8.0 * N1 * m / max(q_n / a.steps, 1)   # R read once: 8 (n+nc) B per point
-
-    line = {"metric": "kriged domain points/sec (OK, 1000 3-D data, Matern-3/2, global neighbourhood)",
-            "value": round(value, 1), "unit": "points/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "configs[1]: OK, %d 3-D data -> %d domain points per GPU, Matern-3/2 range 30, "
-                                   "global neighbourhood; step = device fit + predict" % (n, m),
-                       "points_per_gpu": m, "ndata": n, "factor": "broadcast" if a.factor_broadcast else "replicated"},
-            "roofline": roofline}
+    line["roofline"] = roofline
 
     if rank == 0:
         # sanity: a handful of points against the oracle so a wrong-but-fast kernel cannot post a number
@@ -264,6 +290,26 @@ def main():
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(d, mu, var, st):
+    """--dump-outputs: the arrays predict_global returned in the last timed step, as float64 / float32 .npy files.
+    Beyond DUMP_MAX_POINTS points a fixed, seeded sample of them (index.npy: their positions, ascending)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    m = mu.shape[0]
+    sel = None
+    if m > DUMP_MAX_POINTS:
+        sel = np.sort(np.random.default_rng(12345).choice(m, DUMP_MAX_POINTS, replace=False))
+        np.save(os.path.join(d, "index.npy"), sel.astype(np.float64))
+
+    def host(t, dtype):
+        v = t.cpu().numpy()
+        return (v if sel is None else v[sel]).astype(dtype)
+
+    np.save(os.path.join(d, "mean.npy"), host(mu, np.float64))
+    np.save(os.path.join(d, "variance.npy"), host(var, np.float64))
+    np.save(os.path.join(d, "status.npy"), host(st, np.float32))
 
 
 def _latest_profile(suffix):
