@@ -326,6 +326,10 @@ int32_t HostPipe::fetch(int64_t off, int64_t n, hipStream_t s) {
                            (size_t)n * ins[i].stride, hipMemcpyHostToDevice, cin));
   GSS_HIP(hipEventRecord(ev_in, cin));
   GSS_HIP(hipStreamWaitEvent(s, ev_in, 0));
+  if (frame && frame->on && nin > 0) {
+    double* x = reinterpret_cast<double*>(ins[0].dev + (size_t)off * ins[0].stride);
+    GSS_TRY(frame_apply_dev(*frame, x, n, x, s));
+  }
   return GSS_OK;
 }
 
@@ -595,12 +599,136 @@ int32_t dev_copy_f64(double* dst, const double* src, int64_t n, hipStream_t s) {
   return GSS_OK;
 }
 
+// ---- rotated anisotropy ----------------------------------------------------------------------
+template <int DIM>
+__global__ __launch_bounds__(256) void frame_apply_kernel(Frame f, const double* x, int64_t n, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  f.dim = DIM;
+  double p[DIM];
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) p[k] = x[i * DIM + k];
+  frame_point(f, p, p);
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) out[i * DIM + k] = p[k];
+}
+
+int32_t frame_apply_dev(const Frame& f, const double* x, int64_t n, double* out, hipStream_t s) {
+  if (n <= 0) return GSS_OK;
+  const dim3 g((unsigned)((n + 255) / 256));
+  switch (f.dim) {
+    case 1: hipLaunchKernelGGL(frame_apply_kernel<1>, g, dim3(256), 0, s, f, x, n, out); break;
+    case 2: hipLaunchKernelGGL(frame_apply_kernel<2>, g, dim3(256), 0, s, f, x, n, out); break;
+    default: hipLaunchKernelGGL(frame_apply_kernel<3>, g, dim3(256), 0, s, f, x, n, out); break;
+  }
+  GSS_HIP(hipGetLastError());
+  return GSS_OK;
+}
+
+void frame_apply_host(const Frame& f, const double* x, int64_t n, double* out) {
+  for (int64_t i = 0; i < n; ++i) frame_point(f, x + i * f.dim, out + i * f.dim);
+}
+
+int32_t rotation_check(const double* R, int dim, bool* identity) {
+  GSS_REQUIRE(R != nullptr, "rotated ball without a rotation matrix");
+  bool id = true;
+  double err = 0.0;
+  for (int i = 0; i < dim; ++i)
+    for (int j = 0; j < dim; ++j) {
+      const double rij = R[3 * i + j];
+      GSS_REQUIRE(std::isfinite(rij), "rotation matrix has a non-finite entry");
+      if (rij != (i == j ? 1.0 : 0.0)) id = false;
+      double g = 0.0;   // (R^T R)_ij
+      for (int k = 0; k < dim; ++k) g += R[3 * k + i] * R[3 * k + j];
+      const double e = std::fabs(g - (i == j ? 1.0 : 0.0));
+      err = e > err ? e : err;
+    }
+  GSS_REQUIRE(err <= 1e-12, "rotation matrix is not orthonormal (max |R^T R - I| = %.3g > 1e-12)", err);
+  double det = R[0];
+  if (dim == 2) det = R[0] * R[4] - R[1] * R[3];
+  if (dim == 3)
+    det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+  GSS_REQUIRE(det > 0.0, "rotation matrix has det %.3g: a proper rotation (det +1) is needed", det);
+  *identity = id;
+  return GSS_OK;
+}
+
+int32_t vg_frame_split(const gss_variogram_t* vg, gss_variogram_t* plain, Frame* f) {
+  GSS_REQUIRE(vg != nullptr, "variogram is NULL");
+  GSS_REQUIRE(vg->dim >= 1 && vg->dim <= 3, "variogram dim %d outside 1..3", vg->dim);
+  *plain = *vg;
+  *f = Frame();
+  f->dim = vg->dim;
+  bool rotated = vg->aniso == 2;
+  if (plain->aniso == 2) plain->aniso = 1;
+  for (int e = 0; e < 3; ++e) {
+    if (e < vg->nextra && vg->extra[e].aniso == 2) rotated = true;
+    if (plain->extra[e].aniso == 2) plain->extra[e].aniso = 1;
+  }
+  if (!rotated) return GSS_OK;
+  bool id = false;
+  GSS_TRY(rotation_check(vg->rotation, vg->dim, &id));
+  if (id) return GSS_OK;
+  // an axis-aligned anisotropic structure (aniso = 1) has the identity rotation: it cannot be evaluated on the frame of
+  // another one (isotropic structures can: they do not depend on the frame)
+  auto ellipsoid = [&](const double* ir) {   // a sphere (all radii equal) does not depend on the frame either
+    for (int k = 1; k < vg->dim; ++k)
+      if (ir[k] != ir[0]) return true;
+    return false;
+  };
+  bool aligned = vg->aniso == 1 && ellipsoid(vg->inv_radii);
+  for (int e = 0; e < vg->nextra && e < 3; ++e)
+    aligned = aligned || (vg->extra[e].aniso == 1 && ellipsoid(vg->extra[e].inv_radii));
+  GSS_REQUIRE(!aligned, "nested variogram mixes a rotated structure with an axis-aligned anisotropic one: all "
+                        "anisotropic structures of one model must share one rotation");
+  f->on = 1;
+  for (int k = 0; k < 9; ++k) f->R[k] = vg->rotation[k];
+  return GSS_OK;
+}
+
+int32_t ball_frame_split(int metric, const double* inv_radii, int dim, int* metric_out, Frame* f) {
+  *f = Frame();
+  f->dim = dim;
+  *metric_out = metric;
+  if (metric != GSS_METRIC_ROTATED_BALL) return GSS_OK;
+  GSS_REQUIRE(inv_radii != nullptr, "GSS_METRIC_ROTATED_BALL needs inv_radii -> 3 inverse radii + rotation[9]");
+  *metric_out = GSS_METRIC_EUCLIDEAN;
+  bool id = false;
+  GSS_TRY(rotation_check(inv_radii + 3, dim, &id));
+  if (id) return GSS_OK;
+  f->on = 1;
+  for (int k = 0; k < 9; ++k) f->R[k] = inv_radii[3 + k];
+  return GSS_OK;
+}
+
+bool frame_same(const Frame& a, const Frame& b) {
+  if (!a.on || !b.on) return a.on == b.on;
+  for (int k = 0; k < 9; ++k)
+    if (a.R[k] != b.R[k]) return false;
+  return true;
+}
+
+int32_t frame_origin(Frame* f, const double* x, int32_t mem, hipStream_t s) {
+  if (mem == GSS_MEM_DEVICE) {
+    GSS_HIP(hipMemcpyAsync(f->c, x, sizeof(double) * (size_t)f->dim, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipStreamSynchronize(s));
+  } else {
+    for (int k = 0; k < f->dim; ++k) f->c[k] = x[k];
+  }
+  return GSS_OK;
+}
+
 int32_t make_vgdev(const gss_variogram_t* vg, VgDev* out) {
   GSS_REQUIRE(vg != nullptr, "variogram is NULL");
   GSS_REQUIRE(vg->dim >= 1 && vg->dim <= 3, "variogram dim %d outside 1..3", vg->dim);
   GSS_REQUIRE(vg->sill > 0.0 && vg->nugget >= 0.0 && vg->nugget <= vg->sill, "invalid sill/nugget %g/%g",
               vg->sill, vg->nugget);
   GSS_REQUIRE(vg->nextra >= 0 && vg->nextra <= 3, "nested variogram with %d extra structures (at most 3)", vg->nextra);
+  // rotated structures reach the kernels as axis-aligned ones on frame coordinates (vg_frame_split); an entry point
+  // that does not move its coordinates into the frame must not evaluate them
+  bool rot = vg->aniso == 2;
+  for (int e = 0; e < vg->nextra; ++e) rot = rot || vg->extra[e].aniso == 2;
+  GSS_REQUIRE(!rot, "rotated anisotropy (aniso = 2) is not available on this entry point");
   VgDev v;
   std::memset(&v, 0, sizeof(v));
   v.dim = vg->dim;

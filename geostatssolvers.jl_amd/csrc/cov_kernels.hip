@@ -51,8 +51,12 @@ extern "C" int32_t gss_cov_pairwise(const gss_variogram_t* vg, const double* a, 
                                     int64_t nb, double* out, int64_t ldo, int32_t mem, void* stream) {
   GSS_ENTRY();
   VgDev v;
-  GSS_TRY(make_vgdev(vg, &v));
+  gss_variogram_t plain;
+  Frame fr;   // rotated structures: covariances on frame coordinates, origin a[0] (gss.h, rotation)
+  GSS_TRY(vg_frame_split(vg, &plain, &fr));
+  GSS_TRY(make_vgdev(&plain, &v));
   GSS_REQUIRE(a != nullptr && out != nullptr && na >= 0, "gss_cov_pairwise: bad arguments");
+  const bool same = b == nullptr;
   if (b == nullptr) {
     b = a;
     nb = na;
@@ -63,8 +67,23 @@ extern "C" int32_t gss_cov_pairwise(const gss_variogram_t* vg, const double* a, 
   GSS_TRY(sa.in(a, sizeof(double) * na * v.dim, mem, s));
   if (b == a) sb.p = sa.p;
   else GSS_TRY(sb.in(b, sizeof(double) * nb * v.dim, mem, s));
+  DevBuf fa, fb;
+  if (fr.on && na > 0 && nb > 0) {
+    GSS_TRY(frame_origin(&fr, a, mem, s));
+    GSS_TRY(fa.alloc(sizeof(double) * (size_t)(na * v.dim)));
+    GSS_TRY(frame_apply_dev(fr, sa.as<double>(), na, fa.as<double>(), s));
+    if (same) {
+      sa.p = sb.p = fa.p;
+    } else {
+      GSS_TRY(fb.alloc(sizeof(double) * (size_t)(nb * v.dim)));
+      GSS_TRY(frame_apply_dev(fr, sb.as<double>(), nb, fb.as<double>(), s));
+      sa.p = fa.p;
+      sb.p = fb.p;
+    }
+  }
   if (mem == GSS_MEM_DEVICE) {
     GSS_TRY(cov_pairwise_dev(v, sa.as<double>(), na, sb.as<double>(), nb, out, ldo, s));
+    if (fr.on) GSS_HIP(hipStreamSynchronize(s));   // the frame copies are released on return
   } else {
     DevBuf tmp;  // compact device image, copied back row by row into the caller's pitch
     GSS_TRY(tmp.alloc(sizeof(double) * (size_t)(na * nb)));

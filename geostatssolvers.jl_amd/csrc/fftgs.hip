@@ -65,6 +65,19 @@ __global__ __launch_bounds__(256) void fftgs_cov_kernel(VgDev vg, GridSpec g, do
   }
 }
 
+// the same for a rotated variogram: lag := R^T lag (R row-major 3 x 3 in HBM)
+__global__ __launch_bounds__(256) void fftgs_cov_rot_kernel(VgDev vg, GridSpec g, const double* __restrict__ R,
+                                                            double* __restrict__ C) {
+  const int64_t N = g.n1 * g.n2 * g.n3;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < N; e += (int64_t)gridDim.x * 256) {
+    const int64_t i1 = e % g.n1, i2 = (e / g.n1) % g.n2, i3 = e / (g.n1 * g.n2);
+    double a[3] = {(double)(i1 - g.c1) * g.s1, (double)(i2 - g.c2) * g.s2, (double)(i3 - g.c3) * g.s3};
+    rotate_lag(R, a);
+    const double zero[3] = {0.0, 0.0, 0.0};
+    C[e] = cov_pair<3>(vg, a, zero);
+  }
+}
+
 constexpr int RED_BLOCKS = 1024;
 
 // Fh[idx] = sqrt(|X[idx]|) (DC = 0); partial[b] = sum over this block's elements of w * F^2 where w
@@ -190,6 +203,10 @@ struct FftPlans {
 struct gss_fftgs {
   VgDev vg;
   GridSpec g;
+  // rotated variogram (gss.h, rotation): the covariance grid is evaluated at rotated lags R^T lag; rot holds R as a
+  // row-major 3 x 3 in HBM (identity on absent axes)
+  bool rotated = false;
+  DevBuf rot;
   int ndim = 0;
   int64_t N = 0, NH = 0;
   double mean = 0.0;
@@ -504,6 +521,8 @@ static int32_t fftgs_setup_fused(gss_fftgs* h, hipStream_t s) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_xfwd2_lds(M, f.l1 - 1, ROWS)));  \
     GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ff_x_fwd2_kernel<FF_SRC_COV, ROWS, 256, LOGM>),         \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_xfwd2_lds(M, f.l1 - 1, ROWS)));  \
+    GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ff_x_fwd2_kernel<FF_SRC_COV_ROT, ROWS, 256, LOGM>),     \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_xfwd2_lds(M, f.l1 - 1, ROWS)));  \
     GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ff_x_inv2_kernel<ROWS, 256, LOGM>),                    \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_xinv2_lds(M, f.l1 - 1, ROWS)));  \
   } while (0)
@@ -684,6 +703,7 @@ static int32_t fftgs_setup_generic(gss_fftgs* h, hipStream_t s) {
   GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gen_x_fwd_kernel<FF_SRC_PHILOX, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lx));
   GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gen_x_fwd_kernel<FF_SRC_ARRAY, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lx));
   GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gen_x_fwd_kernel<FF_SRC_COV, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lx));
+  GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gen_x_fwd_kernel<FF_SRC_COV_ROT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lx));
   GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gen_x_inv_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lx));
   const int la = 96 * 1024;
 #define GSS_GEN_ATTR(MODE, TXL) \
@@ -764,7 +784,8 @@ static void gen_launch_long(gss_fftgs* h, hipStream_t s, int nb = 1) {
 
 // fft.jl:96-103 on the generic passes
 static int32_t fftgs_spectrum_generic(gss_fftgs* h, double* partial, hipStream_t s) {
-  gen_launch_p1<FF_SRC_COV>(h, 0, 0, nullptr, s);
+  if (h->rotated) gen_launch_p1<FF_SRC_COV_ROT>(h, 0, 0, h->rot.as<double>(), s);
+  else gen_launch_p1<FF_SRC_COV>(h, 0, 0, nullptr, s);
   if (h->g_long) gen_launch_long<0>(h, s);
   else if (h->ndim >= 2) gen_launch_axis<0>(h, 1, s);
   if (h->ndim == 3) gen_launch_axis<0>(h, 2, s);
@@ -864,6 +885,7 @@ static void launch_p1_src(gss_fftgs* h, uint64_t seed, uint32_t real, const doub
 // launches of the forward passes shared by the realisations and the spectrum build
 static void launch_p1(gss_fftgs* h, int src, uint64_t seed, uint32_t real, const double* noise, hipStream_t s) {
   if (src == FF_SRC_COV) launch_p1_src<FF_SRC_COV>(h, seed, real, noise, s);
+  else if (src == FF_SRC_COV_ROT) launch_p1_src<FF_SRC_COV_ROT>(h, seed, real, noise, s);
   else if (src == FF_SRC_ARRAY) launch_p1_src<FF_SRC_ARRAY>(h, seed, real, noise, s);
   else launch_p1_src<FF_SRC_PHILOX>(h, seed, real, noise, s);
 }
@@ -899,7 +921,8 @@ static int32_t fftgs_spectrum_fused(gss_fftgs* h, double* partial, hipStream_t s
   GSS_TRY(h->covsrc.alloc(sizeof(CovSrc)));
   GSS_HIP(hipMemcpyAsync(h->covsrc.p, &cs, sizeof(CovSrc), hipMemcpyHostToDevice, s));
   GSS_HIP(hipStreamSynchronize(s));  // `cs` is a stack object
-  launch_p1(h, FF_SRC_COV, 0, 0, nullptr, s);
+  if (h->rotated) launch_p1(h, FF_SRC_COV_ROT, 0, 0, h->rot.as<double>(), s);
+  else launch_p1(h, FF_SRC_COV, 0, 0, nullptr, s);
   launch_p2(h, s);
   GSS_TRY(launch_axis_mode<0>(h, 2, s));
   hipLaunchKernelGGL(ff_amp_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, f, h->Xcur, h->Fh(), partial);
@@ -1039,7 +1062,10 @@ int32_t gss_fftgs_create(gss_fftgs_t** out, const gss_variogram_t* vg, int32_t n
   GSS_REQUIRE(out != nullptr, "gss_fftgs_create: out is NULL");
   *out = nullptr;
   GSS_REQUIRE(ndim >= 1 && ndim <= 3 && dims != nullptr, "FFTGS needs a 1-D, 2-D or 3-D Cartesian grid");
-  gss_variogram_t v3 = *vg;
+  GSS_REQUIRE(vg != nullptr, "variogram is NULL");
+  gss_variogram_t v3;
+  Frame fr;   // rotated variogram: the lags are rotated instead of the grid (fftgs_cov_rot_kernel, FF_SRC_COV_ROT)
+  GSS_TRY(vg_frame_split(vg, &v3, &fr));
   GSS_REQUIRE(vg->dim == ndim, "variogram dimension %d does not match the grid dimension %d", vg->dim, ndim);
   v3.dim = 3;  // lags of absent axes are zero
   for (int k = ndim; k < 3; ++k) {
@@ -1054,6 +1080,14 @@ int32_t gss_fftgs_create(gss_fftgs_t** out, const gss_variogram_t* vg, int32_t n
   } guard{h};
   GSS_REQUIRE(vg_is_stationary(&v3), "variogram model must be stationary");  // fft.jl:91, lu.jl:110
   GSS_TRY(make_vgdev(&v3, &h->vg));
+  if (fr.on) {
+    double R3[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};   // the leading ndim x ndim block, identity beyond
+    for (int i = 0; i < ndim; ++i)
+      for (int j = 0; j < ndim; ++j) R3[3 * i + j] = fr.R[3 * i + j];
+    GSS_TRY(h->rot.alloc(sizeof(R3)));
+    GSS_HIP(hipMemcpy(h->rot.p, R3, sizeof(R3), hipMemcpyHostToDevice));
+    h->rotated = true;
+  }
   int64_t d[3] = {1, 1, 1};
   double sp[3] = {1.0, 1.0, 1.0};
   for (int k = 0; k < ndim; ++k) {
@@ -1091,7 +1125,11 @@ int32_t gss_fftgs_create(gss_fftgs_t** out, const gss_variogram_t* vg, int32_t n
     GSS_TRY(fftgs_spectrum_generic(h, partial.as<double>(), s));
   } else {
     GSS_TRY(ensure_rocfft(h));
-    hipLaunchKernelGGL(fftgs_cov_kernel, dim3(grid_blocks(h->N)), dim3(256), 0, s, h->vg, h->g, h->U.as<double>());
+    if (h->rotated)
+      hipLaunchKernelGGL(fftgs_cov_rot_kernel, dim3(grid_blocks(h->N)), dim3(256), 0, s, h->vg, h->g, h->rot.as<double>(),
+                         h->U.as<double>());
+    else
+      hipLaunchKernelGGL(fftgs_cov_kernel, dim3(grid_blocks(h->N)), dim3(256), 0, s, h->vg, h->g, h->U.as<double>());
     GSS_HIP(hipGetLastError());
     GSS_TRY(fft_exec(h, h->fwd, h->U.p, h->Xn.p, s));
     hipLaunchKernelGGL(fftgs_amp_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, h->g, h->Xn.as<double2>(), h->Fh(),

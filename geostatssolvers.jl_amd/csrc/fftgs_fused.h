@@ -27,7 +27,8 @@ namespace gss {
 // source of the real input of P1
 enum { FF_SRC_PHILOX = 0,   // uniform noise generated in registers (fft.jl:163 `rand(rng, V, dims)`)
        FF_SRC_ARRAY = 1,    // caller-supplied noise
-       FF_SRC_COV = 2 };    // covariance to the centre cell (fft.jl:96-99): the spectrum build runs on the same passes
+       FF_SRC_COV = 2,      // covariance to the centre cell (fft.jl:96-99): the spectrum build runs on the same passes
+       FF_SRC_COV_ROT = 3 };  // the same for a rotated variogram: lag := R^T lag, `noise` carries R (row-major 3 x 3)
 struct CovSrc {
   VgDev vg;
   int c1, c2, c3;     // 0-based centre cell
@@ -254,6 +255,15 @@ __global__ __launch_bounds__(NT) void ff_x_fwd2_kernel(FusedGrid g, const double
             x.x = cov_pair<3>(cs->vg, a, zero);
             a[0] = (double)(2 * n + 1 - cs->c1) * cs->s1;
             x.y = cov_pair<3>(cs->vg, a, zero);
+          } else if (SRC == FF_SRC_COV_ROT) {
+            const int i2 = (int)(grow % g.n2), i3 = (int)(grow / g.n2);
+            const double zero[3] = {0.0, 0.0, 0.0};
+            double a[3] = {(double)(2 * n - cs->c1) * cs->s1, (double)(i2 - cs->c2) * cs->s2, (double)(i3 - cs->c3) * cs->s3};
+            rotate_lag(noise, a);
+            x.x = cov_pair<3>(cs->vg, a, zero);
+            double b[3] = {(double)(2 * n + 1 - cs->c1) * cs->s1, (double)(i2 - cs->c2) * cs->s2, (double)(i3 - cs->c3) * cs->s3};
+            rotate_lag(noise, b);
+            x.y = cov_pair<3>(cs->vg, b, zero);
           } else {
             philox_pair(seed, real, STREAM_UNIFORM, (uint64_t)blk, x.x, x.y);
           }

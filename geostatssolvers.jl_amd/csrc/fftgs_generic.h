@@ -244,6 +244,15 @@ __global__ __launch_bounds__(GEN_XNT) void gen_x_fwd_kernel(GenGrid g, GenPlan p
         x.x = cov_pair<3>(vg, a, zero);
         a[0] = (double)(2 * n + 1 - g.c1) * g.s1;
         x.y = cov_pair<3>(vg, a, zero);
+      } else if (SRC == FF_SRC_COV_ROT) {   // rotated variogram: lag := R^T lag, `noise` carries R
+        const int i2 = (int)(grow % g.n2), i3 = (int)(grow / g.n2);
+        const double zero[3] = {0.0, 0.0, 0.0};
+        double a[3] = {(double)(2 * n - g.c1) * g.s1, (double)(i2 - g.c2) * g.s2, (double)(i3 - g.c3) * g.s3};
+        rotate_lag(noise, a);
+        x.x = cov_pair<3>(vg, a, zero);
+        double b[3] = {(double)(2 * n + 1 - g.c1) * g.s1, (double)(i2 - g.c2) * g.s2, (double)(i3 - g.c3) * g.s3};
+        rotate_lag(noise, b);
+        x.y = cov_pair<3>(vg, b, zero);
       } else {
         philox_pair(seed, real, STREAM_UNIFORM, (uint64_t)blk, x.x, x.y);
       }

@@ -107,6 +107,64 @@ struct Staged {
 // a piece only leave once the NEXT piece has been queued.  Usage: begin(); add_in / add_out; per piece fetch(),
 // launches, deliver(); finish().  `on` is false (and every method a no-op) for device arrays, short calls,
 // GSS_HOST_PIPELINE=0, or when the copy streams cannot be had: the caller then copies in one go as before.
+// ---------------------------------------------------------------------------------------------
+// rotated anisotropy (gss.h, gss_variogram_t::rotation): the kernels only know axis-aligned
+// balls, so a rotated ball is handled by evaluating the axis-aligned ball with the same radii on frame coordinates
+// x' = R^T (x - c).  c is the first point of the array the handle or call is created with (never a domain shard).
+// ---------------------------------------------------------------------------------------------
+struct Frame {
+  int on = 0;   // 0: raw coordinates (identity rotation), nothing is transformed
+  int dim = 0;
+  double c[3] = {0.0, 0.0, 0.0};
+  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};   // row-major, principal axes in the columns
+};
+
+// One point, the fixed arithmetic neighbour indices are compared by: u = x - c; x'_k = (R0k u0 + R1k u1) + R2k u2
+// over the d leading terms, every product and sum rounded on its own (no FMA).  y may alias x.
+__host__ __device__ __forceinline__ void frame_point(const Frame& f, const double* x, double* y) {
+#pragma clang fp contract(off)
+  double u[3];
+  for (int k = 0; k < f.dim; ++k) u[k] = x[k] - f.c[k];
+  double r[3];
+  for (int k = 0; k < f.dim; ++k) {
+    double acc = f.R[k] * u[0];
+    if (f.dim > 1) acc = acc + f.R[3 + k] * u[1];
+    if (f.dim > 2) acc = acc + f.R[6 + k] * u[2];
+    r[k] = acc;
+  }
+  for (int k = 0; k < f.dim; ++k) y[k] = r[k];
+}
+
+// FFTGS lag vectors (a grid cannot be rotated): a := R^T a for a row-major 3 x 3 R (identity on absent axes), with the
+// rounding order of frame_point
+__device__ __forceinline__ void rotate_lag(const double* __restrict__ R, double* a) {
+#pragma clang fp contract(off)
+  double r[3];
+  for (int k = 0; k < 3; ++k) {
+    double acc = R[k] * a[0];
+    acc = acc + R[3 + k] * a[1];
+    acc = acc + R[6 + k] * a[2];
+    r[k] = acc;
+  }
+  for (int k = 0; k < 3; ++k) a[k] = r[k];
+}
+
+// R: row-major 3 x 3; checks the leading dim x dim block (orthonormal to 1e-12, det > 0); *identity: exactly I
+int32_t rotation_check(const double* R, int dim, bool* identity);
+// A copy of `vg` for the kernels (aniso = 2 -> 1) and the covariance frame (f->on = 0 when no structure is rotated
+// or the rotation is the identity); f->c is left to the caller.
+int32_t vg_frame_split(const gss_variogram_t* vg, gss_variogram_t* plain, Frame* f);
+// Search metric GSS_METRIC_ROTATED_BALL -> Euclidean ball on the frame of its rotation (f->on = 0 for an identity);
+// other metrics pass through with f->on = 0.
+int32_t ball_frame_split(int metric, const double* inv_radii, int dim, int* metric_out, Frame* f);
+// same rotation (or both raw)
+bool frame_same(const Frame& a, const Frame& b);
+// f->c := the first point of x (host or device memory)
+int32_t frame_origin(Frame* f, const double* x, int32_t mem, hipStream_t s);
+// out = frame coordinates of n point-major points (device; out may equal x) / the same on the host
+int32_t frame_apply_dev(const Frame& f, const double* x, int64_t n, double* out, hipStream_t s);
+void frame_apply_host(const Frame& f, const double* x, int64_t n, double* out);
+
 struct HostPipe {
   static constexpr int64_t PIECE = 131072;
   struct Arr {
@@ -121,6 +179,7 @@ struct HostPipe {
   hipEvent_t ev_in = nullptr, ev_done = nullptr;
   int64_t pend_off = 0, pend_n = 0;
   bool on = false;
+  const Frame* frame = nullptr;   // set: each fetched piece of ins[0] (coordinates) is moved into this frame in place
   HostPipe() = default;
   HostPipe(const HostPipe&) = delete;
   HostPipe& operator=(const HostPipe&) = delete;

@@ -865,11 +865,22 @@ static int32_t est_predict(EstSpec sp, const double* xdata, const double* z, int
               (long long)n);
   GSS_REQUIRE(minneighbors <= k, "invalid min/max number of neighbors");  // idw.jl:97, lwr.jl:99
   GSS_TRY(check_metric(sp.metric, sp.mparam, dim, radius, inv_radii));
+  // GSS_METRIC_ROTATED_BALL: the axis-aligned ball on frame coordinates (origin xdata[0]); the weights then use the
+  // ball-metric distances, and LWR's affine regression does not depend on the frame
+  Frame fb;
+  GSS_TRY(ball_frame_split(sp.metric, inv_radii, dim, &sp.metric, &fb));
   GSS_REQUIRE(m >= 0 && (m == 0 || (xdata && z && xdom && mean && aux)), "NULL array");
   if (m == 0) return GSS_OK;
   hipStream_t s = to_stream(stream);
   Staged sxd, sz, sx, smean, saux, sstat;
   GSS_TRY(sxd.in(xdata, sizeof(double) * n * dim, mem, s));
+  DevBuf fxd, fx;
+  if (fb.on) {
+    GSS_TRY(frame_origin(&fb, xdata, mem, s));
+    GSS_TRY(fxd.alloc(sizeof(double) * (size_t)(n * dim)));
+    GSS_TRY(frame_apply_dev(fb, sxd.as<double>(), n, fxd.as<double>(), s));
+    sxd.p = fxd.p;
+  }
   GSS_TRY(sz.in(z, sizeof(double) * n * nz, mem, s));
   HostPipe pipe;   // host arrays of the domain: in and out piece by piece beside the computation (k <= 64, one column)
   GSS_TRY(pipe.begin(k <= 64 && nz == 1 ? mem : GSS_MEM_DEVICE, m, s));
@@ -891,6 +902,11 @@ static int32_t est_predict(EstSpec sp, const double* xdata, const double* z, int
     pipe.add_out(mean, smean.p, sizeof(double));
     pipe.add_out(aux, saux.p, sizeof(double));
     pipe.add_out(status, status ? sstat.p : nullptr, 1);
+    pipe.frame = &fb;
+  } else if (fb.on) {
+    GSS_TRY(fx.alloc(sizeof(double) * (size_t)(m * dim)));
+    GSS_TRY(frame_apply_dev(fb, sx.as<double>(), m, fx.as<double>(), s));
+    sx.p = fx.p;
   }
   GSS_TRY(est_local_dev(sp, sxd.as<double>(), sz.as<double>(), n, dim, sx.as<double>(), m, k, minneighbors, radius,
                         inv_radii, smean.as<double>(), saux.as<double>(), st, s, &pipe));
@@ -898,7 +914,7 @@ static int32_t est_predict(EstSpec sp, const double* xdata, const double* z, int
   GSS_TRY(smean.back(mean, sizeof(double) * m * nz, mem, s));
   GSS_TRY(saux.back(aux, sizeof(double) * m, mem, s));
   if (status) GSS_TRY(sstat.back(status, (size_t)m, mem, s));
-  if (!status) GSS_HIP(hipStreamSynchronize(s));  // st_own is released on return
+  if (!status || fb.on) GSS_HIP(hipStreamSynchronize(s));  // st_own and the frame copies are released on return
   return GSS_OK;
 }
 

@@ -613,8 +613,12 @@ int32_t knn_search_indexed_any(const KnnIndex& ix, const double* xdata, const do
 }
 
 int32_t check_metric(int metric, double metric_param, int dim, double radius, const double* inv_radii) {
-  GSS_REQUIRE(metric >= GSS_METRIC_EUCLIDEAN && metric <= GSS_METRIC_HAVERSINE, "unknown search metric %d", metric);
+  GSS_REQUIRE(metric >= GSS_METRIC_EUCLIDEAN && metric <= GSS_METRIC_ROTATED_BALL, "unknown search metric %d", metric);
   if (metric == GSS_METRIC_EUCLIDEAN) return GSS_OK;
+  if (metric == GSS_METRIC_ROTATED_BALL) {   // the entry points move it to a Euclidean ball on its frame
+    GSS_REQUIRE(inv_radii != nullptr, "GSS_METRIC_ROTATED_BALL needs inv_radii -> 3 inverse radii + rotation[9]");
+    return GSS_OK;
+  }
   // searcher_ui (ui.jl:25-31): a neighbourhood replaces the metric search, the two are never combined
   GSS_REQUIRE(radius < 0.0 && inv_radii == nullptr, "a search ball cannot be combined with a non-Euclidean distance");
   if (metric == GSS_METRIC_HAVERSINE) {
@@ -737,14 +741,28 @@ extern "C" int32_t gss_knn_search(const double* xdata, int64_t n, int32_t dim, c
   GSS_REQUIRE(xdata && centers && idx, "gss_knn_search: NULL array");
   GSS_REQUIRE(k >= 1 && k <= n, "gss_knn_search: k = %d outside 1..n = %lld", k, (long long)n);
   GSS_TRY(check_metric(metric, metric_param, dim, radius, inv_radii));
+  GSS_REQUIRE(dim >= 1 && dim <= 3, "gss_knn_search: dim %d outside 1..3", dim);
+  Frame fb;   // GSS_METRIC_ROTATED_BALL: the axis-aligned ball on frame coordinates, origin xdata[0]
+  GSS_TRY(ball_frame_split(metric, inv_radii, dim, &metric, &fb));
   hipStream_t s = to_stream(stream);
   Staged sx, sc, si, sn;
   GSS_TRY(sx.in(xdata, sizeof(double) * (size_t)(n * dim), mem, s));
   GSS_TRY(sc.in(centers, sizeof(double) * (size_t)(m * dim), mem, s));
   GSS_TRY(si.out(idx, sizeof(int32_t) * (size_t)(m * k), mem));
   GSS_TRY(sn.out(count, sizeof(int32_t) * (size_t)m, mem));
+  DevBuf fx, fc;
+  if (fb.on) {
+    GSS_TRY(frame_origin(&fb, xdata, mem, s));
+    GSS_TRY(fx.alloc(sizeof(double) * (size_t)(n * dim)));
+    GSS_TRY(fc.alloc(sizeof(double) * (size_t)(m * dim)));
+    GSS_TRY(frame_apply_dev(fb, sx.as<double>(), n, fx.as<double>(), s));
+    GSS_TRY(frame_apply_dev(fb, sc.as<double>(), m, fc.as<double>(), s));
+    sx.p = fx.p;
+    sc.p = fc.p;
+  }
   GSS_TRY(knn_search_dev(sx.as<double>(), n, dim, sc.as<double>(), m, k, radius, inv_radii, si.as<int>(),
                          sn.as<int>(), s, metric));
+  if (fb.on && mem == GSS_MEM_DEVICE) GSS_HIP(hipStreamSynchronize(s));   // the frame copies are released on return
   GSS_TRY(si.back(idx, sizeof(int32_t) * (size_t)(m * k), mem, s));
   GSS_TRY(sn.back(count, sizeof(int32_t) * (size_t)m, mem, s));
   return GSS_OK;

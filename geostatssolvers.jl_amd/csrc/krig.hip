@@ -512,6 +512,10 @@ struct gss_krig {
   int64_t N1 = 0, N1pad = 0, ldw = 0;
   DriftSpec ds;
   DevBuf xdata, z, drift_data;
+  // rotated variogram: xdata holds the frame coordinates R^T (x - c) of the samples, xraw the coordinates as given
+  // (for searches in another frame); c = the first sample.  Every predict call moves its domain into the same frame.
+  Frame fr;
+  DevBuf xraw;
   DevBuf factor;  // W' (ldw x N1pad, column-major) followed by wd (N1pad)
   // fit in flight: workspace, completion event and status words (joined by krig_fit_wait)
   DevBuf fit_ws;
@@ -545,7 +549,8 @@ int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const sign
                        const double* x0, const double* drift_dom, int64_t m, int k, int minneighbors, double radius,
                        const double* inv_radii_host, double* mean, double* var, uint8_t* status, int* idx_out,
                        int* count_out, hipStream_t s, int metric, HostPipe* pipe = nullptr, int block_nsub = 0,
-                       const double* block_cell = nullptr, double block_cvv = 0.0);
+                       const double* block_cell = nullptr, double block_cvv = 0.0, const double* xs_data = nullptr,
+                       const double* xs0 = nullptr);
 }
 
 
@@ -926,9 +931,19 @@ int32_t gss_krig_create(gss_krig_t** out, const gss_variogram_t* vg, int32_t var
     gss_krig* h;
     ~Guard() { delete h; }
   } guard{h};
-  GSS_TRY(make_vgdev(vg, &h->vg));
+  gss_variogram_t plain;
+  GSS_TRY(vg_frame_split(vg, &plain, &h->fr));
+  GSS_TRY(make_vgdev(&plain, &h->vg));
   GSS_REQUIRE(variant != GSS_KRIG_SIMPLE || vg_is_stationary(vg),
               "simple kriging needs a stationary variogram (a power variogram has no sill)");
+  GSS_TRY(frame_origin(&h->fr, xdata, GSS_MEM_HOST, nullptr));
+  // the host logic below (drift centring) sees the coordinates the kernels see
+  std::vector<double> xframe;
+  if (h->fr.on) {
+    xframe.resize((size_t)(n * h->fr.dim));
+    frame_apply_host(h->fr, xdata, n, xframe.data());
+  }
+  const double* xhost = h->fr.on ? xframe.data() : xdata;
   h->variant = variant;
   h->sk_mean = sk_mean;
   h->degree = degree;
@@ -955,9 +970,9 @@ int32_t gss_krig_create(gss_krig_t** out, const gss_variogram_t* vg, int32_t var
         for (int k = 0; k < 3; ++k) h->ds.e[c][k] = e[3 * c + k];
       // centre / scale the monomials' coordinates (same polynomial space, better conditioning)
       for (int k = 0; k < h->dim; ++k) {
-        double lo = xdata[k], hi = xdata[k];
+        double lo = xhost[k], hi = xhost[k];
         for (int64_t i = 1; i < n; ++i) {
-          const double v = xdata[i * h->dim + k];
+          const double v = xhost[i * h->dim + k];
           lo = v < lo ? v : lo;
           hi = v > hi ? v : hi;
         }
@@ -988,7 +1003,13 @@ int32_t gss_krig_create(gss_krig_t** out, const gss_variogram_t* vg, int32_t var
   hipStream_t s = to_stream(stream);
   GSS_TRY(h->xdata.alloc(sizeof(double) * (size_t)(n * h->dim)));
   GSS_TRY(h->z.alloc(sizeof(double) * (size_t)n));
-  GSS_HIP(hipMemcpyAsync(h->xdata.p, xdata, sizeof(double) * n * h->dim, hipMemcpyHostToDevice, s));
+  if (h->fr.on) {
+    GSS_TRY(h->xraw.alloc(sizeof(double) * (size_t)(n * h->dim)));
+    GSS_HIP(hipMemcpyAsync(h->xraw.p, xdata, sizeof(double) * n * h->dim, hipMemcpyHostToDevice, s));
+    GSS_TRY(frame_apply_dev(h->fr, h->xraw.as<double>(), n, h->xdata.as<double>(), s));
+  } else {
+    GSS_HIP(hipMemcpyAsync(h->xdata.p, xdata, sizeof(double) * n * h->dim, hipMemcpyHostToDevice, s));
+  }
   GSS_HIP(hipMemcpyAsync(h->z.p, z, sizeof(double) * n, hipMemcpyHostToDevice, s));
   if (variant == GSS_KRIG_EXTDRIFT) {
     GSS_TRY(h->drift_data.alloc(sizeof(double) * (size_t)(n * ndrift)));
@@ -1087,6 +1108,13 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
     pipe.add_out(mean, smean.p, sizeof(double));
     pipe.add_out(var, svar.p, sizeof(double));
     pipe.add_out(status, sstat.p, 1);
+    pipe.frame = &h->fr;   // rotated variogram: each piece moves into the frame where it lands
+  }
+  DevBuf xfr;
+  if (h->fr.on && !piped) {
+    GSS_TRY(xfr.alloc(sizeof(double) * (size_t)(m * dim)));
+    GSS_TRY(frame_apply_dev(h->fr, sx.as<double>(), m, xfr.as<double>(), s));
+    sx.p = xfr.p;
   }
 
   for (int64_t off = 0; off < m; off += mc) {
@@ -1159,6 +1187,7 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
     GSS_TRY(svar.back(var, sizeof(double) * m, mem, s));
     GSS_TRY(sstat.back(status, (size_t)m, mem, s));
   }
+  if (xfr.p) GSS_HIP(hipStreamSynchronize(s));   // the frame copy of the domain is released on return
   return krig_fit_wait(h);   // status of an asynchronous fit (it finished while the assembly ran)
 }
 
@@ -1171,6 +1200,9 @@ int32_t gss_krig_set_block_support(gss_krig_t* h, const double* cell, int32_t ns
     return GSS_OK;
   }
   GSS_REQUIRE(nsub <= 8, "block support: at most 8 samples per axis (got %d)", nsub);
+  GSS_REQUIRE(nsub == 0 || cell == nullptr || !h->fr.on,
+              "block support with a rotated variogram is not available (its sub-cell offsets are axis-aligned in "
+              "the raw frame, DESIGN.md section 7)");
   GSS_REQUIRE(h->vg.kind != GSS_VG_POWER, "block support needs a stationary variogram");
   GSS_REQUIRE(h->variant != GSS_KRIG_EXTDRIFT && !(h->variant == GSS_KRIG_UNIVERSAL && h->degree > 1),
               "block support: simple / ordinary kriging or a drift of degree <= 1 (the cell average of a linear drift is "
@@ -1204,6 +1236,13 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
   GSS_REQUIRE(h != nullptr, "NULL handle");
 
   GSS_TRY(check_metric(metric, metric_param, h->dim, radius, inv_radii));
+  // search frame: a rotated ball searches on its own frame, a non-Euclidean distance on the raw
+  // coordinates, a plain k-NN or isotropic ball (rotation invariant) on the covariance frame
+  Frame fs;
+  GSS_TRY(ball_frame_split(metric, inv_radii, h->dim, &metric, &fs));
+  if (metric == GSS_METRIC_EUCLIDEAN && inv_radii == nullptr) fs = h->fr;
+  for (int a = 0; a < 3; ++a) fs.c[a] = h->fr.c[a];
+  const bool two_frames = !frame_same(fs, h->fr);
   GSS_REQUIRE(m >= 0 && (m == 0 || (xdom && mean && var)), "gss_krig_predict_knn: NULL array");
   GSS_REQUIRE(k >= 1 && k <= h->n, "maxneighbors %d outside 1..%lld (searcher_ui clamps it, ui.jl:18-20)", k,
               (long long)h->n);
@@ -1213,7 +1252,7 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
   const int dim = h->dim;
   Staged sx, sd, smean, svar, sstat, sidx, scnt;
   HostPipe pipe;   // host arrays: in and out piece by piece beside the computation (gss_internal.h)
-  GSS_TRY(pipe.begin(mem, m, s));
+  if (!two_frames) GSS_TRY(pipe.begin(mem, m, s));   // two frames: the domain is needed twice, it comes in whole
   if (pipe.on) {
     GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
     if (h->variant == GSS_KRIG_EXTDRIFT)
@@ -1235,12 +1274,32 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
     pipe.add_out(status, sstat.p, 1);
     pipe.add_out(idx_out, sidx.p, sizeof(int32_t) * (size_t)k);
     pipe.add_out(count_out, scnt.p, sizeof(int32_t));
+    pipe.frame = &h->fr;
+  }
+  DevBuf xfr, xsd, xs0;   // domain in the covariance frame; samples and domain in the search frame
+  const double* xs_data = nullptr;
+  if (two_frames) {
+    const double* raw = h->fr.on ? h->xraw.as<double>() : h->xdata.as<double>();
+    xs_data = raw;
+    if (fs.on) {
+      GSS_TRY(xsd.alloc(sizeof(double) * (size_t)(h->n * dim)));
+      GSS_TRY(frame_apply_dev(fs, raw, h->n, xsd.as<double>(), s));
+      xs_data = xsd.as<double>();
+      GSS_TRY(xs0.alloc(sizeof(double) * (size_t)(m * dim)));
+      GSS_TRY(frame_apply_dev(fs, sx.as<double>(), m, xs0.as<double>(), s));
+    }
+  }
+  const double* xs_dom = two_frames ? (fs.on ? xs0.as<double>() : sx.as<double>()) : nullptr;
+  if (h->fr.on && !pipe.on) {
+    GSS_TRY(xfr.alloc(sizeof(double) * (size_t)(m * dim)));
+    GSS_TRY(frame_apply_dev(h->fr, sx.as<double>(), m, xfr.as<double>(), s));
+    sx.p = xfr.p;
   }
   GSS_TRY(krig_local_dev(h->vg, h->variant, h->nc, dim, &h->ds.e[0][0], h->ds.inv_scale[0], h->sk_mean,
                          h->xdata.as<double>(), h->z.as<double>(), h->drift_data.as<double>(), h->n,
                          sx.as<double>(), sd.as<double>(), m, k, minneighbors, radius, inv_radii, smean.as<double>(),
                          svar.as<double>(), sstat.as<uint8_t>(), sidx.as<int>(), scnt.as<int>(), s, metric, &pipe,
-                         h->block_nsub, h->block_cell, h->block_cvv));
+                         h->block_nsub, h->block_cell, h->block_cvv, xs_data, xs_dom));
   if (pipe.on) return GSS_OK;   // everything is home (krig_local_dev ends with pipe.finish)
   GSS_TRY(smean.back(mean, sizeof(double) * m, mem, s));
   GSS_TRY(svar.back(var, sizeof(double) * m, mem, s));
@@ -1271,6 +1330,12 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
   Staged sx, sz, so;
   GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
   GSS_TRY(sz.in(zbatch, sizeof(double) * nbatch * n, mem, s));
+  DevBuf xfr;   // rotated variogram: the domain in the frame of the samples
+  if (h->fr.on) {
+    GSS_TRY(xfr.alloc(sizeof(double) * (size_t)(m * dim)));
+    GSS_TRY(frame_apply_dev(h->fr, sx.as<double>(), m, xfr.as<double>(), s));
+    sx.p = xfr.p;
+  }
   GSS_TRY(so.out(mean_out, sizeof(double) * (size_t)(nbatch * m), mem));
 
   DevBuf Zm, U, WD;

@@ -126,7 +126,11 @@ static int32_t lugs_create_impl(gss_lugs_t** out, const gss_variogram_t* vg, con
     }
   } guard{h};
   GSS_REQUIRE(vg_is_stationary(vg), "variogram model must be stationary");  // fft.jl:91, lu.jl:110
-  GSS_TRY(make_vgdev(vg, &h->vg));
+  gss_variogram_t plain;
+  Frame fr;   // rotated variogram: covariances on frame coordinates, origin = the first centroid
+  GSS_TRY(vg_frame_split(vg, &plain, &fr));
+  GSS_TRY(make_vgdev(&plain, &h->vg));
+  GSS_TRY(frame_origin(&fr, centroids, GSS_MEM_HOST, nullptr));
   const int dim = h->dim = h->vg.dim;
   h->N = N;
   h->nd = nd;
@@ -161,9 +165,11 @@ static int32_t lugs_create_impl(gss_lugs_t** out, const gss_variogram_t* vg, con
   GSS_TRY(h->z1.alloc(sizeof(double) * (size_t)nd));
   GSS_TRY(h->state.alloc(sizeof(double) * (size_t)(ns * ns + ns)));
   if (ns) GSS_HIP(hipMemcpyAsync(dxs.p, xs.data(), sizeof(double) * xs.size(), hipMemcpyHostToDevice, s));
+  if (ns && fr.on) GSS_TRY(frame_apply_dev(fr, dxs.as<double>(), ns, dxs.as<double>(), s));
   if (ns) GSS_HIP(hipMemcpyAsync(h->slocs.p, sl.data(), sizeof(int64_t) * (size_t)ns, hipMemcpyHostToDevice, s));
   if (nd) {
     GSS_HIP(hipMemcpyAsync(dxd.p, xd.data(), sizeof(double) * xd.size(), hipMemcpyHostToDevice, s));
+    if (fr.on) GSS_TRY(frame_apply_dev(fr, dxd.as<double>(), nd, dxd.as<double>(), s));
     GSS_HIP(hipMemcpyAsync(h->dlocs.p, dlocs, sizeof(int64_t) * (size_t)nd, hipMemcpyHostToDevice, s));
     GSS_HIP(hipMemcpyAsync(h->z1.p, z1, sizeof(double) * (size_t)nd, hipMemcpyHostToDevice, s));
   }

@@ -1089,7 +1089,10 @@ int32_t gss_sgs_create_paths(gss_sgs_t** out, const gss_variogram_t* vg, double 
     ~Guard() { delete p; }
   } guard{h};
   GSS_REQUIRE(vg_is_stationary(vg), "variogram model must be stationary");  // fft.jl:91, lu.jl:110
-  GSS_TRY(make_vgdev(vg, &h->vg));
+  gss_variogram_t plain;
+  Frame fv;   // rotated variogram: covariances on frame coordinates, origin = the first centroid
+  GSS_TRY(vg_frame_split(vg, &plain, &fv));
+  GSS_TRY(make_vgdev(&plain, &h->vg));
   GSS_REQUIRE(h->vg.dim == dim, "variogram dimension %d != domain dimension %d", h->vg.dim, dim);
   h->dim = dim;
   h->k = maxneighbors;
@@ -1099,7 +1102,17 @@ int32_t gss_sgs_create_paths(gss_sgs_t** out, const gss_variogram_t* vg, double 
   h->npaths = npaths;
   h->path_base = path_base;
   h->filter_after = (flags & GSS_SGS_MASK_AFTER_SEARCH) ? 1 : 0;
-  const int metric = (flags >> GSS_SGS_METRIC_SHIFT) & 7;
+  int metric = (flags >> GSS_SGS_METRIC_SHIFT) & 7;
+  // search frame: a rotated ball searches on its own frame, a non-Euclidean distance on the raw
+  // coordinates, a plain k-NN or isotropic ball on the covariance frame
+  GSS_REQUIRE(metric != GSS_METRIC_ROTATED_BALL || inv_radii != nullptr,
+              "GSS_METRIC_ROTATED_BALL needs inv_radii -> 3 inverse radii + rotation[9]");
+  Frame fs;
+  GSS_TRY(ball_frame_split(metric, inv_radii, dim, &metric, &fs));
+  if (metric == GSS_METRIC_EUCLIDEAN && inv_radii == nullptr) fs = fv;
+  GSS_TRY(frame_origin(&fv, centroids, GSS_MEM_HOST, nullptr));
+  for (int a = 0; a < 3; ++a) fs.c[a] = fv.c[a];
+  const bool two_frames = !frame_same(fs, fv);
   // Haversine(r) (seq.jl:91-98 hands `distance` to the searcher): its ranking key does not depend on r and has no box
   // bounds, so it runs on the exhaustive search -- which exists unmasked only: available with the mask applied to the
   // search result (GSS_SGS_MASK_AFTER_SEARCH, the front-ends' default), not for the masked search
@@ -1148,8 +1161,18 @@ int32_t gss_sgs_create_paths(gss_sgs_t** out, const gss_variogram_t* vg, double 
     GSS_HIP(hipMemcpyAsync(h->dlocs.p, dlocs, h->dlocs.bytes, hipMemcpyHostToDevice, s));
     GSS_HIP(hipMemcpyAsync(h->zd.p, zdata, h->zd.bytes, hipMemcpyHostToDevice, s));
   }
+  if (fv.on) GSS_TRY(frame_apply_dev(fv, cent.as<double>(), N, cent.as<double>(), s));
+  DevBuf scent;   // centroids in the search frame when it is not the covariance frame
+  const double* sc = cent.as<double>();
+  if (two_frames) {
+    GSS_TRY(scent.alloc(cent.bytes));
+    GSS_HIP(hipMemcpyAsync(scent.p, centroids, scent.bytes, hipMemcpyHostToDevice, s));
+    if (fs.on) GSS_TRY(frame_apply_dev(fs, scent.as<double>(), N, scent.as<double>(), s));
+    sc = scent.as<double>();
+  }
   KnnIndex ix;
-  if (N >= KNN_DEVICE_BUILD_MIN) GSS_TRY(knn_index_build_device(cent.as<double>(), N, dim, &ix, s));  // already in HBM
+  if (N >= KNN_DEVICE_BUILD_MIN) GSS_TRY(knn_index_build_device(sc, N, dim, &ix, s));  // already in HBM
+  else if (fv.on || two_frames) GSS_TRY(knn_index_build_from_device(sc, N, dim, &ix, s));
   else GSS_TRY(knn_index_build(centroids, N, dim, &ix, s));
   GSS_TRY(bmin.alloc(sizeof(int) * (size_t)ix.nb));
   DevBuf rawidx;   // GSS_SGS_MASK_AFTER_SEARCH: the unmasked neighbour lists, shared by every path
@@ -1166,21 +1189,21 @@ int32_t gss_sgs_create_paths(gss_sgs_t** out, const gss_variogram_t* vg, double 
         if (pp == 0) {
           GSS_TRY(rawidx.alloc(sizeof(int) * (size_t)(N * h->k)));
           if (metric == GSS_METRIC_HAVERSINE)   // exhaustive (passes of 64 beyond 64 neighbours)
-            GSS_TRY(knn_search_dev(cent.as<double>(), N, dim, cent.as<double>(), N, h->k, -1.0, nullptr, rawidx.as<int>(),
+            GSS_TRY(knn_search_dev(sc, N, dim, sc, N, h->k, -1.0, nullptr, rawidx.as<int>(),
                                    cnt.as<int>(), s, metric));
           else if (h->k > SGS_MAX_K)
-            GSS_TRY(knn_search_indexed_any(ix, cent.as<double>(), cent.as<double>(), N, h->k, radius, inv_radii,
+            GSS_TRY(knn_search_indexed_any(ix, sc, sc, N, h->k, radius, inv_radii,
                                            rawidx.as<int>(), cnt.as<int>(), s, metric));
           else
-            GSS_TRY(knn_search_indexed(ix, cent.as<double>(), N, h->k, radius, inv_radii, rawidx.as<int>(), cnt.as<int>(), s,
+            GSS_TRY(knn_search_indexed(ix, sc, N, h->k, radius, inv_radii, rawidx.as<int>(), cnt.as<int>(), s,
                                        nullptr, nullptr, nullptr, metric));
         }
       } else if (h->k > SGS_MAX_K) {   // masked search in passes of 64; the lists go through the big weights kernel
         if (pp == 0) GSS_TRY(rawidx.alloc(sizeof(int) * (size_t)(N * h->k)));
-        GSS_TRY(knn_search_indexed_any(ix, cent.as<double>(), cent.as<double>(), N, h->k, radius, inv_radii,
+        GSS_TRY(knn_search_indexed_any(ix, sc, sc, N, h->k, radius, inv_radii,
                                        rawidx.as<int>(), cnt.as<int>(), s, metric, rk, rk, bmin.as<int>()));
       } else {
-        GSS_TRY(knn_search_indexed(ix, cent.as<double>(), N, h->k, radius, inv_radii, idxp, cnt.as<int>(), s, rk, rk,
+        GSS_TRY(knn_search_indexed(ix, sc, N, h->k, radius, inv_radii, idxp, cnt.as<int>(), s, rk, rk,
                                    bmin.as<int>(), metric));
       }
     }

@@ -46,7 +46,7 @@ class Variogram(C.Structure):
     _fields_ = [("kind", C.c_int32), ("dim", C.c_int32), ("sill", C.c_double), ("nugget", C.c_double),
                 ("range", C.c_double), ("nu", C.c_double), ("aniso", C.c_int32), ("reserved", C.c_int32),
                 ("inv_radii", C.c_double * 3), ("nextra", C.c_int32), ("reserved2", C.c_int32),
-                ("extra", VariogramExtra * 3)]
+                ("extra", VariogramExtra * 3), ("rotation", C.c_double * 9)]
 
 
 _p = C.c_void_p
@@ -193,8 +193,17 @@ _KINDS = {"gaussian": 0, "exponential": 1, "spherical": 2, "matern": 3, "cubic":
           "sinehole": 6, "power": 7}
 
 
-def make_variogram(kind: str, dim: int, sill=1.0, nugget=0.0, range=1.0, nu=1.0, radii=None, extras=()) -> Variogram:
-    """`extras`: further nested structures as (kind, contribution, range, nu, radii) tuples (at most 3)."""
+def _rotation3(rotation, dim):
+    """d x d rotation (row tuples) -> the row-major 3 x 3 of gss_variogram_t::rotation (identity on absent axes)."""
+    R = np.eye(3)
+    R[:dim, :dim] = np.asarray(rotation, dtype=np.float64).reshape(dim, dim)
+    return R.ravel()
+
+
+def make_variogram(kind: str, dim: int, sill=1.0, nugget=0.0, range=1.0, nu=1.0, radii=None, extras=(),
+                   rotation=None) -> Variogram:
+    """`extras`: further nested structures as (kind, contribution, range, nu, radii[, rotation]) tuples (at most 3).
+    `rotation`: the d x d rotation of the first structure's ball (aniso = 2); every rotated structure shares it."""
     v = Variogram()
     v.kind = _KINDS[kind]
     v.dim = int(dim)
@@ -213,7 +222,12 @@ def make_variogram(kind: str, dim: int, sill=1.0, nugget=0.0, range=1.0, nu=1.0,
     if len(extras) > 3:
         raise ValueError("at most 4 nested structures are supported on the device")
     v.nextra = len(extras)
-    for e, (ekind, esill, erange, enu, eradii) in enumerate(extras):
+    rot = rotation if radii is not None else None
+    if rot is not None:
+        v.aniso = 2
+    for e, ex in enumerate(extras):
+        ekind, esill, erange, enu, eradii = ex[:5]
+        erot = ex[5] if len(ex) > 5 else None
         x = v.extra[e]
         x.kind, x.aniso, x.sill, x.range, x.nu = _KINDS[ekind], 0, float(esill), float(erange), float(enu)
         for k in (0, 1, 2):
@@ -224,10 +238,31 @@ def make_variogram(kind: str, dim: int, sill=1.0, nugget=0.0, range=1.0, nu=1.0,
             x.aniso, x.range = 1, 1.0
             for k, r in enumerate(eradii):
                 x.inv_radii[k] = 1.0 / float(r)
+            if erot is not None:
+                if rot is not None and tuple(map(tuple, erot)) != tuple(map(tuple, rot)):
+                    raise ValueError("nested variogram: all rotated structures must share one rotation")
+                rot, x.aniso = erot, 2
+    ellipsoids = [radii] + [ex[4] for ex in extras]
+    if rot is not None and any(a == 1 and len(set(r)) > 1 for a, r in
+                                zip([v.aniso] + [x.aniso for x in v.extra[:len(extras)]], ellipsoids)):
+        raise ValueError("nested variogram mixes a rotated structure with an axis-aligned anisotropic one: all "
+                         "anisotropic structures of one model must share one rotation")
+    for k, val in enumerate(_rotation3(rot, dim) if rot is not None else np.eye(3).ravel()):
+        v.rotation[k] = val
     return v
 
 
+def rotated_ball_spec(radii, rotation):
+    """inv_radii argument of GSS_METRIC_ROTATED_BALL: three inverse radii (1 on absent axes), then rotation[9]."""
+    d = len(radii)
+    ir = np.ones(12)
+    ir[:d] = 1.0 / np.asarray(radii, dtype=np.float64)
+    ir[3:] = _rotation3(rotation, d)
+    return ir
+
+
 METRICS = {"euclidean": 0, "cityblock": 1, "chebyshev": 2, "haversine": 3}
+METRIC_ROTATED_BALL = 4
 
 
 def metric_spec(distance):

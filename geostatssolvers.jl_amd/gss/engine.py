@@ -40,10 +40,23 @@ def _vg_struct(vg, dim, extent=None):
             raise ValueError("nested variogram without a structured (non-nugget) component")
         w0, m0 = terms[0]
         nug = vg.effective_nugget
-        extras = [(m.kind, w * (m.sill - m.effective_nugget), m.range, m.nu, m.radii) for w, m in terms[1:]]
+        extras = [(m.kind, w * (m.sill - m.effective_nugget), m.range, m.nu, m.radii, getattr(m, "rotation", None))
+                  for w, m in terms[1:]]
         return make_variogram(m0.kind, dim, w0 * (m0.sill - m0.effective_nugget) + nug, nug, m0.range, m0.nu, m0.radii,
-                              extras)
-    return make_variogram(vg.kind, dim, vg.sill, getattr(vg, "effective_nugget", vg.nugget), vg.range, vg.nu, vg.radii)
+                              extras, rotation=getattr(m0, "rotation", None))
+    return make_variogram(vg.kind, dim, vg.sill, getattr(vg, "effective_nugget", vg.nugget), vg.range, vg.nu, vg.radii,
+                          rotation=getattr(vg, "rotation", None))
+
+
+def _ball_metric(met, ir, radii, rotation):
+    """A rotated search ball: GSS_METRIC_ROTATED_BALL with the 12-double inv_radii (gss.h, gss_knn_search)."""
+    if rotation is None:
+        return met, ir
+    if radii is None:
+        raise ValueError("a rotation needs an anisotropic ball (radii)")
+    if met != 0:
+        raise ValueError("a search ball cannot be combined with a non-Euclidean distance")
+    return _lib.METRIC_ROTATED_BALL, _lib.rotated_ball_spec(radii, rotation)
 
 
 def _extent(x):
@@ -184,7 +197,8 @@ class KrigHandle(_NativeState):
         return mean, var, status
 
     def predict_knn(self, xdom, k, minneighbors=1, radius=None, radii=None, drift_dom=None, return_idx=False,
-                    distance=None):
+                    distance=None, rotation=None):
+        """`rotation`: of the search ball `radii` (MetricBall.rotation; GSS_METRIC_ROTATED_BALL)."""
         xdom = _prep_in(xdom)
         m = xdom.shape[0]
         mem = _space(xdom)
@@ -197,6 +211,7 @@ class KrigHandle(_NativeState):
         r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
         dd = _prep_in(drift_dom)
         met, mpar = _lib.metric_spec(distance)
+        met, ir = _ball_metric(met, ir, radii, rotation)
         check(self._l.gss_krig_predict_knn(self._h, ptr(xdom), ptr(dd), m, int(k), int(minneighbors), r, ptr(ir),
                                            met, mpar, ptr(mean), ptr(var), ptr(status), ptr(idx), ptr(cnt), mem,
                                            current_stream()))
@@ -360,7 +375,7 @@ class SGSHandle:
     one visiting order per realisation -- row p belongs to realisation `path_base + p` (seq.jl:99-102)."""
 
     def __init__(self, vg, centroids, path, dlocs, zdata, mean=0.0, maxneighbors=10, minneighbors=1, radius=None,
-                 radii=None, path_base=0, mask_after_search=False, distance=None):
+                 radii=None, path_base=0, mask_after_search=False, distance=None, rotation=None):
         """`mask_after_search`: GSS_SGS_MASK_AFTER_SEARCH (the k nearest cells of the whole domain, then the simulated
         ones) instead of the k nearest among the simulated cells.  `distance`: the search metric (euclidean,
         cityblock, chebyshev)."""
@@ -380,12 +395,13 @@ class SGSHandle:
         zd = np.ascontiguousarray(zdata if zdata is not None else [], dtype=np.float64)
         ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
         r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
+        met, ir = _ball_metric(_lib.metric_spec(distance)[0], ir, radii, rotation)
         v = _vg_struct(vg, dim)
         h = C.c_void_p()
         check(self._l.gss_sgs_create_paths(C.byref(h), C.byref(v), float(mean), ptr(c), self.N, dim, ptr(pa), npaths,
                                            int(path_base), ptr(dl), ptr(zd), dl.size, self.k, int(minneighbors), r,
                                            ptr(ir), (_lib.SGS_MASK_AFTER_SEARCH if mask_after_search else 0) |
-                                           (_lib.metric_spec(distance)[0] << _lib.SGS_METRIC_SHIFT),
+                                           (met << _lib.SGS_METRIC_SHIFT),
                                            current_stream()))
         self._h = h
 
@@ -442,7 +458,7 @@ class HipEngine:
         return out
 
     @staticmethod
-    def knn_search(xdata, centers, k, radius=None, radii=None, distance=None):
+    def knn_search(xdata, centers, k, radius=None, radii=None, distance=None, rotation=None):
         """Host arrays in -> host arrays out; CUDA tensors for both point sets keep the search in HBM."""
         l = _lib.lib()
         met, mpar = _lib.metric_spec(distance)
@@ -466,12 +482,13 @@ class HipEngine:
             cnt = np.empty(m, dtype=np.int32)
         ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
         r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
+        met, ir = _ball_metric(met, ir, radii, rotation)
         check(l.gss_knn_search(ptr(x), x.shape[0], x.shape[1], ptr(c), m, int(k), r, ptr(ir), met, mpar, ptr(idx),
                                ptr(cnt), MEM_DEVICE if dev else MEM_HOST, current_stream()))
         return idx, cnt
 
     @staticmethod
-    def _estimate(fn_name, extra, xdata, z, xdom, k, minneighbors, radius, radii, distance=None):
+    def _estimate(fn_name, extra, xdata, z, xdom, k, minneighbors, radius, radii, distance=None, rotation=None):
         """Host arrays in -> host arrays out; if `xdom` is a CUDA tensor everything stays in HBM.  `z` of shape (n,) is
         one value column; (nz, n) is nz columns that share the search and the weights (gss_*_predict_cols: the mean
         comes back as (nz, m), distance / variance / status per point)."""
@@ -502,6 +519,7 @@ class HipEngine:
         ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
         r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
         met, mpar = _lib.metric_spec(distance)
+        met, ir = _ball_metric(met, ir, radii, rotation)
         if zz.ndim == 1:
             check(getattr(l, fn_name)(ptr(x), ptr(zz), x.shape[0], x.shape[1], ptr(c), m, int(k), int(minneighbors), r,
                                       ptr(ir), met, mpar, *extra, ptr(mean), ptr(aux), ptr(st),
@@ -513,21 +531,22 @@ class HipEngine:
         return mean, aux, st
 
     @staticmethod
-    def idw(xdata, z, xdom, k, minneighbors=1, exponent=1.0, radius=None, radii=None, distance=None):
+    def idw(xdata, z, xdom, k, minneighbors=1, exponent=1.0, radius=None, radii=None, distance=None, rotation=None):
         """gss_idw_predict (idw.jl:111-142) -> mean, distance to the nearest sample, status."""
         return HipEngine._estimate("gss_idw_predict", (float(exponent),), xdata, z, xdom, k, minneighbors, radius,
-                                   radii, distance)
+                                   radii, distance, rotation)
 
     @staticmethod
-    def lwr(xdata, z, xdom, k, minneighbors=1, weight=(0, 3.0, 2.0), radius=None, radii=None, distance=None):
+    def lwr(xdata, z, xdom, k, minneighbors=1, weight=(0, 3.0, 2.0), radius=None, radii=None, distance=None,
+            rotation=None):
         """gss_lwr_predict (lwr.jl:114-147); weight = (kind, a, p) -> mean, norm(r), status."""
         kind, a, p = weight
         return HipEngine._estimate("gss_lwr_predict", (int(kind), float(a), float(p)), xdata, z, xdom, k,
-                                   minneighbors, radius, radii, distance)
+                                   minneighbors, radius, radii, distance, rotation)
 
 
     @staticmethod
-    def lwr_callable(xdata, z, xdom, k, minneighbors, weightfun, radius=None, radii=None, distance=None):
+    def lwr_callable(xdata, z, xdom, k, minneighbors, weightfun, radius=None, radii=None, distance=None, rotation=None):
         """LWR with an arbitrary `weightfun` callable (lwr.jl:58,136): the search runs on the device, delta = d / max d
         and w = weightfun(delta) are evaluated here on the host (the callable cannot cross the C-ABI), the normal
         equations and norm(r) on the device again (gss_lwr_predict_weights).  Host arrays."""
@@ -537,11 +556,13 @@ class HipEngine:
         zz = np.ascontiguousarray(z, dtype=np.float64)
         c = np.ascontiguousarray(xdom, dtype=np.float64).reshape(-1, x.shape[1])
         m = c.shape[0]
-        idx, cnt = HipEngine.knn_search(x, c, k, radius, radii, distance)
+        idx, cnt = HipEngine.knn_search(x, c, k, radius, radii, distance, rotation)
         valid = np.arange(k)[None, :] < cnt[:, None]
         nb = np.where(valid, idx, 0)
         diff = x[nb] - c[:, None, :]                              # m x k x d
         name = "euclidean" if distance is None else (distance if isinstance(distance, str) else distance[0])
+        if rotation is not None:                                 # frame of the ball: R^T (x - c) per neighbour
+            diff = diff @ np.asarray(rotation, dtype=np.float64)
         if radii is not None:
             diff = diff / np.asarray(radii, dtype=np.float64)
         if name == "euclidean":

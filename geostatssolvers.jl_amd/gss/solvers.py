@@ -269,6 +269,13 @@ def _ball(neighborhood):
     return None, neighborhood.radii
 
 
+def _rot_kw(neighborhood):
+    """The ball's rotation as the engines' `rotation=` keyword -- only when there is one, so that calls with
+    axis-aligned balls keep their exact form."""
+    rot = getattr(neighborhood, "rotation", None)
+    return {} if rot is None else {"rotation": rot}
+
+
 # ------------------------------------------------------------------------------------------
 # ui.jl
 # ------------------------------------------------------------------------------------------
@@ -398,7 +405,7 @@ class KrigingSolver(_Solver):
                     else:
                         radius, radii = _ball(p["neighborhood"])
                         mu, var_, st = h.predict_knn(xdom, q["nmax"], q["minneighbors"], radius, radii, drift_dom,
-                                                     distance=_distance(p))
+                                                     distance=_distance(p), **_rot_kw(p["neighborhood"]))
                     mu, var_, st = _host(mu), _host(var_), _host(st)
                 else:
                     mu, var_, st = np.empty(0), np.empty(0), np.empty(0, dtype=np.uint8)
@@ -563,7 +570,8 @@ class IDWSolver(_NeighborEstimator):
         assert p["exponent"] > 0, "exponent must be positive"                                  # idw.jl:96
 
     def _estimate(self, p, x, z, xdom, k, nmin, radius, radii):
-        return self.engine.idw(x, z, xdom, k, nmin, float(p["exponent"]), radius, radii, distance=_distance(p))
+        return self.engine.idw(x, z, xdom, k, nmin, float(p["exponent"]), radius, radii, distance=_distance(p),
+                               **_rot_kw(p["neighborhood"]))
 
 
 class LWRSolver(_NeighborEstimator):
@@ -578,8 +586,10 @@ class LWRSolver(_NeighborEstimator):
             # the host between the device's search and the device's normal equations (engine.lwr_callable)
             if not callable(wf) or not hasattr(self.engine, "lwr_callable"):
                 raise NotImplementedError("weightfun must be ExpWeight(a, p), TricubeWeight() or a callable h -> weight")
-            return self.engine.lwr_callable(x, z, _host(xdom), k, nmin, wf, radius, radii, distance=_distance(p))
-        return self.engine.lwr(x, z, xdom, k, nmin, wf.spec(), radius, radii, distance=_distance(p))
+            return self.engine.lwr_callable(x, z, _host(xdom), k, nmin, wf, radius, radii, distance=_distance(p),
+                                            **_rot_kw(p["neighborhood"]))
+        return self.engine.lwr(x, z, xdom, k, nmin, wf.spec(), radius, radii, distance=_distance(p),
+                               **_rot_kw(p["neighborhood"]))
 
 
 # ------------------------------------------------------------------------------------------
@@ -859,12 +869,14 @@ class _SGSPlan:
     the reference draws a new permutation in every solvesingle (seq.jl:99-102), so realisation r gets the permutation
     `default_rng([seed, r])` and the handles are built per block of realisations, on demand."""
 
-    def __init__(self, engine, make_args, N, path_seed=None, order=None, mask_after=True, distance=None):
+    def __init__(self, engine, make_args, N, path_seed=None, order=None, mask_after=True, distance=None, rotation=None):
         self.engine, self.args, self.N = engine, make_args, N
         self.path_seed, self.order = path_seed, order
         self.kw = dict(mask_after_search=True) if mask_after else {}
         if distance not in (None, "euclidean"):
             self.kw["distance"] = distance
+        if rotation is not None:
+            self.kw["rotation"] = rotation
         self.shared = None
 
     def path_of(self, r):
@@ -939,7 +951,7 @@ class SGS(_Solver):
                 raise ValueError(f"mask={mask!r}: 'after' or 'during'")
             pre[var] = _SGSPlan(self.engine, (p["variogram"], cent, dlocs, zd, float(p["mean"]), nmax,
                                               p["minneighbors"], radius, radii), N, path_seed, order, mask == "after",
-                                dist)
+                                dist, **_rot_kw(p["neighborhood"]))
         pre["_run"] = _run_state(self, problem)
         return pre
 

@@ -11,20 +11,60 @@ handed to the device (`engine._vg_struct`); `GaussianVariogram(..., regularize=F
 nothing of it: it is a parameter change."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
+
 GAUSSIAN_NUGGET_EPS = 1e-6
+ROTATION_TOL = 1e-12      # max |R^T R - I| accepted, as the library checks it (include/gss.h, rotation)
+
+
+def rotation_matrix(rotation, d):
+    """`rotation` (a d x d array-like, or in 2-D an angle in radians, counter-clockwise) -> a validated proper
+    rotation as a tuple of row tuples, or None for the identity."""
+    if rotation is None:
+        return None
+    if isinstance(rotation, (int, float, np.floating, np.integer)) and not isinstance(rotation, bool):
+        if d != 2:
+            raise ValueError(f"a rotation angle describes a 2-D ball, this ball is {d}-D: give a {d} x {d} matrix")
+        c, s = math.cos(float(rotation)), math.sin(float(rotation))
+        R = np.array([[c, -s], [s, c]])
+    else:
+        R = np.asarray(rotation, dtype=np.float64)
+    if R.shape != (d, d):
+        raise ValueError(f"rotation must be a {d} x {d} matrix for a {d}-D ball (got shape {R.shape})")
+    if not np.all(np.isfinite(R)):
+        raise ValueError("rotation has a non-finite entry")
+    err = float(np.max(np.abs(R.T @ R - np.eye(d))))
+    if err > ROTATION_TOL:
+        raise ValueError(f"rotation is not orthonormal (max |R^T R - I| = {err:.3g} > {ROTATION_TOL:g})")
+    if np.linalg.det(R) <= 0.0:
+        raise ValueError("rotation has det -1: a proper rotation (det +1) is needed")
+    if np.array_equal(R, np.eye(d)):
+        return None
+    return tuple(tuple(float(v) for v in row) for row in R)
 
 
 @dataclass(frozen=True)
 class MetricBall:
+    """Ellipsoid with `radii` along principal axes given by the columns of a proper rotation R (Meshes' MetricBall):
+    d(x, y) = || diag(1/r) R^T (x - y) ||, the Mahalanobis distance with M = R diag(r^-2) R^T.  `rotation`: a d x d
+    array-like or, in 2-D, an angle in radians (counter-clockwise, as Rotations.jl Angle2d).  The identity, and any
+    rotation of an isotropic ball (one radius, or all radii equal), is stored as None."""
     radii: Tuple[float, ...]
+    rotation: Optional[Tuple[Tuple[float, ...], ...]] = None
 
-    def __init__(self, radii):
+    def __init__(self, radii, rotation=None):
         if not isinstance(radii, (tuple, list)):
             radii = (radii,)
-        object.__setattr__(self, "radii", tuple(float(r) for r in radii))
+        radii = tuple(float(r) for r in radii)
+        object.__setattr__(self, "radii", radii)
+        rot = rotation_matrix(rotation, len(radii)) if len(radii) > 1 else None
+        if len(set(radii)) == 1:      # a sphere: every rotation describes the same ball
+            rot = None
+        object.__setattr__(self, "rotation", rot)
 
     @property
     def isotropic(self):
@@ -40,6 +80,7 @@ class VariogramModel:
     nu: float = 1.0
     radii: Optional[Tuple[float, ...]] = None
     regularize: bool = True      # Gaussian model only (module docstring)
+    rotation: Optional[Tuple[Tuple[float, ...], ...]] = None    # of the ball (MetricBall), with `radii`
 
     def isstationary(self):
         return self.kind != "power"
@@ -64,6 +105,23 @@ class NestedVariogram:
     """gamma = sum_i c_i gamma_i; sill and nugget are the weighted sums of the structures'."""
     terms: Tuple[Tuple[float, VariogramModel], ...]
     kind: str = "nested"
+
+    def __post_init__(self):
+        # anisotropic structures share one rotation; an axis-aligned one has the identity (isotropic ones do not care)
+        rots = {getattr(m, "rotation", None) for _, m in self.terms
+                if getattr(m, "radii", None) is not None and len(set(m.radii)) > 1}
+        if len(rots) > 1:
+            raise ValueError("nested variogram: the anisotropic structures have different rotations (an axis-aligned "
+                             "ball counts as the identity); all anisotropic structures of one model must share one "
+                             "rotation")
+
+    @property
+    def rotation(self):
+        """The rotation its rotated structures share (None: none is rotated)."""
+        for _, m in self.terms:
+            if getattr(m, "rotation", None) is not None:
+                return m.rotation
+        return None
 
     def __add__(self, other):
         o = other.terms if isinstance(other, NestedVariogram) else ((1.0, other),)
@@ -91,20 +149,20 @@ class NestedVariogram:
 
 
 def _make(kind, ball=None, *, sill=1.0, nugget=0.0, range=1.0, order=None, nu=None, regularize=True):
-    radii = None
+    radii = rotation = None
     if ball is not None:
         if not isinstance(ball, MetricBall):
             raise TypeError("positional argument must be a MetricBall")
         if ball.isotropic:
             range = ball.radii[0]
         else:
-            radii, range = ball.radii, 1.0
+            radii, range, rotation = ball.radii, 1.0, ball.rotation
     o = order if order is not None else (nu if nu is not None else 1.0)
     # gamma(h) = (sill - nugget) f(h) + nugget for h > 0: a nugget beyond the sill would make the structured part
     # negative (no valid model; inside a nested model the device would otherwise drop the structure and keep its nugget)
     if not (float(sill) > 0.0 and 0.0 <= float(nugget) <= float(sill)):
         raise ValueError(f"variogram needs sill > 0 and 0 <= nugget <= sill (got sill={sill}, nugget={nugget})")
-    return VariogramModel(kind, float(sill), float(nugget), float(range), float(o), radii, bool(regularize))
+    return VariogramModel(kind, float(sill), float(nugget), float(range), float(o), radii, bool(regularize), rotation)
 
 
 def GaussianVariogram(ball=None, **kw):

@@ -34,6 +34,7 @@ using Tables
 using Random
 using Unitful
 using LinearAlgebra: cholesky, lu      # values of LUGS' `factorization` parameter (lu.jl:70)
+using LinearAlgebra: Symmetric, det, eigen   # principal axes of a ball's metric (ballrotmatrix)
 using Distances: evaluate              # the search metric applied to a pair of points (closure weights of LWR)
 using CoDa: Composition, components    # compositional value columns (test/estimation/idw.jl:47-65); [RECALL] accessor names
 using Distributed: myid, remotecall_fetch
@@ -139,9 +140,44 @@ struct GssVariogram            # gss_variogram_t
   nextra::Int32
   reserved2::Int32
   extra::NTuple{3,GssVgExtra}
+  rotation::NTuple{9,Float64}  # row-major 3 x 3, read where a structure has aniso = 2
 end
 
 const NOEXTRA = GssVgExtra(Int32(0), Int32(0), 0.0, 1.0, 1.0, (1.0, 1.0, 1.0))
+const NOROT = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+const GSS_METRIC_ROTATED_BALL = Int32(4)
+
+# Rotation of a ball as the row-major 3 x 3 of gss_variogram_t (identity on absent axes), or `nothing` for an
+# isotropic ball or the identity.  Convention (gss.h): principal axes in the columns of R, d(x, y) =
+# ||diag(1/r) R' (x - y)||, M = R diag(r^-2) R'.  [RECALL] Meshes' `rotation(ball)` accessor; if the loaded Meshes
+# differs, derive R and r from `metric(ball).qmat` by `eigen(Symmetric(Q))` (INTEGRATION.md).
+function ballrotation(ball)
+  rs = radii(ball)
+  d = length(rs)
+  (d == 1 || allequal(rs)) && return nothing        # a sphere: every rotation describes the same ball
+  R = Matrix{Float64}(ballrotmatrix(ball))
+  size(R) == (d, d) || throw(ArgumentError("rotation of a $d-D ball must be $d x $d"))
+  all(R[i, j] == (i == j ? 1.0 : 0.0) for i in 1:d, j in 1:d) && return nothing
+  ntuple(k -> (i = (k - 1) ÷ 3 + 1; j = (k - 1) % 3 + 1; i <= d && j <= d ? R[i, j] : Float64(i == j)), 9)
+end
+
+# R of a ball: the `rotation` accessor where the loaded Meshes has one, otherwise the principal axes of its metric
+# (Q = R diag(r^-2) R', columns ordered as the radii, det R = +1)
+function ballrotmatrix(ball)
+  isdefined(Meshes, :rotation) && hasmethod(Meshes.rotation, Tuple{typeof(ball)}) && return Meshes.rotation(ball)
+  Q = Matrix{Float64}(metric(ball).qmat)
+  F = eigen(Symmetric(Q))
+  r = ustrip.(radii(ball))
+  R = zeros(length(r), length(r))
+  used = falses(length(r))
+  for j in eachindex(r)          # the eigenvector whose eigenvalue is r_j^-2
+    i = argmin([used[k] ? Inf : abs(F.values[k] - 1 / r[j]^2) for k in eachindex(r)])
+    used[i] = true
+    R[:, j] = F.vectors[:, i]
+  end
+  det(R) < 0 && (R[:, end] .*= -1)
+  R
+end
 
 function check(code::Int32)
   code == 0 && return nothing
@@ -171,12 +207,14 @@ effnugget(γ) = Float64(ustrip(nugget(γ)))
 effnugget(γ::GaussianVariogram) = Float64(ustrip(nugget(γ))) + GAUSSIAN_NUGGET_EPS[]
 effnugget(γ::NestedVariogram) = sum(Float64(c) * effnugget(g) for (c, g) in zip(γ.cs, γ.γs))
 
-function structure(γ)            # (kind, aniso, range, nu, inv_radii) of one basic model
-  rs = radii(metricball(γ))
+function structure(γ)            # (kind, aniso, range, nu, inv_radii, rotation or nothing) of one basic model
+  ball = metricball(γ)
+  rs = radii(ball)
   aniso = length(rs) > 1
   ir = ntuple(i -> aniso && i <= length(rs) ? 1.0 / ustrip(rs[i]) : 1.0, 3)
   ν = γ isa MaternVariogram ? Float64(γ.order) : 1.0
-  (vgkind(γ), Int32(aniso), aniso ? 1.0 : Float64(ustrip(range(γ))), ν, ir)
+  rot = aniso ? ballrotation(ball) : nothing
+  (vgkind(γ), Int32(isnothing(rot) ? aniso : 2), aniso ? 1.0 : Float64(ustrip(range(γ))), ν, ir, rot)
 end
 
 # `extent` = diameter of the data bounding box: only needed for the non-stationary PowerVariogram, which the
@@ -186,7 +224,7 @@ function cvariogram(γ, dim; extent=nothing)
   if γ isa PowerVariogram && !isnothing(extent)
     A = 2 * Float64(γ.scaling) * Float64(extent)^Float64(γ.exponent) + Float64(nugget(γ)) + floatmin(Float64)
     return GssVariogram(Int32(7), Int32(dim), A, Float64(nugget(γ)), Float64(γ.scaling), Float64(γ.exponent), Int32(0),
-                        Int32(0), (1.0, 1.0, 1.0), Int32(0), Int32(0), (NOEXTRA, NOEXTRA, NOEXTRA))
+                        Int32(0), (1.0, 1.0, 1.0), Int32(0), Int32(0), (NOEXTRA, NOEXTRA, NOEXTRA), NOROT)
   end
   isstationary(γ) || throw(ArgumentError("variogram model must be stationary"))   # fft.jl:91-93, lu.jl:110
   if γ isa NestedVariogram       # gamma = sum c_i gamma_i: first structure carries the total nugget
@@ -197,20 +235,28 @@ function cvariogram(γ, dim; extent=nothing)
     end
     keep = [i for i in eachindex(γs) if cs[i] * (sill(γs[i]) - effnugget(γs[i])) > 0]
     length(keep) <= 4 || throw(ArgumentError("at most 4 nested structures are supported on the device"))
-    k0, a0, r0, ν0, ir0 = structure(γs[keep[1]])
+    k0, a0, r0, ν0, ir0, rot0 = structure(γs[keep[1]])
+    # one rotation for every rotated structure (gss.h); different rotations per structure are not supported
+    # anisotropic structures share one rotation; an axis-aligned one (aniso = 1) counts as the identity
+    aniso_rots = [structure(γs[i])[6] for i in keep if structure(γs[i])[2] != 0 && !allequal(structure(γs[i])[5][1:dim])]
+    rots = unique([r for r in aniso_rots if !isnothing(r)])
+    (isempty(rots) || (length(rots) == 1 && !any(isnothing, aniso_rots))) ||
+      throw(ArgumentError("nested variogram: the anisotropic structures have different rotations (an axis-aligned " *
+                          "ball counts as the identity); all anisotropic structures of one model must share one rotation"))
     nug = effnugget(γ)
     extras = ntuple(3) do j
       j + 1 > length(keep) && return NOEXTRA
       i = keep[j+1]
-      k, a, r, ν, ir = structure(γs[i])
+      k, a, r, ν, ir, _ = structure(γs[i])
       GssVgExtra(k, a, Float64(cs[i] * (sill(γs[i]) - effnugget(γs[i]))), r, ν, ir)
     end
     c0 = Float64(cs[keep[1]] * (sill(γs[keep[1]]) - effnugget(γs[keep[1]])))
-    return GssVariogram(k0, Int32(dim), c0 + nug, nug, r0, ν0, a0, Int32(0), ir0, Int32(length(keep) - 1), Int32(0), extras)
+    return GssVariogram(k0, Int32(dim), c0 + nug, nug, r0, ν0, a0, Int32(0), ir0, Int32(length(keep) - 1), Int32(0), extras,
+                        isempty(rots) ? NOROT : rots[1])
   end
-  k, a, r, ν, ir = structure(γ)
+  k, a, r, ν, ir, rot = structure(γ)
   GssVariogram(k, Int32(dim), Float64(sill(γ)), effnugget(γ), r, ν, a, Int32(0), ir, Int32(0), Int32(0),
-               (NOEXTRA, NOEXTRA, NOEXTRA))
+               (NOEXTRA, NOEXTRA, NOEXTRA), isnothing(rot) ? NOROT : rot)
 end
 
 # solver parameter `distance` (krig.jl:72, idw.jl:54, lwr.jl:57) -> (GSS_METRIC_*, parameter); a neighbourhood
@@ -220,7 +266,8 @@ metricspec(::Cityblock) = (Int32(1), 0.0)
 metricspec(::Chebyshev) = (Int32(2), 0.0)
 metricspec(d::Haversine) = (Int32(3), Float64(d.radius))
 metricspec(d) = throw(ArgumentError("search distance $d is not available on the device"))
-searchmetric(p) = isnothing(p.neighborhood) ? metricspec(p.distance) : (Int32(0), 0.0)
+searchmetric(p) = isnothing(p.neighborhood) ? metricspec(p.distance) :
+                  (isnothing(ballrotation(p.neighborhood)) ? Int32(0) : GSS_METRIC_ROTATED_BALL, 0.0)
 
 # Point-major coordinates: a d x n Julia matrix is already in the layout the C-ABI wants.  Three methods, because for
 # 10^6 - 10^7 elements the generic one -- a `centroid` call and a small vector per element -- would be the `solve` time:
@@ -337,11 +384,7 @@ function solve(problem::EstimationProblem, solver::KrigingSolverHIP; procs=[myid
                       (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32,
                        Ptr{Cvoid}), h[], X0, F0, m, μ, σ², status, GSS_MEM_HOST, C_NULL))
         else                                                             # krig.jl:188-234
-          radius, ir = -1.0, C_NULL
-          if !isnothing(p.neighborhood)
-            rs = ustrip.(radii(p.neighborhood))
-            length(rs) == 1 ? (radius = Float64(rs[1])) : (radius = 1.0; ir = Float64[1 / r for r in rs])
-          end
+          radius, ir = ballspec(p.neighborhood)
           met, mpar = searchmetric(p)
           check(ccall((:gss_krig_predict_knn, libgss), Int32,
                       (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Float64, Ptr{Float64}, Int32,
@@ -414,11 +457,7 @@ function neighbor_estimate(problem, solver, auxname, auxunit, call, callcols)
       @warn "Invalid maximum number of neighbors. Adjusting to $n..."
       k = n
     end
-    radius, ir = -1.0, C_NULL
-    if !isnothing(p.neighborhood)
-      rs = ustrip.(radii(p.neighborhood))
-      length(rs) == 1 ? (radius = Float64(rs[1])) : (radius = 1.0; ir = Float64[1 / r for r in rs])
-    end
+    radius, ir = ballspec(p.neighborhood)
     aux = Vector{Float64}(undef, m); status = Vector{UInt8}(undef, m)
     if iscomp
       # compositional data (test/estimation/idw.jl:47-65): the loop is generic over the value type -- idw.jl:138
@@ -515,11 +554,17 @@ function ensemble(problem, reals::Dict)
   Ensemble(domain(problem), reals)
 end
 
+# (radius, inv_radii) of the search ball; a rotated ball (searchmetric: GSS_METRIC_ROTATED_BALL) hands 12 doubles:
+# three inverse radii, then the row-major rotation
 function ballspec(neighborhood)
   radius, ir = -1.0, C_NULL
   if !isnothing(neighborhood)
     rs = ustrip.(radii(neighborhood))
     length(rs) == 1 ? (radius = Float64(rs[1])) : (radius = 1.0; ir = Float64[1 / r for r in rs])
+    rot = ballrotation(neighborhood)
+    if !isnothing(rot)
+      ir = vcat(Float64[i <= length(rs) ? 1 / rs[i] : 1.0 for i in 1:3], collect(rot))
+    end
   end
   radius, ir
 end

@@ -88,7 +88,8 @@ typedef struct gss_variogram {
   double nugget;
   double range;        /* isotropic range; ignored (==1) when aniso != 0             */
   double nu;           /* Matern order                                               */
-  int32_t aniso;       /* 1: Mahalanobis distance with inv_radii (MetricBall((a,b))) */
+  int32_t aniso;       /* 1: Mahalanobis distance with inv_radii (MetricBall((a,b)));
+                        * 2: rotated ball (MetricBall((a,b), R)): inv_radii along the columns of `rotation`  */
   int32_t reserved;
   double inv_radii[3]; /* 1 / ball radii                                             */
   /* nested models gamma = sum_i c_i gamma_i ([DEP] Variography NestedVariogram): the fields above describe the
@@ -104,6 +105,14 @@ typedef struct gss_variogram {
     double nu;
     double inv_radii[3];
   } extra[3];
+  /* Rotated anisotropy (read only where a structure has aniso = 2): row-major 3 x 3 proper rotation R whose leading
+   * d x d block holds the principal axes of the ball as columns; d(x, y) = || diag(1/r) R^T (x - y) ||, i.e. the
+   * Mahalanobis distance with M = R diag(r^-2) R^T.  One rotation serves every rotated structure of the model.
+   * The library checks max |R^T R - I| <= 1e-12 and det R > 0 (GSS_ERR_INVALID otherwise); an exact identity takes
+   * the axis-aligned path.  Covariances are evaluated on the frame coordinates x' = R^T (x - c), c = the first point
+   * of the array the call or handle is created with.  Appended: the offsets above are
+   * unchanged and callers that never set aniso = 2 need not fill it. */
+  double rotation[9];
 } gss_variogram_t;
 
 /* ---- kriging variant: replaces ui.jl:40-50 (kriging_ui) model choice ---------------------- */
@@ -191,7 +200,9 @@ enum {                        /* solver parameter `distance` (krig.jl:72, idw.jl
   GSS_METRIC_EUCLIDEAN = 0,   /* default; with inv_radii: Mahalanobis ball                                       */
   GSS_METRIC_CITYBLOCK = 1,
   GSS_METRIC_CHEBYSHEV = 2,
-  GSS_METRIC_HAVERSINE = 3    /* points are (longitude, latitude) in degrees, metric_param = sphere radius       */
+  GSS_METRIC_HAVERSINE = 3,   /* points are (longitude, latitude) in degrees, metric_param = sphere radius       */
+  GSS_METRIC_ROTATED_BALL = 4 /* rotated ball: inv_radii points at 12 doubles -- three inverse radii, then the
+                               * row-major rotation[9] of gss_variogram_t; the ball is d <= 1 (radius = 1)        */
 };
 /* metric != EUCLIDEAN cannot be combined with a ball (searcher_ui uses either the ball or the metric, ui.jl:25-31). */
 int32_t gss_knn_search(const double* xdata, int64_t n, int32_t dim, const double* centers, int64_t m,
@@ -392,7 +403,8 @@ int32_t gss_lugs_realize(gss_lugs_t* h, uint64_t seed, int64_t first_real, int64
 enum { GSS_SGS_MASK_AFTER_SEARCH = 1 };
 /* bits 4..6 of flags: GSS_METRIC_* of the neighbour search (the solver parameter `distance`, seq.jl:91-98):
  * Euclidean (0, the only one that combines with a ball), Cityblock or Chebyshev; Haversine (its key has no box bounds:
- * exhaustive search) with GSS_SGS_MASK_AFTER_SEARCH only -- the masked search has no exhaustive variant. */
+ * exhaustive search) with GSS_SGS_MASK_AFTER_SEARCH only -- the masked search has no exhaustive variant;
+ * GSS_METRIC_ROTATED_BALL (4) with inv_radii -> 12 doubles (see gss_knn_search). */
 #define GSS_SGS_METRIC_SHIFT 4
 int32_t gss_sgs_create(gss_sgs_t** out, const gss_variogram_t* vg, double mean, const double* centroids, int64_t N,
                        int32_t dim, const int64_t* path, const int64_t* dlocs, const double* zdata, int64_t nd,
