@@ -629,6 +629,19 @@ void frame_apply_host(const Frame& f, const double* x, int64_t n, double* out) {
   for (int64_t i = 0; i < n; ++i) frame_point(f, x + i * f.dim, out + i * f.dim);
 }
 
+FrameCopy::~FrameCopy() {
+  if (buf.p) (void)hipStreamSynchronize(stream);
+}
+
+int32_t FrameCopy::of(const Frame& f, Staged* a, int64_t n, hipStream_t s) {
+  if (!f.on || n <= 0) return GSS_OK;
+  stream = s;
+  GSS_TRY(buf.alloc(sizeof(double) * (size_t)(n * f.dim)));
+  GSS_TRY(frame_apply_dev(f, a->as<double>(), n, buf.as<double>(), s));
+  a->p = buf.p;
+  return GSS_OK;
+}
+
 int32_t rotation_check(const double* R, int dim, bool* identity) {
   GSS_REQUIRE(R != nullptr, "rotated ball without a rotation matrix");
   bool id = true;
@@ -684,28 +697,6 @@ int32_t vg_frame_split(const gss_variogram_t* vg, gss_variogram_t* plain, Frame*
   f->on = 1;
   for (int k = 0; k < 9; ++k) f->R[k] = vg->rotation[k];
   return GSS_OK;
-}
-
-int32_t ball_frame_split(int metric, const double* inv_radii, int dim, int* metric_out, Frame* f) {
-  *f = Frame();
-  f->dim = dim;
-  *metric_out = metric;
-  if (metric != GSS_METRIC_ROTATED_BALL) return GSS_OK;
-  GSS_REQUIRE(inv_radii != nullptr, "GSS_METRIC_ROTATED_BALL needs inv_radii -> 3 inverse radii + rotation[9]");
-  *metric_out = GSS_METRIC_EUCLIDEAN;
-  bool id = false;
-  GSS_TRY(rotation_check(inv_radii + 3, dim, &id));
-  if (id) return GSS_OK;
-  f->on = 1;
-  for (int k = 0; k < 9; ++k) f->R[k] = inv_radii[3 + k];
-  return GSS_OK;
-}
-
-bool frame_same(const Frame& a, const Frame& b) {
-  if (!a.on || !b.on) return a.on == b.on;
-  for (int k = 0; k < 9; ++k)
-    if (a.R[k] != b.R[k]) return false;
-  return true;
 }
 
 int32_t frame_origin(Frame* f, const double* x, int32_t mem, hipStream_t s) {

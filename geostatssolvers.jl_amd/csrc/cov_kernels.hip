@@ -67,23 +67,15 @@ extern "C" int32_t gss_cov_pairwise(const gss_variogram_t* vg, const double* a, 
   GSS_TRY(sa.in(a, sizeof(double) * na * v.dim, mem, s));
   if (b == a) sb.p = sa.p;
   else GSS_TRY(sb.in(b, sizeof(double) * nb * v.dim, mem, s));
-  DevBuf fa, fb;
+  FrameCopy fa, fb;
   if (fr.on && na > 0 && nb > 0) {
     GSS_TRY(frame_origin(&fr, a, mem, s));
-    GSS_TRY(fa.alloc(sizeof(double) * (size_t)(na * v.dim)));
-    GSS_TRY(frame_apply_dev(fr, sa.as<double>(), na, fa.as<double>(), s));
-    if (same) {
-      sa.p = sb.p = fa.p;
-    } else {
-      GSS_TRY(fb.alloc(sizeof(double) * (size_t)(nb * v.dim)));
-      GSS_TRY(frame_apply_dev(fr, sb.as<double>(), nb, fb.as<double>(), s));
-      sa.p = fa.p;
-      sb.p = fb.p;
-    }
+    GSS_TRY(fa.of(fr, &sa, na, s));
+    if (same) sb.p = sa.p;
+    else GSS_TRY(fb.of(fr, &sb, nb, s));
   }
   if (mem == GSS_MEM_DEVICE) {
     GSS_TRY(cov_pairwise_dev(v, sa.as<double>(), na, sb.as<double>(), nb, out, ldo, s));
-    if (fr.on) GSS_HIP(hipStreamSynchronize(s));   // the frame copies are released on return
   } else {
     DevBuf tmp;  // compact device image, copied back row by row into the caller's pitch
     GSS_TRY(tmp.alloc(sizeof(double) * (size_t)(na * nb)));

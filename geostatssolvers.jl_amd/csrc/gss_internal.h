@@ -154,16 +154,19 @@ int32_t rotation_check(const double* R, int dim, bool* identity);
 // A copy of `vg` for the kernels (aniso = 2 -> 1) and the covariance frame (f->on = 0 when no structure is rotated
 // or the rotation is the identity); f->c is left to the caller.
 int32_t vg_frame_split(const gss_variogram_t* vg, gss_variogram_t* plain, Frame* f);
-// Search metric GSS_METRIC_ROTATED_BALL -> Euclidean ball on the frame of its rotation (f->on = 0 for an identity);
-// other metrics pass through with f->on = 0.
-int32_t ball_frame_split(int metric, const double* inv_radii, int dim, int* metric_out, Frame* f);
-// same rotation (or both raw)
-bool frame_same(const Frame& a, const Frame& b);
 // f->c := the first point of x (host or device memory)
 int32_t frame_origin(Frame* f, const double* x, int32_t mem, hipStream_t s);
 // out = frame coordinates of n point-major points (device; out may equal x) / the same on the host
 int32_t frame_apply_dev(const Frame& f, const double* x, int64_t n, double* out, hipStream_t s);
 void frame_apply_host(const Frame& f, const double* x, int64_t n, double* out);
+// A staged array of n points, in frame coordinates: a->p is redirected to a copy that lives as long as this holder,
+// which waits for the stream before it lets the copy go.  Nothing happens when f.on == 0.
+struct FrameCopy {
+  DevBuf buf;
+  hipStream_t stream = nullptr;
+  ~FrameCopy();
+  int32_t of(const Frame& f, Staged* a, int64_t n, hipStream_t s);
+};
 
 struct HostPipe {
   static constexpr int64_t PIECE = 131072;
@@ -957,29 +960,60 @@ struct KnnIndex {
   int64_t n = 0;
   int nb = 0, nb1 = 0, dim = 0;
 };
-int32_t knn_index_build(const double* xhost, int64_t n, int dim, KnnIndex* ix, hipStream_t s);
-int32_t knn_index_build_from_device(const double* xdev, int64_t n, int dim, KnnIndex* ix, hipStream_t s);
-// the same ordering rule carried out on the device (knn_build.hip); used from KNN_DEVICE_BUILD_MIN samples
-int32_t knn_index_build_device(const double* xdev, int64_t n, int dim, KnnIndex* ix, hipStream_t s);
-constexpr int64_t KNN_DEVICE_BUILD_MIN = 16384;
-// rank / qrank / bminrank (all or none): masked search of sequential simulation, see knn.hip
-int32_t knn_search_indexed(const KnnIndex& ix, const double* centers, int64_t m, int k, double radius,
-                           const double* inv_radii_host, int* idx, int* count, hipStream_t s,
-                           const int* rank = nullptr, const int* qrank = nullptr, const int* bminrank = nullptr,
-                           int metric = 0 /* Euclidean, Cityblock or Chebyshev */, const double* lowd = nullptr,
-                           const int* lowi = nullptr /* per-query lower bound of the accepted keys */);
-// any k <= n: passes of 64 neighbours, each bounded below by the last key of the pass before (idx is m x k);
-// xdata = the samples in their original order (device)
-// rank / qrank / bminrank: the mask of SGS (candidates whose rank is below the query's), as in knn_search_indexed
-int32_t knn_search_indexed_any(const KnnIndex& ix, const double* xdata, const double* centers, int64_t m, int k,
-                               double radius, const double* inv_radii_host, int* idx, int* count, hipStream_t s,
-                               int metric = 0, const int* rank = nullptr, const int* qrank = nullptr,
-                               const int* bminrank = nullptr);
-// Haversine: exhaustive kernel (no box bounds for that key); non-Euclidean metrics do not combine with balls
-int32_t knn_search_dev(const double* xdata, int64_t n, int dim, const double* centers, int64_t m, int k,
-                       double radius, const double* inv_radii_host, int* idx, int* count, hipStream_t s,
-                       int metric = 0);
-int32_t check_metric(int metric, double metric_param, int dim, double radius, const double* inv_radii);
+// The mask of sequential simulation (seq.jl:105): a sample qualifies only if its visiting rank lies below the query's.
+// rank: per sample; qrank: per query; bminrank: lowest rank inside each batch of 64 of the index (Searcher::index).
+struct KnnMask {
+  const int* rank;
+  const int* qrank;
+  const int* bminrank;
+};
+
+// The k nearest samples of each centre under a metric / inside a ball: the one way to search.  It validates what the
+// C ABI hands over, unpacks the ball, chooses the frame the search runs in and keeps the samples
+// there, builds the index at most once (host or device), and at each query picks the exhaustive or the indexed kernel
+// and one pass or passes of 64.  Usage: init(); samples(); query() as often as needed.  Everything is queued on the
+// stream of the call; the destructor waits for that stream before copies, index and scratch are released.
+struct Searcher {
+  int metric = 0;      // the key the kernels rank by (a rotated ball has become Euclidean on `frame`)
+  int dim = 0;
+  int use_ball = 0, aniso = 0;   // the ball, unpacked once: key <= r2 on coordinates scaled by ir[] when aniso
+  double r2 = 0.0, ir[3] = {1.0, 1.0, 1.0};
+  // The search frame: a plain k-NN or an isotropic ball (rotation invariant) searches on the caller's covariance frame,
+  // a rotated ball on its own frame, a non-Euclidean distance on raw coordinates.  Without a covariance frame the
+  // caller's kernels work on `frame` coordinates themselves and, for a rotated ball, the caller sets frame.c.
+  Frame frame;
+  bool two_frames = false;       // a covariance frame was given and the search runs in another one
+  bool one_shot = false;         // set by a caller that asks one query only: few centres may then skip the index
+  const double* xs = nullptr;    // the samples on `frame`, original order (device)
+  int64_t n = 0;
+
+  Searcher() = default;
+  Searcher(const Searcher&) = delete;
+  Searcher& operator=(const Searcher&) = delete;
+  ~Searcher();
+  int32_t init(int metric_, double metric_param, double radius, const double* inv_radii, int dim_,
+               const Frame* cov = nullptr);
+  // x: the samples as the caller's kernels use them (device); x_raw: the same before the covariance frame (device;
+  // NULL: not kept) and x_host: a host copy of the raw samples (NULL: none), which spares the upload or the copy back
+  // where one is needed
+  int32_t samples(const double* x, const double* x_raw, int64_t n_, hipStream_t s, const double* x_host = nullptr);
+  // c: m centres as the caller's kernels use them; c_raw: the same before the covariance frame (read when two_frames);
+  // c == NULL: the samples themselves are the centres (m = n).
+  // idx: m x k sample indices nearest first, -1 beyond count[p] (count may be NULL).  mask: indexed metrics only.
+  int32_t query(const double* c, const double* c_raw, int64_t m, int k, int* idx, int* count, hipStream_t s,
+                const KnnMask* mask = nullptr);
+  // the index (built now if need be), for the per-batch ranks of a mask; NULL for a metric without box bounds
+  int32_t index(hipStream_t s, const KnnIndex** out);
+
+ private:
+  bool cov_on_ = false, built_ = false;
+  const double* x_host_ = nullptr;
+  hipStream_t stream_ = nullptr;
+  DevBuf xs_own_, cq_;
+  KnnIndex ix_;
+  int32_t pass(const double* q, int64_t m, int kk, int* idx, int* count, hipStream_t s, const KnnMask* mask,
+               bool indexed, const double* lowd, const int* lowi);
+};
 
 // ---------------------------------------------------------------------------------------------
 // noise (noise.hip)

@@ -704,25 +704,21 @@ __global__ __launch_bounds__(256) void est_list_kernel(EstSpec sp, const double*
   }
 }
 
-static int32_t est_local_dev(const EstSpec& sp, const double* xdata, const double* z, int64_t n, int dim,
-                             const double* x0, int64_t m, int k, int minneighbors, double radius,
-                             const double* inv_radii_host, double* mean, double* aux, uint8_t* status,
-                             hipStream_t s, HostPipe* pipe = nullptr /* k <= 64 only */) {
-  const int use_ball = (radius >= 0.0 || inv_radii_host != nullptr) ? 1 : 0;
-  const int aniso = inv_radii_host != nullptr ? 1 : 0;
-  const double r2 = aniso ? 1.0 : radius * radius;
-  double ir[3] = {1.0, 1.0, 1.0};
-  if (aniso)
-    for (int a = 0; a < dim; ++a) ir[a] = inv_radii_host[a];
+// xdata / x0: samples and domain on the Searcher's frame, which the weights are evaluated on as well
+static int32_t est_local_dev(const EstSpec& sp, Searcher& sr, const double* z, const double* x0, int64_t m, int k,
+                             int minneighbors, double* mean, double* aux, uint8_t* status, hipStream_t s,
+                             HostPipe* pipe = nullptr /* k <= 64 only */) {
+  const double* xdata = sr.xs;
+  const int64_t n = sr.n;
+  const int dim = sr.dim, use_ball = sr.use_ball, aniso = sr.aniso;
+  const double r2 = sr.r2;
+  const double* ir = sr.ir;
   const char* pname = sp.method == 0 ? "idw" : "lwr";
 
   if (k > 64 && (int64_t)k < n) {
     // 65 .. n - 1 neighbours (ui.jl:16-23 accepts any count): the search runs in passes of 64, the estimator walks
     // the lists with one thread per point
     const int64_t chunk = k > 512 ? (1 << 16) : (1 << 19);
-    const bool hav = sp.metric == GSS_METRIC_HAVERSINE;   // no box bounds for the indexed search: exhaustive passes
-    KnnIndex ix;
-    if (!hav) GSS_TRY(knn_index_build_from_device(xdata, n, dim, &ix, s));
     DevBuf idx_s, cnt_s;
     GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
     GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(m < chunk ? m : chunk)));
@@ -730,12 +726,7 @@ static int32_t est_local_dev(const EstSpec& sp, const double* xdata, const doubl
       const int64_t mv = (m - off) < chunk ? (m - off) : chunk;
       {
         ProfScope ps("knn", s);
-        if (hav)
-          GSS_TRY(knn_search_dev(xdata, n, dim, x0 + off * dim, mv, k, radius, inv_radii_host, idx_s.as<int>(),
-                                 cnt_s.as<int>(), s, sp.metric));
-        else
-          GSS_TRY(knn_search_indexed_any(ix, xdata, x0 + off * dim, mv, k, radius, inv_radii_host, idx_s.as<int>(),
-                                         cnt_s.as<int>(), s, sp.metric));
+        GSS_TRY(sr.query(x0 + off * dim, nullptr, mv, k, idx_s.as<int>(), cnt_s.as<int>(), s));
       }
       ProfScope pl(pname, s);
       const dim3 grid((unsigned)((mv + 255) / 256));
@@ -806,9 +797,6 @@ static int32_t est_local_dev(const EstSpec& sp, const double* xdata, const doubl
 
   const bool piped = pipe && pipe->on;   // host arrays of the domain arrive and leave piece by piece (gss_internal.h)
   const int64_t chunk = piped ? HostPipe::PIECE : (1 << 20);
-  KnnIndex ix;  // k-d ordered batches + boxes, built once per call (Euclidean / Mahalanobis search only)
-  const bool use_index = sp.metric != GSS_METRIC_HAVERSINE;
-  if (use_index) GSS_TRY(knn_index_build_from_device(xdata, n, dim, &ix, s));
   DevBuf idx_s, cnt_s;
   GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
   GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(m < chunk ? m : chunk)));
@@ -817,12 +805,7 @@ static int32_t est_local_dev(const EstSpec& sp, const double* xdata, const doubl
     if (piped) GSS_TRY(pipe->fetch(off, mv, s));
     {
       ProfScope ps("knn", s);
-      if (use_index)
-        GSS_TRY(knn_search_indexed(ix, x0 + off * dim, mv, k, radius, inv_radii_host, idx_s.as<int>(),
-                                   cnt_s.as<int>(), s, nullptr, nullptr, nullptr, sp.metric));
-      else
-        GSS_TRY(knn_search_dev(xdata, n, dim, x0 + off * dim, mv, k, radius, inv_radii_host, idx_s.as<int>(),
-                               cnt_s.as<int>(), s, sp.metric));
+      GSS_TRY(sr.query(x0 + off * dim, nullptr, mv, k, idx_s.as<int>(), cnt_s.as<int>(), s));
     }
     ProfScope pl(pname, s);
 #define GSS_EST_KNN_ARGS sp, xdata, z, x0 + off * dim, mv, k, minneighbors, idx_s.as<int>(), cnt_s.as<int>(), aniso, \
@@ -864,23 +847,19 @@ static int32_t est_predict(EstSpec sp, const double* xdata, const double* z, int
   GSS_REQUIRE(k >= 1 && k <= n, "maxneighbors %d outside 1..%lld (searcher_ui clamps it, ui.jl:18-20)", k,
               (long long)n);
   GSS_REQUIRE(minneighbors <= k, "invalid min/max number of neighbors");  // idw.jl:97, lwr.jl:99
-  GSS_TRY(check_metric(sp.metric, sp.mparam, dim, radius, inv_radii));
   // GSS_METRIC_ROTATED_BALL: the axis-aligned ball on frame coordinates (origin xdata[0]); the weights then use the
   // ball-metric distances, and LWR's affine regression does not depend on the frame
-  Frame fb;
-  GSS_TRY(ball_frame_split(sp.metric, inv_radii, dim, &sp.metric, &fb));
+  Searcher sr;
+  GSS_TRY(sr.init(sp.metric, sp.mparam, radius, inv_radii, dim));
+  sp.metric = sr.metric;
   GSS_REQUIRE(m >= 0 && (m == 0 || (xdata && z && xdom && mean && aux)), "NULL array");
   if (m == 0) return GSS_OK;
   hipStream_t s = to_stream(stream);
   Staged sxd, sz, sx, smean, saux, sstat;
+  FrameCopy fx;
   GSS_TRY(sxd.in(xdata, sizeof(double) * n * dim, mem, s));
-  DevBuf fxd, fx;
-  if (fb.on) {
-    GSS_TRY(frame_origin(&fb, xdata, mem, s));
-    GSS_TRY(fxd.alloc(sizeof(double) * (size_t)(n * dim)));
-    GSS_TRY(frame_apply_dev(fb, sxd.as<double>(), n, fxd.as<double>(), s));
-    sxd.p = fxd.p;
-  }
+  if (sr.frame.on) GSS_TRY(frame_origin(&sr.frame, xdata, mem, s));
+  GSS_TRY(sr.samples(sxd.as<double>(), nullptr, n, s));
   GSS_TRY(sz.in(z, sizeof(double) * n * nz, mem, s));
   HostPipe pipe;   // host arrays of the domain: in and out piece by piece beside the computation (k <= 64, one column)
   GSS_TRY(pipe.begin(k <= 64 && nz == 1 ? mem : GSS_MEM_DEVICE, m, s));
@@ -902,19 +881,17 @@ static int32_t est_predict(EstSpec sp, const double* xdata, const double* z, int
     pipe.add_out(mean, smean.p, sizeof(double));
     pipe.add_out(aux, saux.p, sizeof(double));
     pipe.add_out(status, status ? sstat.p : nullptr, 1);
-    pipe.frame = &fb;
-  } else if (fb.on) {
-    GSS_TRY(fx.alloc(sizeof(double) * (size_t)(m * dim)));
-    GSS_TRY(frame_apply_dev(fb, sx.as<double>(), m, fx.as<double>(), s));
-    sx.p = fx.p;
+    pipe.frame = &sr.frame;
+  } else {
+    GSS_TRY(fx.of(sr.frame, &sx, m, s));
   }
-  GSS_TRY(est_local_dev(sp, sxd.as<double>(), sz.as<double>(), n, dim, sx.as<double>(), m, k, minneighbors, radius,
-                        inv_radii, smean.as<double>(), saux.as<double>(), st, s, &pipe));
+  GSS_TRY(est_local_dev(sp, sr, sz.as<double>(), sx.as<double>(), m, k, minneighbors, smean.as<double>(),
+                        saux.as<double>(), st, s, &pipe));
   if (pipe.on) return GSS_OK;   // everything is home (est_local_dev ends with pipe.finish and a synchronisation)
   GSS_TRY(smean.back(mean, sizeof(double) * m * nz, mem, s));
   GSS_TRY(saux.back(aux, sizeof(double) * m, mem, s));
   if (status) GSS_TRY(sstat.back(status, (size_t)m, mem, s));
-  if (!status || fb.on) GSS_HIP(hipStreamSynchronize(s));  // st_own and the frame copies are released on return
+  if (!status) GSS_HIP(hipStreamSynchronize(s));  // st_own is released on return
   return GSS_OK;
 }
 

@@ -249,7 +249,7 @@ static void kd_order(KdPoint* pts, int dim, int64_t lo, int64_t hi, int depth) {
   }
 }
 
-int32_t knn_index_build(const double* xhost, int64_t n, int dim, KnnIndex* ix, hipStream_t s) {
+static int32_t knn_index_build(const double* xhost, int64_t n, int dim, KnnIndex* ix, hipStream_t s) {
   std::vector<KdPoint> pts((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
     for (int a = 0; a < 3; ++a) pts[(size_t)i].c[a] = a < dim ? xhost[i * dim + a] : 0.0;
@@ -310,16 +310,9 @@ int32_t knn_index_build(const double* xhost, int64_t n, int dim, KnnIndex* ix, h
   return GSS_OK;
 }
 
-int32_t knn_index_build_from_device(const double* xdev, int64_t n, int dim, KnnIndex* ix, hipStream_t s) {
-  // large sets are ordered on the device (no copy back, no host sort); GSS_KNN_BUILD=host / device forces one path
-  const char* e = std::getenv("GSS_KNN_BUILD");
-  const bool dev = e ? (e[0] == 'd') : (n >= KNN_DEVICE_BUILD_MIN);
-  if (dev) return knn_index_build_device(xdev, n, dim, ix, s);
-  std::vector<double> xh((size_t)(n * dim));
-  GSS_HIP(hipMemcpyAsync(xh.data(), xdev, sizeof(double) * xh.size(), hipMemcpyDeviceToHost, s));
-  GSS_HIP(hipStreamSynchronize(s));
-  return knn_index_build(xh.data(), n, dim, ix, s);
-}
+// the same ordering rule carried out on the device (knn_build.hip)
+int32_t knn_index_build_device(const double* xdev, int64_t n, int dim, KnnIndex* ix, hipStream_t s);
+constexpr int64_t KNN_DEVICE_BUILD_MIN = 16384;   // samples from which the device orders them (no copy back, no host sort)
 
 // lower bound of sqdist_nofma(point in box, q): same operation order, every step monotone in |t|
 template <int DIM>
@@ -483,46 +476,6 @@ __global__ __launch_bounds__(256) void knn_pruned_kernel(const double* __restric
   if (lane == 0 && count_out) count_out[p] = cnt;
 }
 
-int32_t knn_search_indexed(const KnnIndex& ix, const double* centers, int64_t m, int k, double radius,
-                           const double* inv_radii_host, int* idx, int* count, hipStream_t s, const int* rank,
-                           const int* qrank, const int* bminrank, int metric, const double* lowd, const int* lowi) {
-  GSS_REQUIRE(k >= 1 && k <= 64, "knn_search_indexed: one pass finds at most 64 neighbours (got k = %d); "
-                                 "knn_search_indexed_any runs the passes for more", k);
-  if (m <= 0) return GSS_OK;
-  const int use_ball = (radius >= 0.0 || inv_radii_host != nullptr) ? 1 : 0;
-  const int aniso = inv_radii_host != nullptr ? 1 : 0;
-  const double r2 = aniso ? 1.0 : radius * radius;
-  double ir[3] = {1.0, 1.0, 1.0};
-  if (aniso)
-    for (int a = 0; a < ix.dim; ++a) ir[a] = inv_radii_host[a];
-  dim3 grid((unsigned)((m + 3) / 4));
-#define GSS_KNN_ARGS ix.xs.as<double>(), ix.perm.as<int>(), ix.lo.as<double>(), ix.hi.as<double>(), \
-                     ix.lo1.as<double>(), ix.hi1.as<double>(), (int)ix.n, ix.nb, ix.nb1, \
-                     centers, m, k, r2, use_ball, aniso, ir[0], ir[1], ir[2], rank, qrank, bminrank, idx, count, lowd, lowi
-  GSS_REQUIRE(metric == GSS_METRIC_EUCLIDEAN || metric == GSS_METRIC_CITYBLOCK || metric == GSS_METRIC_CHEBYSHEV,
-              "the indexed search has box bounds for the Euclidean, Cityblock and Chebyshev keys only");
-  if (rank) GSS_REQUIRE(qrank && bminrank, "masked search needs query ranks and per-batch minimum ranks");
-#define GSS_KNN_LAUNCH(MASKED, METRIC)                                                                               \
-  switch (ix.dim) {                                                                                                   \
-    case 1: hipLaunchKernelGGL((knn_pruned_kernel<1, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;   \
-    case 2: hipLaunchKernelGGL((knn_pruned_kernel<2, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;   \
-    default: hipLaunchKernelGGL((knn_pruned_kernel<3, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;  \
-  }
-  if (rank) {   // SGS: candidates whose rank lies below the query's
-    if (metric == GSS_METRIC_CITYBLOCK) { GSS_KNN_LAUNCH(true, GSS_METRIC_CITYBLOCK) }
-    else if (metric == GSS_METRIC_CHEBYSHEV) { GSS_KNN_LAUNCH(true, GSS_METRIC_CHEBYSHEV) }
-    else { GSS_KNN_LAUNCH(true, GSS_METRIC_EUCLIDEAN) }
-  } else {
-    if (metric == GSS_METRIC_CITYBLOCK) { GSS_KNN_LAUNCH(false, GSS_METRIC_CITYBLOCK) }
-    else if (metric == GSS_METRIC_CHEBYSHEV) { GSS_KNN_LAUNCH(false, GSS_METRIC_CHEBYSHEV) }
-    else { GSS_KNN_LAUNCH(false, GSS_METRIC_EUCLIDEAN) }
-  }
-#undef GSS_KNN_LAUNCH
-#undef GSS_KNN_ARGS
-  GSS_HIP(hipGetLastError());
-  return GSS_OK;
-}
-
 // ---- more than 64 neighbours (ui.jl:16-23 accepts any maxneighbors <= n): passes of 64 -----------------------------
 __global__ __launch_bounds__(256) void knn_any_init_kernel(int64_t m, int* __restrict__ count, double* __restrict__ lowd,
                                                            int* __restrict__ lowi) {
@@ -572,12 +525,199 @@ __global__ __launch_bounds__(256) void knn_any_append_kernel(const double* __res
   lowi[p] = last;
 }
 
-int32_t knn_search_indexed_any(const KnnIndex& ix, const double* xdata, const double* centers, int64_t m, int k,
-                               double radius, const double* inv_radii_host, int* idx, int* count, hipStream_t s,
-                               int metric, const int* rank, const int* qrank, const int* bminrank) {
-  if (k <= 64) return knn_search_indexed(ix, centers, m, k, radius, inv_radii_host, idx, count, s, rank, qrank,
-                                         bminrank, metric);
+// ---------------------------------------------------------------------------------------------
+// Searcher (gss_internal.h)
+// ---------------------------------------------------------------------------------------------
+// same rotation (or both raw)
+static bool frame_same(const Frame& a, const Frame& b) {
+  if (!a.on || !b.on) return a.on == b.on;
+  for (int k = 0; k < 9; ++k)
+    if (a.R[k] != b.R[k]) return false;
+  return true;
+}
+
+int32_t Searcher::init(int metric_, double metric_param, double radius, const double* inv_radii, int dim_,
+                       const Frame* cov) {
+  GSS_REQUIRE(metric_ >= GSS_METRIC_EUCLIDEAN && metric_ <= GSS_METRIC_ROTATED_BALL, "unknown search metric %d", metric_);
+  if (metric_ == GSS_METRIC_ROTATED_BALL) {
+    GSS_REQUIRE(inv_radii != nullptr, "GSS_METRIC_ROTATED_BALL needs inv_radii -> 3 inverse radii + rotation[9]");
+  } else if (metric_ != GSS_METRIC_EUCLIDEAN) {
+    // searcher_ui (ui.jl:25-31): a neighbourhood replaces the metric search, the two are never combined
+    GSS_REQUIRE(radius < 0.0 && inv_radii == nullptr, "a search ball cannot be combined with a non-Euclidean distance");
+    if (metric_ == GSS_METRIC_HAVERSINE) {
+      GSS_REQUIRE(dim_ == 2, "the haversine distance needs (longitude, latitude) points, got %d-D", dim_);
+      GSS_REQUIRE(metric_param > 0.0, "the haversine distance needs a positive sphere radius");
+    }
+  }
+  metric = metric_;
+  dim = dim_;
+  frame = Frame();
+  frame.dim = dim;
+  if (metric == GSS_METRIC_ROTATED_BALL) {   // the Euclidean ball with the same radii on the frame of its rotation
+    metric = GSS_METRIC_EUCLIDEAN;
+    bool id = false;
+    GSS_TRY(rotation_check(inv_radii + 3, dim, &id));
+    if (!id) {
+      frame.on = 1;
+      for (int k = 0; k < 9; ++k) frame.R[k] = inv_radii[3 + k];
+    }
+  }
+  if (cov) {
+    if (metric == GSS_METRIC_EUCLIDEAN && inv_radii == nullptr) frame = *cov;
+    for (int a = 0; a < 3; ++a) frame.c[a] = cov->c[a];
+    two_frames = !frame_same(frame, *cov);
+    cov_on_ = cov->on != 0;
+  }
+  use_ball = (radius >= 0.0 || inv_radii != nullptr) ? 1 : 0;
+  aniso = inv_radii != nullptr ? 1 : 0;
+  r2 = aniso ? 1.0 : radius * radius;
+  for (int a = 0; a < 3; ++a) ir[a] = (aniso && a < dim) ? inv_radii[a] : 1.0;
+  return GSS_OK;
+}
+
+Searcher::~Searcher() {
+  if (built_ || xs_own_.p || cq_.p) (void)hipStreamSynchronize(stream_);
+}
+
+int32_t Searcher::samples(const double* x, const double* x_raw, int64_t n_, hipStream_t s, const double* x_host) {
+  GSS_REQUIRE(n_ >= 1 && n_ < INT_MAX && dim >= 1 && dim <= 3, "knn: bad sizes");
+  n = n_;
+  x_host_ = x_host;
+  stream_ = s;
+  const double* raw = cov_on_ ? x_raw : x;
+  if (!(two_frames || (!cov_on_ && frame.on))) {   // the caller's coordinates are the search frame's
+    xs = x;
+  } else if (raw && !frame.on) {
+    xs = raw;
+  } else {
+    GSS_REQUIRE(raw || x_host, "Searcher: the search frame needs the raw samples");
+    GSS_TRY(xs_own_.alloc(sizeof(double) * (size_t)(n * dim)));
+    if (!raw) {
+      GSS_HIP(hipMemcpyAsync(xs_own_.p, x_host, xs_own_.bytes, hipMemcpyHostToDevice, s));
+      raw = xs_own_.as<double>();
+    }
+    if (frame.on) GSS_TRY(frame_apply_dev(frame, raw, n, xs_own_.as<double>(), s));
+    xs = xs_own_.as<double>();
+  }
+  return GSS_OK;
+}
+
+int32_t Searcher::index(hipStream_t s, const KnnIndex** out) {
+  if (out) *out = nullptr;
+  if (metric == GSS_METRIC_HAVERSINE) return GSS_OK;   // its key has no box bounds
+  if (!built_) {
+    stream_ = s;
+    // GSS_KNN_BUILD=host / device forces one path
+    const char* e = std::getenv("GSS_KNN_BUILD");
+    const bool dev = e ? (e[0] == 'd') : (n >= KNN_DEVICE_BUILD_MIN);
+    if (dev) {
+      GSS_TRY(knn_index_build_device(xs, n, dim, &ix_, s));
+    } else if (x_host_ && !frame.on) {   // the search frame is the raw one: the caller's host copy serves
+      GSS_TRY(knn_index_build(x_host_, n, dim, &ix_, s));
+    } else {
+      std::vector<double> xh((size_t)(n * dim));
+      GSS_HIP(hipMemcpyAsync(xh.data(), xs, sizeof(double) * xh.size(), hipMemcpyDeviceToHost, s));
+      GSS_HIP(hipStreamSynchronize(s));
+      GSS_TRY(knn_index_build(xh.data(), n, dim, &ix_, s));
+    }
+    built_ = true;
+  }
+  if (out) *out = &ix_;
+  return GSS_OK;
+}
+
+// one pass: the kk <= 64 nearest whose key lies above (lowd, lowi) where given
+int32_t Searcher::pass(const double* q, int64_t m, int kk, int* idx, int* count, hipStream_t s, const KnnMask* mask,
+                       bool indexed, const double* lowd, const int* lowi) {
+  if (!indexed) {
+    const dim3 grid((unsigned)((m + 4 * KNN_Q - 1) / (4 * KNN_Q)));
+#define GSS_BRUTE_ARGS xs, (int)n, q, m, kk, r2, use_ball, aniso, ir[0], ir[1], ir[2], idx, count, lowd, lowi
+#define GSS_BRUTE_LAUNCH(D)                                                                                             \
+  switch (metric) {                                                                                                     \
+    case GSS_METRIC_CITYBLOCK:                                                                                          \
+      hipLaunchKernelGGL((knn_kernel<D, GSS_METRIC_CITYBLOCK>), grid, dim3(256), 0, s, GSS_BRUTE_ARGS); break;          \
+    case GSS_METRIC_CHEBYSHEV:                                                                                          \
+      hipLaunchKernelGGL((knn_kernel<D, GSS_METRIC_CHEBYSHEV>), grid, dim3(256), 0, s, GSS_BRUTE_ARGS); break;          \
+    case GSS_METRIC_HAVERSINE:                                                                                          \
+      hipLaunchKernelGGL((knn_kernel<D, GSS_METRIC_HAVERSINE>), grid, dim3(256), 0, s, GSS_BRUTE_ARGS); break;          \
+    default:                                                                                                            \
+      hipLaunchKernelGGL((knn_kernel<D, GSS_METRIC_EUCLIDEAN>), grid, dim3(256), 0, s, GSS_BRUTE_ARGS); break;          \
+  }
+    switch (dim) {
+      case 1: GSS_BRUTE_LAUNCH(1) break;
+      case 2: GSS_BRUTE_LAUNCH(2) break;
+      default: GSS_BRUTE_LAUNCH(3) break;
+    }
+#undef GSS_BRUTE_LAUNCH
+#undef GSS_BRUTE_ARGS
+    GSS_HIP(hipGetLastError());
+    return GSS_OK;
+  }
+  const KnnIndex& ix = ix_;
+  const int *rank = mask ? mask->rank : nullptr, *qrank = mask ? mask->qrank : nullptr,
+            *bminrank = mask ? mask->bminrank : nullptr;
+  if (rank) GSS_REQUIRE(qrank && bminrank, "masked search needs query ranks and per-batch minimum ranks");
+  const dim3 grid((unsigned)((m + 3) / 4));
+#define GSS_KNN_ARGS ix.xs.as<double>(), ix.perm.as<int>(), ix.lo.as<double>(), ix.hi.as<double>(), \
+                     ix.lo1.as<double>(), ix.hi1.as<double>(), (int)ix.n, ix.nb, ix.nb1, \
+                     q, m, kk, r2, use_ball, aniso, ir[0], ir[1], ir[2], rank, qrank, bminrank, idx, count, lowd, lowi
+#define GSS_KNN_LAUNCH(MASKED, METRIC)                                                                               \
+  switch (ix.dim) {                                                                                                   \
+    case 1: hipLaunchKernelGGL((knn_pruned_kernel<1, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;   \
+    case 2: hipLaunchKernelGGL((knn_pruned_kernel<2, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;   \
+    default: hipLaunchKernelGGL((knn_pruned_kernel<3, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;  \
+  }
+  if (rank) {   // SGS: candidates whose rank lies below the query's
+    if (metric == GSS_METRIC_CITYBLOCK) { GSS_KNN_LAUNCH(true, GSS_METRIC_CITYBLOCK) }
+    else if (metric == GSS_METRIC_CHEBYSHEV) { GSS_KNN_LAUNCH(true, GSS_METRIC_CHEBYSHEV) }
+    else { GSS_KNN_LAUNCH(true, GSS_METRIC_EUCLIDEAN) }
+  } else {
+    if (metric == GSS_METRIC_CITYBLOCK) { GSS_KNN_LAUNCH(false, GSS_METRIC_CITYBLOCK) }
+    else if (metric == GSS_METRIC_CHEBYSHEV) { GSS_KNN_LAUNCH(false, GSS_METRIC_CHEBYSHEV) }
+    else { GSS_KNN_LAUNCH(false, GSS_METRIC_EUCLIDEAN) }
+  }
+#undef GSS_KNN_LAUNCH
+#undef GSS_KNN_ARGS
+  GSS_HIP(hipGetLastError());
+  return GSS_OK;
+}
+
+int32_t Searcher::query(const double* c, const double* c_raw, int64_t m, int k, int* idx, int* count, hipStream_t s,
+                        const KnnMask* mask) {
+  GSS_REQUIRE(k >= 1, "maxneighbors = %d", k);
+  GSS_REQUIRE(xs != nullptr, "Searcher: query before samples");
   if (m <= 0) return GSS_OK;
+  stream_ = s;
+  const double* q = c ? c : xs;
+  GSS_REQUIRE(c || m == n, "Searcher: the samples as centres are %lld, not %lld", (long long)n, (long long)m);
+  if (c && two_frames) {
+    GSS_REQUIRE(c_raw != nullptr, "Searcher: the search frame needs the raw centres");
+    q = c_raw;
+    if (frame.on) {
+      if (cq_.bytes < sizeof(double) * (size_t)(m * dim)) {
+        if (cq_.p) GSS_HIP(hipStreamSynchronize(s));   // an earlier query may still read it
+        cq_.release();
+        GSS_TRY(cq_.alloc(sizeof(double) * (size_t)(m * dim)));
+      }
+      GSS_TRY(frame_apply_dev(frame, c_raw, m, cq_.as<double>(), s));
+      q = cq_.as<double>();
+    }
+  }
+  // Which kernel runs.  The index prunes with box bounds, which the Haversine key does not have: that one is always
+  // exhaustive.  GSS_KNN_BRUTE=1 (A/B checks; same results) selects the exhaustive kernel too, and so do few centres
+  // into a large set when this is the only query (e.g. the data -> grid-cell lookup of conditional simulation,
+  // fft.jl:129-132): one sweep of the set costs less than ordering it.  Neither applies beyond 64 neighbours or to a
+  // masked query, which always take the index (there is no masked exhaustive kernel).
+  const char* e = std::getenv("GSS_KNN_BRUTE");
+  const bool few_queries = one_shot && m <= 4096 && n >= 32768;
+  const bool indexed =
+      metric != GSS_METRIC_HAVERSINE && (mask || k > 64 || (!(e && e[0] == '1') && !few_queries));
+  GSS_REQUIRE(!mask || indexed, "there is no masked exhaustive search (search distance %d)", metric);
+  if (indexed) GSS_TRY(index(s, nullptr));
+  if (k <= 64) return pass(q, m, k, idx, count, s, mask, indexed, nullptr, nullptr);
+
+  // more than 64 neighbours (ui.jl:16-23 accepts any maxneighbors <= n): passes of 64, each restricted to the keys
+  // above the last neighbour of the pass before
   DevBuf tidx, tcnt, lowd, lowi, cnt_own;
   GSS_TRY(tidx.alloc(sizeof(int) * (size_t)(m * 64)));
   GSS_TRY(tcnt.alloc(sizeof(int) * (size_t)m));
@@ -587,20 +727,15 @@ int32_t knn_search_indexed_any(const KnnIndex& ix, const double* xdata, const do
     GSS_TRY(cnt_own.alloc(sizeof(int) * (size_t)m));
     count = cnt_own.as<int>();
   }
-  const int aniso = inv_radii_host != nullptr ? 1 : 0;
-  double ir[3] = {1.0, 1.0, 1.0};
-  if (aniso)
-    for (int a = 0; a < ix.dim; ++a) ir[a] = inv_radii_host[a];
   const dim3 grid((unsigned)((m + 255) / 256));
   hipLaunchKernelGGL(knn_any_init_kernel, grid, dim3(256), 0, s, m, count, lowd.as<double>(), lowi.as<int>());
   for (int base = 0; base < k; base += 64) {
     const int kk = (k - base) < 64 ? (k - base) : 64;
-    GSS_TRY(knn_search_indexed(ix, centers, m, kk, radius, inv_radii_host, tidx.as<int>(), tcnt.as<int>(), s, rank,
-                               qrank, bminrank, metric, lowd.as<double>(), lowi.as<int>()));
+    GSS_TRY(pass(q, m, kk, tidx.as<int>(), tcnt.as<int>(), s, mask, indexed, lowd.as<double>(), lowi.as<int>()));
 #define GSS_APPEND(D)                                                                                                  \
-  hipLaunchKernelGGL(knn_any_append_kernel<D>, grid, dim3(256), 0, s, xdata, centers, m, k, base, kk, tidx.as<int>(),  \
+  hipLaunchKernelGGL(knn_any_append_kernel<D>, grid, dim3(256), 0, s, xs, q, m, k, base, kk, tidx.as<int>(),           \
                      tcnt.as<int>(), metric, aniso, ir[0], ir[1], ir[2], idx, count, lowd.as<double>(), lowi.as<int>())
-    switch (ix.dim) {
+    switch (dim) {
       case 1: GSS_APPEND(1); break;
       case 2: GSS_APPEND(2); break;
       default: GSS_APPEND(3); break;
@@ -609,124 +744,6 @@ int32_t knn_search_indexed_any(const KnnIndex& ix, const double* xdata, const do
     GSS_HIP(hipGetLastError());
   }
   GSS_HIP(hipStreamSynchronize(s));  // the pass buffers are released on return
-  return GSS_OK;
-}
-
-int32_t check_metric(int metric, double metric_param, int dim, double radius, const double* inv_radii) {
-  GSS_REQUIRE(metric >= GSS_METRIC_EUCLIDEAN && metric <= GSS_METRIC_ROTATED_BALL, "unknown search metric %d", metric);
-  if (metric == GSS_METRIC_EUCLIDEAN) return GSS_OK;
-  if (metric == GSS_METRIC_ROTATED_BALL) {   // the entry points move it to a Euclidean ball on its frame
-    GSS_REQUIRE(inv_radii != nullptr, "GSS_METRIC_ROTATED_BALL needs inv_radii -> 3 inverse radii + rotation[9]");
-    return GSS_OK;
-  }
-  // searcher_ui (ui.jl:25-31): a neighbourhood replaces the metric search, the two are never combined
-  GSS_REQUIRE(radius < 0.0 && inv_radii == nullptr, "a search ball cannot be combined with a non-Euclidean distance");
-  if (metric == GSS_METRIC_HAVERSINE) {
-    GSS_REQUIRE(dim == 2, "the haversine distance needs (longitude, latitude) points, got %d-D", dim);
-    GSS_REQUIRE(metric_param > 0.0, "the haversine distance needs a positive sphere radius");
-  }
-  return GSS_OK;
-}
-
-template <int DIM, int METRIC>
-static void launch_brute(dim3 grid, hipStream_t s, const double* xdata, int n, const double* centers, int64_t m, int k,
-                         double r2, int use_ball, int aniso, const double* ir, int* idx, int* count,
-                         const double* lowd = nullptr, const int* lowi = nullptr) {
-  hipLaunchKernelGGL((knn_kernel<DIM, METRIC>), grid, dim3(256), 0, s, xdata, n, centers, m, k, r2, use_ball, aniso,
-                     ir[0], ir[1], ir[2], idx, count, lowd, lowi);
-}
-
-template <int DIM>
-static void launch_brute_metric(int metric, dim3 grid, hipStream_t s, const double* xdata, int n,
-                                const double* centers, int64_t m, int k, double r2, int use_ball, int aniso,
-                                const double* ir, int* idx, int* count, const double* lowd = nullptr,
-                                const int* lowi = nullptr) {
-  switch (metric) {
-    case GSS_METRIC_CITYBLOCK:
-      launch_brute<DIM, GSS_METRIC_CITYBLOCK>(grid, s, xdata, n, centers, m, k, r2, use_ball, aniso, ir, idx, count, lowd, lowi);
-      break;
-    case GSS_METRIC_CHEBYSHEV:
-      launch_brute<DIM, GSS_METRIC_CHEBYSHEV>(grid, s, xdata, n, centers, m, k, r2, use_ball, aniso, ir, idx, count, lowd, lowi);
-      break;
-    case GSS_METRIC_HAVERSINE:
-      launch_brute<DIM, GSS_METRIC_HAVERSINE>(grid, s, xdata, n, centers, m, k, r2, use_ball, aniso, ir, idx, count, lowd, lowi);
-      break;
-    default:
-      launch_brute<DIM, GSS_METRIC_EUCLIDEAN>(grid, s, xdata, n, centers, m, k, r2, use_ball, aniso, ir, idx, count, lowd, lowi);
-      break;
-  }
-}
-
-// more than 64 neighbours on the exhaustive kernel (the haversine distance has no box bounds for the indexed search):
-// passes of 64, each restricted to the keys above the last neighbour of the pass before
-static int32_t knn_search_brute_any(const double* xdata, int64_t n, int dim, const double* centers, int64_t m, int k,
-                                    double r2, int use_ball, int aniso, const double* ir, int* idx, int* count,
-                                    hipStream_t s, int metric) {
-  DevBuf tidx, tcnt, lowd, lowi, cnt_own;
-  GSS_TRY(tidx.alloc(sizeof(int) * (size_t)(m * 64)));
-  GSS_TRY(tcnt.alloc(sizeof(int) * (size_t)m));
-  GSS_TRY(lowd.alloc(sizeof(double) * (size_t)m));
-  GSS_TRY(lowi.alloc(sizeof(int) * (size_t)m));
-  if (!count) {
-    GSS_TRY(cnt_own.alloc(sizeof(int) * (size_t)m));
-    count = cnt_own.as<int>();
-  }
-  const dim3 g1((unsigned)((m + 255) / 256));
-  const dim3 grid((unsigned)((m + 4 * KNN_Q - 1) / (4 * KNN_Q)));
-  hipLaunchKernelGGL(knn_any_init_kernel, g1, dim3(256), 0, s, m, count, lowd.as<double>(), lowi.as<int>());
-  for (int base = 0; base < k; base += 64) {
-    const int kk = (k - base) < 64 ? (k - base) : 64;
-#define GSS_BRUTE_PASS(D)                                                                                               \
-  do {                                                                                                                   \
-    launch_brute_metric<D>(metric, grid, s, xdata, (int)n, centers, m, kk, r2, use_ball, aniso, ir, tidx.as<int>(),     \
-                           tcnt.as<int>(), lowd.as<double>(), lowi.as<int>());                                          \
-    hipLaunchKernelGGL(knn_any_append_kernel<D>, g1, dim3(256), 0, s, xdata, centers, m, k, base, kk, tidx.as<int>(),   \
-                       tcnt.as<int>(), metric, aniso, ir[0], ir[1], ir[2], idx, count, lowd.as<double>(),               \
-                       lowi.as<int>());                                                                                  \
-  } while (0)
-    switch (dim) {
-      case 1: GSS_BRUTE_PASS(1); break;
-      case 2: GSS_BRUTE_PASS(2); break;
-      default: GSS_BRUTE_PASS(3); break;
-    }
-#undef GSS_BRUTE_PASS
-    GSS_HIP(hipGetLastError());
-  }
-  GSS_HIP(hipStreamSynchronize(s));  // the pass buffers are released on return
-  return GSS_OK;
-}
-
-// Euclidean: pruned search (exhaustive kernel with GSS_KNN_BRUTE=1, kept for A/B checks); other metrics: exhaustive
-int32_t knn_search_dev(const double* xdata, int64_t n, int dim, const double* centers, int64_t m, int k,
-                       double radius, const double* inv_radii_host, int* idx, int* count, hipStream_t s, int metric) {
-  GSS_REQUIRE(k >= 1, "maxneighbors = %d", k);
-  GSS_REQUIRE(n >= 1 && n < INT_MAX && dim >= 1 && dim <= 3, "knn: bad sizes");
-  if (m <= 0) return GSS_OK;
-  const char* e = std::getenv("GSS_KNN_BRUTE");
-  // few queries into a large set (e.g. the data -> grid-cell lookup of conditional simulation, fft.jl:129-132):
-  // one brute-force sweep of the set costs less than ordering it on the host for the index
-  const bool few_queries = m <= 4096 && n >= 32768 && k <= 64;
-  if (metric != GSS_METRIC_HAVERSINE && (k > 64 || (!(e && e[0] == '1') && !few_queries))) {
-    KnnIndex ix;
-    GSS_TRY(knn_index_build_from_device(xdata, n, dim, &ix, s));
-    GSS_TRY(knn_search_indexed_any(ix, xdata, centers, m, k, radius, inv_radii_host, idx, count, s, metric));
-    GSS_HIP(hipStreamSynchronize(s));  // the index is released on return
-    return GSS_OK;
-  }
-  const int use_ball = (radius >= 0.0 || inv_radii_host != nullptr) ? 1 : 0;
-  const int aniso = inv_radii_host != nullptr ? 1 : 0;
-  const double r2 = aniso ? 1.0 : radius * radius;
-  double ir[3] = {1.0, 1.0, 1.0};
-  if (aniso)
-    for (int a = 0; a < dim; ++a) ir[a] = inv_radii_host[a];
-  if (k > 64) return knn_search_brute_any(xdata, n, dim, centers, m, k, r2, use_ball, aniso, ir, idx, count, s, metric);
-  dim3 grid((unsigned)((m + 4 * KNN_Q - 1) / (4 * KNN_Q)));
-  switch (dim) {
-    case 1: launch_brute_metric<1>(metric, grid, s, xdata, (int)n, centers, m, k, r2, use_ball, aniso, ir, idx, count); break;
-    case 2: launch_brute_metric<2>(metric, grid, s, xdata, (int)n, centers, m, k, r2, use_ball, aniso, ir, idx, count); break;
-    default: launch_brute_metric<3>(metric, grid, s, xdata, (int)n, centers, m, k, r2, use_ball, aniso, ir, idx, count); break;
-  }
-  GSS_HIP(hipGetLastError());
   return GSS_OK;
 }
 
@@ -740,29 +757,21 @@ extern "C" int32_t gss_knn_search(const double* xdata, int64_t n, int32_t dim, c
   GSS_ENTRY();
   GSS_REQUIRE(xdata && centers && idx, "gss_knn_search: NULL array");
   GSS_REQUIRE(k >= 1 && k <= n, "gss_knn_search: k = %d outside 1..n = %lld", k, (long long)n);
-  GSS_TRY(check_metric(metric, metric_param, dim, radius, inv_radii));
   GSS_REQUIRE(dim >= 1 && dim <= 3, "gss_knn_search: dim %d outside 1..3", dim);
-  Frame fb;   // GSS_METRIC_ROTATED_BALL: the axis-aligned ball on frame coordinates, origin xdata[0]
-  GSS_TRY(ball_frame_split(metric, inv_radii, dim, &metric, &fb));
+  Searcher sr;
+  GSS_TRY(sr.init(metric, metric_param, radius, inv_radii, dim));
+  sr.one_shot = true;
   hipStream_t s = to_stream(stream);
   Staged sx, sc, si, sn;
   GSS_TRY(sx.in(xdata, sizeof(double) * (size_t)(n * dim), mem, s));
   GSS_TRY(sc.in(centers, sizeof(double) * (size_t)(m * dim), mem, s));
   GSS_TRY(si.out(idx, sizeof(int32_t) * (size_t)(m * k), mem));
   GSS_TRY(sn.out(count, sizeof(int32_t) * (size_t)m, mem));
-  DevBuf fx, fc;
-  if (fb.on) {
-    GSS_TRY(frame_origin(&fb, xdata, mem, s));
-    GSS_TRY(fx.alloc(sizeof(double) * (size_t)(n * dim)));
-    GSS_TRY(fc.alloc(sizeof(double) * (size_t)(m * dim)));
-    GSS_TRY(frame_apply_dev(fb, sx.as<double>(), n, fx.as<double>(), s));
-    GSS_TRY(frame_apply_dev(fb, sc.as<double>(), m, fc.as<double>(), s));
-    sx.p = fx.p;
-    sc.p = fc.p;
-  }
-  GSS_TRY(knn_search_dev(sx.as<double>(), n, dim, sc.as<double>(), m, k, radius, inv_radii, si.as<int>(),
-                         sn.as<int>(), s, metric));
-  if (fb.on && mem == GSS_MEM_DEVICE) GSS_HIP(hipStreamSynchronize(s));   // the frame copies are released on return
+  if (sr.frame.on) GSS_TRY(frame_origin(&sr.frame, xdata, mem, s));   // a rotated ball: origin xdata[0]
+  FrameCopy fc;
+  GSS_TRY(sr.samples(sx.as<double>(), nullptr, n, s));
+  GSS_TRY(fc.of(sr.frame, &sc, m, s));
+  GSS_TRY(sr.query(sc.as<double>(), nullptr, m, k, si.as<int>(), sn.as<int>(), s));
   GSS_TRY(si.back(idx, sizeof(int32_t) * (size_t)(m * k), mem, s));
   GSS_TRY(sn.back(count, sizeof(int32_t) * (size_t)m, mem, s));
   return GSS_OK;

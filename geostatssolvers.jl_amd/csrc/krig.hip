@@ -545,12 +545,10 @@ struct gss_krig {
 
 namespace gss {
 int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const signed char* exps, double inv_scale,
-                       double sk_mean, const double* xdata, const double* z, const double* drift_data, int64_t n,
-                       const double* x0, const double* drift_dom, int64_t m, int k, int minneighbors, double radius,
-                       const double* inv_radii_host, double* mean, double* var, uint8_t* status, int* idx_out,
-                       int* count_out, hipStream_t s, int metric, HostPipe* pipe = nullptr, int block_nsub = 0,
-                       const double* block_cell = nullptr, double block_cvv = 0.0, const double* xs_data = nullptr,
-                       const double* xs0 = nullptr);
+                       double sk_mean, Searcher& sr, const double* xdata, const double* z, const double* drift_data,
+                       const double* x0, const double* x0_raw, const double* drift_dom, int64_t m, int k,
+                       int minneighbors, double* mean, double* var, uint8_t* status, int* idx_out, int* count_out,
+                       hipStream_t s, HostPipe* pipe, int block_nsub, const double* block_cell, double block_cvv);
 }
 
 
@@ -1110,12 +1108,8 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
     pipe.add_out(status, sstat.p, 1);
     pipe.frame = &h->fr;   // rotated variogram: each piece moves into the frame where it lands
   }
-  DevBuf xfr;
-  if (h->fr.on && !piped) {
-    GSS_TRY(xfr.alloc(sizeof(double) * (size_t)(m * dim)));
-    GSS_TRY(frame_apply_dev(h->fr, sx.as<double>(), m, xfr.as<double>(), s));
-    sx.p = xfr.p;
-  }
+  FrameCopy xfr;
+  if (!piped) GSS_TRY(xfr.of(h->fr, &sx, m, s));
 
   for (int64_t off = 0; off < m; off += mc) {
     const int64_t mv = (m - off) < mc ? (m - off) : mc;
@@ -1187,7 +1181,6 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
     GSS_TRY(svar.back(var, sizeof(double) * m, mem, s));
     GSS_TRY(sstat.back(status, (size_t)m, mem, s));
   }
-  if (xfr.p) GSS_HIP(hipStreamSynchronize(s));   // the frame copy of the domain is released on return
   return krig_fit_wait(h);   // status of an asynchronous fit (it finished while the assembly ran)
 }
 
@@ -1235,14 +1228,8 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr, "NULL handle");
 
-  GSS_TRY(check_metric(metric, metric_param, h->dim, radius, inv_radii));
-  // search frame: a rotated ball searches on its own frame, a non-Euclidean distance on the raw
-  // coordinates, a plain k-NN or isotropic ball (rotation invariant) on the covariance frame
-  Frame fs;
-  GSS_TRY(ball_frame_split(metric, inv_radii, h->dim, &metric, &fs));
-  if (metric == GSS_METRIC_EUCLIDEAN && inv_radii == nullptr) fs = h->fr;
-  for (int a = 0; a < 3; ++a) fs.c[a] = h->fr.c[a];
-  const bool two_frames = !frame_same(fs, h->fr);
+  Searcher sr;
+  GSS_TRY(sr.init(metric, metric_param, radius, inv_radii, h->dim, &h->fr));
   GSS_REQUIRE(m >= 0 && (m == 0 || (xdom && mean && var)), "gss_krig_predict_knn: NULL array");
   GSS_REQUIRE(k >= 1 && k <= h->n, "maxneighbors %d outside 1..%lld (searcher_ui clamps it, ui.jl:18-20)", k,
               (long long)h->n);
@@ -1252,7 +1239,7 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
   const int dim = h->dim;
   Staged sx, sd, smean, svar, sstat, sidx, scnt;
   HostPipe pipe;   // host arrays: in and out piece by piece beside the computation (gss_internal.h)
-  if (!two_frames) GSS_TRY(pipe.begin(mem, m, s));   // two frames: the domain is needed twice, it comes in whole
+  if (!sr.two_frames) GSS_TRY(pipe.begin(mem, m, s));   // two frames: the domain is needed twice, it comes in whole
   if (pipe.on) {
     GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
     if (h->variant == GSS_KRIG_EXTDRIFT)
@@ -1276,30 +1263,15 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
     pipe.add_out(count_out, scnt.p, sizeof(int32_t));
     pipe.frame = &h->fr;
   }
-  DevBuf xfr, xsd, xs0;   // domain in the covariance frame; samples and domain in the search frame
-  const double* xs_data = nullptr;
-  if (two_frames) {
-    const double* raw = h->fr.on ? h->xraw.as<double>() : h->xdata.as<double>();
-    xs_data = raw;
-    if (fs.on) {
-      GSS_TRY(xsd.alloc(sizeof(double) * (size_t)(h->n * dim)));
-      GSS_TRY(frame_apply_dev(fs, raw, h->n, xsd.as<double>(), s));
-      xs_data = xsd.as<double>();
-      GSS_TRY(xs0.alloc(sizeof(double) * (size_t)(m * dim)));
-      GSS_TRY(frame_apply_dev(fs, sx.as<double>(), m, xs0.as<double>(), s));
-    }
-  }
-  const double* xs_dom = two_frames ? (fs.on ? xs0.as<double>() : sx.as<double>()) : nullptr;
-  if (h->fr.on && !pipe.on) {
-    GSS_TRY(xfr.alloc(sizeof(double) * (size_t)(m * dim)));
-    GSS_TRY(frame_apply_dev(h->fr, sx.as<double>(), m, xfr.as<double>(), s));
-    sx.p = xfr.p;
-  }
-  GSS_TRY(krig_local_dev(h->vg, h->variant, h->nc, dim, &h->ds.e[0][0], h->ds.inv_scale[0], h->sk_mean,
-                         h->xdata.as<double>(), h->z.as<double>(), h->drift_data.as<double>(), h->n,
-                         sx.as<double>(), sd.as<double>(), m, k, minneighbors, radius, inv_radii, smean.as<double>(),
-                         svar.as<double>(), sstat.as<uint8_t>(), sidx.as<int>(), scnt.as<int>(), s, metric, &pipe,
-                         h->block_nsub, h->block_cell, h->block_cvv, xs_data, xs_dom));
+  GSS_TRY(sr.samples(h->xdata.as<double>(), h->xraw.as<double>(), h->n, s));
+  const double* x0_raw = sx.as<double>();   // as staged; the covariance-frame copy follows
+  FrameCopy xfr;
+  if (!pipe.on) GSS_TRY(xfr.of(h->fr, &sx, m, s));
+  GSS_TRY(krig_local_dev(h->vg, h->variant, h->nc, dim, &h->ds.e[0][0], h->ds.inv_scale[0], h->sk_mean, sr,
+                         h->xdata.as<double>(), h->z.as<double>(), h->drift_data.as<double>(), sx.as<double>(),
+                         sr.two_frames ? x0_raw : nullptr, sd.as<double>(), m, k, minneighbors, smean.as<double>(),
+                         svar.as<double>(), sstat.as<uint8_t>(), sidx.as<int>(), scnt.as<int>(), s, &pipe,
+                         h->block_nsub, h->block_cell, h->block_cvv));
   if (pipe.on) return GSS_OK;   // everything is home (krig_local_dev ends with pipe.finish)
   GSS_TRY(smean.back(mean, sizeof(double) * m, mem, s));
   GSS_TRY(svar.back(var, sizeof(double) * m, mem, s));
@@ -1330,12 +1302,8 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
   Staged sx, sz, so;
   GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
   GSS_TRY(sz.in(zbatch, sizeof(double) * nbatch * n, mem, s));
-  DevBuf xfr;   // rotated variogram: the domain in the frame of the samples
-  if (h->fr.on) {
-    GSS_TRY(xfr.alloc(sizeof(double) * (size_t)(m * dim)));
-    GSS_TRY(frame_apply_dev(h->fr, sx.as<double>(), m, xfr.as<double>(), s));
-    sx.p = xfr.p;
-  }
+  FrameCopy xfr;   // rotated variogram: the domain in the frame of the samples
+  GSS_TRY(xfr.of(h->fr, &sx, m, s));
   GSS_TRY(so.out(mean_out, sizeof(double) * (size_t)(nbatch * m), mem));
 
   DevBuf Zm, U, WD;

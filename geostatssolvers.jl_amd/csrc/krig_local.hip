@@ -540,12 +540,10 @@ void krig_local_mfma_kernel(VgDev vg, LocalSpec sp, const double* __restrict__ x
 
 // Host driver: chunks the domain so that the neighbour-index scratch stays small, runs K4 then K5.
 int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const signed char* exps, double inv_scale,
-                       double sk_mean, const double* xdata, const double* z, const double* drift_data, int64_t n,
-                       const double* x0, const double* drift_dom, int64_t m, int k, int minneighbors, double radius,
-                       const double* inv_radii_host, double* mean, double* var, uint8_t* status, int* idx_out,
-                       int* count_out, hipStream_t s, int metric, HostPipe* pipe, int block_nsub,
-                       const double* block_cell, double block_cvv, const double* xs_data,
-                       const double* xs0) {
+                       double sk_mean, Searcher& sr, const double* xdata, const double* z, const double* drift_data,
+                       const double* x0, const double* x0_raw, const double* drift_dom, int64_t m, int k,
+                       int minneighbors, double* mean, double* var, uint8_t* status, int* idx_out, int* count_out,
+                       hipStream_t s, HostPipe* pipe, int block_nsub, const double* block_cell, double block_cvv) {
   GSS_REQUIRE(nc <= LMAX_NC, "moving-neighbourhood kriging supports at most %d drift terms (got %d)", LMAX_NC, nc);
   GSS_REQUIRE(k >= 1 && k <= BIG_MAX_K, "maxneighbors = %d: moving neighbourhoods hold at most %d neighbours "
                                         "(use the global neighbourhood beyond that)", k, BIG_MAX_K);
@@ -565,14 +563,6 @@ int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const sign
 
   const bool piped = pipe && pipe->on;   // host arrays arrive and leave piece by piece (gss_internal.h)
   const int64_t chunk = big ? (k > 512 ? (1 << 14) : (1 << 17)) : (piped ? HostPipe::PIECE : (1 << 20));
-  // the search may run on coordinates of its own frame (a rotated ball other than the variogram's)
-  const double* sxd = xs_data ? xs_data : xdata;
-  const double* sx0 = xs_data ? xs0 : x0;
-  KnnIndex ix;  // k-d ordered batches + boxes, built once per call
-  const char* brute = std::getenv("GSS_KNN_BRUTE");
-  // (the haversine distance always searches exhaustively, in passes of 64 beyond 64 neighbours)
-  const bool use_index = metric != GSS_METRIC_HAVERSINE && (big || !(brute && brute[0] == '1'));
-  if (use_index) GSS_TRY(knn_index_build_from_device(sxd, n, dim, &ix, s));
   DevBuf idx_s, cnt_s, st_s;
   if (!idx_out) GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
   if (!count_out) GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(m < chunk ? m : chunk)));
@@ -585,9 +575,7 @@ int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const sign
     if (piped) GSS_TRY(pipe->fetch(off, mv, s));
     {
       ProfScope ps("knn", s);
-      if (use_index)
-        GSS_TRY(knn_search_indexed_any(ix, sxd, sx0 + off * dim, mv, k, radius, inv_radii_host, idx, cnt, s, metric));
-      else GSS_TRY(knn_search_dev(sxd, n, dim, sx0 + off * dim, mv, k, radius, inv_radii_host, idx, cnt, s, metric));
+      GSS_TRY(sr.query(x0 + off * dim, x0_raw ? x0_raw + off * dim : nullptr, mv, k, idx, cnt, s));
     }
     const double* dd = drift_dom ? drift_dom + off * nc : nullptr;
     ProfScope pl("krig_local", s);

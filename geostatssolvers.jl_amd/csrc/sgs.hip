@@ -1103,24 +1103,16 @@ int32_t gss_sgs_create_paths(gss_sgs_t** out, const gss_variogram_t* vg, double 
   h->path_base = path_base;
   h->filter_after = (flags & GSS_SGS_MASK_AFTER_SEARCH) ? 1 : 0;
   int metric = (flags >> GSS_SGS_METRIC_SHIFT) & 7;
-  // search frame: a rotated ball searches on its own frame, a non-Euclidean distance on the raw
-  // coordinates, a plain k-NN or isotropic ball on the covariance frame
-  GSS_REQUIRE(metric != GSS_METRIC_ROTATED_BALL || inv_radii != nullptr,
-              "GSS_METRIC_ROTATED_BALL needs inv_radii -> 3 inverse radii + rotation[9]");
-  Frame fs;
-  GSS_TRY(ball_frame_split(metric, inv_radii, dim, &metric, &fs));
-  if (metric == GSS_METRIC_EUCLIDEAN && inv_radii == nullptr) fs = fv;
-  GSS_TRY(frame_origin(&fv, centroids, GSS_MEM_HOST, nullptr));
-  for (int a = 0; a < 3; ++a) fs.c[a] = fv.c[a];
-  const bool two_frames = !frame_same(fs, fv);
   // Haversine(r) (seq.jl:91-98 hands `distance` to the searcher): its ranking key does not depend on r and has no box
   // bounds, so it runs on the exhaustive search -- which exists unmasked only: available with the mask applied to the
   // search result (GSS_SGS_MASK_AFTER_SEARCH, the front-ends' default), not for the masked search
   GSS_REQUIRE(metric == GSS_METRIC_EUCLIDEAN || metric == GSS_METRIC_CITYBLOCK || metric == GSS_METRIC_CHEBYSHEV ||
-                  (metric == GSS_METRIC_HAVERSINE && h->filter_after),
+                  metric == GSS_METRIC_ROTATED_BALL || (metric == GSS_METRIC_HAVERSINE && h->filter_after),
               "gss_sgs_create: search distance %d -- Euclidean, Cityblock or Chebyshev; Haversine only with "
               "GSS_SGS_MASK_AFTER_SEARCH (there is no masked exhaustive search)", metric);
-  GSS_TRY(check_metric(metric, 1.0, dim, radius, inv_radii));   // a ball only with the Euclidean distance (ui.jl:25-31)
+  GSS_TRY(frame_origin(&fv, centroids, GSS_MEM_HOST, nullptr));
+  Searcher sr;
+  GSS_TRY(sr.init(metric, 1.0, radius, inv_radii, dim, &fv));
   const int64_t P = npaths;
 
   // visiting rank of every cell (-1 = conditioning cell) per path; each path must be a permutation of 0..N-1
@@ -1162,49 +1154,32 @@ int32_t gss_sgs_create_paths(gss_sgs_t** out, const gss_variogram_t* vg, double 
     GSS_HIP(hipMemcpyAsync(h->zd.p, zdata, h->zd.bytes, hipMemcpyHostToDevice, s));
   }
   if (fv.on) GSS_TRY(frame_apply_dev(fv, cent.as<double>(), N, cent.as<double>(), s));
-  DevBuf scent;   // centroids in the search frame when it is not the covariance frame
-  const double* sc = cent.as<double>();
-  if (two_frames) {
-    GSS_TRY(scent.alloc(cent.bytes));
-    GSS_HIP(hipMemcpyAsync(scent.p, centroids, scent.bytes, hipMemcpyHostToDevice, s));
-    if (fs.on) GSS_TRY(frame_apply_dev(fs, scent.as<double>(), N, scent.as<double>(), s));
-    sc = scent.as<double>();
-  }
-  KnnIndex ix;
-  if (N >= KNN_DEVICE_BUILD_MIN) GSS_TRY(knn_index_build_device(sc, N, dim, &ix, s));  // already in HBM
-  else if (fv.on || two_frames) GSS_TRY(knn_index_build_from_device(sc, N, dim, &ix, s));
-  else GSS_TRY(knn_index_build(centroids, N, dim, &ix, s));
-  GSS_TRY(bmin.alloc(sizeof(int) * (size_t)ix.nb));
+  GSS_TRY(sr.samples(cent.as<double>(), nullptr, N, s, centroids));
+  const KnnIndex* ix = nullptr;   // NULL: exhaustive search (Haversine), which takes no mask
+  GSS_TRY(sr.index(s, &ix));
+  if (ix) GSS_TRY(bmin.alloc(sizeof(int) * (size_t)ix->nb));
   DevBuf rawidx;   // GSS_SGS_MASK_AFTER_SEARCH: the unmasked neighbour lists, shared by every path
   DevBuf bigscr;   // more than 180 neighbours: covariance triangles of the workgroups of sgs_weights_big_kernel
   for (int64_t pp = 0; pp < P; ++pp) {   // stage A once per visiting order
     int* rk = h->rank.as<int>() + pp * N;
     int* idxp = h->idx.as<int>() + pp * N * h->k;
-    hipLaunchKernelGGL(sgs_batch_minrank_kernel, dim3((unsigned)((ix.nb + 3) / 4)), dim3(256), 0, s, ix.perm.as<int>(),
-                       rk, (int)N, ix.nb, bmin.as<int>());
+    if (ix)
+      hipLaunchKernelGGL(sgs_batch_minrank_kernel, dim3((unsigned)((ix->nb + 3) / 4)), dim3(256), 0, s,
+                         ix->perm.as<int>(), rk, (int)N, ix->nb, bmin.as<int>());
     GSS_HIP(hipGetLastError());
     {
       ProfScope ps("sgs_search", s);
+      const KnnMask mask{rk, rk, bmin.as<int>()};
       if (h->filter_after) {   // one unmasked search serves every path: k nearest cells of the whole domain
         if (pp == 0) {
           GSS_TRY(rawidx.alloc(sizeof(int) * (size_t)(N * h->k)));
-          if (metric == GSS_METRIC_HAVERSINE)   // exhaustive (passes of 64 beyond 64 neighbours)
-            GSS_TRY(knn_search_dev(sc, N, dim, sc, N, h->k, -1.0, nullptr, rawidx.as<int>(),
-                                   cnt.as<int>(), s, metric));
-          else if (h->k > SGS_MAX_K)
-            GSS_TRY(knn_search_indexed_any(ix, sc, sc, N, h->k, radius, inv_radii,
-                                           rawidx.as<int>(), cnt.as<int>(), s, metric));
-          else
-            GSS_TRY(knn_search_indexed(ix, sc, N, h->k, radius, inv_radii, rawidx.as<int>(), cnt.as<int>(), s,
-                                       nullptr, nullptr, nullptr, metric));
+          GSS_TRY(sr.query(nullptr, nullptr, N, h->k, rawidx.as<int>(), cnt.as<int>(), s));
         }
       } else if (h->k > SGS_MAX_K) {   // masked search in passes of 64; the lists go through the big weights kernel
         if (pp == 0) GSS_TRY(rawidx.alloc(sizeof(int) * (size_t)(N * h->k)));
-        GSS_TRY(knn_search_indexed_any(ix, sc, sc, N, h->k, radius, inv_radii,
-                                       rawidx.as<int>(), cnt.as<int>(), s, metric, rk, rk, bmin.as<int>()));
+        GSS_TRY(sr.query(nullptr, nullptr, N, h->k, rawidx.as<int>(), cnt.as<int>(), s, &mask));
       } else {
-        GSS_TRY(knn_search_indexed(ix, sc, N, h->k, radius, inv_radii, idxp, cnt.as<int>(), s, rk, rk,
-                                   bmin.as<int>(), metric));
+        GSS_TRY(sr.query(nullptr, nullptr, N, h->k, idxp, cnt.as<int>(), s, &mask));
       }
     }
     {
