@@ -887,6 +887,10 @@ int32_t gss_stat(const char* name, int64_t* value) {
     *value = g_stat_chunks.load();
   } else if (!std::strcmp(name, "panel_giveups")) {
     *value = panel_giveups();
+  } else if (!std::strcmp(name, "gemm_launches_128")) {
+    *value = gemm_launches(128);
+  } else if (!std::strcmp(name, "gemm_launches_64")) {
+    *value = gemm_launches(64);
   } else if (!std::strcmp(name, "ipc_route")) {
     *value = comm_last_ipc_route();   // of the last gss_state_ipc_import: 0 same device, 1 peer, 2 not visible, 3 refused
   } else {

@@ -238,8 +238,14 @@ static int32_t gemm_launch(const GemmArgs& g, hipStream_t s) {
   return GSS_OK;
 }
 
+// products that gemm_f64 sent to each tile shape (gss_stat "gemm_launches_128" / "gemm_launches_64"): a test that means
+// one of the two kernels reads here which one ran
+static std::atomic<int64_t> g_gemm_launches_128{0}, g_gemm_launches_64{0};
+int64_t gemm_launches(int tile) { return (tile == 128 ? g_gemm_launches_128 : g_gemm_launches_64).load(); }
+
 template <int T>
 static int32_t gemm_dispatch(const GemmArgs& g, bool ai, bool bj, hipStream_t s) {
+  (T == 128 ? g_gemm_launches_128 : g_gemm_launches_64).fetch_add(1, std::memory_order_relaxed);
   if (ai && bj) return gemm_launch<T, true, true>(g, s);
   if (ai && !bj) return gemm_launch<T, true, false>(g, s);
   if (!ai && bj) return gemm_launch<T, false, true>(g, s);

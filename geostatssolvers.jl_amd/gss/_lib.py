@@ -327,7 +327,8 @@ def state_ipc_import(kind: int, handle, token: bytes):
 
 
 def stat(name: str) -> int:
-    """A library counter: "pool_bytes", "out_ring_bytes", "out_chunks", "panel_giveups", "ipc_route" (gss.h, gss_stat)."""
+    """A library counter: "pool_bytes", "out_ring_bytes", "out_chunks", "panel_giveups", "gemm_launches_128",
+    "gemm_launches_64", "ipc_route" (gss.h, gss_stat)."""
     v = C.c_int64()
     check(load().gss_stat(name.encode(), C.byref(v)))
     return v.value

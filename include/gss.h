@@ -145,6 +145,8 @@ int32_t gss_trim_pool(void);
 /* Counters for tests and diagnostics: "pool_bytes" (device bytes in the block cache), "out_ring_bytes" (HBM staged for
  * the host outputs of the last simulation call), "out_chunks" (chunks that call moved), "panel_giveups" (times a
  * single-launch factorisation left through its bounded wait and was repeated on the launch-per-block path),
+ * "gemm_launches_128" / "gemm_launches_64" (FP64 matrix products launched so far on the 128 x 128 and on the 64 x 64
+ * tile kernel: which of the two a given shape ran on),
  * "ipc_route" (how the last gss_state_ipc_import reached the owner's device: 0 same device, 1 visible peer, 2 not among
  * the visible devices, 3 refused -- visible but not peer-accessible). */
 int32_t gss_stat(const char* name, int64_t* value);

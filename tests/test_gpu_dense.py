@@ -1,5 +1,14 @@
 """FP64 MFMA toolkit vs numpy/LAPACK (FP64).  Tolerances: GEMM 1e-12 relative to |A||B|,
-Cholesky / inverse 1e-10 relative on well-conditioned SPD matrices."""
+Cholesky / inverse 1e-10 relative on well-conditioned SPD matrices.
+
+Two rules for the GEMM tests that mean a particular kernel:
+* exact integers: operands with integer entries in -8 .. 8 make every partial sum an integer far below 2^53, so the
+  FP64 sum is exact in any order and the result must be `array_equal` to numpy's -- a skipped, repeated or misplaced
+  k-tile shows with no tolerance to argue about; the same case then runs on standard normals under the rounded bound
+  max |got - ref| / (|A| |B|) < 1e-14 K;
+* counters: which of the two tile kernels a shape runs on is the library's decision (a cost rule that may be retuned),
+  so a test never restates it: it reads `gemm_launches_128` / `gemm_launches_64` (gss_stat) around its product and
+  asserts that the kernel it means is the one that ran."""
 import ctypes as C
 
 import numpy as np
@@ -67,6 +76,201 @@ def test_gemm_alpha_beta_and_lower_only():
     assert np.allclose(got[il], ref[il], atol=1e-11)
     # tiles strictly above the diagonal blocks are untouched
     assert np.array_equal(got[:128, 128:], C0[:128, 128:])
+
+
+# ---------------------------------------------------------------------------------------------
+# the 128 x 128 tile kernel and the zero-structure modes, each pinned by the launch counters
+# ---------------------------------------------------------------------------------------------
+def _launches():
+    from gss import _lib
+    return _lib.stat("gemm_launches_128"), _lib.stat("gemm_launches_64")
+
+
+def _assert_ran(tile, before, n=1):
+    """The counter rule: since `before`, `n` products went to the `tile`-tile kernel and none to the other one."""
+    after = _launches()
+    got = (after[0] - before[0], after[1] - before[1])
+    assert got == ((n, 0) if tile == 128 else (0, n)), "(128-tile, 64-tile) launches %r, meant %d on %d" % (got, n, tile)
+
+
+def _draw(kind, rng, *shape):
+    """"int": integers in -8 .. 8 (every partial sum is an integer far below 2^53: exact in any order);
+    "normal": standard normals (the rounded comparison)."""
+    if kind == "int":
+        return rng.integers(-8, 9, size=shape).astype(np.float64)
+    return rng.normal(size=shape)
+
+
+def _place(X, cm, ld=None, off=0, pad=np.nan):
+    """X on the device, column-major when `cm`, with leading dimension `ld` and `off` elements in front of it; what lies
+    between the lines is `pad` (NaN for operands: a load that strays into it shows in the result).
+    Returns (whole buffer, view that starts at X(0, 0), (row stride, column stride))."""
+    import torch
+    r, c = X.shape
+    lead, nline = (r, c) if cm else (c, r)
+    ld = lead if ld is None else ld
+    assert ld >= lead
+    buf = np.full(off + nline * ld, pad)
+    buf[off:].reshape(nline, ld)[:, :lead] = X.T if cm else X
+    t = torch.as_tensor(buf, device="cuda")
+    return t, t[off:], ((1, ld) if cm else (ld, 1))
+
+
+def _fetch(t, shape, cm, ld=None, off=0, pad=None):
+    """The matrix back from a buffer laid out by `_place`; with `pad`, whatever lies between the lines still holds it."""
+    r, c = shape
+    lead, nline = (r, c) if cm else (c, r)
+    ld = lead if ld is None else ld
+    buf = t.cpu().numpy()
+    v = buf[off:].reshape(nline, ld)
+    if pad is not None:
+        assert np.all(v[:, lead:] == pad) and np.all(buf[:off] == pad)
+    return v[:, :lead].T if cm else v[:, :lead]
+
+
+def _same(kind, got, ref, scale, K):
+    if kind == "int":
+        assert np.array_equal(got, ref)
+    else:
+        assert np.max(np.abs(got - ref) / scale) < 1e-14 * K
+
+
+def _even(n):
+    return n + (n & 1)
+
+
+@pytest.mark.parametrize("kind", ["int", "normal"])
+@pytest.mark.parametrize("K", [16, 48, 129, 1024])
+@pytest.mark.parametrize("M,N", [(2048, 2048), (1990, 2041), (3703, 990)])
+def test_gemm_128_tile_full_products(M, N, K, kind):
+    """Column-major A, row-major B with even leading dimensions (the layout of the factorisations' products): with K a
+    multiple of 16 the interior tiles stage with 16-byte loads and the ragged edge tiles with checked scalar loads in
+    the same launch; K = 129 takes the scalar loads everywhere and ends on a partial k-step."""
+    rng = np.random.default_rng(M + 3 * N + 7 * K)
+    A, B = _draw(kind, rng, M, K), _draw(kind, rng, K, N)
+    _, vA, sa = _place(A, True, _even(M))
+    _, vB, sb = _place(B, False, _even(N))
+    tD, vD, sd = _place(np.zeros((M, N)), True, M + 3, pad=7.0)
+    before = _launches()
+    _gemm(M, N, K, vA, sa, vB, sb, vD, sd)
+    _assert_ran(128, before)
+    _same(kind, _fetch(tD, (M, N), True, M + 3, pad=7.0), A @ B, np.abs(A) @ np.abs(B), K)
+
+
+@pytest.mark.parametrize("kind", ["int", "normal"])
+@pytest.mark.parametrize("K", [48, 129])
+def test_gemm_128_tile_all_layouts(K, kind):
+    """The eight storage layouts of A, B and D (the four <A_ICONTIG, B_JCONTIG> instantiations of the 128-tile kernel) on
+    a product that is ragged in both directions."""
+    M, N = 1990, 2041
+    rng = np.random.default_rng(K)
+    A, B = _draw(kind, rng, M, K), _draw(kind, rng, K, N)
+    ref, scale = A @ B, np.abs(A) @ np.abs(B)
+    for a_cm in (False, True):
+        for b_cm in (False, True):
+            for d_cm in (False, True):
+                _, vA, sa = _place(A, a_cm)
+                _, vB, sb = _place(B, b_cm)
+                tD, vD, sd = _place(np.zeros((M, N)), d_cm)
+                before = _launches()
+                _gemm(M, N, K, vA, sa, vB, sb, vD, sd)
+                _assert_ran(128, before)
+                _same(kind, _fetch(tD, (M, N), d_cm), ref, scale, K)
+
+
+@pytest.mark.parametrize("kind", ["int", "normal"])
+@pytest.mark.parametrize("what", ["odd_lda", "odd_ldb", "offset_a", "offset_b"])
+def test_gemm_128_tile_operands_that_forbid_16_byte_loads(what, kind):
+    """(2048, 2048, 48) in the layout that stages with 16-byte loads, except for one thing: an odd leading dimension,
+    or an operand that starts 8 bytes off a 16-byte boundary."""
+    M = N = 2048
+    K = 48
+    rng = np.random.default_rng(len(what))
+    A, B = _draw(kind, rng, M, K), _draw(kind, rng, K, N)
+    _, vA, sa = _place(A, True, M + 1 if what == "odd_lda" else M + 2, off=1 if what == "offset_a" else 0)
+    _, vB, sb = _place(B, False, N + 1 if what == "odd_ldb" else N + 2, off=1 if what == "offset_b" else 0)
+    assert (vA.data_ptr() % 16 == 8) == (what == "offset_a") and (vB.data_ptr() % 16 == 8) == (what == "offset_b")
+    tD, vD, sd = _place(np.zeros((M, N)), True)
+    before = _launches()
+    _gemm(M, N, K, vA, sa, vB, sb, vD, sd)
+    _assert_ran(128, before)
+    _same(kind, _fetch(tD, (M, N), True), A @ B, np.abs(A) @ np.abs(B), K)
+
+
+@pytest.mark.parametrize("kind", ["int", "normal"])
+@pytest.mark.parametrize("M,N,K", [(2816, 2816, 1024), (2816, 2816, 129), (3250, 1500, 1024), (3250, 1500, 129)])
+def test_gemm_128_tile_lower_only_with_alpha_beta(M, N, K, kind):
+    """D <- D - A B on the tiles on and below the block diagonal (the trailing updates; 3 250 x 1 500 has more row
+    tiles than column tiles, the full rows below the block triangle): the lower triangle equals the reference, and
+    the 128 x 128 tiles strictly above the block diagonal keep D's old bits."""
+    rng = np.random.default_rng(M + N + K)
+    A, B, D0 = _draw(kind, rng, M, K), _draw(kind, rng, K, N), _draw(kind, rng, M, N)
+    _, vA, sa = _place(A, True)
+    _, vB, sb = _place(B, False)
+    tD, vD, sd = _place(D0, True, M + 2, pad=7.0)
+    before = _launches()
+    _gemm(M, N, K, vA, sa, vB, sb, vD, sd, alpha=-1.0, beta=1.0, lower=1)
+    _assert_ran(128, before)
+    got = _fetch(tD, (M, N), True, M + 2, pad=7.0)
+    i, j = np.arange(M)[:, None], np.arange(N)[None, :]
+    low = np.broadcast_to(i >= j, (M, N))
+    above = np.broadcast_to(j // 128 > i // 128, (M, N))
+    assert np.array_equal(got[above], D0[above])
+    _same(kind, got[low], (D0 - A @ B)[low], (np.abs(A) @ np.abs(B))[low], K)
+
+
+# operand shapes of the callers: the panel solve P = A21 Wk' (Wk' upper triangular, M >> N = K), the recursion's
+# L21 W (W lower triangular) and W22 T with M = K (W22 lower triangular on the left)
+@pytest.mark.parametrize("kind", ["int", "normal"])
+@pytest.mark.parametrize("mode,M,N,K,tile", [
+    (1, 4096, 1024, 1024, 128), (1, 3990, 1000, 1000, 128), (1, 300, 260, 260, 64),
+    (2, 4096, 1024, 1024, 128), (2, 3990, 1000, 1000, 128), (2, 300, 260, 260, 64),
+    (4, 4096, 1024, 4096, 128), (4, 3990, 1024, 3990, 128), (4, 300, 260, 300, 64)])
+def test_gemm_zero_structure_modes(mode, M, N, K, tile, kind):
+    """`lower_only` bits 1..3 tell the kernel where an operand is zero, so that it skips those k-tiles (and walks the
+    grid by columns for the two B modes).  The operand carries exact zeros there and the reference is the plain full
+    product: a k-tile skipped that should not be, or a tile computed for the wrong place, shows.  Sizes that are
+    multiples of 16 stage with 16-byte loads, the others end on a partial k-step.  No caller combines a mode with the
+    lower-tiles-only bit, so neither does this test."""
+    rng = np.random.default_rng(mode * 1000 + M + K)
+    A, B = _draw(kind, rng, M, K), _draw(kind, rng, K, N)
+    if mode == 1:
+        B = np.triu(B)                        # B(k, j) = 0 for k > j, stored as the lower-triangular Wk (B = Wk')
+        b_cm = False
+    elif mode == 2:
+        B = np.tril(B)                        # B(k, j) = 0 for k < j: a column-major lower-triangular factor
+        b_cm = True
+    else:
+        A = np.tril(A)                        # A(i, k) = 0 for k > i
+        b_cm = True
+    _, vA, sa = _place(A, True)
+    _, vB, sb = _place(B, b_cm)
+    tD, vD, sd = _place(np.zeros((M, N)), True)
+    before = _launches()
+    _gemm(M, N, K, vA, sa, vB, sb, vD, sd, lower=mode << 1)
+    _assert_ran(tile, before)
+    _same(kind, _fetch(tD, (M, N), True), A @ B, np.maximum(np.abs(A) @ np.abs(B), 1e-300), K)
+
+
+@pytest.mark.parametrize("kind", ["int", "normal"])
+@pytest.mark.parametrize("n,c0,k,R,tile", [(4374, 384, 896, 1024, 128), (4374, 384, 820, 1024, 128),
+                                           (5300, 896, 896, 100, 64), (5300, 4480, 820, 100, 64)])
+def test_gemm_column_block_of_a_triangular_factor(n, c0, k, R, tile, kind):
+    """One column block of the split product Y = L W (gss_lugs_realize): the operands are views into larger arrays,
+    A = L + c0 + c0 * n (rows c0 .. n - 1, columns c0 .. c0 + k - 1, lower triangular on the left), B = W + c0,
+    D = Y + c0, all with the leading dimension n of the whole.  Rows above c0 of Y are not touched."""
+    rng = np.random.default_rng(n + c0 + k)
+    L, W = np.tril(_draw(kind, rng, n, n)), _draw(kind, rng, n, R)
+    _, vL, sl = _place(L, True)
+    _, vW, sw = _place(W, True)
+    tY, vY, sy = _place(np.full((n, R), 7.0), True)
+    before = _launches()
+    _gemm(n - c0, R, k, vL[c0 + c0 * n:], sl, vW[c0:], sw, vY[c0:], sy, lower=4 << 1)
+    _assert_ran(tile, before)
+    Y = _fetch(tY, (n, R), True)
+    assert np.all(Y[:c0] == 7.0)
+    Ab, Bb = L[c0:, c0:c0 + k], W[c0:c0 + k]
+    _same(kind, Y[c0:], Ab @ Bb, np.maximum(np.abs(Ab) @ np.abs(Bb), 1e-300), k)
 
 
 @pytest.mark.parametrize("n", [1, 7, 64, 65, 200, 1000, 1537])

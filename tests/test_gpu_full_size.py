@@ -139,3 +139,53 @@ def test_large_data_set_global_universal_kriging():
     mu2 = h.predict_global(xd)[0].cpu().numpy()
     h.close()
     assert np.max(np.abs(mu2 - (2.0 - 0.3 * x0[:, 0] + 0.05 * x0[:, 1] + 0.7 * x0[:, 2]))) < 1e-8
+
+
+def test_config4_lugs_full_size_factor_and_split_product_against_lapack():
+    """configs[3] again (same grid, seed, data cells, variogram), now against LAPACK in full: the n_s = 12 288 factor
+    L22 and d2 (lu.jl:134-139 as oracle/lugs.py restates them) to the 1e-9 that tests/test_gpu_lugs.py holds for the
+    same quantities at smaller sizes, and 100 realisations from supplied normals -- the split product at the shape the
+    benchmark times (12 288 x 100, six column blocks of 2 048).  The 128-tile GEMM must have run inside the
+    factorisation (counter), so this is also where that kernel meets LAPACK inside a blocked Cholesky."""
+    import scipy.linalg as sla
+    import torch
+    import gss
+    from gss import _lib
+    from gss.engine import LUGSHandle
+    from oracle import fftgs as offt
+    from oracle.variogram import cov_pairwise
+    g = 128
+    cent = offt.grid_centroids((g, g))
+    N = g * g
+    rng = np.random.default_rng(5)
+    dl = np.sort(rng.permutation(N)[:4096])
+    z1 = rng.normal(size=4096)
+    n128 = _lib.stat("gemm_launches_128")
+    h = LUGSHandle(gss.SphericalVariogram(range=20.0), cent, dl, z1)
+    assert _lib.stat("gemm_launches_128") > n128
+    L22, d2 = h.factor()
+    w = np.random.default_rng(6).normal(size=(100, h.ns))
+    nprod = _lib.stat("gemm_launches_128") + _lib.stat("gemm_launches_64")
+    y, _ = h.realize(0, 0, 100, noise=torch.as_tensor(w, device="cuda"))
+    y = y.cpu().numpy()
+    assert _lib.stat("gemm_launches_128") + _lib.stat("gemm_launches_64") - nprod == 6     # six column blocks
+    h.close()
+    sl = np.setdiff1d(np.arange(N), dl)
+    ovg = Variogram("spherical", range=20.0)
+    L11 = np.linalg.cholesky(cov_pairwise(ovg, cent[dl]))
+    B = sla.solve_triangular(L11, cov_pairwise(ovg, cent[dl], cent[sl]), lower=True)
+    d2_ref = B.T @ sla.solve_triangular(L11, z1, lower=True)
+    S = cov_pairwise(ovg, cent[sl])
+    S -= B.T @ B
+    del B
+    L22_ref = np.linalg.cholesky(S)
+    del S
+    dL, dd = np.max(np.abs(L22 - L22_ref)), np.max(np.abs(d2 - d2_ref))
+    print("configs[3] factor: max |L22 - ref| %.3e, max |d2 - ref| %.3e" % (dL, dd))
+    assert not np.triu(L22, 1).any()
+    assert dL < 1e-9 and dd < 1e-9
+    ref = d2_ref[None, :] + w @ L22_ref.T
+    dy = np.max(np.abs(y[:, sl] - ref))
+    print("configs[3] realisations: max difference %.3e" % dy)
+    assert dy < 1e-9
+    assert np.array_equal(y[:, dl], np.tile(z1, (100, 1)))

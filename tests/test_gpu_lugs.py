@@ -274,3 +274,136 @@ def test_lu_factorization_matches_oracle(dims, ndata):
         ref, _ = O.lusim(p, noise[r])
         assert np.max(np.abs(y[r] - ref)) < 1e-9
     h.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# the split product of gss_lugs_realize (ns >= 4096 and at most 512 realisations in a block)
+# ---------------------------------------------------------------------------------------------
+_SPLIT_KW = dict(range=12.0, nugget=0.02)
+SPLIT_BOUND = 1e-13      # split against single product: measured 5.3e-15, see the test that uses it
+
+
+def _split_inputs():
+    """80 x 70 grid, 300 conditioning cells: ns = 5 300, six column blocks of 896, the last one 820 wide."""
+    cent = offt.grid_centroids((80, 70))
+    rng = np.random.default_rng(5300)
+    dlocs = np.sort(rng.choice(cent.shape[0], 300, replace=False))
+    return cent, dlocs, rng.normal(size=300)
+
+
+def _products():
+    from gss import _lib
+    return _lib.stat("gemm_launches_128") + _lib.stat("gemm_launches_64")
+
+
+def _realize_dev(h, w, **kw):
+    """Realisations from the normals `w` with every array on the device (one block, whatever the count), and the
+    number of matrix products the call launched: six for the split product, one without it."""
+    import torch
+    before = _products()
+    y, _ = h.realize(0, 0, w.shape[0], noise=torch.as_tensor(w, device="cuda"), **kw)
+    return y.cpu().numpy(), _products() - before
+
+
+@pytest.fixture(scope="module")
+def split_case():
+    from gss.engine import LUGSHandle
+    cent, dlocs, z1 = _split_inputs()
+    h = LUGSHandle(_mk("spherical", **_SPLIT_KW), cent, dlocs, z1)
+    p = O.preprocess(Variogram("spherical", **_SPLIT_KW), cent, cent[dlocs], z1)
+    assert h.ns == 5300 and np.array_equal(p.dlocs, dlocs)
+    yield h, p, cent, dlocs, z1
+    h.close()
+
+
+def test_split_product_factor_and_realisations_match_oracle(split_case):
+    h, p, cent, dlocs, z1 = split_case
+    L22, d2 = h.factor()
+    assert np.array_equal(np.triu(L22, 1), np.zeros_like(L22))
+    assert np.max(np.abs(L22 - p.L22)) < 1e-9 and np.max(np.abs(d2 - p.d2)) < 1e-9
+    rng = np.random.default_rng(11)
+    for R in (3, 100):
+        w = rng.normal(size=(R, h.ns))
+        y, nprod = _realize_dev(h, w)
+        assert nprod == 6                                              # the split product ran
+        for r in range(R):
+            ref, _ = O.lusim(p, w[r])
+            assert np.max(np.abs(y[r] - ref)) < 1e-9
+            assert np.array_equal(y[r][dlocs], z1)                     # lu.jl:217
+    # host arrays in and out, the library's own Philox normals
+    y2, w2 = h.realize(123, 5, 4)
+    ry, rw = O.realize(p, 123, 5, 4)
+    assert np.max(np.abs(w2 - rw)) < 1e-12 and np.max(np.abs(y2 - ry)) < 1e-9
+
+
+def test_split_product_cosimulation_matches_oracle(split_case):
+    from gss.engine import LUGSHandle
+    h1, p1, cent, dlocs, z1 = split_case
+    kw2 = dict(range=9.0, nugget=0.02)
+    z12 = np.random.default_rng(12).normal(size=dlocs.size)
+    h2 = LUGSHandle(_mk("exponential", **kw2), cent, dlocs, z12)
+    p2 = O.preprocess(Variogram("exponential", **kw2), cent, cent[dlocs], z12)
+    y1, w1 = h1.realize(7, 0, 4)
+    y2, w2 = h2.realize(8, 0, 4, rho=0.95, w1=w1)
+    h2.close()
+    ry1, rw1 = O.realize(p1, 7, 0, 4)
+    ry2, rw2 = O.realize(p2, 8, 0, 4, rho=0.95, w1=rw1)
+    assert np.max(np.abs(y1 - ry1)) < 1e-9 and np.max(np.abs(y2 - ry2)) < 1e-9
+    assert np.max(np.abs(w2 - rw2)) < 1e-12
+
+
+def test_split_product_against_the_single_product_and_repeatable(split_case):
+    """513 realisations in one block take the single product, 512 the split one: the first 512 of both, from the same
+    normals, differ by the order of summation only.  Measured on an MI355X: 5.3e-15 (values of order 1);
+    SPLIT_BOUND = 1e-13 is about an order of magnitude above that and far inside the 1e-11 it may not exceed.
+    The split product adds its partial results in a fixed order, so two identical calls agree bit for bit."""
+    h, p, cent, dlocs, z1 = split_case
+    w = np.random.default_rng(13).normal(size=(513, h.ns))
+    y513, n513 = _realize_dev(h, w)
+    y512, n512 = _realize_dev(h, w[:512])
+    assert (n513, n512) == (1, 6)
+    diff = np.max(np.abs(y513[:512] - y512))
+    print("split against single product: max difference %.3e" % diff)
+    assert diff < SPLIT_BOUND
+    ya, na = _realize_dev(h, w[:100])
+    yb, nb = _realize_dev(h, w[:100])
+    assert (na, nb) == (6, 6) and np.array_equal(ya, yb)
+
+
+@pytest.mark.parametrize("switch", ["GSS_LUGS_SPLITK", "GSS_POTRF_LOOKAHEAD"])
+def test_split_and_lookahead_switched_off_stay_alive(switch, split_case, tmp_path):
+    """GSS_LUGS_SPLITK=0 (one product instead of six column blocks) and GSS_POTRF_LOOKAHEAD=0 (the blocked Cholesky
+    without its helper stream) are read once per process: a child with the switch set factors the same problem and
+    realises from the same normals, and agrees with the oracle to the same 1e-9."""
+    import os
+    import subprocess
+    import sys
+    h, p, cent, dlocs, z1 = split_case
+    w = np.random.default_rng(14).normal(size=(2, h.ns))
+    yref = np.stack([O.lusim(p, w[r])[0] for r in range(2)])
+    np.savez(tmp_path / "case.npz", cent=cent, dlocs=dlocs, z1=z1, L22=p.L22, d2=p.d2, w=w, yref=yref)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (
+        "import sys\n"
+        "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "import numpy as np, torch, gss\n"
+        "from gss import _lib\n"
+        "from gss.engine import LUGSHandle\n"
+        "c = np.load(%r)\n"
+        "h = LUGSHandle(gss.SphericalVariogram(range=%r, nugget=%r), c['cent'], c['dlocs'], c['z1'])\n"
+        "L22, d2 = h.factor()\n"
+        "n0 = _lib.stat('gemm_launches_128') + _lib.stat('gemm_launches_64')\n"
+        "y, _ = h.realize(0, 0, 2, noise=torch.as_tensor(c['w'], device='cuda'))\n"
+        "n1 = _lib.stat('gemm_launches_128') + _lib.stat('gemm_launches_64')\n"
+        "print('CHILD %%.3e %%.3e %%.3e %%d' %% (np.max(np.abs(L22 - c['L22'])), np.max(np.abs(d2 - c['d2'])),\n"
+        "                                     np.max(np.abs(y.cpu().numpy() - c['yref'])), n1 - n0))\n"
+    ) % (root, os.path.join(root, "geostatssolvers.jl_amd"), str(tmp_path / "case.npz"), _SPLIT_KW["range"],
+         _SPLIT_KW["nugget"])
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **{switch: "0"}), capture_output=True,
+                       text=True, timeout=300)
+    line = [l for l in r.stdout.splitlines() if l.startswith("CHILD")]
+    assert r.returncode == 0 and line, (r.stdout[-500:], r.stderr[-2000:])
+    print(switch, line[0])
+    dl, dd, dy, nprod = line[0].split()[1:]
+    assert float(dl) < 1e-9 and float(dd) < 1e-9 and float(dy) < 1e-9
+    assert int(nprod) == (1 if switch == "GSS_LUGS_SPLITK" else 6)
