@@ -331,19 +331,15 @@ __global__ __launch_bounds__(256, 2) void krig_quadform_kernel(
   int buf = 0;  // LDS stage holding the operands of the stage about to be multiplied; runs on across row blocks
   for (int I = Ibeg; I < Iend; ++I) {
     const int i0 = I * BM;
-    const int kend = (i0 + BM < N1pad) ? i0 + BM : N1pad;
-    const int ntile = kend / BK;
-    // rows i0 .. N1 of this block carry data (row N1 = dual weights); 16-row tiles beyond them are zero padding
+    // rows i0 .. N1 of this block carry data (row N1 = dual weights); 16-row tiles beyond them are zero padding.
+    // N1pad = N1 + 1 rounded up to 16, so the block's k range ends with its last live tile: t0 + tm_max stages.
     const int tm_max = (N1 + 1 - i0 + 15) / 16 < 8 ? (N1 + 1 - i0 + 15) / 16 : 8;
+    const int t0 = i0 / BK;  // stages in front of the diagonal block
 
-    d4 accw[8][2];   // 1 x 4 wave layout: every wave sees all 128 rows (8 tiles) of 32 columns (2 tiles)
-#pragma unroll
-    for (int tm = 0; tm < 8; ++tm) accw[tm][0] = accw[tm][1] = d4{0.0, 0.0, 0.0, 0.0};
-
-    d2v ra[4], rb[4];
     const double* wp = W + (int64_t)kq * ldw + i0 + i2;
     const double* rp = R + (int64_t)kq * ldr + p0 + i2;
     if (I == Ibeg) {  // later row blocks find their first stage in LDS: the last stage of the block before fetched it
+      d2v ra[4], rb[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         ra[r] = *reinterpret_cast<const d2v*>(wp + (int64_t)(4 * r) * ldw);
@@ -357,63 +353,84 @@ __global__ __launch_bounds__(256, 2) void krig_quadform_kernel(
       __syncthreads();
     }
 
-    auto stage = [&](int t, auto guard) {
-      constexpr bool GUARD = decltype(guard)::value;
-      const int cur = buf;
-      const bool last = (t + 1) >= ntile;
-      const bool more = !last || (I + 1 < Iend);
-      if (more) {
-        // next stage of this row block, or stage 0 of the next one (same strip of R from k = 0, rows i0 + BM.. of W)
-        const double* wq = last ? wp + BM : wp + (int64_t)(t + 1) * BK * ldw;
-        const double* rq = last ? rp : rp + (int64_t)(t + 1) * BK * ldr;
+    // The row block with its live-tile count as a constant: t0 full stages, then the TM_MAX stages of the diagonal
+    // block, stage s touching row tiles s .. TM_MAX - 1 only (k > i0 + 16 s meets zeros of W' above them).  Every
+    // stage is straight-line MFMA code; the bounds cost neither branches nor dead LDS reads.
+    auto row_block = [&](auto tmx) __attribute__((always_inline)) {
+      constexpr int TM_MAX = decltype(tmx)::value;
+      d4 accw[8][2];   // 1 x 4 wave layout: every wave sees all 128 rows (8 tiles) of 32 columns (2 tiles)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          ra[r] = *reinterpret_cast<const d2v*>(wq + (int64_t)(4 * r) * ldw);
-          rb[r] = *reinterpret_cast<const d2v*>(rq + (int64_t)(4 * r) * ldr);
-        }
-      }
-      {
-        // stages inside the diagonal block (k > i0) only touch row tiles tm >= (k - i0) / 16
-        const int tmn = (t * BK - i0) >> 4;
-        mma_stage_w14<GUARD>(As + cur * TILE_LDS, Bs + cur * TILE_LDS, accw, wave, lane, tmn > 0 ? tmn : 0, tm_max);
-      }
-      if (more) {
-        double* an = As + (cur ^ 1) * TILE_LDS;
-        double* bn = Bs + (cur ^ 1) * TILE_LDS;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          *reinterpret_cast<d2v*>(an + (kq + 4 * r) * LDS_LD + i2) = ra[r];
-          *reinterpret_cast<d2v*>(bn + (kq + 4 * r) * LDS_LD + i2) = rb[r];
-        }
-      }
-      __syncthreads();
-      buf ^= 1;
-    };
-    {
-      const int tdiag = (i0 / BK + 1) < ntile ? (i0 / BK + 1) : ntile;
-      if (tm_max < 8) {  // last row block: its bottom row tiles are padding, every stage is guarded
-        for (int t = 0; t < ntile; ++t) stage(t, std::true_type{});
-      } else {
-        for (int t = 0; t < tdiag; ++t) stage(t, std::false_type{});
-        for (int t = tdiag; t < ntile; ++t) stage(t, std::true_type{});
-      }
-    }
+      for (int tm = 0; tm < TM_MAX; ++tm) accw[tm][0] = accw[tm][1] = d4{0.0, 0.0, 0.0, 0.0};
 
-    // signed squares: rows < n count +, constraint rows n..N1-1 count -, padding rows are zero
+      auto stage = [&](int t, auto tmn, auto is_last) __attribute__((always_inline)) {
+        constexpr int TM_MIN = decltype(tmn)::value;
+        constexpr bool last = decltype(is_last)::value;
+        const int cur = buf;
+        const bool more = !last || (I + 1 < Iend);
+        d2v ra[4], rb[4];
+        if (more) {
+          // next stage of this row block, or stage 0 of the next one (same strip of R from k = 0, rows i0 + BM.. of W)
+          const double* wq = last ? wp + BM : wp + (int64_t)(t + 1) * BK * ldw;
+          const double* rq = last ? rp : rp + (int64_t)(t + 1) * BK * ldr;
 #pragma unroll
-    for (int tn = 0; tn < 2; ++tn) {
-      double s = 0.0;
-#pragma unroll
-      for (int tm = 0; tm < 8; ++tm)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = i0 + tm * 16 + lk + 4 * r;
-          const double v = accw[tm][tn][r];
-          const double vv = v * v;
-          s += (row < n) ? vv : (row < N1 ? -vv : 0.0);
-          if (row == N1) macc[tn] += v;
+          for (int r = 0; r < 4; ++r) {
+            ra[r] = *reinterpret_cast<const d2v*>(wq + (int64_t)(4 * r) * ldw);
+            rb[r] = *reinterpret_cast<const d2v*>(rq + (int64_t)(4 * r) * ldr);
+          }
         }
-      qacc[tn] += s;
+        mma_stage_w14<TM_MIN, TM_MAX>(As + cur * TILE_LDS, Bs + cur * TILE_LDS, accw, wave, lane);
+        if (more) {
+          double* an = As + (cur ^ 1) * TILE_LDS;
+          double* bn = Bs + (cur ^ 1) * TILE_LDS;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            *reinterpret_cast<d2v*>(an + (kq + 4 * r) * LDS_LD + i2) = ra[r];
+            *reinterpret_cast<d2v*>(bn + (kq + 4 * r) * LDS_LD + i2) = rb[r];
+          }
+        }
+        __syncthreads();
+        buf ^= 1;
+      };
+      for (int t = 0; t < t0; ++t) stage(t, std::integral_constant<int, 0>{}, std::false_type{});
+#define GSS_K3_DIAG_STAGE(S) \
+  if constexpr (S < TM_MAX) stage(t0 + S, std::integral_constant<int, S>{}, std::bool_constant<S + 1 == TM_MAX>{})
+      GSS_K3_DIAG_STAGE(0);
+      GSS_K3_DIAG_STAGE(1);
+      GSS_K3_DIAG_STAGE(2);
+      GSS_K3_DIAG_STAGE(3);
+      GSS_K3_DIAG_STAGE(4);
+      GSS_K3_DIAG_STAGE(5);
+      GSS_K3_DIAG_STAGE(6);
+      GSS_K3_DIAG_STAGE(7);
+#undef GSS_K3_DIAG_STAGE
+
+      // signed squares: rows < n count +, constraint rows n..N1-1 count -, padding rows are zero
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) {
+        double s = 0.0;
+#pragma unroll
+        for (int tm = 0; tm < TM_MAX; ++tm)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = i0 + tm * 16 + lk + 4 * r;
+            const double v = accw[tm][tn][r];
+            const double vv = v * v;
+            s += (row < n) ? vv : (row < N1 ? -vv : 0.0);
+            if (row == N1) macc[tn] += v;
+          }
+        qacc[tn] += s;
+      }
+    };
+    // only the last row block can have fewer than 8 live tiles
+    switch (tm_max) {
+      case 1: row_block(std::integral_constant<int, 1>{}); break;
+      case 2: row_block(std::integral_constant<int, 2>{}); break;
+      case 3: row_block(std::integral_constant<int, 3>{}); break;
+      case 4: row_block(std::integral_constant<int, 4>{}); break;
+      case 5: row_block(std::integral_constant<int, 5>{}); break;
+      case 6: row_block(std::integral_constant<int, 6>{}); break;
+      case 7: row_block(std::integral_constant<int, 7>{}); break;
+      default: row_block(std::integral_constant<int, 8>{}); break;
     }
   }
 

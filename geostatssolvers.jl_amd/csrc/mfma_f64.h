@@ -48,14 +48,18 @@ __device__ __forceinline__ void mma_stage(const double* __restrict__ As, const d
 // 1 x 4 wave arrangement for triangular operands: every wave owns all 128 rows of the workgroup tile and 32 of
 // its columns (8 x 2 MFMA tiles, still 128 accumulator VGPRs).  All waves then see the same rows, so the zero
 // 16-row tiles of a lower-triangular A can be skipped uniformly: in the stage that covers k = i0 + 16 s .. + 15
-// of the diagonal block only row tiles tm >= s are non-zero (tm_min = s; 0 for ordinary stages).
+// of the diagonal block only row tiles tm >= s are non-zero (TM_MIN = s; 0 for ordinary stages).
 // Measured alternative, kept out of the build: the 4-block form v_mfma_f64_4x4x4_4b_f64 (lane maps
 // A = 16k + 4b + i, B = 16k + 4b + j, D = 16i + 4b + j, tools/probe_mfma4x4.hip) runs this kernel at the same
 // rate as the 16x16x4 form although it is 1.5x faster in a register-only loop (tools/probe_f64.hip).
-// tm_max < 8: row tiles tm >= tm_max lie entirely in the zero padding below the last row of the operand.
-template <bool GUARD>
+// Both bounds are compile-time: a stage reads the A fragments of its live row tiles TM_MIN <= tm < TM_MAX only and
+// issues their MFMAs as straight-line code, without a branch or an exec-mask change between them.  TM_MAX < 8: row
+// tiles tm >= TM_MAX lie entirely in the zero padding below the last row of the operand (last row block).  Every
+// accumulator sees its k in ascending order whatever the bounds, and the products left out are exact zeros.
+template <int TM_MIN, int TM_MAX>
 __device__ __forceinline__ void mma_stage_w14(const double* __restrict__ As, const double* __restrict__ Bs,
-                                              d4 (&acc)[8][2], int wave, int lane, int tm_min, int tm_max = 8) {
+                                              d4 (&acc)[8][2], int wave, int lane) {
+  static_assert(0 <= TM_MIN && TM_MIN < TM_MAX && TM_MAX <= 8, "live row tiles of a 128-row block");
   const int lr = lane & 15;
   const int lk = lane >> 4;
 #pragma unroll
@@ -65,13 +69,11 @@ __device__ __forceinline__ void mma_stage_w14(const double* __restrict__ As, con
     const double b0 = bp[0], b1 = bp[16];
     double a[8];
 #pragma unroll
-    for (int tm = 0; tm < 8; ++tm) a[tm] = ap[tm * 16];
+    for (int tm = TM_MIN; tm < TM_MAX; ++tm) a[tm] = ap[tm * 16];
 #pragma unroll
-    for (int tm = 0; tm < 8; ++tm) {
-      if (!GUARD || (tm >= tm_min && tm < tm_max)) {
-        acc[tm][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b0, acc[tm][0], 0, 0, 0);
-        acc[tm][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b1, acc[tm][1], 0, 0, 0);
-      }
+    for (int tm = TM_MIN; tm < TM_MAX; ++tm) {
+      acc[tm][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b0, acc[tm][0], 0, 0, 0);
+      acc[tm][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b1, acc[tm][1], 0, 0, 0);
     }
   }
 }
