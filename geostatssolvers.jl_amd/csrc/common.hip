@@ -819,6 +819,7 @@ int32_t gss_init(int32_t device) {
 int32_t gss_shutdown(void) {
   GSS_ENTRY();
   free_bounce_buffers();
+  vario_release();
   std::lock_guard<std::mutex> lock(g_pool_mu);
   for (auto& b : g_pool) (void)hipFree(b.p);
   g_pool.clear();
@@ -893,6 +894,12 @@ int32_t gss_stat(const char* name, int64_t* value) {
     *value = gemm_launches(64);
   } else if (!std::strcmp(name, "ipc_route")) {
     *value = comm_last_ipc_route();   // of the last gss_state_ipc_import: 0 same device, 1 peer, 2 not visible, 3 refused
+  } else if (!std::strncmp(name, "vario_", 6)) {
+    std::lock_guard<std::recursive_mutex> lock(api_mutex());   // the counters belong to the last call
+    const int32_t rc = vario_stat(name, value);
+    if (rc >= 0) return rc;
+    set_error("gss_stat: unknown counter '%s'", name);
+    return GSS_ERR_INVALID;
   } else {
     set_error("gss_stat: unknown counter '%s'", name);
     return GSS_ERR_INVALID;

@@ -1016,6 +1016,16 @@ struct Searcher {
                bool indexed, const double* lowd, const int* lowi);
 };
 
+// the k-d ordering and the boxes of KnnIndex built on the device (knn_build.hip); synchronises s
+int32_t knn_index_build_device(const double* xdev, int64_t n, int dim, KnnIndex* ix, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// variography (variography.hip)
+// ---------------------------------------------------------------------------------------------
+// gss_stat counters "vario_tiles_total" / "vario_tiles_opened" of the last gss_variogram_empirical; -1: not one of them
+int32_t vario_stat(const char* name, int64_t* value);
+void vario_release();   // gss_shutdown: the page-locked counter and its event
+
 // ---------------------------------------------------------------------------------------------
 // noise (noise.hip)
 // ---------------------------------------------------------------------------------------------

@@ -1,0 +1,907 @@
+// K7: empirical variograms on the device (gss_variogram_empirical) and the model fit (gss_variogram_fit, host code).
+// Replaces [DEP] Variography's EmpiricalVariogram / DirectionalVariogram / fit -- the step that produces the
+// `variogram=` parameter every solver takes.  The conventions are the library's own (include/gss.h).
+//
+// Layout.  The samples are put in a space-filling order -- the Searcher's k-d order (knn_build.hip) from 32 768 samples,
+// one sort by Morton key below that, where the level-by-level build would cost as much as the pair pass: batches of 64
+// consecutive points with a bounding box each.  A tile is a pair of batches (I, J), I <= J: 64 x 64 sample pairs, the lower triangle only when
+// I == J.  One wave works on one tile at a time: lane = point of batch J (coordinates and values in registers), the
+// points of batch I are wave uniform and arrive through the scalar cache -- the operand layout of K1 (cov_kernels.hip).
+//
+// Work units are (batch I, 16 consecutive batches J -- 4 for small sets); the waves of a persistent grid draw them from
+// one counter (one global atomic per unit of up to 65 536 pairs, per run of up to 64 units on large sets), so no round of workgroups waits for a straggler and the empty half of
+// the triangle costs a comparison per unit.  In a unit, lanes 0..15 each bound one tile: the box-to-box lower bound of
+// the squared distance, accumulated with the rounded operations of the pair key itself, so it never exceeds a real
+// pair's key; a tile whose bound lies beyond the last bin edge is never opened, and the results cannot depend on that.
+//
+// Accumulation.  Pairs of one tile fall into few neighbouring bins, all of them at or above the bin of the tile's lower
+// bound.  Every lane therefore keeps a window of VW consecutive bins, starting at that bin, in registers (count, sum of
+// h, sums per value column: selected with an exact 0 / 1 factor); the rare pair beyond the window goes to the
+// workgroup's histogram in LDS with one LDS atomic per quantity.  After the tile the window is flushed to the same
+// histogram.  At the end each workgroup writes its histogram to its own slice of a scratch array and a second kernel adds
+// the slices in workgroup order: no global atomic per pair, 64-bit integer counts that do not depend on the schedule.
+#include "gss_internal.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+namespace gss {
+
+namespace {
+
+constexpr int VARIO_MAX_LAGS = 256;
+constexpr int VARIO_MAX_NZ = 8;
+constexpr int VARIO_JW_MAX = 16;   // tiles per work unit: 16, or 4 when there are few batches (more, smaller units)
+constexpr int VARIO_THREADS = 256;
+
+struct VarioArgs {
+  int64_t n;
+  int nb;
+  int jw;               // tiles per unit
+  int nchunks;          // ceil(nb / jw)
+  int grab;             // units a wave draws per atomic (large sets: the counter must not become the bottleneck)
+  int nlags;
+  int estimator;
+  int directional;
+  int nocull;
+  double delta, inv_delta;
+  double u[3];
+  double dtol2, cos2;
+};
+
+// the pair key: ((D0 D0) + (D1 D1)) + (D2 D2), one rounding per operation
+template <int DIM>
+__device__ __forceinline__ double vario_d2(const double* a, const double* b, double* delta) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) {
+    const double t = a[k] - b[k];
+    delta[k] = t;
+    const double tt = t * t;
+    acc = k == 0 ? tt : acc + tt;
+  }
+  return acc;
+}
+
+// lower bound of vario_d2 over two boxes: per axis the gap max(loA - hiB, loB - hiA, 0) never exceeds |a - b| for
+// points inside (rounded subtraction is monotone and antisymmetric), and squares and sums are accumulated as above
+template <int DIM>
+__device__ __forceinline__ double vario_box_d2(const double* loa, const double* hia, const double* lob,
+                                               const double* hib) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) {
+    const double g1 = loa[k] - hib[k], g2 = lob[k] - hia[k];
+    double t = g1 > g2 ? g1 : g2;
+    t = t > 0.0 ? t : 0.0;
+    const double tt = t * t;
+    acc = k == 0 ? tt : acc + tt;
+  }
+  return acc;
+}
+
+// bin k with edge2[k] < d2 <= edge2[k + 1], for 0 < d2 <= edge2[nlags]; h = sqrt(d2).  The quotient h / delta places
+// the pair within one bin of the right one (its error is a few ulp, a bin is at least 1 / 256 of the range); the two
+// comparisons on d2 decide.
+__device__ __forceinline__ int vario_bin(const double* edge2, int nlags, double d2, double h, double inv_delta) {
+  int k = (int)(h * inv_delta);
+  k = k < 0 ? 0 : (k > nlags - 1 ? nlags - 1 : k);
+  const double e0 = edge2[k], e1 = edge2[k + 1];
+  k += (d2 > e1 ? 1 : 0) - (d2 <= e0 ? 1 : 0);   // both edges are read: no divergent branch around the second
+  return k < 0 ? 0 : (k > nlags - 1 ? nlags - 1 : k);
+}
+
+__device__ __forceinline__ void lds_add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
+
+template <int DIM, int NZ, bool CRESSIE>
+__global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
+    const double* __restrict__ xs,      // n x DIM, k-d order
+    const double* __restrict__ zs,      // NZ columns of n, k-d order
+    const double* __restrict__ blo,     // nb x DIM batch boxes
+    const double* __restrict__ bhi,
+    VarioArgs A, unsigned long long* __restrict__ unit_counter,
+    unsigned long long* __restrict__ partial) {   // per workgroup: cnt[nlags], ndup, opened, hsum[nlags], zsum[NZ nlags]
+  constexpr int VW = NZ <= 2 ? 6 : 4;   // bins of the register window
+  extern __shared__ double smem[];
+  const int nlags = A.nlags;
+  double* s_edge = smem;                                                  // nlags + 1
+  unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + nlags + 1);   // nlags + 2 (ndup, opened)
+  double* s_h = smem + 2 * nlags + 3;                                     // nlags
+  double* s_z = s_h + nlags;                                              // NZ * nlags
+  const int nwords = (nlags + 2) + nlags + NZ * nlags;                    // what is flushed: s_cnt onwards
+  // squared bin edges edge2[k] = fl(fl(k delta)^2): two rounded products of exactly represented operands, the same
+  // doubles on every workgroup and on the host
+  for (int t = threadIdx.x; t <= nlags; t += VARIO_THREADS) {
+    const double e = mul_rounded((double)t, A.delta);
+    s_edge[t] = mul_rounded(e, e);
+  }
+  for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) s_cnt[t] = 0ull;   // +0.0 is all-zero bits
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const double emax2 = s_edge[nlags];
+  const int64_t n = A.n;
+  const unsigned long long nunits = (unsigned long long)A.nb * (unsigned long long)A.nchunks;
+  unsigned long long ndup = 0ull, opened = 0ull;
+
+  unsigned long long unext = 0ull, uend = 0ull;
+  while (true) {
+    if (unext == uend) {
+      unsigned long long u0 = 0ull;
+      if (lane == 0) u0 = atomicAdd(unit_counter, (unsigned long long)A.grab);
+      unext = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u0 >> 32)) << 32) |
+              (unsigned)__builtin_amdgcn_readfirstlane((int)u0);
+      if (unext >= nunits) break;
+      uend = unext + (unsigned long long)A.grab < nunits ? unext + (unsigned long long)A.grab : nunits;
+    }
+    const unsigned long long u = unext++;
+    const int I = (int)(u / (unsigned)A.nchunks);
+    const int J0 = (int)(u % (unsigned)A.nchunks) * A.jw;
+    if (J0 + A.jw - 1 < I) continue;   // the empty half of the triangle
+
+    // lanes 0..15: bound of tile (I, J0 + lane)
+    const int Jl = J0 + lane;
+    bool cand = lane < A.jw && Jl >= I && Jl < A.nb;
+    double lb = 0.0;
+    if (cand) {
+      double loa[DIM], hia[DIM], lob[DIM], hib[DIM];
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        loa[a] = blo[(int64_t)I * DIM + a];
+        hia[a] = bhi[(int64_t)I * DIM + a];
+        lob[a] = blo[(int64_t)Jl * DIM + a];
+        hib[a] = bhi[(int64_t)Jl * DIM + a];
+      }
+      lb = vario_box_d2<DIM>(loa, hia, lob, hib);
+      cand = A.nocull || lb <= emax2;
+    }
+    unsigned long long open = __ballot(cand);
+    opened += (unsigned long long)__popcll(open);
+
+    const int ni = (int64_t)I * 64 + 64 <= n ? 64 : (int)(n - (int64_t)I * 64);
+    while (open) {
+      const int pick = __builtin_ctzll(open);
+      open &= open - 1;
+      const int J = J0 + pick;
+      const double lbJ = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lb), pick),
+                                          __builtin_amdgcn_readlane(__double2loint(lb), pick));
+      // first bin any pair of this tile can fall into (wave uniform)
+      int kb = 0;
+      if (lbJ > 0.0 && lbJ <= emax2) kb = vario_bin(s_edge, nlags, lbJ, gss_sqrt(lbJ), A.inv_delta);
+      kb = __builtin_amdgcn_readfirstlane(kb);
+      const bool diag = I == J;
+
+      const int64_t j = (int64_t)J * 64 + lane;
+      const bool vj = j < n;
+      const int64_t jc = vj ? j : n - 1;
+      double xj[DIM], zj[NZ];
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) xj[a] = xs[jc * DIM + a];
+#pragma unroll
+      for (int c = 0; c < NZ; ++c) zj[c] = zs[(int64_t)c * n + jc];
+
+      unsigned int wc[VW];
+      double wh[VW], wz[NZ][VW];
+#pragma unroll
+      for (int w = 0; w < VW; ++w) {
+        wc[w] = 0u;
+        wh[w] = 0.0;
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) wz[c][w] = 0.0;
+      }
+
+#pragma unroll 2
+      for (int ii = 0; ii < ni; ++ii) {
+        const int64_t i = (int64_t)I * 64 + ii;   // wave uniform: scalar loads
+        double xi[DIM], dl[DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) xi[a] = xs[i * DIM + a];
+        const double d2 = vario_d2<DIM>(xi, xj, dl);
+        const bool pairok = vj && (!diag || ii < lane);
+        ndup += (pairok && d2 == 0.0) ? 1ull : 0ull;
+        bool keep = pairok && d2 > 0.0 && d2 <= emax2;
+        if (A.directional) {
+#pragma clang fp contract(off)
+          double t = dl[0] * A.u[0];
+          if (DIM > 1) t = t + dl[1] * A.u[1];
+          if (DIM > 2) t = t + dl[2] * A.u[2];
+          const double tt = t * t;
+          const double p2 = d2 - tt;
+          const double cd = A.cos2 * d2;
+          keep = keep && p2 <= A.dtol2 && tt >= cd;
+        }
+        const double h = gss_sqrt(d2);
+        const int k = vario_bin(s_edge, nlags, d2, h, A.inv_delta);
+        const int w = keep ? k - kb : -1;
+        double val[NZ];
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) {
+          const double dz = zs[(int64_t)c * n + i] - zj[c];
+          val[c] = CRESSIE ? gss_sqrt(fabs(dz)) : mul_rounded(dz, dz);
+        }
+#pragma unroll
+        for (int s = 0; s < VW; ++s) {
+          const bool m = w == s;
+          const double mf = m ? 1.0 : 0.0;   // exact selector: fma(1, v, acc) = acc + v rounded once, fma(0, v, acc) = acc
+          wc[s] += m ? 1u : 0u;
+          wh[s] = fma(mf, h, wh[s]);
+#pragma unroll
+          for (int c = 0; c < NZ; ++c) wz[c][s] = fma(mf, val[c], wz[c][s]);
+        }
+        if (keep && (unsigned)w >= (unsigned)VW) {   // beyond the window: straight to the workgroup's histogram
+          atomicAdd(&s_cnt[k], 1ull);
+          lds_add_f64(&s_h[k], h);
+#pragma unroll
+          for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nlags + k], val[c]);
+        }
+      }
+      // flush the window (bins kb .. kb + VW - 1, those that exist)
+#pragma unroll
+      for (int s = 0; s < VW; ++s) {
+        if (wc[s] != 0u) {
+          const int k = kb + s;   // wc > 0 only for a real bin
+          atomicAdd(&s_cnt[k], (unsigned long long)wc[s]);
+          lds_add_f64(&s_h[k], wh[s]);
+#pragma unroll
+          for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nlags + k], wz[c][s]);
+        }
+      }
+    }
+  }
+  if (ndup) atomicAdd(&s_cnt[nlags], ndup);
+  if (lane == 0 && opened) atomicAdd(&s_cnt[nlags + 1], opened);
+  __syncthreads();
+  unsigned long long* out = partial + (size_t)blockIdx.x * nwords;
+  for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) out[t] = s_cnt[t];
+}
+
+// Sum of the workgroup slices, one workgroup per output word: thread j adds the slices j, j + 256, ... in ascending
+// order, then the 256 partial sums are folded pairwise in a fixed pattern -- the integer totals are exact and the
+// floating-point ones depend only on which pairs each workgroup of the pair kernel drew.
+__global__ __launch_bounds__(256) void vario_reduce_kernel(const unsigned long long* __restrict__ partial, int nwg,
+                                                           int nlags, int nz, int64_t* __restrict__ count,
+                                                           double* __restrict__ lagsum, double* __restrict__ zsum,
+                                                           int64_t* __restrict__ ndup, int64_t* __restrict__ stats,
+                                                           const int* __restrict__ bad) {
+  __shared__ unsigned long long su[256];
+  __shared__ double sd[256];
+  const int nwords = (nlags + 2) + nlags + nz * nlags;
+  const int t = blockIdx.x;   // < nwords
+  const bool integer = t < nlags + 2;
+  unsigned long long au = 0ull;
+  double ad = 0.0;
+  for (int g = threadIdx.x; g < nwg; g += 256) {
+    const unsigned long long v = partial[(size_t)g * nwords + t];
+    if (integer) au += v;
+    else ad += __longlong_as_double((long long)v);
+  }
+  su[threadIdx.x] = au;
+  sd[threadIdx.x] = ad;
+  __syncthreads();
+  for (int w = 128; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      su[threadIdx.x] += su[threadIdx.x + w];
+      sd[threadIdx.x] += sd[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const bool poisoned = *bad != 0;   // a non-finite input: counts and *ndup = -1, sums NaN (gss.h)
+  if (integer) {
+    if (t < nlags) count[t] = poisoned ? -1 : (int64_t)su[0];
+    else if (t == nlags) *ndup = poisoned ? -1 : (int64_t)su[0];
+    else stats[0] = (int64_t)su[0];
+  } else {
+    const double v = poisoned ? __longlong_as_double(0x7ff8000000000000LL) : sd[0];
+    const int q = t - (nlags + 2);
+    if (q < nlags) lagsum[q] = v;
+    else zsum[q - nlags] = v;
+  }
+}
+
+// *bad is set when a coordinate or a value is not finite (before anything is ordered by them)
+__global__ __launch_bounds__(256) void vario_check_kernel(const double* __restrict__ x, const double* __restrict__ z,
+                                                          int64_t nx, int64_t nzv, int* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool ok = (i >= nx || isfinite(x[i])) && (i >= nzv || isfinite(z[i]));
+  if (!ok) *bad = 1;
+}
+
+// values into the order of the index
+__global__ __launch_bounds__(256) void vario_gather_kernel(const double* __restrict__ z, const int* __restrict__ perm,
+                                                           int64_t n, int nz, double* __restrict__ zs) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int p = perm[i];
+  for (int c = 0; c < nz; ++c) zs[(int64_t)c * n + i] = z[(int64_t)c * n + p];
+}
+
+// ---- ordering of small sets: one sort by Morton key ------------------------------------------------------------------
+// Below VARIO_KD_MIN samples the level-by-level k-d ordering of the search index (a radix sort and a bounding-box pass
+// per level, and a wait for the stream) costs as much as the pair pass itself.  Such a set is ordered by ONE radix sort
+// of 30-bit Morton keys on its bounding box instead; the batches of 64 and their boxes are formed from that order in the
+// same arrays (KnnIndex xs / perm / lo / hi).  Any order gives the same counts; a compact one keeps a tile's pairs in
+// few bins.  Everything is queued on the stream, nothing waits.
+constexpr int64_t VARIO_KD_MIN = 32768;
+
+__device__ __forceinline__ unsigned long long vario_f64_key(double v) {   // monotone image of a double
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double vario_key_f64(unsigned long long k) {
+  const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)b);
+}
+
+// box[0..2] = min, box[3..5] = max as monotone keys; also clears the unit counter and the bad-value flag
+__global__ void vario_init_kernel(unsigned long long* __restrict__ box, unsigned long long* __restrict__ flags) {
+  if (threadIdx.x < 3) box[threadIdx.x] = ~0ull;
+  else if (threadIdx.x < 6) box[threadIdx.x] = 0ull;
+  else if (threadIdx.x < 8) flags[threadIdx.x - 6] = 0ull;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void vario_bbox_kernel(const double* __restrict__ x, int64_t n,
+                                                         unsigned long long* __restrict__ box) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t ic = i < n ? i : n - 1;
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) {
+    unsigned long long lo = vario_f64_key(x[ic * DIM + a]), hi = lo;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const unsigned long long l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+      lo = l2 < lo ? l2 : lo;
+      hi = h2 > hi ? h2 : hi;
+    }
+    if ((threadIdx.x & 63) == 0) {
+      atomicMin(&box[a], lo);
+      atomicMax(&box[3 + a], hi);
+    }
+  }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void vario_morton_kernel(const double* __restrict__ x, int64_t n,
+                                                           const unsigned long long* __restrict__ box,
+                                                           unsigned int* __restrict__ key, int* __restrict__ val) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  constexpr int BITS = 30 / DIM;
+  unsigned int q[DIM];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) {
+    const double lo = vario_key_f64(box[a]), ext = vario_key_f64(box[3 + a]) - lo;
+    const double t = ext > 0.0 ? (x[i * DIM + a] - lo) / ext * (double)(1u << BITS) : 0.0;
+    q[a] = t >= (double)((1u << BITS) - 1u) ? (1u << BITS) - 1u : (t > 0.0 ? (unsigned int)t : 0u);
+  }
+  unsigned int k = 0u;
+#pragma unroll
+  for (int b = 0; b < BITS; ++b) {
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) k |= ((q[a] >> b) & 1u) << (b * DIM + a);
+  }
+  key[i] = k;
+  val[i] = (int)i;
+}
+
+// ordered coordinates and the box of every batch of 64: one wave per batch
+template <int DIM>
+__global__ __launch_bounds__(256) void vario_batches_kernel(const double* __restrict__ x, const int* __restrict__ perm,
+                                                            int64_t n, int nb, double* __restrict__ xs,
+                                                            double* __restrict__ blo, double* __restrict__ bhi) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= nb) return;   // whole wave
+  const int64_t j = (int64_t)b * 64 + lane;
+  const int64_t jc = j < n ? j : n - 1;   // a clamped duplicate does not change the box
+  const int p = perm[jc];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) {
+    const double v = x[(int64_t)p * DIM + a];
+    if (j < n) xs[j * DIM + a] = v;
+    double lo = v, hi = v;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const double l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+      lo = l2 < lo ? l2 : lo;
+      hi = h2 > hi ? h2 : hi;
+    }
+    if (lane == 0) {
+      blo[(int64_t)b * DIM + a] = lo;
+      bhi[(int64_t)b * DIM + a] = hi;
+    }
+  }
+}
+
+template <int DIM>
+int32_t vario_morton_index(const double* xdev, int64_t n, unsigned long long* box, KnnIndex* ix, hipStream_t s) {
+  const int nb = (int)((n + 63) / 64);
+  const dim3 gn((unsigned)((n + 255) / 256));
+  DevBuf k0, k1, v0, tmp;
+  GSS_TRY(k0.alloc(sizeof(unsigned int) * (size_t)n));
+  GSS_TRY(k1.alloc(sizeof(unsigned int) * (size_t)n));
+  GSS_TRY(v0.alloc(sizeof(int) * (size_t)n));
+  GSS_TRY(ix->perm.alloc(sizeof(int) * (size_t)n));
+  GSS_TRY(ix->xs.alloc(sizeof(double) * (size_t)n * DIM));
+  GSS_TRY(ix->lo.alloc(sizeof(double) * (size_t)nb * DIM));
+  GSS_TRY(ix->hi.alloc(sizeof(double) * (size_t)nb * DIM));
+  hipLaunchKernelGGL(vario_bbox_kernel<DIM>, gn, dim3(256), 0, s, xdev, n, box);
+  hipLaunchKernelGGL(vario_morton_kernel<DIM>, gn, dim3(256), 0, s, xdev, n, box, k0.as<unsigned int>(), v0.as<int>());
+  GSS_HIP(hipGetLastError());
+  size_t tb = 0;
+  GSS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0.as<unsigned int>(), k1.as<unsigned int>(), v0.as<int>(),
+                                             ix->perm.as<int>(), (int)n, 0, 30, s));
+  GSS_TRY(tmp.alloc(tb));
+  GSS_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, k0.as<unsigned int>(), k1.as<unsigned int>(), v0.as<int>(),
+                                             ix->perm.as<int>(), (int)n, 0, 30, s));
+  hipLaunchKernelGGL(vario_batches_kernel<DIM>, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, xdev, ix->perm.as<int>(),
+                     n, nb, ix->xs.as<double>(), ix->lo.as<double>(), ix->hi.as<double>());
+  GSS_HIP(hipGetLastError());
+  ix->n = n;
+  ix->nb = nb;
+  ix->nb1 = 0;
+  ix->dim = DIM;
+  return GSS_OK;   // (the sort buffers return to the block cache: their re-use is ordered behind this stream)
+}
+
+struct VarioPtrs {
+  const double *xs, *zs, *lo, *hi;
+  unsigned long long *unit_counter, *partial;
+};
+
+// nwg == 0: *resident = workgroups of this instantiation that fit one CU at a time (nothing is launched)
+template <int DIM, int NZ>
+int32_t vario_launch_nz(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds, hipStream_t s, int* resident) {
+  if (nwg == 0) {
+    if (A.estimator == GSS_VARIO_CRESSIE)
+      GSS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, vario_pairs_kernel<DIM, NZ, true>, VARIO_THREADS, lds));
+    else
+      GSS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, vario_pairs_kernel<DIM, NZ, false>, VARIO_THREADS, lds));
+    return GSS_OK;
+  }
+  if (A.estimator == GSS_VARIO_CRESSIE)
+    hipLaunchKernelGGL((vario_pairs_kernel<DIM, NZ, true>), dim3((unsigned)nwg), dim3(VARIO_THREADS), lds, s, P.xs, P.zs,
+                       P.lo, P.hi, A, P.unit_counter, P.partial);
+  else
+    hipLaunchKernelGGL((vario_pairs_kernel<DIM, NZ, false>), dim3((unsigned)nwg), dim3(VARIO_THREADS), lds, s, P.xs, P.zs,
+                       P.lo, P.hi, A, P.unit_counter, P.partial);
+  GSS_HIP(hipGetLastError());
+  return GSS_OK;
+}
+
+template <int DIM>
+int32_t vario_launch(const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
+                     int* resident) {
+  switch (nz) {
+    case 1: return vario_launch_nz<DIM, 1>(P, A, nwg, lds, s, resident);
+    case 2: return vario_launch_nz<DIM, 2>(P, A, nwg, lds, s, resident);
+    case 3: return vario_launch_nz<DIM, 3>(P, A, nwg, lds, s, resident);
+    case 4: return vario_launch_nz<DIM, 4>(P, A, nwg, lds, s, resident);
+    case 5: return vario_launch_nz<DIM, 5>(P, A, nwg, lds, s, resident);
+    case 6: return vario_launch_nz<DIM, 6>(P, A, nwg, lds, s, resident);
+    case 7: return vario_launch_nz<DIM, 7>(P, A, nwg, lds, s, resident);
+    default: return vario_launch_nz<DIM, 8>(P, A, nwg, lds, s, resident);
+  }
+}
+
+// tile counters of the last call: written by the reduction into page-locked memory, read after the event
+int64_t* g_vario_stats = nullptr;   // [0] tiles opened
+hipEvent_t g_vario_event = nullptr;
+int64_t g_vario_tiles_total = 0;
+bool g_vario_pending = false;
+
+}  // namespace
+
+int32_t vario_stat(const char* name, int64_t* value) {
+  if (!std::strcmp(name, "vario_tiles_total")) {
+    *value = g_vario_tiles_total;
+    return GSS_OK;
+  }
+  if (!std::strcmp(name, "vario_tiles_opened")) {
+    if (g_vario_pending) {
+      GSS_HIP(hipEventSynchronize(g_vario_event));
+      g_vario_pending = false;
+    }
+    *value = g_vario_stats ? g_vario_stats[0] : 0;
+    return GSS_OK;
+  }
+  return -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// model fit (host)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// f(x), x = h / range: the shapes of vg_shape (gss_internal.h), gamma = nugget + (sill - nugget) f
+double fit_shape(int kind, double x, double nu) {
+  const double pi = 3.14159265358979323846;
+  switch (kind) {
+    case GSS_VG_GAUSSIAN: return -std::expm1(-3.0 * x * x);
+    case GSS_VG_EXPONENTIAL: return -std::expm1(-3.0 * x);
+    case GSS_VG_SPHERICAL: return x < 1.0 ? 1.5 * x - 0.5 * x * x * x : 1.0;
+    case GSS_VG_CUBIC: {
+      const double x2 = x * x, x3 = x2 * x;
+      return x < 1.0 ? 7.0 * x2 - 8.75 * x3 + 3.5 * x3 * x2 - 0.75 * x3 * x3 * x : 1.0;
+    }
+    case GSS_VG_PENTASPHERICAL: {
+      const double x2 = x * x, x3 = x2 * x;
+      return x < 1.0 ? 1.875 * x - 1.25 * x3 + 0.375 * x3 * x2 : 1.0;
+    }
+    case GSS_VG_SINEHOLE: {
+      const double t = pi * x;
+      return t > 0.0 ? 1.0 - std::sin(t) / t : 0.0;
+    }
+    default: {  // GSS_VG_MATERN
+      const double d = std::sqrt(2.0 * nu) * 3.0 * x;
+      if (!(d > 0.0)) return 0.0;
+      if (d > 700.0) return 1.0;
+      if (nu == 0.5) return -std::expm1(-d);
+      if (nu == 1.5) return 1.0 - (1.0 + d) * std::exp(-d);
+      if (nu == 2.5) return 1.0 - (1.0 + d + d * d / 3.0) * std::exp(-d);
+      if (nu * std::log(2.0 / d) > 690.0) return 0.0;
+      const double c = std::exp((1.0 - nu) * 0.6931471805599453 - std::lgamma(nu) + nu * std::log(d));
+      return 1.0 - c * std::cyl_bessel_k(nu, d);
+    }
+  }
+}
+
+struct FitData {
+  std::vector<double> h, g, w;
+  double frac;   // nugget <= frac * sill
+};
+
+double fit_residual(const FitData& D, const std::vector<double>& f, double a, double b) {
+  double s = 0.0;
+  for (size_t k = 0; k < f.size(); ++k) {
+    const double r = a + b * f[k] - D.g[k];
+    s += D.w[k] * r * r;
+  }
+  return s;
+}
+
+// For a fixed range the objective is a quadratic in (a, b) = (nugget, sill - nugget) over the cone a >= 0, b >= 0,
+// (1 - frac) a <= frac b.  Its minimum is the unconstrained one if feasible, else it lies on one of the three edges
+// (each a one-variable least squares) or at their common vertex, the origin.  Returns the objective.
+double fit_inner(const FitData& D, int kind, double nu, double range, double* a_out, double* b_out) {
+  const size_t m = D.h.size();
+  std::vector<double> f(m);
+  for (size_t k = 0; k < m; ++k) f[k] = fit_shape(kind, D.h[k] / range, nu);
+  double sw = 0.0, swf = 0.0, swg = 0.0;
+  for (size_t k = 0; k < m; ++k) {
+    sw += D.w[k];
+    swf += D.w[k] * f[k];
+    swg += D.w[k] * D.g[k];
+  }
+  const double fb = swf / sw, gb = swg / sw;
+  double sff = 0.0, sfg = 0.0, swff = 0.0, swfg = 0.0;
+  for (size_t k = 0; k < m; ++k) {
+    sff += D.w[k] * (f[k] - fb) * (f[k] - fb);
+    sfg += D.w[k] * (f[k] - fb) * (D.g[k] - gb);
+    swff += D.w[k] * f[k] * f[k];
+    swfg += D.w[k] * f[k] * D.g[k];
+  }
+  const double frac = D.frac;
+  double best = fit_residual(D, f, 0.0, 0.0), ba = 0.0, bb = 0.0;   // the vertex
+  auto feasible = [&](double a, double b) { return a >= 0.0 && b >= 0.0 && (1.0 - frac) * a <= frac * b; };
+  auto offer = [&](double a, double b) {
+    if (!(std::isfinite(a) && std::isfinite(b)) || !feasible(a, b)) return;
+    const double o = fit_residual(D, f, a, b);
+    if (o < best) {
+      best = o;
+      ba = a;
+      bb = b;
+    }
+  };
+  if (sff > 0.0) {
+    const double b = sfg / sff;
+    offer(gb - b * fb, b);                   // unconstrained
+  }
+  if (swff > 0.0) offer(0.0, swfg / swff);   // nugget = 0
+  offer(gb, 0.0);                            // sill = nugget (feasible only when frac = 1)
+  if (frac < 1.0) {                          // nugget = frac * sill: a = c b, gamma = b (c + f)
+    const double c = frac / (1.0 - frac);
+    double num = 0.0, den = 0.0;
+    for (size_t k = 0; k < m; ++k) {
+      num += D.w[k] * (c + f[k]) * D.g[k];
+      den += D.w[k] * (c + f[k]) * (c + f[k]);
+    }
+    if (den > 0.0) offer(c * (num / den), num / den);
+  }
+  *a_out = ba;
+  *b_out = bb;
+  return best;
+}
+
+constexpr int FIT_GRID = 256;
+
+// range: log-spaced grid over [hmin / 4, 4 hmax], then golden section on the best bracket to 1e-8 relative width
+double fit_kind(const FitData& D, int kind, double nu, double* nugget, double* sill, double* range) {
+  double hmin = D.h[0], hmax = D.h[0];
+  for (double v : D.h) {
+    hmin = v < hmin ? v : hmin;
+    hmax = v > hmax ? v : hmax;
+  }
+  const double r0 = 0.25 * hmin, r1 = 4.0 * hmax;
+  std::vector<double> rg(FIT_GRID), og(FIT_GRID);
+  int ib = 0;
+  double a, b;
+  for (int i = 0; i < FIT_GRID; ++i) {
+    rg[i] = r0 * std::pow(r1 / r0, (double)i / (double)(FIT_GRID - 1));
+    og[i] = fit_inner(D, kind, nu, rg[i], &a, &b);
+    if (og[i] < og[ib]) ib = i;
+  }
+  double lo = rg[ib > 0 ? ib - 1 : 0], hi = rg[ib < FIT_GRID - 1 ? ib + 1 : FIT_GRID - 1];
+  double rbest = rg[ib], obest = og[ib];
+  const double gr = 0.6180339887498949;
+  double x1 = hi - gr * (hi - lo), x2 = lo + gr * (hi - lo);
+  double o1 = fit_inner(D, kind, nu, x1, &a, &b), o2 = fit_inner(D, kind, nu, x2, &a, &b);
+  for (int it = 0; it < 200 && (hi - lo) > 1e-8 * 0.5 * (hi + lo); ++it) {
+    if (o1 < obest) { obest = o1; rbest = x1; }
+    if (o2 < obest) { obest = o2; rbest = x2; }
+    if (o1 <= o2) {
+      hi = x2;
+      x2 = x1;
+      o2 = o1;
+      x1 = hi - gr * (hi - lo);
+      o1 = fit_inner(D, kind, nu, x1, &a, &b);
+    } else {
+      lo = x1;
+      x1 = x2;
+      o1 = o2;
+      x2 = lo + gr * (hi - lo);
+      o2 = fit_inner(D, kind, nu, x2, &a, &b);
+    }
+  }
+  if (o1 < obest) { obest = o1; rbest = x1; }
+  if (o2 < obest) { obest = o2; rbest = x2; }
+  obest = fit_inner(D, kind, nu, rbest, &a, &b);
+  *nugget = a;
+  *sill = a + b;
+  *range = rbest;
+  return obest;
+}
+
+}  // namespace
+
+}  // namespace gss
+
+using namespace gss;
+
+extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
+                                           int32_t nlags, double maxlag, const double* direction, double dtol,
+                                           double cos_atol, int32_t estimator, int64_t* count, double* lagsum,
+                                           double* zsum, int64_t* nduplicates, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(x != nullptr && z != nullptr && count != nullptr && lagsum != nullptr && zsum != nullptr &&
+                  nduplicates != nullptr, "gss_variogram_empirical: NULL argument");
+  GSS_REQUIRE(dim >= 1 && dim <= 3, "gss_variogram_empirical: dim %d outside 1..3", dim);
+  GSS_REQUIRE(n >= 2 && n < (int64_t)INT32_MAX, "gss_variogram_empirical: n = %lld samples (2 .. 2^31 - 2)",
+              (long long)n);
+  GSS_REQUIRE(nz >= 1 && nz <= VARIO_MAX_NZ, "gss_variogram_empirical: nz %d outside 1..%d", nz, VARIO_MAX_NZ);
+  GSS_REQUIRE(nlags >= 1 && nlags <= VARIO_MAX_LAGS, "gss_variogram_empirical: nlags %d outside 1..%d", nlags,
+              VARIO_MAX_LAGS);
+  GSS_REQUIRE(std::isfinite(maxlag) && maxlag > 0.0, "gss_variogram_empirical: maxlag must be positive and finite");
+  GSS_REQUIRE(estimator == GSS_VARIO_MATHERON || estimator == GSS_VARIO_CRESSIE,
+              "gss_variogram_empirical: unknown estimator %d", estimator);
+  GSS_REQUIRE(mem == GSS_MEM_HOST || mem == GSS_MEM_DEVICE, "gss_variogram_empirical: bad mem %d", mem);
+  VarioArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.dtol2 = __builtin_huge_val();
+  if (direction != nullptr) {
+    // the direction is a HOST array of `dim` doubles in both memory modes (it is a parameter, not data)
+    double nn = 0.0;
+    for (int a = 0; a < dim; ++a) {
+      GSS_REQUIRE(std::isfinite(direction[a]), "gss_variogram_empirical: direction is not finite");
+      nn += direction[a] * direction[a];
+      A.u[a] = direction[a];
+    }
+    GSS_REQUIRE(std::fabs(std::sqrt(nn) - 1.0) <= 1e-12, "gss_variogram_empirical: direction is not a unit vector "
+                "(norm %.17g)", std::sqrt(nn));
+    GSS_REQUIRE(dtol > 0.0 && !std::isnan(dtol), "gss_variogram_empirical: dtol must be positive (+inf: no band)");
+    GSS_REQUIRE(cos_atol >= 0.0 && cos_atol <= 1.0, "gss_variogram_empirical: cos_atol outside [0, 1]");
+    A.directional = 1;
+    A.dtol2 = dtol * dtol;
+    A.cos2 = cos_atol * cos_atol;
+  }
+  // squared bin edges edge2[k] = fl(fl(k delta)^2): the kernel forms the same doubles; only the ends are checked here
+  const double delta = maxlag / (double)nlags;
+  {
+    volatile double e1 = delta * delta, en = (double)nlags * delta;
+    volatile double en2 = en * en;
+    GSS_REQUIRE(e1 > 0.0 && std::isfinite(en2), "gss_variogram_empirical: maxlag^2 leaves the range of a double");
+  }
+
+  hipStream_t s = to_stream(stream);
+  Staged sx, sz, scount, slag, szsum, sdup;
+  GSS_TRY(sx.in(x, sizeof(double) * (size_t)n * dim, mem, s));
+  GSS_TRY(sz.in(z, sizeof(double) * (size_t)n * nz, mem, s));
+  DevBuf zs, flags, partial;
+  GSS_TRY(zs.alloc(sizeof(double) * (size_t)n * nz));
+  GSS_TRY(flags.alloc(sizeof(unsigned long long) * 8));   // [0] unit counter, [1] bad-value flag, [2..7] bounding box
+  unsigned long long* d_flags = flags.as<unsigned long long>();
+  int* d_bad = reinterpret_cast<int*>(d_flags + 1);
+  hipLaunchKernelGGL(vario_init_kernel, dim3(1), dim3(64), 0, s, d_flags + 2, d_flags);
+  {
+    const int64_t nx = n * dim, nzv = n * nz, nmax = nx > nzv ? nx : nzv;
+    hipLaunchKernelGGL(vario_check_kernel, dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, s, sx.as<double>(),
+                       sz.as<double>(), nx, nzv, d_bad);
+  }
+  GSS_HIP(hipGetLastError());
+  KnnIndex ix;
+  if (n >= VARIO_KD_MIN) {
+    GSS_TRY(knn_index_build_device(sx.as<double>(), n, dim, &ix, s));   // the Searcher's k-d order; waits for s once
+  } else {
+    switch (dim) {
+      case 1: GSS_TRY(vario_morton_index<1>(sx.as<double>(), n, d_flags + 2, &ix, s)); break;
+      case 2: GSS_TRY(vario_morton_index<2>(sx.as<double>(), n, d_flags + 2, &ix, s)); break;
+      default: GSS_TRY(vario_morton_index<3>(sx.as<double>(), n, d_flags + 2, &ix, s)); break;
+    }
+  }
+  hipLaunchKernelGGL(vario_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sz.as<double>(),
+                     ix.perm.as<int>(), n, (int)nz, zs.as<double>());
+  GSS_HIP(hipGetLastError());
+
+  int dev = 0, ncu = 0;
+  GSS_HIP(hipGetDevice(&dev));
+  GSS_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  VarioPtrs P;
+  P.xs = ix.xs.as<double>();
+  P.zs = zs.as<double>();
+  P.lo = ix.lo.as<double>();
+  P.hi = ix.hi.as<double>();
+  A.n = n;
+  A.nb = ix.nb;
+  A.jw = ix.nb < 512 ? 4 : VARIO_JW_MAX;   // below ~32 000 samples 16-tile units are too few to fill the device
+  A.nchunks = (ix.nb + A.jw - 1) / A.jw;
+  A.nlags = nlags;
+  A.estimator = estimator;
+  {
+    const char* e = std::getenv("GSS_VARIO_CULL");   // "0": open every tile (tests: results do not depend on it)
+    A.nocull = e && e[0] == '0';
+  }
+  A.delta = delta;
+  A.inv_delta = 1.0 / delta;
+  P.unit_counter = d_flags;
+  const size_t nwords = (size_t)(nlags + 2) + nlags + (size_t)nz * nlags;
+  const size_t lds = sizeof(double) * ((size_t)nlags + 1 + nwords);
+  // the grid: as many workgroups as are resident at a time for this instantiation (registers and LDS decide: 6 per CU
+  // for one value column, 2 for eight), fewer when there are not two units per wave; a workgroup beyond that would only
+  // start once the others have emptied the counter
+  int resident = 0;
+  switch (dim) {
+    case 1: GSS_TRY(vario_launch<1>(P, A, nz, 0, lds, s, &resident)); break;
+    case 2: GSS_TRY(vario_launch<2>(P, A, nz, 0, lds, s, &resident)); break;
+    default: GSS_TRY(vario_launch<3>(P, A, nz, 0, lds, s, &resident)); break;
+  }
+  if (resident < 1) resident = 1;
+  const int64_t nunits = (int64_t)A.nb * A.nchunks;
+  const int64_t want = (nunits + 7) / 8, cap = (int64_t)ncu * resident;
+  const int nwg = (int)(want < 1 ? 1 : (want > cap ? cap : want));
+  {
+    const int64_t g = nunits / ((int64_t)nwg * 4 * 32);   // at least 32 draws per wave
+    A.grab = (int)(g < 1 ? 1 : (g > 64 ? 64 : g));
+  }
+  GSS_TRY(partial.alloc(sizeof(unsigned long long) * nwords * (size_t)nwg));
+  P.partial = partial.as<unsigned long long>();
+
+  GSS_TRY(scount.out(count, sizeof(int64_t) * nlags, mem));
+  GSS_TRY(slag.out(lagsum, sizeof(double) * nlags, mem));
+  GSS_TRY(szsum.out(zsum, sizeof(double) * nlags * nz, mem));
+  GSS_TRY(sdup.out(nduplicates, sizeof(int64_t), mem));
+  if (!g_vario_stats) {
+    GSS_HIP(hipHostMalloc(reinterpret_cast<void**>(&g_vario_stats), 2 * sizeof(int64_t), hipHostMallocDefault));
+    g_vario_stats[0] = g_vario_stats[1] = 0;
+    GSS_HIP(hipEventCreateWithFlags(&g_vario_event, hipEventDisableTiming));
+  }
+  {
+    ProfScope prof("vario_pairs", s);
+    switch (dim) {
+      case 1: GSS_TRY(vario_launch<1>(P, A, nz, nwg, lds, s, nullptr)); break;
+      case 2: GSS_TRY(vario_launch<2>(P, A, nz, nwg, lds, s, nullptr)); break;
+      default: GSS_TRY(vario_launch<3>(P, A, nz, nwg, lds, s, nullptr)); break;
+    }
+  }
+  hipLaunchKernelGGL(vario_reduce_kernel, dim3((unsigned)nwords), dim3(256), 0, s, P.partial, nwg,
+                     (int)nlags, (int)nz, scount.as<int64_t>(), slag.as<double>(), szsum.as<double>(),
+                     sdup.as<int64_t>(), g_vario_stats, d_bad);
+  GSS_HIP(hipGetLastError());
+  GSS_HIP(hipEventRecord(g_vario_event, s));
+  g_vario_pending = true;
+  g_vario_tiles_total = (int64_t)A.nb * ((int64_t)A.nb + 1) / 2;
+  // (the index, the ordered values and the slices are scratch: released into the block cache, whose re-use is ordered
+  //  behind this call by the stream chain)
+  if (mem == GSS_MEM_HOST) {
+    GSS_HIP(hipMemcpyAsync(count, scount.p, sizeof(int64_t) * nlags, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(lagsum, slag.p, sizeof(double) * nlags, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(zsum, szsum.p, sizeof(double) * nlags * nz, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(nduplicates, sdup.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipStreamSynchronize(s));
+    // a non-finite input is found on the device and reported through the outputs (gss.h); here they have arrived
+    GSS_REQUIRE(*nduplicates >= 0, "gss_variogram_empirical: a coordinate or a value is NaN or infinite (missing values "
+                "are dropped by the caller: a pair takes part only if both of its values exist)");
+  }
+  return GSS_OK;
+}
+
+// gss_shutdown: the page-locked tile counter and its event
+void gss::vario_release() {
+  if (g_vario_event) (void)hipEventDestroy(g_vario_event);
+  if (g_vario_stats) (void)hipHostFree(g_vario_stats);
+  g_vario_event = nullptr;
+  g_vario_stats = nullptr;
+  g_vario_pending = false;
+}
+
+extern "C" int32_t gss_variogram_fit(const double* h, const double* gamma, const int64_t* count, int32_t nlags,
+                                     const int32_t* kinds, int32_t nkinds, double nu, int32_t weighting,
+                                     double max_nugget_frac, gss_variogram_t* best, double* objective) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr && gamma != nullptr && count != nullptr && kinds != nullptr && best != nullptr &&
+                  objective != nullptr, "gss_variogram_fit: NULL argument");
+  GSS_REQUIRE(nlags >= 1 && nlags <= 65536, "gss_variogram_fit: nlags %d outside 1..65536", nlags);
+  GSS_REQUIRE(nkinds >= 1 && nkinds <= 64, "gss_variogram_fit: nkinds %d outside 1..64", nkinds);
+  GSS_REQUIRE(weighting >= GSS_FIT_W_COUNT && weighting <= GSS_FIT_W_UNIFORM, "gss_variogram_fit: unknown weighting %d",
+              weighting);
+  GSS_REQUIRE(max_nugget_frac >= 0.0 && max_nugget_frac <= 1.0, "gss_variogram_fit: max_nugget_frac outside [0, 1]");
+  bool matern = false;
+  for (int i = 0; i < nkinds; ++i) {
+    if (kinds[i] == GSS_VG_POWER) {
+      set_error("gss_variogram_fit: the power model has no sill and no range to search; only the stationary kinds are "
+                "fitted");
+      return GSS_ERR_UNSUPPORTED;
+    }
+    GSS_REQUIRE(kinds[i] >= GSS_VG_GAUSSIAN && kinds[i] <= GSS_VG_SINEHOLE, "gss_variogram_fit: unknown kind %d",
+                kinds[i]);
+    matern = matern || kinds[i] == GSS_VG_MATERN;
+  }
+  if (matern) GSS_REQUIRE(nu > 0.0 && nu <= 50.0, "gss_variogram_fit: Matern order must lie in (0, 50]");
+  FitData D;
+  D.frac = max_nugget_frac;
+  for (int k = 0; k < nlags; ++k) {
+    if (count[k] <= 0) continue;
+    GSS_REQUIRE(std::isfinite(h[k]) && h[k] > 0.0 && std::isfinite(gamma[k]), "gss_variogram_fit: bin %d has pairs but "
+                "no finite positive lag / finite ordinate", k);
+    const double c = (double)count[k];
+    D.h.push_back(h[k]);
+    D.g.push_back(gamma[k]);
+    D.w.push_back(weighting == GSS_FIT_W_COUNT ? c : (weighting == GSS_FIT_W_COUNT_OVER_H2 ? c / (h[k] * h[k]) : 1.0));
+  }
+  GSS_REQUIRE(D.h.size() >= 2, "gss_variogram_fit: fewer than two bins hold pairs");
+  int ibest = -1;
+  double nbest = 0.0, sbest = 0.0, rbest = 0.0;
+  for (int i = 0; i < nkinds; ++i) {
+    double ng, sl, rg;
+    objective[i] = fit_kind(D, kinds[i], nu, &ng, &sl, &rg);
+    if (!(sl > 0.0)) {   // the ordinates admit no model of this kind with a positive sill
+      objective[i] = std::nan("");
+      continue;
+    }
+    if (ibest < 0 || objective[i] < objective[ibest]) {
+      ibest = i;
+      nbest = ng;
+      sbest = sl;
+      rbest = rg;
+    }
+  }
+  GSS_REQUIRE(ibest >= 0, "gss_variogram_fit: no kind fits these ordinates with a positive sill");
+  std::memset(best, 0, sizeof(*best));
+  best->kind = kinds[ibest];
+  best->dim = 0;   // left to the caller
+  best->sill = sbest;
+  best->nugget = nbest;
+  best->range = rbest;
+  best->nu = kinds[ibest] == GSS_VG_MATERN ? nu : 1.0;
+  for (int a = 0; a < 3; ++a) {
+    best->inv_radii[a] = 1.0;
+    best->rotation[4 * a] = 1.0;
+  }
+  return GSS_OK;
+}

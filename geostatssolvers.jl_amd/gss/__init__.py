@@ -12,5 +12,6 @@ from .solvers import (FFTGS, LUGS, SGS, ExpWeight, IDWSolver, KrigingSolver, LWR
 from .variograms import (CubicVariogram, ExponentialVariogram, GaussianVariogram, MaternVariogram, MetricBall,
                          NestedVariogram, PentasphericalVariogram, PowerVariogram, SineHoleVariogram,
                          SphericalVariogram)
+from .variography import DirectionalVariogram, EmpiricalVariogram, EmpiricalVariogramResult, fit
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -75,6 +75,8 @@ SIGNATURES = {
     "gss_profile_reset": [],
     "gss_profile_read": [C.c_char_p, C.POINTER(_f64), C.POINTER(_i64)],
     "gss_cov_pairwise": [_VG, _p, _i64, _p, _i64, _p, _i64, _i32, _p],
+    "gss_variogram_empirical": [_p, _i64, _i32, _p, _i32, _i32, _f64, _p, _f64, _f64, _i32, _p, _p, _p, _p, _i32, _p],
+    "gss_variogram_fit": [_p, _p, _p, _i32, _p, _i32, _f64, _i32, _f64, _VG, _p],
     "gss_knn_search": [_p, _i64, _i32, _p, _i64, _i32, _f64, _p, _i32, _f64, _p, _p, _i32, _p],
     "gss_krig_create": [C.POINTER(_p), _VG, _i32, _f64, _i32, _i32, _p, _p, _p, _i64, _i32, _p],
     "gss_krig_destroy": [_p],
@@ -328,7 +330,7 @@ def state_ipc_import(kind: int, handle, token: bytes):
 
 def stat(name: str) -> int:
     """A library counter: "pool_bytes", "out_ring_bytes", "out_chunks", "panel_giveups", "gemm_launches_128",
-    "gemm_launches_64", "ipc_route" (gss.h, gss_stat)."""
+    "gemm_launches_64", "ipc_route", "vario_tiles_total", "vario_tiles_opened" (gss.h, gss_stat)."""
     v = C.c_int64()
     check(load().gss_stat(name.encode(), C.byref(v)))
     return v.value

@@ -601,5 +601,64 @@ class HipEngine:
         return mean, var, st
 
 
+    # ---- variography (gss.h "variography") --------------------------------------------------------------------
+    @staticmethod
+    def variogram_empirical(x, z, nlags, maxlag, direction=None, dtol=float("inf"), cos_atol=0.0, estimator=0,
+                            distance=None):
+        """Bin sums of the empirical variogram: x (n, d), z (nz, n) -> count (nlags,) int64, lagsum (nlags,),
+        zsum (nz, nlags), nduplicates.  numpy arrays in -> numpy out; CUDA tensors for x and z keep everything in HBM
+        (the outputs are tensors, nduplicates a 1-element tensor).  `direction`: a unit vector (host) or None."""
+        if _lib.metric_spec(distance)[0] != 0:
+            raise _lib.GSSError(_lib.ERR_UNSUPPORTED, "empirical variograms use the Euclidean distance only")
+        l = _lib.lib()
+        dev = is_torch(x) and x.is_cuda
+        if dev != (is_torch(z) and z.is_cuda):
+            raise ValueError("x and z must live in the same memory space")
+        x = _prep_in(x)
+        z = _prep_in(z)
+        if x.ndim == 1:
+            x = x[:, None]
+        n, d = x.shape
+        z = z.reshape(-1, n)
+        nz = z.shape[0]
+        nlags = int(nlags)
+        if dev:
+            import torch
+            count = torch.empty(max(nlags, 0), dtype=torch.int64, device=x.device)
+            lagsum = torch.empty(max(nlags, 0), dtype=torch.float64, device=x.device)
+            zsum = torch.empty((nz, max(nlags, 0)), dtype=torch.float64, device=x.device)
+            ndup = torch.empty(1, dtype=torch.int64, device=x.device)
+        else:
+            count = np.empty(max(nlags, 0), dtype=np.int64)
+            lagsum = np.empty(max(nlags, 0))
+            zsum = np.empty((nz, max(nlags, 0)))
+            ndup = np.zeros(1, dtype=np.int64)
+        u = None if direction is None else np.ascontiguousarray(direction, dtype=np.float64).reshape(-1)
+        if u is not None and u.size != d:
+            raise ValueError(f"direction has {u.size} components for {d}-D samples")
+        check(l.gss_variogram_empirical(ptr(x), n, d, ptr(z), nz, nlags, float(maxlag), ptr(u), float(dtol),
+                                        float(cos_atol), int(estimator), ptr(count), ptr(lagsum), ptr(zsum), ptr(ndup),
+                                        MEM_DEVICE if dev else MEM_HOST, current_stream()))
+        return count, lagsum, zsum, (ndup if dev else int(ndup[0]))
+
+    @staticmethod
+    def variogram_fit(h, gamma, count, kinds, nu=1.0, weighting=0, max_nugget_frac=1.0):
+        """gss_variogram_fit (host code of the library, no device): -> (kind name, sill, nugget, range, nu,
+        objective per kind)."""
+        l = _lib.load()
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        g = np.ascontiguousarray(gamma, dtype=np.float64)
+        c = np.ascontiguousarray(count, dtype=np.int64)
+        if not (h.shape == g.shape == c.shape and h.ndim == 1):
+            raise ValueError("h, gamma and count must be vectors of one length")
+        names = {v: k for k, v in _lib._KINDS.items()}
+        kk = np.ascontiguousarray([_lib._KINDS[k] for k in kinds], dtype=np.int32)
+        obj = np.empty(len(kk))
+        best = _lib.Variogram()
+        check(l.gss_variogram_fit(ptr(h), ptr(g), ptr(c), h.size, ptr(kk), len(kk), float(nu), int(weighting),
+                                  float(max_nugget_frac), C.byref(best), ptr(obj)))
+        return names[best.kind], best.sill, best.nugget, best.range, best.nu, obj
+
+
 def default_engine():
     return HipEngine

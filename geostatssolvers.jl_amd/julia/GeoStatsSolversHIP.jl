@@ -43,6 +43,7 @@ import GeoStatsBase: solve, preprocess, solvesingle
 
 export KrigingSolverHIP, IDWSolverHIP, LWRSolverHIP, ExpWeight, TricubeWeight, FFTGSHIP, LUGSHIP, SGSHIP
 export krig_fit, krig_predict_device!, fftgs_realize_device!, bind_device
+export empirical_variogram, fit_variogram
 
 const libgss = get(ENV, "LIBGSS_HIP", "libgss_hip.so")
 
@@ -889,6 +890,76 @@ function fftgs_realize_device!(dst::Ptr{Float64}, preproc, var::Symbol, first::I
               (Ptr{Cvoid}, UInt64, Int64, Int64, Ptr{Float64}, Ptr{Int64}, Int64, Ptr{Float64}, Int32, Ptr{Cvoid}),
               preproc[var].handle, varseed(preproc[:_run], var), Int64(first), Int64(count), C_NULL, C_NULL, Int64(0),
               dst, GSS_MEM_DEVICE, stream))
+end
+
+# ---- variography: replaces Variography's EmpiricalVariogram / DirectionalVariogram / fit (include/gss.h) ----------
+const GAMMA_CONSTRUCTORS = (GaussianVariogram, ExponentialVariogram, SphericalVariogram, MaternVariogram, CubicVariogram,
+                            PentasphericalVariogram, SineHoleVariogram)          # index - 1 = GSS_VG_*
+
+"""
+    empirical_variogram(data, vars; nlags=20, maxlag=nothing, estimator=:matheron, direction=nothing, dtol=Inf, atol=π/8)
+
+Empirical variogram(s) of the variable(s) `vars` (a Symbol or a collection of up to 8 Symbols measured on the same samples:
+one pass over the pairs serves them all) on the device.  `maxlag` defaults to a tenth of the diagonal of the samples'
+bounding box ([RECALL] Variography's default); `direction` (any non-zero vector) keeps the pairs inside a band of
+half-width `dtol` and a cone of half-angle `atol` about it, either sense.  Rows with a missing value in any of `vars`
+are dropped.  Returns `(abscissa, ordinate, counts, nduplicates)`; `ordinate` is a Dict var => Vector for several
+variables.  Bins without pairs hold NaN.
+"""
+function empirical_variogram(data, vars; nlags::Integer=20, maxlag=nothing, estimator::Symbol=:matheron,
+                             direction=nothing, dtol::Real=Inf, atol::Real=π / 8)
+  names = vars isa Symbol ? [vars] : collect(Symbol, vars)
+  tab = Tables.columns(values(data))
+  cols = [Tables.getcolumn(tab, v) for v in names]
+  keep = [i for i in 1:nelements(domain(data)) if all(c -> !ismissing(c[i]) && isfinite(ustrip(c[i])), cols)]
+  X = coordmatrix(domain(data))[:, keep]
+  d, n = size(X)
+  Z = Matrix{Float64}(undef, n, length(names))          # column c at Z + c * n
+  for (c, col) in enumerate(cols), (r, i) in enumerate(keep)
+    Z[r, c] = Float64(ustrip(col[i]))
+  end
+  lag = isnothing(maxlag) ? 0.1 * sqrt(sum(abs2, maximum(X, dims=2) .- minimum(X, dims=2))) : Float64(ustrip(maxlag))
+  u = isnothing(direction) ? nothing : collect(Float64, direction) ./ sqrt(sum(abs2, direction))
+  cosatol = isnothing(direction) || atol >= π / 2 ? 0.0 : cos(Float64(atol))
+  est = estimator == :cressie ? Int32(1) : Int32(0)
+  count = Vector{Int64}(undef, nlags)
+  lagsum = Vector{Float64}(undef, nlags)
+  zsum = Matrix{Float64}(undef, nlags, length(names))
+  ndup = Ref{Int64}(0)
+  GC.@preserve X Z u check(ccall((:gss_variogram_empirical, libgss), Int32,
+    (Ptr{Float64}, Int64, Int32, Ptr{Float64}, Int32, Int32, Float64, Ptr{Float64}, Float64, Float64, Int32, Ptr{Int64},
+     Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int32, Ptr{Cvoid}),
+    X, Int64(n), Int32(d), Z, Int32(length(names)), Int32(nlags), lag, isnothing(u) ? C_NULL : pointer(u), Float64(dtol),
+    cosatol, est, count, lagsum, zsum, ndup, GSS_MEM_HOST, C_NULL))
+  abscissa = [c > 0 ? s / c : NaN for (s, c) in zip(lagsum, count)]
+  gamma(col) = [c == 0 ? NaN : est == 0 ? s / 2c : (s / c)^4 / (2 * (0.457 + 0.494 / c)) for (s, c) in zip(col, count)]
+  ordinate = vars isa Symbol ? gamma(zsum[:, 1]) : Dict(v => gamma(zsum[:, c]) for (c, v) in enumerate(names))
+  (abscissa=abscissa, ordinate=ordinate, counts=count, nduplicates=ndup[])
+end
+
+"""
+    fit_variogram(kinds, abscissa, ordinate, counts; weighting=:count, order=1.0, maxnuggetfrac=1.0)
+
+Weighted least-squares fit (gss_variogram_fit, host code of the library) of the best of `kinds` -- variogram types such
+as `GaussianVariogram`, or one of them -- to an empirical variogram; returns the Variography model.  The library fits
+the Gaussian kind as the bare formula: the nugget handed to `GaussianVariogram` is the fitted one minus the constant
+the loaded Variography adds on evaluation (GAUSSIAN_NUGGET_EPS), not below zero.
+"""
+function fit_variogram(kinds, abscissa::Vector{Float64}, ordinate::Vector{Float64}, counts::Vector{Int64};
+                       weighting::Symbol=:count, order::Real=1.0, maxnuggetfrac::Real=1.0)
+  ks = kinds isa Type ? [kinds] : collect(kinds)
+  codes = Int32[something(findfirst(==(k), GAMMA_CONSTRUCTORS), 8) - 1 for k in ks]      # anything else: GSS_VG_POWER
+  w = weighting == :count ? Int32(0) : weighting == :uniform ? Int32(2) : Int32(1)
+  best = Ref(cvariogram(GaussianVariogram(), 1))
+  objective = Vector{Float64}(undef, length(codes))
+  check(ccall((:gss_variogram_fit, libgss), Int32,
+    (Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int32, Ptr{Int32}, Int32, Float64, Int32, Float64, Ptr{GssVariogram},
+     Ptr{Float64}), abscissa, ordinate, counts, Int32(length(counts)), codes, Int32(length(codes)), Float64(order), w,
+    Float64(maxnuggetfrac), best, objective))
+  b = best[]
+  T = GAMMA_CONSTRUCTORS[b.kind+1]
+  nug = T === GaussianVariogram ? max(b.nugget - GAUSSIAN_NUGGET_EPS[], 0.0) : b.nugget
+  T === MaternVariogram ? T(sill=b.sill, nugget=nug, range=b.range, order=b.nu) : T(sill=b.sill, nugget=nug, range=b.range)
 end
 
 # ---- several GPUs: one worker process per GPU ---------------------------------------------------------------------

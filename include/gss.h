@@ -147,6 +147,8 @@ int32_t gss_trim_pool(void);
  * single-launch factorisation left through its bounded wait and was repeated on the launch-per-block path),
  * "gemm_launches_128" / "gemm_launches_64" (FP64 matrix products launched so far on the 128 x 128 and on the 64 x 64
  * tile kernel: which of the two a given shape ran on),
+ * "vario_tiles_total" / "vario_tiles_opened" (batch pairs of the last gss_variogram_empirical and how many of them its
+ * box bound let through),
  * "ipc_route" (how the last gss_state_ipc_import reached the owner's device: 0 same device, 1 visible peer, 2 not among
  * the visible devices, 3 refused -- visible but not peer-accessible). */
 int32_t gss_stat(const char* name, int64_t* value);
@@ -192,6 +194,60 @@ int32_t gss_profile_read(const char* name, double* total_ms, int64_t* launches);
  *      b == NULL computes the symmetric na x na matrix. ---------------------------------------- */
 int32_t gss_cov_pairwise(const gss_variogram_t* vg, const double* a, int64_t na, const double* b,
                          int64_t nb, double* out, int64_t ldo, int32_t mem, void* stream);
+
+/* ---- variography: replaces [DEP] Variography's EmpiricalVariogram / DirectionalVariogram and `fit`, the step that
+ *      produces the solver parameter `variogram` (krig.jl:65, fft.jl:52, lu.jl:68).  That package is not in the
+ *      reference tree: the conventions below are this library's own, stated so that every pair's bin can be reproduced.
+ *
+ * gss_variogram_empirical: one pass over the n (n - 1) / 2 unordered sample pairs (Euclidean distance only).
+ *   x n x dim point-major (dim 1..3), z: nz columns of n (column c at z + c * n).  Limits: n in 2 .. 2^31 - 2,
+ *   nlags in 1 .. 256, nz in 1 .. 8.  Every coordinate and value must be finite (GSS_ERR_INVALID otherwise): a missing
+ *   value is the caller's to drop, and `count` is therefore one vector for all columns.
+ *   Pair key   d2 = ((D0 D0) + (D1 D1)) + (D2 D2), D = x_i - x_j, one rounding per operation, no FMA (the key of
+ *              gss_knn_search).  Bins are decided on d2, never on a square root: with delta = maxlag / nlags and
+ *              edge2[k] = fl(fl(k delta)^2), k = 0 .. nlags, a pair belongs to bin k iff edge2[k] < d2 <= edge2[k + 1]
+ *              (the bin (k delta, (k + 1) delta]).  d2 == 0 is counted in *nduplicates and otherwise skipped;
+ *              d2 > edge2[nlags] is skipped.
+ *   Direction  NULL: omnidirectional.  Else `dim` doubles IN HOST MEMORY whatever `mem` is (a parameter, not data), a
+ *              unit vector u (| ||u|| - 1 | <= 1e-12): t = (D0 u0 + D1 u1) + D2 u2, p2 = d2 - t t (rounded operations in
+ *              that order); the pair is kept iff p2 <= fl(dtol^2) (bandwidth; dtol = +inf: none) and
+ *              t t >= fl(fl(cos_atol^2) d2) (cone of half-angle acos(cos_atol); 0: none).  Both senses +-u count.
+ *   Outputs    count[nlags]; lagsum[nlags] = sum of h = sqrt(d2); zsum[nz x nlags] (column c at zsum + c * nlags) =
+ *              sum (z_i - z_j)^2 (GSS_VARIO_MATHERON) or sum |z_i - z_j|^(1/2) (GSS_VARIO_CRESSIE).  The front-ends form
+ *              the abscissa lagsum / count and gamma = zsum / (2 count)  resp.
+ *              gamma = (zsum / count)^4 / (2 (0.457 + 0.494 / count)) (Cressie-Hawkins).
+ *              The counts are exact and the same on every run; the floating-point sums depend on the order the device
+ *              happened to add in (relative difference below 2 count 2^-53).
+ *   mem        GSS_MEM_DEVICE: x, z and the four outputs are device arrays, written in stream order.  Below 32 768
+ *              samples nothing waits for the stream; from there on the call waits for it once, while the samples are
+ *              put in the k-d order of the neighbour search.  A non-finite input is found on the device: the call on
+ *              host arrays returns GSS_ERR_INVALID; the call on device arrays cannot know it without waiting and
+ *              reports it through the outputs instead -- every count and *nduplicates are -1 and the sums NaN.
+ *   Samples are visited batch by batch of 64 in a space-filling order (the k-d order of the neighbour search from
+ *   32 768 samples, one sort by Morton key below); a pair of batches whose bounding boxes are farther apart than maxlag
+ *   is never opened.  gss_stat "vario_tiles_total" / "vario_tiles_opened" are process-wide counters for tests and
+ *   tools: they describe the call whose reduction ran last (calls in flight on several streams share them), and
+ *   reading the second waits for that call.  The environment variable GSS_VARIO_CULL=0 opens every tile, for tests:
+ *   the results are the same.  The bin edges are formed as fl(fl(k delta)^2) where they are used. */
+enum { GSS_VARIO_MATHERON = 0, GSS_VARIO_CRESSIE = 1 };
+int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
+                                int32_t nlags, double maxlag, const double* direction, double dtol, double cos_atol,
+                                int32_t estimator, int64_t* count, double* lagsum, double* zsum,
+                                int64_t* nduplicates, int32_t mem, void* stream);
+/* gss_variogram_fit (host code, no device): weighted least squares of gamma(h) = nugget + (sill - nugget) f(h / range)
+ *   to the bins with count > 0; objective sum_k w_k (gamma_model(h_k) - gamma_k)^2 with w = count, count / h^2 or 1.
+ *   For a fixed range the objective is linear least squares in (nugget, sill - nugget) >= 0 with
+ *   nugget <= max_nugget_frac * sill (1: free), solved in closed form (unconstrained, else the best feasible edge);
+ *   the range is searched on a log-spaced grid of 256 points over [h_min / 4, 4 h_max] and refined by golden section
+ *   to a relative width of 1e-8.  Deterministic.  kinds: GSS_VG_GAUSSIAN .. GSS_VG_SINEHOLE (Matern at order nu);
+ *   GSS_VG_POWER -> GSS_ERR_UNSUPPORTED.  The Gaussian kind is fitted as the bare formula: a front-end that applies
+ *   the `nugget + 1e-6` rule hands the solvers nugget - 1e-6, or switches the rule off when
+ *   the fitted nugget is smaller.  objective[nkinds]: per kind (NaN where no positive sill fits); *best: the kind with
+ *   the smallest objective -- kind, sill, nugget, range, nu filled in, isotropic, dim = 0 left to the caller. */
+enum { GSS_FIT_W_COUNT = 0, GSS_FIT_W_COUNT_OVER_H2 = 1, GSS_FIT_W_UNIFORM = 2 };
+int32_t gss_variogram_fit(const double* h, const double* gamma, const int64_t* count, int32_t nlags,
+                          const int32_t* kinds, int32_t nkinds, double nu, int32_t weighting,
+                          double max_nugget_frac, gss_variogram_t* best, double* objective);
 
 /* ---- neighbour search: replaces `search!(neighbors, center, searcher)` krig.jl:210 and the
  *      KNearestSearch / KBallSearch construction ui.jl:27,30.  Exact; neighbours ordered by

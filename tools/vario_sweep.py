@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""Timing of gss_variogram_empirical on device arrays: uniform 3-D samples, nz = 1, nlags = 20.
+
+  * n = 2*10^4 and 10^5 with maxlag = the full diameter and with 5 % of the extent; n = 10^6 with 5 % only;
+  * the yardstick: gss_cov_pairwise with b == NULL (exponential model, device memory) on the same 2*10^4 samples runs
+    the same pair loop over BOTH triangles plus an exp and an 8-byte store per pair -- the full-diameter variogram call
+    at that size must not take longer.  The two are measured alternating in one session.
+
+Method: warm-up, then `--reps` timed runs, each bracketed by events on the stream (the call includes the ordering of the
+samples and the reduction: what a user pays; both calls are bare ctypes calls on preallocated outputs); the median is
+reported.  One JSON line
+per row on stdout.  python tools/vario_sweep.py [--reps 7] [--max-n 1000000]"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "geostatssolvers.jl_amd")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from gss import _lib  # noqa: E402
+from gss.engine import _vg_struct  # noqa: E402
+import gss  # noqa: E402
+
+
+def timed(fn, reps, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms)
+
+
+def bare_variogram(lib, x, z, nlags, maxlag):
+    """The call as a bare ctypes call on preallocated outputs -- what the yardstick's call is timed as."""
+    n, d = x.shape
+    count = torch.empty(nlags, dtype=torch.int64, device="cuda")
+    lagsum = torch.empty(nlags, dtype=torch.float64, device="cuda")
+    zsum = torch.empty((z.shape[0], nlags), dtype=torch.float64, device="cuda")
+    ndup = torch.empty(1, dtype=torch.int64, device="cuda")
+    args = (C.c_void_p(x.data_ptr()), n, d, C.c_void_p(z.data_ptr()), z.shape[0], nlags, float(maxlag), None,
+            float("inf"), 0.0, 0, C.c_void_p(count.data_ptr()), C.c_void_p(lagsum.data_ptr()),
+            C.c_void_p(zsum.data_ptr()), C.c_void_p(ndup.data_ptr()), _lib.MEM_DEVICE)
+
+    def run():
+        _lib.check(lib.gss_variogram_empirical(*args, _lib.current_stream()))
+    return run, (count, lagsum, zsum, ndup)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--max-n", type=int, default=1_000_000)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    lib = _lib.lib()
+    rng = np.random.default_rng(1)
+    for n in (20_000, 100_000, 1_000_000):
+        if n > args.max_n:
+            continue
+        x = torch.as_tensor(rng.uniform(0.0, 1000.0, (n, 3)), device="cuda")
+        z = torch.as_tensor(rng.normal(size=(1, n)), device="cuda")
+        diam = 1000.0 * 3 ** 0.5
+        for label, maxlag in (("full", diam), ("5pct", 50.0)):
+            if label == "full" and n > 100_000:
+                continue
+            run, outs = bare_variogram(lib, x, z, 20, maxlag)
+            reps = args.reps if n <= 100_000 else 3
+            _lib.profile_enable(True)
+            _lib.profile_reset()
+            med, best = timed(run, reps)
+            kms, launches = _lib.profile_read("vario_pairs")
+            _lib.profile_enable(False)
+            pairs = int(outs[0].sum().item())
+            row = {"what": "variogram", "n": n, "maxlag": label, "nlags": 20, "nz": 1, "median_ms": round(med, 4),
+                   "min_ms": round(best, 4), "pairs_kernel_ms": round(kms / max(launches, 1), 4),
+                   "pairs_binned": pairs, "pairs_visited": n * (n - 1) // 2 if label == "full" else None,
+                   "binned_pairs_per_s": round(pairs / (med * 1e-3), 1),
+                   "tiles_opened": _lib.stat("vario_tiles_opened"), "tiles_total": _lib.stat("vario_tiles_total")}
+            print(json.dumps(row), flush=True)
+        if n == 20_000:
+            # the yardstick, alternating with the full-diameter call
+            vg = _vg_struct(gss.ExponentialVariogram(range=300.0), 3)
+            cov = torch.empty((n, n), dtype=torch.float64, device="cuda")
+
+            def run_cov():
+                _lib.check(lib.gss_cov_pairwise(C.byref(vg), C.c_void_p(x.data_ptr()), n, None, n,
+                                                C.c_void_p(cov.data_ptr()), n, _lib.MEM_DEVICE, _lib.current_stream()))
+
+            run_var, _ = bare_variogram(lib, x, z, 20, diam)
+            tv, tc = [], []
+            for _ in range(3):
+                tv.append(timed(run_var, args.reps, warm=1)[0])
+                tc.append(timed(run_cov, args.reps, warm=1)[0])
+            print(json.dumps({"what": "yardstick", "n": n, "variogram_full_ms": [round(t, 4) for t in tv],
+                              "cov_pairwise_ms": [round(t, 4) for t in tc],
+                              "variogram_median_ms": round(statistics.median(tv), 4),
+                              "cov_pairwise_median_ms": round(statistics.median(tc), 4),
+                              "variogram_not_slower": statistics.median(tv) <= statistics.median(tc)}), flush=True)
+            del cov
+
+
+if __name__ == "__main__":
+    main()
