@@ -722,9 +722,10 @@ __device__ __forceinline__ double vg_shape_k(double d2, double inv_range, double
 }
 
 template <int DIM, int KIND, bool UNIT>
-__device__ __forceinline__ double cov_pair_k(const VgDev& v, const double* a, const double* b);
+__device__ __forceinline__ double cov_pair_k(const VgDev& v, const double* a, const double* b, const double* sca);
 template <int DIM, int KIND, bool UNIT>
-__device__ __forceinline__ void cov_pair4_k(const VgDev& v, const double (*a)[DIM], const double* b, double* out);
+__device__ __forceinline__ void cov_pair4_k(const VgDev& v, const double (*a)[DIM], const double* b, double* out,
+                                            const double* sca);
 
 // out[u] = C(a_u, b) for four points a_u and one point b
 template <int DIM>
@@ -749,13 +750,13 @@ __device__ __forceinline__ void cov_pair4(const VgDev& v, const double (*a)[DIM]
 }
 
 // KIND < 0: any model (the general functions above); otherwise one structure of device kind KIND, v.nextra == 0
-// KIND >= 0 (single structure): the coordinates arrive already divided by the radii of the structure's ball (the caller
-// scales each point once, krig_local.hip), so a pair costs three differences and one fused sum of squares instead of
-// a multiply and a select per coordinate; the square root runs on max(d2, 1e-300) without its zero guard (a zero lag
-// is replaced by the total sill afterwards anyway).  KIND < 0: any model, coordinates as they are.
-// UNIT: the caller has also multiplied the coordinates by the model's own scale (kpos_scale below), so the scaled
-// distance IS the argument of the shape -- two multiplications fewer per pair (the moving-neighbourhood kernel scales its
-// 64 neighbours once and evaluates 2 048 pairs).
+// KIND >= 0 (single structure): the square root runs on max(d2, 1e-300) without its zero guard (a zero lag is replaced
+// by the total sill afterwards anyway).  KIND < 0: any model, coordinates as they are.
+// UNIT: every coordinate DIFFERENCE is multiplied by sca[axis] = (1 / radius of the structure's ball) x the model's own
+// scale (kpos_scale below), a wave-uniform factor, so the scaled distance IS the argument of the shape.  The difference
+// is taken first: a product x * sca rounds at 2^-53 |x sca|, and coordinates scaled before the subtraction lose
+// |x| / lag relative accuracy in the lag (samples thousands of ranges from the origin: 1e-13 in C, the one case of
+// tests/kernel_cases.py that missed its bar); the difference of two nearby doubles is exact.
 template <int KIND>
 __device__ __forceinline__ double kpos_scale(const VgDev& v) {
   if (KIND == GSS_VG_GAUSSIAN) return 1.7320508075688772 * v.inv_range;   // exp(-3 (h / r)^2) = exp(-|sqrt(3) h / r|^2)
@@ -788,42 +789,44 @@ __device__ __forceinline__ double vg_shape_kpos(double d2, double inv_range, dou
   return vg_shape(KIND, d2, inv_range, mscale, pw);
 }
 
-// a * b rounded once and never fused into a following addition: the scaled coordinates of a sample and of an estimation
-// point that coincide must be the SAME doubles, so that their distance is exactly zero (C(0) = sill, not sill - nugget)
+// a * b rounded once and never fused into a following addition or subtraction (variography.hip: bin edges and squared
+// increments that must be the same doubles wherever they are formed)
 __device__ __forceinline__ double mul_rounded(double a, double b) {
 #pragma clang fp contract(off)
   const double r = a * b;
   return r;
 }
 
-template <int DIM>
-__device__ __forceinline__ double sqdist_scaled(const double* a, const double* b) {
+template <int DIM, bool UNIT>
+__device__ __forceinline__ double sqdist_scaled(const double* a, const double* b, const double* sca) {
   double acc = 0.0;
 #pragma unroll
   for (int k = 0; k < DIM; ++k) {
-    const double t = a[k] - b[k];
+    const double t0 = a[k] - b[k];            // zero for coincident points whatever the scale: C(0) = sill
+    const double t = UNIT ? t0 * sca[k] : t0;
     acc = fma(t, t, acc);
   }
   return acc;
 }
 
 template <int DIM, int KIND, bool UNIT = false>
-__device__ __forceinline__ double cov_pair_k(const VgDev& v, const double* a, const double* b) {
+__device__ __forceinline__ double cov_pair_k(const VgDev& v, const double* a, const double* b, const double* sca) {
   if (KIND < 0) return cov_pair<DIM>(v, a, b);
-  const double d2 = sqdist_scaled<DIM>(a, b);
+  const double d2 = sqdist_scaled<DIM, UNIT>(a, b, sca);
   const double g = vg_shape_kpos<(KIND < 0 ? 0 : KIND), UNIT>(fmax(d2, 1e-300), v.inv_range, v.mscale, v.pw);
   return d2 <= 0.0 ? v.sill : v.cs * g;
 }
 
 template <int DIM, int KIND, bool UNIT = false>
-__device__ __forceinline__ void cov_pair4_k(const VgDev& v, const double (*a)[DIM], const double* b, double* out) {
+__device__ __forceinline__ void cov_pair4_k(const VgDev& v, const double (*a)[DIM], const double* b, double* out,
+                                            const double* sca) {
   if (KIND < 0) {
     cov_pair4<DIM>(v, a, b, out);
     return;
   }
   double d2[4];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) d2[u] = sqdist_scaled<DIM>(a[u], b);
+  for (int u = 0; u < 4; ++u) d2[u] = sqdist_scaled<DIM, UNIT>(a[u], b, sca);
 #pragma unroll
   for (int u = 0; u < 4; ++u)
     out[u] = v.cs * vg_shape_kpos<(KIND < 0 ? 0 : KIND), UNIT>(fmax(d2[u], 1e-300), v.inv_range, v.mscale, v.pw);
@@ -838,7 +841,8 @@ __device__ __forceinline__ void cov_pair4_k(const VgDev& v, const double (*a)[DI
 // four independent pairs (a[u], b[u]): the paired diagonal tiles of the moving-neighbourhood kernel, where the column
 // a lane works on depends on the row (krig_local.hip)
 template <int DIM, int KIND, bool UNIT = false>
-__device__ __forceinline__ void cov_pairs4_k(const VgDev& v, const double (*a)[DIM], const double (*b)[DIM], double* out) {
+__device__ __forceinline__ void cov_pairs4_k(const VgDev& v, const double (*a)[DIM], const double (*b)[DIM], double* out,
+                                             const double* sca) {
   if (KIND < 0) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) out[u] = cov_pair<DIM>(v, a[u], b[u]);
@@ -846,7 +850,7 @@ __device__ __forceinline__ void cov_pairs4_k(const VgDev& v, const double (*a)[D
   }
   double d2[4];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) d2[u] = sqdist_scaled<DIM>(a[u], b[u]);
+  for (int u = 0; u < 4; ++u) d2[u] = sqdist_scaled<DIM, UNIT>(a[u], b[u], sca);
 #pragma unroll
   for (int u = 0; u < 4; ++u)
     out[u] = v.cs * vg_shape_kpos<(KIND < 0 ? 0 : KIND), UNIT>(fmax(d2[u], 1e-300), v.inv_range, v.mscale, v.pw);

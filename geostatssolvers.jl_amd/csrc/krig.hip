@@ -12,7 +12,7 @@
 // evaluations, and nothing of size n x m ever returns to the host.
 //
 // Kernels:
-//   krig_rhs_kernel       K1+K2: assembles R = [c0; f0] for a chunk of points (coalesced HBM stores)
+//   krig_rhs2_kernel      K1+K2: assembles R = [c0; f0] for a chunk of points (coalesced HBM stores)
 //                         and accumulates the dual-form mean on the fly
 //   krig_quadform_kernel  K3: FP64 MFMA triangular GEMM W' * R fused with the signed column norms
 #include "gss_internal.h"
@@ -79,46 +79,15 @@ __device__ __forceinline__ double cov_d2_select(const VgDev& vg, double d2) {
   return d2 <= 0.0 ? vg.sill : val;
 }
 
-// R[j * ldr + p] = C(x_j, x0_p) for the j rows of segment blockIdx.y
+// R[j * ldr + p] = C(x_j, x0_p) for the j rows of segment (unit % NSEG); units = (point block, row segment), walked with
+// a grid stride.
 // KIND >= 0: single-structure model fixed at compile time -- the same arithmetic as cov_pair (which the fit uses, so
 // a domain point on a datum reproduces that datum's column of C bit for bit) with the model switch folded away; the
 // common models then carry no out-of-line call (the Bessel routines of the rarer Matern orders would otherwise set the
 // register budget of every launch).  KIND < 0: any model, nested or not.
-template <int DIM, int KIND>
-__global__ __launch_bounds__(256) void krig_rhs_kernel(VgDev vg, const double* __restrict__ xd, int n,
-                                                       const double* __restrict__ x0, int64_t m_valid,
-                                                       double* __restrict__ R, int64_t ldr, int seg_len,
-                                                       int nblk) {
-  // units = (point block, row segment), walked with a grid stride
-  for (int unit = blockIdx.x; unit < nblk * NSEG; unit += gridDim.x) {
-    const int seg = unit % NSEG;
-    const int64_t p = (int64_t)(unit / NSEG) * 256 + threadIdx.x;
-    const int64_t pc = p < m_valid ? p : m_valid - 1;
-    double c[DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) c[k] = x0[pc * DIM + k];
-    const int j0 = seg * seg_len;
-    const int j1 = j0 + seg_len < n ? j0 + seg_len : n;
-    double* rp = R + (int64_t)j0 * ldr + p;
-#pragma unroll 4
-    for (int j = j0; j < j1; ++j) {
-      double x[DIM];
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) x[k] = xd[j * DIM + k];
-      if (KIND < 0) {
-        *rp = cov_pair<DIM>(vg, x, c);
-      } else {
-        const double d2 = sqdist_nofma<DIM>(x, c, vg.ir, vg.aniso != 0);
-        *rp = d2 <= 0.0 ? vg.sill : vg.cs * vg_shape(KIND < 0 ? 0 : KIND, d2, vg.inv_range, vg.mscale, vg.pw);
-      }
-      rp += ldr;
-    }
-  }
-}
-
-// The same assembly with two adjacent points per thread: every store instruction writes 16 B per lane (1 KiB per
-// wave and row) instead of 8 -- the store path of this device takes 16-B-per-lane streams at 6.0-6.2 TB/s
-// (tools/probe_hbm.hip) against 4.8 TB/s for the 8-B form of this kernel.  ncols = padded point count (even).
+// Two adjacent points per thread: every store instruction writes 16 B per lane (1 KiB per wave and row) -- the store
+// path of this device takes 16-B-per-lane streams at 6.0-6.2 TB/s (tools/probe_hbm.hip) against 4.8 TB/s for 8-B
+// stores.  ncols = padded point count (even); ldr is even (every workspace is a multiple of 256 columns wide).
 template <int DIM, int KIND>
 __global__ __launch_bounds__(256) void krig_rhs2_kernel(VgDev vg, const double* __restrict__ xd, int n,
                                                         const double* __restrict__ x0, int64_t m_valid,
@@ -163,40 +132,27 @@ __global__ __launch_bounds__(256) void krig_rhs2_kernel(VgDev vg, const double* 
 }
 
 template <int DIM>
-static void launch_krig_rhs(dim3 grid, hipStream_t s, const VgDev& vg, const double* xd, int n, const double* x0,
-                            int64_t m_valid, double* R, int64_t ldr, int seg_len, int nblk) {
-  if ((ldr & 1) == 0) {   // two adjacent points per thread, 16-B stores (every workspace the library makes is even)
-    const int64_t ncols = (int64_t)nblk * 256;
-    const int nblk2 = (int)((ncols + 511) / 512);
-    const dim3 g2((unsigned)(nblk2 * NSEG));
+static int32_t launch_krig_rhs(hipStream_t s, const VgDev& vg, const double* xd, int n, const double* x0,
+                               int64_t m_valid, double* R, int64_t ldr, int seg_len, int nblk) {
+  GSS_REQUIRE((ldr & 1) == 0, "launch_krig_rhs: odd leading dimension %lld (16-B stores need an even one)",
+              (long long)ldr);
+  const int64_t ncols = (int64_t)nblk * 256;
+  const int nblk2 = (int)((ncols + 511) / 512);
+  const dim3 g2((unsigned)(nblk2 * NSEG));
 #define GSS_K1W_LAUNCH(KIND)                                                                                         \
   hipLaunchKernelGGL((krig_rhs2_kernel<DIM, KIND>), g2, dim3(256), 0, s, vg, xd, n, x0, m_valid, R, ldr, seg_len,    \
                      nblk2, ncols)
-    switch (vg.nextra == 0 ? vg.kind : -1) {
-      case GSS_VG_GAUSSIAN: GSS_K1W_LAUNCH(GSS_VG_GAUSSIAN); break;
-      case GSS_VG_EXPONENTIAL: GSS_K1W_LAUNCH(GSS_VG_EXPONENTIAL); break;
-      case GSS_VG_SPHERICAL: GSS_K1W_LAUNCH(GSS_VG_SPHERICAL); break;
-      case VG_MATERN12: GSS_K1W_LAUNCH(VG_MATERN12); break;
-      case VG_MATERN32: GSS_K1W_LAUNCH(VG_MATERN32); break;
-      case VG_MATERN52: GSS_K1W_LAUNCH(VG_MATERN52); break;
-      default: GSS_K1W_LAUNCH(-1); break;
-    }
-#undef GSS_K1W_LAUNCH
-    return;
-  }
-#define GSS_K1_LAUNCH(KIND)                                                                                       \
-  hipLaunchKernelGGL((krig_rhs_kernel<DIM, KIND>), grid, dim3(256), 0, s, vg, xd, n, x0, m_valid, R, ldr, seg_len, \
-                     nblk)
   switch (vg.nextra == 0 ? vg.kind : -1) {
-    case GSS_VG_GAUSSIAN: GSS_K1_LAUNCH(GSS_VG_GAUSSIAN); break;
-    case GSS_VG_EXPONENTIAL: GSS_K1_LAUNCH(GSS_VG_EXPONENTIAL); break;
-    case GSS_VG_SPHERICAL: GSS_K1_LAUNCH(GSS_VG_SPHERICAL); break;
-    case VG_MATERN12: GSS_K1_LAUNCH(VG_MATERN12); break;
-    case VG_MATERN32: GSS_K1_LAUNCH(VG_MATERN32); break;
-    case VG_MATERN52: GSS_K1_LAUNCH(VG_MATERN52); break;
-    default: GSS_K1_LAUNCH(-1); break;
+    case GSS_VG_GAUSSIAN: GSS_K1W_LAUNCH(GSS_VG_GAUSSIAN); break;
+    case GSS_VG_EXPONENTIAL: GSS_K1W_LAUNCH(GSS_VG_EXPONENTIAL); break;
+    case GSS_VG_SPHERICAL: GSS_K1W_LAUNCH(GSS_VG_SPHERICAL); break;
+    case VG_MATERN12: GSS_K1W_LAUNCH(VG_MATERN12); break;
+    case VG_MATERN32: GSS_K1W_LAUNCH(VG_MATERN32); break;
+    case VG_MATERN52: GSS_K1W_LAUNCH(VG_MATERN52); break;
+    default: GSS_K1W_LAUNCH(-1); break;
   }
-#undef GSS_K1_LAUNCH
+#undef GSS_K1W_LAUNCH
+  return GSS_OK;
 }
 
 // Means only, for up to BATCH_NB data vectors at once (conditional simulation: fft.jl:125,187 krige the data and every
@@ -1134,7 +1090,6 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
     const double* x0 = sx.as<double>() + off * dim;
     GSS_TRY(pipe.fetch(off, mv, s));
     const int nblk = (int)(cols / 256);
-    dim3 g1((unsigned)(nblk * NSEG));
     const int nrows = (int)(h->N1pad - h->n);
     {
       ProfScope ps("krig_rhs", s);
@@ -1148,9 +1103,9 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
         }
       } else
       switch (dim) {
-        case 1: launch_krig_rhs<1>(g1, s, h->vg, h->xdata.as<double>(), (int)h->n, x0, mv, Rws, ldr, seg_len, nblk); break;
-        case 2: launch_krig_rhs<2>(g1, s, h->vg, h->xdata.as<double>(), (int)h->n, x0, mv, Rws, ldr, seg_len, nblk); break;
-        default: launch_krig_rhs<3>(g1, s, h->vg, h->xdata.as<double>(), (int)h->n, x0, mv, Rws, ldr, seg_len, nblk); break;
+        case 1: GSS_TRY(launch_krig_rhs<1>(s, h->vg, h->xdata.as<double>(), (int)h->n, x0, mv, Rws, ldr, seg_len, nblk)); break;
+        case 2: GSS_TRY(launch_krig_rhs<2>(s, h->vg, h->xdata.as<double>(), (int)h->n, x0, mv, Rws, ldr, seg_len, nblk)); break;
+        default: GSS_TRY(launch_krig_rhs<3>(s, h->vg, h->xdata.as<double>(), (int)h->n, x0, mv, Rws, ldr, seg_len, nblk)); break;
       }
     GSS_HIP(hipGetLastError());
     // drift rows n..N1-1 and zero rows up to N1pad, plus their share of the mean

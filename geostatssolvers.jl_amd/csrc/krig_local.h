@@ -25,14 +25,13 @@ struct LocalSpec {
   double c00;
 };
 
-// c0 entry of one neighbour.  xs: the neighbour (already divided by the radii of the model's ball when KIND >= 0 and the
-// model is anisotropic, and -- UNIT -- multiplied by the model's own scale, kpos_scale), c: the estimation point as given,
-// cs: the same scaled like xs, sca: the per-axis factor xs and cs carry (UNIT only).  Point support: one covariance;
+// c0 entry of one neighbour.  xs: the neighbour, c and cs: the estimation point, all as given; sca: the per-axis factor
+// of the coordinate differences (UNIT: 1 / radius of the model's ball x kpos_scale, cov_pair_k).  Point support: one covariance;
 // block support: the mean over the sub-cell centres, first axis slowest as in the oracle.
 template <int DIM, int KIND, bool UNIT = false>
 __device__ __forceinline__ double c0_entry(const VgDev& vg, const LocalSpec& sp, const double* xs, const double* c,
                                            const double* cs, const double* sca = nullptr) {
-  if (sp.bsub <= 0) return cov_pair_k<DIM, KIND, UNIT>(vg, xs, cs);
+  if (sp.bsub <= 0) return cov_pair_k<DIM, KIND, UNIT>(vg, xs, cs, sca);
   const int nsub = sp.bsub;
   const int ns = DIM == 1 ? nsub : (DIM == 2 ? nsub * nsub : nsub * nsub * nsub);
   double acc = 0.0;
@@ -44,9 +43,9 @@ __device__ __forceinline__ double c0_entry(const VgDev& vg, const LocalSpec& sp,
       const int ia = q % nsub;
       q /= nsub;
       const double v = c[a] + (((double)ia + 0.5) / (double)nsub - 0.5) * sp.bcell[a];
-      pt[a] = UNIT ? mul_rounded(v, sca[a]) : ((KIND >= 0 && vg.aniso) ? mul_rounded(v, vg.ir[a]) : v);
+      pt[a] = v;
     }
-    acc += cov_pair_k<DIM, KIND, UNIT>(vg, xs, pt);
+    acc += cov_pair_k<DIM, KIND, UNIT>(vg, xs, pt, sca);
   }
   return acc / (double)ns;
 }

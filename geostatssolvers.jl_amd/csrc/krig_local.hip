@@ -299,7 +299,7 @@ void krig_local_mfma_kernel(VgDev vg, LocalSpec sp, const double* __restrict__ x
                                                              double* __restrict__ mean_out,
                                                              double* __restrict__ var_out,
                                                              uint8_t* __restrict__ status_out) {
-  __shared__ double nxs_[K5_WAVES][LMAX_K][3];   // neighbour coordinates, divided by the radii of the model's ball (KIND >= 0)
+  __shared__ double nxs_[K5_WAVES][LMAX_K][3];   // neighbour coordinates
   __shared__ signed char se[LMAX_NC][4];
   __shared__ double S4[2][K5_WAVES][16 * 17];    // diagonal tiles in / inverse factors out, double buffered by step parity
   __shared__ int badflag[2][K5_WAVES];
@@ -337,16 +337,15 @@ void krig_local_mfma_kernel(VgDev vg, LocalSpec sp, const double* __restrict__ x
   }
   const int nc = sp.nc;
   const int g = lane >> 4, c = lane & 15;
-  // (single-structure instantiations: the coordinates carry the radii of the model's ball AND the model's own scale, so
-  //  that the scaled distance is the argument of the shape -- kpos_scale, gss_internal.h)
+  // (single-structure instantiations: coordinate differences are multiplied by sca = 1 / radius of the model's ball x
+  //  the model's own scale, so that the scaled distance is the argument of the shape -- kpos_scale, gss_internal.h)
   constexpr bool UNIT = KIND >= 0;
   double c0[DIM], c0s[DIM], sca[DIM];
 #pragma unroll
   for (int a = 0; a < DIM; ++a) {
     sca[a] = UNIT ? (vg.aniso ? vg.ir[a] : 1.0) * kpos_scale<(KIND < 0 ? 0 : KIND)>(vg) : 1.0;
     c0[a] = x0[p * DIM + a];
-    c0s[a] = UNIT ? mul_rounded(c0[a], sca[a]) : c0[a];   // (rounded products: a contraction with the difference below
-                                                          //  would make a coincident sample's distance nonzero)
+    c0s[a] = c0[a];
   }
   {
     const bool act = lane < cnt;
@@ -355,7 +354,7 @@ void krig_local_mfma_kernel(VgDev vg, LocalSpec sp, const double* __restrict__ x
 #pragma unroll
     for (int a = 0; a < DIM; ++a) {
       xj[a] = act ? xdata[(int64_t)nj * DIM + a] : 0.0;
-      xjs[a] = UNIT ? mul_rounded(xj[a], sca[a]) : xj[a];
+      xjs[a] = xj[a];
       nxs[lane][a] = xjs[a];
     }
     double zz = act ? z[nj] : 0.0;
@@ -418,7 +417,7 @@ void krig_local_mfma_kernel(VgDev vg, LocalSpec sp, const double* __restrict__ x
             xc[r][d] = nxs[blk + c][d];
           }
         }
-        cov_pairs4_k<DIM, KIND, UNIT>(vg, xr, xc, v);
+        cov_pairs4_k<DIM, KIND, UNIT>(vg, xr, xc, v, sca);
         d4_t t0, t1;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -454,7 +453,7 @@ void krig_local_mfma_kernel(VgDev vg, LocalSpec sp, const double* __restrict__ x
           double xcol[DIM], v[4];
 #pragma unroll
           for (int a = 0; a < DIM; ++a) xcol[a] = nxs[col][a];
-          cov_pair4_k<DIM, KIND, UNIT>(vg, xr, xcol, v);
+          cov_pair4_k<DIM, KIND, UNIT>(vg, xr, xcol, v, sca);
 #pragma unroll
           for (int r = 0; r < 4; ++r) T[tile_id(I, J)][r] = v[r];
           if (ragged && J == nt - 1) {

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(64 * SLAB_W) void krig_local_slab_kernel(
     for (int a = 0; a < DIM; ++a) {
       sca[a] = UNIT ? (vg.aniso ? vg.ir[a] : 1.0) * kpos_scale<(KIND < 0 ? 0 : KIND)>(vg) : 1.0;
       c0[a] = x0[p * DIM + a];
-      c0s[a] = UNIT ? mul_rounded(c0[a], sca[a]) : c0[a];
+      c0s[a] = c0[a];
     }
     if (tid == 0) s_bad = 0;
     // neighbour coordinates and the right-hand-side columns (lane = neighbour), staged where the pivot row will live
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(64 * SLAB_W) void krig_local_slab_kernel(
 #pragma unroll
       for (int a = 0; a < DIM; ++a) {
         xj[a] = act ? xdata[(int64_t)nj * DIM + a] : 0.0;
-        xjs[a] = UNIT ? mul_rounded(xj[a], sca[a]) : xj[a];
+        xjs[a] = xj[a];
         nx[j * 3 + a] = xjs[a];
       }
       double zz = act ? z[nj] : 0.0;
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(64 * SLAB_W) void krig_local_slab_kernel(
           const int cj = 16 * j + c;
 #pragma unroll
           for (int a = 0; a < DIM; ++a) xc[a] = nx[cj * 3 + a];
-          cov_pair4_k<DIM, KIND, UNIT>(vg, xr, xc, v);
+          cov_pair4_k<DIM, KIND, UNIT>(vg, xr, xc, v, sca);
           d4_t tl;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
