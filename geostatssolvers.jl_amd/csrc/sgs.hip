@@ -69,6 +69,7 @@ __global__ __launch_bounds__(64) void sgs_weights_kernel(VgDev vg, const double*
   const int64_t p = blockIdx.x;
   const int lane = threadIdx.x;
   if (rank[p] < 0) {  // data cell: never simulated (seq.jl:103)
+    if (filter_after && lane < k) idx_rw[p * k + lane] = -1;   // its list is this kernel's to write: empty
     if (lane == 0) {
       ncond[p] = 0;
       sigma_out[p] = 0.0;
@@ -198,7 +199,8 @@ __global__ __launch_bounds__(SGS_BIG_NT) void sgs_weights_big_kernel(
   const double smarg = sqrt(vg.sill);  // sgs.jl:66
   for (int64_t p = blockIdx.x; p < N; p += gridDim.x) {
     __syncthreads();  // the previous node's shared words have been read
-    if (rank[p] < 0) {  // data cell: never simulated (seq.jl:103)
+    if (rank[p] < 0) {  // data cell: never simulated (seq.jl:103); its list is empty
+      for (int j = tid; j < k; j += SGS_BIG_NT) idx_rw[p * k + j] = -1;
       if (tid == 0) {
         ncond[p] = 0;
         sigma_out[p] = 0.0;

@@ -76,7 +76,7 @@ def split_args(s):
 
 def parse(demangled):
     """'void gss::krig_rhs2_kernel<3, -1>(gss::VgDev, ...)' -> ('krig_rhs2_kernel', ('3', '-1'))."""
-    s = demangled.strip()
+    s = demangled.strip().replace("(anonymous namespace)::", "")   # knn_build.hip keeps its kernels in one
     if s.startswith("void "):
         s = s[5:]
     depth, head = 0, ""
