@@ -20,6 +20,15 @@
 // workgroup's histogram in LDS with one LDS atomic per quantity.  After the tile the window is flushed to the same
 // histogram.  At the end each workgroup writes its histogram to its own slice of a scratch array and a second kernel adds
 // the slices in workgroup order: no global atomic per pair, 64-bit integer counts that do not depend on the schedule.
+//
+// Varioplane (gss_variogram_plane).  The PLANE instantiations of the same kernel bin every kept pair by (direction
+// sector, lag): the sector is found by bisection over the sector boundaries held in LDS (the truth pattern of the
+// header's rule is a prefix, so the bisection returns its count).  The wave-uniform window of lag bins does not carry
+// over -- a near tile scatters over every sector -- but a far tile subtends few sectors and few lags, so consecutive
+// pairs of a lane often share a bin: every lane keeps its current run (bin, count, sums) in registers and sends it to
+// the workgroup's nangles x nlags histogram in LDS, one atomic per quantity, when the bin changes and after the tile.
+// Plain LDS atomics for every pair lost to this by up to 3 x ("Varioplane").  Ordering, check, gather,
+// batches, unit drawing, culling and the reduction are the code of the omnidirectional pass.
 #include "gss_internal.h"
 
 #include <hipcub/hipcub.hpp>
@@ -37,6 +46,9 @@ constexpr int VARIO_MAX_LAGS = 256;
 constexpr int VARIO_MAX_NZ = 8;
 constexpr int VARIO_JW_MAX = 16;   // tiles per work unit: 16, or 4 when there are few batches (more, smaller units)
 constexpr int VARIO_THREADS = 256;
+constexpr int VARIO_PLANE_MAX_NZ = 4;
+constexpr int VARIO_PLANE_MAX_ANGLES = 180;
+constexpr int VARIO_PLANE_MAX_WORDS = 8192;   // nangles nlags (2 + nz): 64 KiB of histogram, two workgroups per CU
 
 struct VarioArgs {
   int64_t n;
@@ -51,6 +63,11 @@ struct VarioArgs {
   double delta, inv_delta;
   double u[3];
   double dtol2, cos2;
+  // varioplane (PLANE instantiations only)
+  int nangles;          // sectors
+  int nsteps;           // ceil(log2(nangles)): bisection steps
+  double e[9];          // 3-D: in-plane axes e1, e2 and the normal
+  double ptol2;         // 3-D: fl(ptol^2), the slab
 };
 
 // the pair key: ((D0 D0) + (D1 D1)) + (D2 D2), one rounding per operation
@@ -99,22 +116,56 @@ __device__ __forceinline__ int vario_bin(const double* edge2, int nlags, double 
 
 __device__ __forceinline__ void lds_add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
 
-template <int DIM, int NZ, bool CRESSIE>
+// (D0 e0 + D1 e1) + D2 e2, one rounding per operation
+__device__ __forceinline__ double vario_project(const double* dl, const double* e) {
+#pragma clang fp contract(off)
+  const double t = dl[0] * e[0] + dl[1] * e[1];
+  return t + dl[2] * e[2];
+}
+
+// Sector of the in-plane lag (a1, a2) by the rule of gss.h: p = c_0 a2, q = s_0 a1; p == q: sector 0; p < q: negate;
+// then the number of s >= 1 with c_s a2 >= s_s a1.  Those s form a prefix 1 .. S (the boundaries turn one way through
+// less than pi), so S is found by bisection: boundary `lo` holds (0 does after the negation), boundary `hi` does not
+// (nangles: there is none).  dir: (c_s, s_s) pairs in LDS; nsteps = ceil(log2(nangles)), the same for every lane.
+__device__ __forceinline__ int vario_sector(const double* dir, int nangles, int nsteps, double a1, double a2) {
+#pragma clang fp contract(off)
+  const double p = dir[0] * a2, q = dir[1] * a1;
+  const bool flip = p < q;
+  a1 = flip ? -a1 : a1;
+  a2 = flip ? -a2 : a2;
+  int lo = 0, hi = nangles;
+  for (int it = 0; it < nsteps; ++it) {
+    const int mid = (lo + hi) >> 1;   // == lo once hi - lo == 1: the comparison below then holds again
+    const double l = dir[2 * mid] * a2, r = dir[2 * mid + 1] * a1;
+    const bool ge = l >= r;
+    lo = ge ? mid : lo;
+    hi = ge ? hi : mid;
+  }
+  return p == q ? 0 : lo;
+}
+
+template <int DIM, int NZ, bool CRESSIE, bool PLANE>
 __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
     const double* __restrict__ xs,      // n x DIM, k-d order
     const double* __restrict__ zs,      // NZ columns of n, k-d order
     const double* __restrict__ blo,     // nb x DIM batch boxes
     const double* __restrict__ bhi,
     VarioArgs A, unsigned long long* __restrict__ unit_counter,
-    unsigned long long* __restrict__ partial) {   // per workgroup: cnt[nlags], ndup, opened, hsum[nlags], zsum[NZ nlags]
+    unsigned long long* __restrict__ partial,     // per workgroup: cnt[nbins], ndup, opened, hsum[nbins], zsum[NZ nbins]
+    const double* __restrict__ dirs) {            // PLANE: (c_s, s_s), 2 nangles doubles
   constexpr int VW = NZ <= 2 ? 6 : 4;   // bins of the register window
   extern __shared__ double smem[];
   const int nlags = A.nlags;
+  const int nbins = PLANE ? A.nangles * nlags : nlags;                    // bins of the histogram: (sector, lag) or lag
   double* s_edge = smem;                                                  // nlags + 1
-  unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + nlags + 1);   // nlags + 2 (ndup, opened)
-  double* s_h = smem + 2 * nlags + 3;                                     // nlags
-  double* s_z = s_h + nlags;                                              // NZ * nlags
-  const int nwords = (nlags + 2) + nlags + NZ * nlags;                    // what is flushed: s_cnt onwards
+  unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + nlags + 1);   // nbins + 2 (ndup, opened)
+  double* s_h = smem + nlags + 1 + nbins + 2;                             // nbins
+  double* s_z = s_h + nbins;                                              // NZ * nbins
+  const int nwords = (nbins + 2) + nbins + NZ * nbins;                    // what is flushed: s_cnt onwards
+  double* s_dir = smem + nlags + 1 + nwords;                              // PLANE: 2 nangles
+  if (PLANE) {
+    for (int t = threadIdx.x; t < 2 * A.nangles; t += VARIO_THREADS) s_dir[t] = dirs[t];
+  }
   // squared bin edges edge2[k] = fl(fl(k delta)^2): two rounded products of exactly represented operands, the same
   // doubles on every workgroup and on the host
   for (int t = threadIdx.x; t <= nlags; t += VARIO_THREADS) {
@@ -173,8 +224,10 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
                                           __builtin_amdgcn_readlane(__double2loint(lb), pick));
       // first bin any pair of this tile can fall into (wave uniform)
       int kb = 0;
-      if (lbJ > 0.0 && lbJ <= emax2) kb = vario_bin(s_edge, nlags, lbJ, gss_sqrt(lbJ), A.inv_delta);
-      kb = __builtin_amdgcn_readfirstlane(kb);
+      if (!PLANE) {
+        if (lbJ > 0.0 && lbJ <= emax2) kb = vario_bin(s_edge, nlags, lbJ, gss_sqrt(lbJ), A.inv_delta);
+        kb = __builtin_amdgcn_readfirstlane(kb);
+      }
       const bool diag = I == J;
 
       const int64_t j = (int64_t)J * 64 + lane;
@@ -196,6 +249,11 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
         for (int c = 0; c < NZ; ++c) wz[c][w] = 0.0;
       }
 
+      int rb = -1;   // PLANE: the lane's current run -- its bin, its pairs, its sums
+      unsigned int rc = 0u;
+      double rh = 0.0, rz[NZ];
+#pragma unroll
+      for (int c = 0; c < NZ; ++c) rz[c] = 0.0;
 #pragma unroll 2
       for (int ii = 0; ii < ni; ++ii) {
         const int64_t i = (int64_t)I * 64 + ii;   // wave uniform: scalar loads
@@ -206,7 +264,7 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
         const bool pairok = vj && (!diag || ii < lane);
         ndup += (pairok && d2 == 0.0) ? 1ull : 0ull;
         bool keep = pairok && d2 > 0.0 && d2 <= emax2;
-        if (A.directional) {
+        if (!PLANE && A.directional) {
 #pragma clang fp contract(off)
           double t = dl[0] * A.u[0];
           if (DIM > 1) t = t + dl[1] * A.u[1];
@@ -225,6 +283,38 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
           const double dz = zs[(int64_t)c * n + i] - zj[c];
           val[c] = CRESSIE ? gss_sqrt(fabs(dz)) : mul_rounded(dz, dz);
         }
+        if constexpr (PLANE) {
+          double a1 = dl[0], a2 = dl[DIM > 1 ? 1 : 0];
+          if (DIM == 3) {
+            a1 = vario_project(dl, A.e);
+            a2 = vario_project(dl, A.e + 3);
+            const double wn = vario_project(dl, A.e + 6);
+            keep = keep && mul_rounded(wn, wn) <= A.ptol2;
+          }
+          const int b = vario_sector(s_dir, A.nangles, A.nsteps, a1, a2) * nlags + k;   // < nbins for every pair
+          // every lane keeps the run of consecutive kept pairs that fall into one bin in registers and sends it to the
+          // histogram when the bin changes
+          if (keep && b != rb) {
+            if (rc != 0u) {
+              atomicAdd(&s_cnt[rb], (unsigned long long)rc);
+              lds_add_f64(&s_h[rb], rh);
+#pragma unroll
+              for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nbins + rb], rz[c]);
+            }
+            rb = b;
+            rc = 0u;
+            rh = 0.0;
+#pragma unroll
+            for (int c = 0; c < NZ; ++c) rz[c] = 0.0;
+          }
+          if (keep) {
+            rc += 1u;
+            rh += h;
+#pragma unroll
+            for (int c = 0; c < NZ; ++c) rz[c] += val[c];
+          }
+          continue;
+        }
 #pragma unroll
         for (int s = 0; s < VW; ++s) {
           const bool m = w == s;
@@ -241,6 +331,12 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
           for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nlags + k], val[c]);
         }
       }
+      if (PLANE && rc != 0u) {   // the last run of the tile
+        atomicAdd(&s_cnt[rb], (unsigned long long)rc);
+        lds_add_f64(&s_h[rb], rh);
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nbins + rb], rz[c]);
+      }
       // flush the window (bins kb .. kb + VW - 1, those that exist)
 #pragma unroll
       for (int s = 0; s < VW; ++s) {
@@ -254,8 +350,8 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
       }
     }
   }
-  if (ndup) atomicAdd(&s_cnt[nlags], ndup);
-  if (lane == 0 && opened) atomicAdd(&s_cnt[nlags + 1], opened);
+  if (ndup) atomicAdd(&s_cnt[nbins], ndup);
+  if (lane == 0 && opened) atomicAdd(&s_cnt[nbins + 1], opened);
   __syncthreads();
   unsigned long long* out = partial + (size_t)blockIdx.x * nwords;
   for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) out[t] = s_cnt[t];
@@ -454,40 +550,68 @@ int32_t vario_morton_index(const double* xdev, int64_t n, unsigned long long* bo
 struct VarioPtrs {
   const double *xs, *zs, *lo, *hi;
   unsigned long long *unit_counter, *partial;
+  const double* dirs;   // varioplane: sector boundaries (device)
 };
 
 // nwg == 0: *resident = workgroups of this instantiation that fit one CU at a time (nothing is launched)
-template <int DIM, int NZ>
-int32_t vario_launch_nz(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds, hipStream_t s, int* resident) {
+template <int DIM, int NZ, bool CRESSIE, bool PLANE>
+int32_t vario_launch_one(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds, hipStream_t s, int* resident) {
+  auto kernel = vario_pairs_kernel<DIM, NZ, CRESSIE, PLANE>;
   if (nwg == 0) {
-    if (A.estimator == GSS_VARIO_CRESSIE)
-      GSS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, vario_pairs_kernel<DIM, NZ, true>, VARIO_THREADS, lds));
-    else
-      GSS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, vario_pairs_kernel<DIM, NZ, false>, VARIO_THREADS, lds));
+    if (PLANE)   // a plane's histogram may pass the 64 KiB a kernel gets without asking
+      GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+    GSS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, kernel, VARIO_THREADS, lds));
     return GSS_OK;
   }
-  if (A.estimator == GSS_VARIO_CRESSIE)
-    hipLaunchKernelGGL((vario_pairs_kernel<DIM, NZ, true>), dim3((unsigned)nwg), dim3(VARIO_THREADS), lds, s, P.xs, P.zs,
-                       P.lo, P.hi, A, P.unit_counter, P.partial);
-  else
-    hipLaunchKernelGGL((vario_pairs_kernel<DIM, NZ, false>), dim3((unsigned)nwg), dim3(VARIO_THREADS), lds, s, P.xs, P.zs,
-                       P.lo, P.hi, A, P.unit_counter, P.partial);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(VARIO_THREADS), lds, s, P.xs, P.zs, P.lo, P.hi, A,
+                     P.unit_counter, P.partial, P.dirs);
   GSS_HIP(hipGetLastError());
   return GSS_OK;
+}
+
+template <int DIM, int NZ, bool PLANE>
+int32_t vario_launch_nz(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds, hipStream_t s, int* resident) {
+  if (A.estimator == GSS_VARIO_CRESSIE) return vario_launch_one<DIM, NZ, true, PLANE>(P, A, nwg, lds, s, resident);
+  return vario_launch_one<DIM, NZ, false, PLANE>(P, A, nwg, lds, s, resident);
 }
 
 template <int DIM>
 int32_t vario_launch(const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
                      int* resident) {
   switch (nz) {
-    case 1: return vario_launch_nz<DIM, 1>(P, A, nwg, lds, s, resident);
-    case 2: return vario_launch_nz<DIM, 2>(P, A, nwg, lds, s, resident);
-    case 3: return vario_launch_nz<DIM, 3>(P, A, nwg, lds, s, resident);
-    case 4: return vario_launch_nz<DIM, 4>(P, A, nwg, lds, s, resident);
-    case 5: return vario_launch_nz<DIM, 5>(P, A, nwg, lds, s, resident);
-    case 6: return vario_launch_nz<DIM, 6>(P, A, nwg, lds, s, resident);
-    case 7: return vario_launch_nz<DIM, 7>(P, A, nwg, lds, s, resident);
-    default: return vario_launch_nz<DIM, 8>(P, A, nwg, lds, s, resident);
+    case 1: return vario_launch_nz<DIM, 1, false>(P, A, nwg, lds, s, resident);
+    case 2: return vario_launch_nz<DIM, 2, false>(P, A, nwg, lds, s, resident);
+    case 3: return vario_launch_nz<DIM, 3, false>(P, A, nwg, lds, s, resident);
+    case 4: return vario_launch_nz<DIM, 4, false>(P, A, nwg, lds, s, resident);
+    case 5: return vario_launch_nz<DIM, 5, false>(P, A, nwg, lds, s, resident);
+    case 6: return vario_launch_nz<DIM, 6, false>(P, A, nwg, lds, s, resident);
+    case 7: return vario_launch_nz<DIM, 7, false>(P, A, nwg, lds, s, resident);
+    default: return vario_launch_nz<DIM, 8, false>(P, A, nwg, lds, s, resident);
+  }
+}
+
+template <int DIM>
+int32_t vario_launch_plane(const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
+                           int* resident) {
+  switch (nz) {
+    case 1: return vario_launch_nz<DIM, 1, true>(P, A, nwg, lds, s, resident);
+    case 2: return vario_launch_nz<DIM, 2, true>(P, A, nwg, lds, s, resident);
+    case 3: return vario_launch_nz<DIM, 3, true>(P, A, nwg, lds, s, resident);
+    default: return vario_launch_nz<DIM, 4, true>(P, A, nwg, lds, s, resident);
+  }
+}
+
+// every instantiation behind one call: plane (dim 2, 3) or lag bins only (dim 1 .. 3)
+int32_t vario_launch_any(bool plane, int dim, const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds,
+                         hipStream_t s, int* resident) {
+  if (plane)
+    return dim == 2 ? vario_launch_plane<2>(P, A, nz, nwg, lds, s, resident)
+                    : vario_launch_plane<3>(P, A, nz, nwg, lds, s, resident);
+  switch (dim) {
+    case 1: return vario_launch<1>(P, A, nz, nwg, lds, s, resident);
+    case 2: return vario_launch<2>(P, A, nz, nwg, lds, s, resident);
+    default: return vario_launch<3>(P, A, nz, nwg, lds, s, resident);
   }
 }
 
@@ -570,10 +694,18 @@ double fit_residual(const FitData& D, const std::vector<double>& f, double a, do
 // For a fixed range the objective is a quadratic in (a, b) = (nugget, sill - nugget) over the cone a >= 0, b >= 0,
 // (1 - frac) a <= frac b.  Its minimum is the unconstrained one if feasible, else it lies on one of the three edges
 // (each a one-variable least squares) or at their common vertex, the origin.  Returns the objective.
+double fit_inner_f(const FitData& D, const std::vector<double>& f, double* a_out, double* b_out);
+
 double fit_inner(const FitData& D, int kind, double nu, double range, double* a_out, double* b_out) {
   const size_t m = D.h.size();
   std::vector<double> f(m);
   for (size_t k = 0; k < m; ++k) f[k] = fit_shape(kind, D.h[k] / range, nu);
+  return fit_inner_f(D, f, a_out, b_out);
+}
+
+// the cone solve for given shape values f_k (isotropic: f(h_k / range); anisotropic: f of the scaled lag)
+double fit_inner_f(const FitData& D, const std::vector<double>& f, double* a_out, double* b_out) {
+  const size_t m = D.h.size();
   double sw = 0.0, swf = 0.0, swg = 0.0;
   for (size_t k = 0; k < m; ++k) {
     sw += D.w[k];
@@ -669,58 +801,204 @@ double fit_kind(const FitData& D, int kind, double nu, double* nugget, double* s
   return obest;
 }
 
+// ---- geometric anisotropy in the plane (gss_variogram_fit_aniso) -----------------------------------------------------
+// Outer parameters u = (log r1, log(r2 / r1) <= 0, theta); for fixed u the scaled lag of bin k is
+// h_k sqrt(cos^2(phi_k - theta) / r1^2 + sin^2(phi_k - theta) / r2^2) and the rest is the cone solve above.
+struct AnisoFit {
+  const FitData& D;
+  const std::vector<double>& phi;
+  int kind;
+  double nu;
+  double ulo, uhi;   // bounds of log r1
+  mutable std::vector<double> f;
+
+  double eval(const double* u, double* a, double* b) const {
+    const double r1 = std::exp(u[0]), r2 = r1 * std::exp(u[1]);
+    const size_t m = D.h.size();
+    f.resize(m);
+    for (size_t k = 0; k < m; ++k) {
+      const double c = std::cos(phi[k] - u[2]) / r1, sn = std::sin(phi[k] - u[2]) / r2;
+      f[k] = fit_shape(kind, D.h[k] * std::sqrt(c * c + sn * sn), nu);
+    }
+    return fit_inner_f(D, f, a, b);
+  }
+  double eval(const double* u) const {
+    double a, b;
+    return eval(u, &a, &b);
+  }
+
+  // golden section along u + t dir over t in [lo, hi] to a width of 1e-8 in the parameter that moves most (u holds
+  // logarithms and an angle: a relative width for the radii); both ends are offered as well, so that a minimum on a
+  // bound (ratio 1) is returned as the bound.  u and *o (the objective at u) are updated when something better is found.
+  void line(double* u, const double* dir, double lo, double hi, double* o) const {
+    const double gr = 0.6180339887498949;
+    const double u0[3] = {u[0], u[1], u[2]};
+    double scale = 0.0;
+    for (int c = 0; c < 3; ++c) scale = std::fabs(dir[c]) > scale ? std::fabs(dir[c]) : scale;
+    double best = *o, tbest = 0.0;
+    auto at = [&](double t) {
+      for (int c = 0; c < 3; ++c) u[c] = u0[c] + t * dir[c];
+      if (u[1] > 0.0) u[1] = 0.0;   // (rounding at the bound)
+      const double val = eval(u);
+      if (val < best) {
+        best = val;
+        tbest = t;
+      }
+      return val;
+    };
+    at(lo);
+    at(hi);
+    double x1 = hi - gr * (hi - lo), x2 = lo + gr * (hi - lo);
+    double o1 = at(x1), o2 = at(x2);
+    for (int it = 0; it < 200 && (hi - lo) * scale > 1e-8; ++it) {
+      if (o1 <= o2) {
+        hi = x2;
+        x2 = x1;
+        o2 = o1;
+        x1 = hi - gr * (hi - lo);
+        o1 = at(x1);
+      } else {
+        lo = x1;
+        x1 = x2;
+        o1 = o2;
+        x2 = lo + gr * (hi - lo);
+        o2 = at(x2);
+      }
+    }
+    for (int c = 0; c < 3; ++c) u[c] = u0[c] + tbest * dir[c];
+    if (u[1] > 0.0) u[1] = 0.0;
+    *o = best;
+  }
+
+  // the part [lo, hi] of t for which u + t dir stays inside the bounds of log r1 and of the log ratio
+  void clip(const double* u, const double* dir, double* lo, double* hi) const {
+    const double blo[2] = {ulo, -2.772588722239781}, bhi[2] = {uhi, 0.0};   // ratio in [1/16, 1]
+    for (int c = 0; c < 2; ++c) {
+      if (dir[c] == 0.0) continue;
+      double t0 = (blo[c] - u[c]) / dir[c], t1 = (bhi[c] - u[c]) / dir[c];
+      if (t0 > t1) {
+        const double t = t0;
+        t0 = t1;
+        t1 = t;
+      }
+      *lo = *lo < t0 ? t0 : *lo;
+      *hi = *hi > t1 ? t1 : *hi;
+    }
+  }
+
+  // Cyclic line searches from u with brackets w that follow the steps taken (twice the last move, at least a quarter
+  // of the last bracket), and after every cycle one search along the cycle's net move, which is what carries the point
+  // along a valley that no axis follows; until a whole cycle moves nothing by more than 1e-10.
+  double refine(double* u, const double* w0) const {
+    double w[3] = {w0[0], w0[1], w0[2]};
+    double o = eval(u);
+    for (int cycle = 0; cycle < 400; ++cycle) {
+      const double start[3] = {u[0], u[1], u[2]};
+      for (int i = 0; i < 3; ++i) {
+        double dir[3] = {0.0, 0.0, 0.0};
+        dir[i] = 1.0;
+        double lo = -w[i], hi = w[i];
+        clip(u, dir, &lo, &hi);
+        const double before = u[i];
+        if (hi > lo) line(u, dir, lo, hi, &o);
+        const double step = std::fabs(u[i] - before);
+        const double shrunk = 0.25 * w[i], grown = 2.0 * step;
+        w[i] = grown > shrunk ? grown : shrunk;
+        if (w[i] < 1e-7) w[i] = 1e-7;
+      }
+      double net[3], moved = 0.0;
+      for (int c = 0; c < 3; ++c) {
+        net[c] = u[c] - start[c];
+        moved = std::fabs(net[c]) > moved ? std::fabs(net[c]) : moved;
+      }
+      if (moved <= 1e-10) break;
+      double lo = -1.0, hi = 8.0;
+      clip(u, net, &lo, &hi);
+      if (hi > lo) line(u, net, lo, hi, &o);
+    }
+    return o;
+  }
+};
+
+constexpr int ANISO_NTHETA = 36, ANISO_NR1 = 32, ANISO_NRATIO = 16, ANISO_STARTS = 4;
+
+// -> objective; u = (log r1, log ratio, theta in [0, pi))
+double fit_kind_aniso(const FitData& D, const std::vector<double>& phi, int kind, double nu, double* nugget,
+                      double* sill, double* u_out) {
+  const double pi = 3.14159265358979323846;
+  double hmin = D.h[0], hmax = D.h[0];
+  for (double v : D.h) {
+    hmin = v < hmin ? v : hmin;
+    hmax = v > hmax ? v : hmax;
+  }
+  AnisoFit F{D, phi, kind, nu, std::log(0.25 * hmin), std::log(4.0 * hmax), {}};
+  const double w0[3] = {(F.uhi - F.ulo) / (ANISO_NR1 - 1), 2.772588722239781 / (ANISO_NRATIO - 1), pi / ANISO_NTHETA};
+  // the grid; the ANISO_STARTS best points (ties: the first met) start a refinement each
+  double so[ANISO_STARTS], su[ANISO_STARTS][3];
+  int ns = 0;
+  for (int it = 0; it < ANISO_NTHETA; ++it) {
+    for (int ir = 0; ir < ANISO_NR1; ++ir) {
+      for (int iq = 0; iq < ANISO_NRATIO; ++iq) {
+        if (iq == ANISO_NRATIO - 1 && it > 0) continue;   // ratio 1: every angle is the same model
+        const double u[3] = {F.ulo + w0[0] * ir, iq == ANISO_NRATIO - 1 ? 0.0 : -2.772588722239781 + w0[1] * iq,
+                             w0[2] * it};
+        const double o = F.eval(u);
+        int pos = ns;
+        while (pos > 0 && o < so[pos - 1]) --pos;
+        if (pos >= ANISO_STARTS) continue;
+        const int last = ns < ANISO_STARTS ? ns : ANISO_STARTS - 1;
+        for (int q = last; q > pos; --q) {
+          so[q] = so[q - 1];
+          for (int c = 0; c < 3; ++c) su[q][c] = su[q - 1][c];
+        }
+        so[pos] = o;
+        for (int c = 0; c < 3; ++c) su[pos][c] = u[c];
+        if (ns < ANISO_STARTS) ++ns;
+      }
+    }
+  }
+  double obest = 0.0;
+  for (int q = 0; q < ns; ++q) {
+    const double o = F.refine(su[q], w0);
+    if (q == 0 || o < obest) {
+      obest = o;
+      for (int c = 0; c < 3; ++c) u_out[c] = su[q][c];
+    }
+  }
+  u_out[2] = u_out[2] - pi * std::floor(u_out[2] / pi);
+  if (!(u_out[2] < pi)) u_out[2] = 0.0;
+  double a, b;
+  obest = F.eval(u_out, &a, &b);
+  *nugget = a;
+  *sill = a + b;
+  return obest;
+}
+
 }  // namespace
 
 }  // namespace gss
 
 using namespace gss;
 
-extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
-                                           int32_t nlags, double maxlag, const double* direction, double dtol,
-                                           double cos_atol, int32_t estimator, int64_t* count, double* lagsum,
-                                           double* zsum, int64_t* nduplicates, int32_t mem, void* stream) {
-  GSS_ENTRY();
-  GSS_REQUIRE(x != nullptr && z != nullptr && count != nullptr && lagsum != nullptr && zsum != nullptr &&
-                  nduplicates != nullptr, "gss_variogram_empirical: NULL argument");
-  GSS_REQUIRE(dim >= 1 && dim <= 3, "gss_variogram_empirical: dim %d outside 1..3", dim);
-  GSS_REQUIRE(n >= 2 && n < (int64_t)INT32_MAX, "gss_variogram_empirical: n = %lld samples (2 .. 2^31 - 2)",
-              (long long)n);
-  GSS_REQUIRE(nz >= 1 && nz <= VARIO_MAX_NZ, "gss_variogram_empirical: nz %d outside 1..%d", nz, VARIO_MAX_NZ);
-  GSS_REQUIRE(nlags >= 1 && nlags <= VARIO_MAX_LAGS, "gss_variogram_empirical: nlags %d outside 1..%d", nlags,
-              VARIO_MAX_LAGS);
-  GSS_REQUIRE(std::isfinite(maxlag) && maxlag > 0.0, "gss_variogram_empirical: maxlag must be positive and finite");
-  GSS_REQUIRE(estimator == GSS_VARIO_MATHERON || estimator == GSS_VARIO_CRESSIE,
-              "gss_variogram_empirical: unknown estimator %d", estimator);
-  GSS_REQUIRE(mem == GSS_MEM_HOST || mem == GSS_MEM_DEVICE, "gss_variogram_empirical: bad mem %d", mem);
-  VarioArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.dtol2 = __builtin_huge_val();
-  if (direction != nullptr) {
-    // the direction is a HOST array of `dim` doubles in both memory modes (it is a parameter, not data)
-    double nn = 0.0;
-    for (int a = 0; a < dim; ++a) {
-      GSS_REQUIRE(std::isfinite(direction[a]), "gss_variogram_empirical: direction is not finite");
-      nn += direction[a] * direction[a];
-      A.u[a] = direction[a];
-    }
-    GSS_REQUIRE(std::fabs(std::sqrt(nn) - 1.0) <= 1e-12, "gss_variogram_empirical: direction is not a unit vector "
-                "(norm %.17g)", std::sqrt(nn));
-    GSS_REQUIRE(dtol > 0.0 && !std::isnan(dtol), "gss_variogram_empirical: dtol must be positive (+inf: no band)");
-    GSS_REQUIRE(cos_atol >= 0.0 && cos_atol <= 1.0, "gss_variogram_empirical: cos_atol outside [0, 1]");
-    A.directional = 1;
-    A.dtol2 = dtol * dtol;
-    A.cos2 = cos_atol * cos_atol;
-  }
+namespace {
+
+// The pass over the pairs that gss_variogram_empirical and gss_variogram_plane share: checks of the common arguments,
+// staging, the finite-input check, the ordering, the gather, the grid, the pair kernel, the reduction and the way home.
+// A: what the caller has filled in of the kernel's arguments (direction or sectors); nbins: bins of the histogram
+// (nlags, or nangles nlags); dirs: the plane's sector boundaries (host), else NULL.
+int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, const double* z, int32_t nz, int32_t nlags, double maxlag, int32_t estimator, VarioArgs& A, int64_t nbins, const double* dirs,
+                  int64_t* count, double* lagsum, double* zsum, int64_t* nduplicates, int32_t mem, void* stream) {
+  const bool plane = dirs != nullptr;
   // squared bin edges edge2[k] = fl(fl(k delta)^2): the kernel forms the same doubles; only the ends are checked here
   const double delta = maxlag / (double)nlags;
   {
     volatile double e1 = delta * delta, en = (double)nlags * delta;
     volatile double en2 = en * en;
-    GSS_REQUIRE(e1 > 0.0 && std::isfinite(en2), "gss_variogram_empirical: maxlag^2 leaves the range of a double");
+    GSS_REQUIRE(e1 > 0.0 && std::isfinite(en2), "%s: maxlag^2 leaves the range of a double", who);
   }
 
   hipStream_t s = to_stream(stream);
-  Staged sx, sz, scount, slag, szsum, sdup;
+  Staged sx, sz, scount, slag, szsum, sdup, sdirs;
   GSS_TRY(sx.in(x, sizeof(double) * (size_t)n * dim, mem, s));
   GSS_TRY(sz.in(z, sizeof(double) * (size_t)n * nz, mem, s));
   DevBuf zs, flags, partial;
@@ -757,6 +1035,11 @@ extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t d
   P.zs = zs.as<double>();
   P.lo = ix.lo.as<double>();
   P.hi = ix.hi.as<double>();
+  P.dirs = nullptr;
+  if (plane) {   // the sector boundaries: a host array in both memory modes
+    GSS_TRY(sdirs.in(dirs, sizeof(double) * 2 * (size_t)A.nangles, GSS_MEM_HOST, s));
+    P.dirs = sdirs.as<double>();
+  }
   A.n = n;
   A.nb = ix.nb;
   A.jw = ix.nb < 512 ? 4 : VARIO_JW_MAX;   // below ~32 000 samples 16-tile units are too few to fill the device
@@ -770,17 +1053,13 @@ extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t d
   A.delta = delta;
   A.inv_delta = 1.0 / delta;
   P.unit_counter = d_flags;
-  const size_t nwords = (size_t)(nlags + 2) + nlags + (size_t)nz * nlags;
-  const size_t lds = sizeof(double) * ((size_t)nlags + 1 + nwords);
+  const size_t nwords = (size_t)(nbins + 2) + nbins + (size_t)nz * nbins;
+  const size_t lds = sizeof(double) * ((size_t)nlags + 1 + nwords + (plane ? 2 * (size_t)A.nangles : 0));
   // the grid: as many workgroups as are resident at a time for this instantiation (registers and LDS decide: 6 per CU
   // for one value column, 2 for eight), fewer when there are not two units per wave; a workgroup beyond that would only
   // start once the others have emptied the counter
   int resident = 0;
-  switch (dim) {
-    case 1: GSS_TRY(vario_launch<1>(P, A, nz, 0, lds, s, &resident)); break;
-    case 2: GSS_TRY(vario_launch<2>(P, A, nz, 0, lds, s, &resident)); break;
-    default: GSS_TRY(vario_launch<3>(P, A, nz, 0, lds, s, &resident)); break;
-  }
+  GSS_TRY(vario_launch_any(plane, dim, P, A, nz, 0, lds, s, &resident));
   if (resident < 1) resident = 1;
   const int64_t nunits = (int64_t)A.nb * A.nchunks;
   const int64_t want = (nunits + 7) / 8, cap = (int64_t)ncu * resident;
@@ -792,9 +1071,9 @@ extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t d
   GSS_TRY(partial.alloc(sizeof(unsigned long long) * nwords * (size_t)nwg));
   P.partial = partial.as<unsigned long long>();
 
-  GSS_TRY(scount.out(count, sizeof(int64_t) * nlags, mem));
-  GSS_TRY(slag.out(lagsum, sizeof(double) * nlags, mem));
-  GSS_TRY(szsum.out(zsum, sizeof(double) * nlags * nz, mem));
+  GSS_TRY(scount.out(count, sizeof(int64_t) * nbins, mem));
+  GSS_TRY(slag.out(lagsum, sizeof(double) * nbins, mem));
+  GSS_TRY(szsum.out(zsum, sizeof(double) * nbins * nz, mem));
   GSS_TRY(sdup.out(nduplicates, sizeof(int64_t), mem));
   if (!g_vario_stats) {
     GSS_HIP(hipHostMalloc(reinterpret_cast<void**>(&g_vario_stats), 2 * sizeof(int64_t), hipHostMallocDefault));
@@ -802,15 +1081,12 @@ extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t d
     GSS_HIP(hipEventCreateWithFlags(&g_vario_event, hipEventDisableTiming));
   }
   {
-    ProfScope prof("vario_pairs", s);
-    switch (dim) {
-      case 1: GSS_TRY(vario_launch<1>(P, A, nz, nwg, lds, s, nullptr)); break;
-      case 2: GSS_TRY(vario_launch<2>(P, A, nz, nwg, lds, s, nullptr)); break;
-      default: GSS_TRY(vario_launch<3>(P, A, nz, nwg, lds, s, nullptr)); break;
-    }
+    ProfScope prof(plane ? "vario_plane" : "vario_pairs", s);
+    GSS_TRY(vario_launch_any(plane, dim, P, A, nz, nwg, lds, s, nullptr));
   }
+  // (a histogram of nbins bins is reduced as one of nbins lags: sector s of the plane at s * nlags)
   hipLaunchKernelGGL(vario_reduce_kernel, dim3((unsigned)nwords), dim3(256), 0, s, P.partial, nwg,
-                     (int)nlags, (int)nz, scount.as<int64_t>(), slag.as<double>(), szsum.as<double>(),
+                     (int)nbins, (int)nz, scount.as<int64_t>(), slag.as<double>(), szsum.as<double>(),
                      sdup.as<int64_t>(), g_vario_stats, d_bad);
   GSS_HIP(hipGetLastError());
   GSS_HIP(hipEventRecord(g_vario_event, s));
@@ -819,16 +1095,125 @@ extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t d
   // (the index, the ordered values and the slices are scratch: released into the block cache, whose re-use is ordered
   //  behind this call by the stream chain)
   if (mem == GSS_MEM_HOST) {
-    GSS_HIP(hipMemcpyAsync(count, scount.p, sizeof(int64_t) * nlags, hipMemcpyDeviceToHost, s));
-    GSS_HIP(hipMemcpyAsync(lagsum, slag.p, sizeof(double) * nlags, hipMemcpyDeviceToHost, s));
-    GSS_HIP(hipMemcpyAsync(zsum, szsum.p, sizeof(double) * nlags * nz, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(count, scount.p, sizeof(int64_t) * nbins, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(lagsum, slag.p, sizeof(double) * nbins, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(zsum, szsum.p, sizeof(double) * nbins * nz, hipMemcpyDeviceToHost, s));
     GSS_HIP(hipMemcpyAsync(nduplicates, sdup.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     GSS_HIP(hipStreamSynchronize(s));
     // a non-finite input is found on the device and reported through the outputs (gss.h); here they have arrived
-    GSS_REQUIRE(*nduplicates >= 0, "gss_variogram_empirical: a coordinate or a value is NaN or infinite (missing values "
-                "are dropped by the caller: a pair takes part only if both of its values exist)");
+    GSS_REQUIRE(*nduplicates >= 0, "%s: a coordinate or a value is NaN or infinite (missing values "
+                "are dropped by the caller: a pair takes part only if both of its values exist)", who);
   }
   return GSS_OK;
+}
+
+// the arguments the two calls share, checked before anything touches the device
+int32_t vario_check_args(const char* who, const double* x, int64_t n, int32_t dim, int32_t mindim, const double* z,
+                         int32_t nz, int32_t maxnz, int32_t nlags, double maxlag, int32_t estimator,
+                         const int64_t* count, const double* lagsum, const double* zsum, const int64_t* nduplicates,
+                         int32_t mem) {
+  GSS_REQUIRE(x != nullptr && z != nullptr && count != nullptr && lagsum != nullptr && zsum != nullptr &&
+                  nduplicates != nullptr, "%s: NULL argument", who);
+  GSS_REQUIRE(dim >= mindim && dim <= 3, "%s: dim %d outside %d..3", who, dim, mindim);
+  GSS_REQUIRE(n >= 2 && n < (int64_t)INT32_MAX, "%s: n = %lld samples (2 .. 2^31 - 2)", who, (long long)n);
+  GSS_REQUIRE(nz >= 1 && nz <= maxnz, "%s: nz %d outside 1..%d", who, nz, maxnz);
+  GSS_REQUIRE(nlags >= 1 && nlags <= VARIO_MAX_LAGS, "%s: nlags %d outside 1..%d", who, nlags, VARIO_MAX_LAGS);
+  GSS_REQUIRE(std::isfinite(maxlag) && maxlag > 0.0, "%s: maxlag must be positive and finite", who);
+  GSS_REQUIRE(estimator == GSS_VARIO_MATHERON || estimator == GSS_VARIO_CRESSIE, "%s: unknown estimator %d", who,
+              estimator);
+  GSS_REQUIRE(mem == GSS_MEM_HOST || mem == GSS_MEM_DEVICE, "%s: bad mem %d", who, mem);
+  return GSS_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
+                                           int32_t nlags, double maxlag, const double* direction, double dtol,
+                                           double cos_atol, int32_t estimator, int64_t* count, double* lagsum,
+                                           double* zsum, int64_t* nduplicates, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_TRY(vario_check_args("gss_variogram_empirical", x, n, dim, 1, z, nz, VARIO_MAX_NZ, nlags, maxlag, estimator, count,
+                           lagsum, zsum, nduplicates, mem));
+  VarioArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.dtol2 = __builtin_huge_val();
+  if (direction != nullptr) {
+    // the direction is a HOST array of `dim` doubles in both memory modes (it is a parameter, not data)
+    double nn = 0.0;
+    for (int a = 0; a < dim; ++a) {
+      GSS_REQUIRE(std::isfinite(direction[a]), "gss_variogram_empirical: direction is not finite");
+      nn += direction[a] * direction[a];
+      A.u[a] = direction[a];
+    }
+    GSS_REQUIRE(std::fabs(std::sqrt(nn) - 1.0) <= 1e-12, "gss_variogram_empirical: direction is not a unit vector "
+                "(norm %.17g)", std::sqrt(nn));
+    GSS_REQUIRE(dtol > 0.0 && !std::isnan(dtol), "gss_variogram_empirical: dtol must be positive (+inf: no band)");
+    GSS_REQUIRE(cos_atol >= 0.0 && cos_atol <= 1.0, "gss_variogram_empirical: cos_atol outside [0, 1]");
+    A.directional = 1;
+    A.dtol2 = dtol * dtol;
+    A.cos2 = cos_atol * cos_atol;
+  }
+  return vario_run("gss_variogram_empirical", x, n, dim, z, nz, nlags, maxlag, estimator, A, nlags, nullptr,
+                   count, lagsum, zsum, nduplicates, mem, stream);
+}
+
+extern "C" int32_t gss_variogram_plane(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
+                                       int32_t nlags, double maxlag, int32_t nangles, const double* dirs,
+                                       const double* basis, double ptol, int32_t estimator, int64_t* count,
+                                       double* lagsum, double* zsum, int64_t* nduplicates, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  const char* who = "gss_variogram_plane";
+  GSS_REQUIRE(dim != 1, "gss_variogram_plane: dim 1 has no directions (a plane needs dim 2 or 3)");
+  GSS_TRY(vario_check_args(who, x, n, dim, 2, z, nz, VARIO_PLANE_MAX_NZ, nlags, maxlag, estimator, count, lagsum, zsum,
+                           nduplicates, mem));
+  GSS_REQUIRE(dirs != nullptr, "gss_variogram_plane: NULL argument (dirs)");
+  GSS_REQUIRE(nangles >= 2 && nangles <= VARIO_PLANE_MAX_ANGLES, "gss_variogram_plane: nangles %d outside 2..%d", nangles,
+              VARIO_PLANE_MAX_ANGLES);
+  GSS_REQUIRE((int64_t)nangles * nlags * (2 + nz) <= VARIO_PLANE_MAX_WORDS,
+              "gss_variogram_plane: nangles * nlags * (2 + nz) = %lld exceeds the limit of %d histogram words (split the "
+              "value columns or the lags over several calls)", (long long)nangles * nlags * (2 + nz),
+              VARIO_PLANE_MAX_WORDS);
+  // sector boundaries: unit vectors whose angles increase strictly, each step and the whole span by less than pi
+  // (cross and dot product of neighbours give the step's angle in (0, pi); the steps add up to the span)
+  double span = 0.0;
+  for (int a = 0; a < nangles; ++a) {
+    const double c = dirs[2 * a], sn = dirs[2 * a + 1];
+    GSS_REQUIRE(std::isfinite(c) && std::isfinite(sn) && std::fabs(std::sqrt(c * c + sn * sn) - 1.0) <= 1e-12,
+                "gss_variogram_plane: dirs[%d] is not a unit vector", a);
+    if (a == 0) continue;
+    const double cross = dirs[2 * a - 2] * sn - dirs[2 * a - 1] * c, dot = dirs[2 * a - 2] * c + dirs[2 * a - 1] * sn;
+    GSS_REQUIRE(cross > 0.0, "gss_variogram_plane: the angles of dirs are not strictly increasing (sector %d)", a);
+    span += std::atan2(cross, dot);
+  }
+  GSS_REQUIRE(span < 3.14159265358979323846, "gss_variogram_plane: dirs span %.17g radians: the sectors partition a "
+              "half-circle, theta_last - theta_0 < pi", span);
+  VarioArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.dtol2 = __builtin_huge_val();
+  A.nangles = nangles;
+  A.nsteps = 0;
+  while ((1 << A.nsteps) < nangles) ++A.nsteps;
+  A.ptol2 = __builtin_huge_val();
+  if (dim == 2) {
+    GSS_REQUIRE(basis == nullptr, "gss_variogram_plane: basis must be NULL for dim 2 (the plane is the plane of the "
+                "samples)");
+  } else {
+    GSS_REQUIRE(basis != nullptr, "gss_variogram_plane: dim 3 needs a basis (e1, e2 and the normal of the plane)");
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b <= a; ++b) {
+        double d = 0.0;
+        for (int k = 0; k < 3; ++k) d += basis[3 * a + k] * basis[3 * b + k];
+        GSS_REQUIRE(std::isfinite(d) && std::fabs(d - (a == b ? 1.0 : 0.0)) <= 1e-12,
+                    "gss_variogram_plane: basis is not orthonormal (vectors %d and %d: %.17g)", b, a, d);
+      }
+    }
+    for (int k = 0; k < 9; ++k) A.e[k] = basis[k];
+    GSS_REQUIRE(ptol > 0.0 && !std::isnan(ptol), "gss_variogram_plane: ptol must be positive (+inf: no slab)");
+    volatile double p2 = ptol * ptol;
+    A.ptol2 = p2;
+  }
+  return vario_run(who, x, n, dim, z, nz, nlags, maxlag, estimator, A, (int64_t)nangles * nlags, dirs,
+                   count, lagsum, zsum, nduplicates, mem, stream);
 }
 
 // gss_shutdown: the page-locked tile counter and its event
@@ -903,5 +1288,89 @@ extern "C" int32_t gss_variogram_fit(const double* h, const double* gamma, const
     best->inv_radii[a] = 1.0;
     best->rotation[4 * a] = 1.0;
   }
+  return GSS_OK;
+}
+
+extern "C" int32_t gss_variogram_fit_aniso(const double* h, const double* phi, const double* gamma, const int64_t* count,
+                                           int32_t nbins, const int32_t* kinds, int32_t nkinds, double nu,
+                                           int32_t weighting, double max_nugget_frac, gss_variogram_t* best,
+                                           double* objective) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr && phi != nullptr && gamma != nullptr && count != nullptr && kinds != nullptr &&
+                  best != nullptr && objective != nullptr, "gss_variogram_fit_aniso: NULL argument");
+  GSS_REQUIRE(nbins >= 1 && nbins <= 65536, "gss_variogram_fit_aniso: nbins %d outside 1..65536", nbins);
+  GSS_REQUIRE(nkinds >= 1 && nkinds <= 64, "gss_variogram_fit_aniso: nkinds %d outside 1..64", nkinds);
+  GSS_REQUIRE(weighting >= GSS_FIT_W_COUNT && weighting <= GSS_FIT_W_UNIFORM,
+              "gss_variogram_fit_aniso: unknown weighting %d", weighting);
+  GSS_REQUIRE(max_nugget_frac >= 0.0 && max_nugget_frac <= 1.0,
+              "gss_variogram_fit_aniso: max_nugget_frac outside [0, 1]");
+  bool matern = false;
+  for (int i = 0; i < nkinds; ++i) {
+    if (kinds[i] == GSS_VG_POWER) {
+      set_error("gss_variogram_fit_aniso: the power model has no sill and no range to search; only the stationary "
+                "kinds are fitted");
+      return GSS_ERR_UNSUPPORTED;
+    }
+    GSS_REQUIRE(kinds[i] >= GSS_VG_GAUSSIAN && kinds[i] <= GSS_VG_SINEHOLE, "gss_variogram_fit_aniso: unknown kind %d",
+                kinds[i]);
+    matern = matern || kinds[i] == GSS_VG_MATERN;
+  }
+  if (matern) GSS_REQUIRE(nu > 0.0 && nu <= 50.0, "gss_variogram_fit_aniso: Matern order must lie in (0, 50]");
+  FitData D;
+  std::vector<double> ph;
+  D.frac = max_nugget_frac;
+  for (int k = 0; k < nbins; ++k) {
+    if (count[k] <= 0) continue;
+    GSS_REQUIRE(std::isfinite(h[k]) && h[k] > 0.0 && std::isfinite(gamma[k]) && std::isfinite(phi[k]),
+                "gss_variogram_fit_aniso: bin %d has pairs but no finite positive lag / finite ordinate / finite angle",
+                k);
+    const double c = (double)count[k];
+    D.h.push_back(h[k]);
+    D.g.push_back(gamma[k]);
+    ph.push_back(phi[k]);
+    D.w.push_back(weighting == GSS_FIT_W_COUNT ? c : (weighting == GSS_FIT_W_COUNT_OVER_H2 ? c / (h[k] * h[k]) : 1.0));
+  }
+  GSS_REQUIRE(D.h.size() >= 4, "gss_variogram_fit_aniso: fewer than four bins hold pairs");
+  int ibest = -1;
+  double nbest = 0.0, sbest = 0.0, ubest[3] = {0.0, 0.0, 0.0};
+  for (int i = 0; i < nkinds; ++i) {
+    double ng, sl, u[3];
+    objective[i] = fit_kind_aniso(D, ph, kinds[i], nu, &ng, &sl, u);
+    if (!(sl > 0.0)) {   // the ordinates admit no model of this kind with a positive sill
+      objective[i] = std::nan("");
+      continue;
+    }
+    if (ibest < 0 || objective[i] < objective[ibest]) {
+      ibest = i;
+      nbest = ng;
+      sbest = sl;
+      for (int c = 0; c < 3; ++c) ubest[c] = u[c];
+    }
+  }
+  GSS_REQUIRE(ibest >= 0, "gss_variogram_fit_aniso: no kind fits these ordinates with a positive sill");
+  std::memset(best, 0, sizeof(*best));
+  best->kind = kinds[ibest];
+  best->dim = 0;   // left to the caller
+  best->sill = sbest;
+  best->nugget = nbest;
+  best->nu = kinds[ibest] == GSS_VG_MATERN ? nu : 1.0;
+  for (int a = 0; a < 3; ++a) {
+    best->inv_radii[a] = 1.0;
+    best->rotation[4 * a] = 1.0;
+  }
+  const double r1 = std::exp(ubest[0]);
+  if (ubest[1] == 0.0) {   // ratio 1: the isotropic form
+    best->range = r1;
+    return GSS_OK;
+  }
+  const double r2 = r1 * std::exp(ubest[1]), c = std::cos(ubest[2]), sn = std::sin(ubest[2]);
+  best->aniso = 2;
+  best->range = 1.0;
+  best->inv_radii[0] = 1.0 / r1;
+  best->inv_radii[1] = 1.0 / r2;
+  best->rotation[0] = c;
+  best->rotation[1] = -sn;
+  best->rotation[3] = sn;
+  best->rotation[4] = c;
   return GSS_OK;
 }

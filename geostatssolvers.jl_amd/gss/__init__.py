@@ -12,6 +12,7 @@ from .solvers import (FFTGS, LUGS, SGS, ExpWeight, IDWSolver, KrigingSolver, LWR
 from .variograms import (CubicVariogram, ExponentialVariogram, GaussianVariogram, MaternVariogram, MetricBall,
                          NestedVariogram, PentasphericalVariogram, PowerVariogram, SineHoleVariogram,
                          SphericalVariogram)
-from .variography import DirectionalVariogram, EmpiricalVariogram, EmpiricalVariogramResult, fit
+from .variography import (DirectionalVariogram, EmpiricalVariogram, EmpiricalVariogramResult, EmpiricalVarioplane,
+                          EmpiricalVarioplaneResult, fit, fit_anisotropic)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -659,6 +659,72 @@ class HipEngine:
                                   float(max_nugget_frac), C.byref(best), ptr(obj)))
         return names[best.kind], best.sill, best.nugget, best.range, best.nu, obj
 
+    @staticmethod
+    def variogram_plane(x, z, nlags, maxlag, dirs, basis=None, ptol=float("inf"), estimator=0):
+        """gss_variogram_plane: x (n, d), d = 2 or 3, z (nz, n), dirs (nangles, 2) = (cos, sin) of the sectors' lower
+        boundaries (host), basis (3, 3) = e1, e2, normal for d = 3 (host) -> count (nangles, nlags) int64,
+        lagsum (nangles, nlags), zsum (nz, nangles, nlags), nduplicates.  Memory as in variogram_empirical."""
+        l = _lib.lib()
+        dev = is_torch(x) and x.is_cuda
+        if dev != (is_torch(z) and z.is_cuda):
+            raise ValueError("x and z must live in the same memory space")
+        x = _prep_in(x)
+        z = _prep_in(z)
+        if x.ndim == 1:
+            x = x[:, None]
+        n, d = x.shape
+        z = z.reshape(-1, n)
+        nz = z.shape[0]
+        nlags = int(nlags)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+        if dirs.ndim != 2 or dirs.shape[1] != 2:
+            raise ValueError("dirs is an (nangles, 2) array of (cos, sin)")
+        nang = dirs.shape[0]
+        b = None
+        if basis is not None:
+            b = np.ascontiguousarray(basis, dtype=np.float64)
+            if b.shape != (3, 3):
+                raise ValueError("basis is a (3, 3) array: e1, e2 and the normal as rows")
+        shape = (nang, max(nlags, 0))
+        if dev:
+            import torch
+            count = torch.empty(shape, dtype=torch.int64, device=x.device)
+            lagsum = torch.empty(shape, dtype=torch.float64, device=x.device)
+            zsum = torch.empty((nz,) + shape, dtype=torch.float64, device=x.device)
+            ndup = torch.empty(1, dtype=torch.int64, device=x.device)
+        else:
+            count = np.empty(shape, dtype=np.int64)
+            lagsum = np.empty(shape)
+            zsum = np.empty((nz,) + shape)
+            ndup = np.zeros(1, dtype=np.int64)
+        check(l.gss_variogram_plane(ptr(x), n, d, ptr(z), nz, nlags, float(maxlag), nang, ptr(dirs), ptr(b), float(ptol),
+                                    int(estimator), ptr(count), ptr(lagsum), ptr(zsum), ptr(ndup),
+                                    MEM_DEVICE if dev else MEM_HOST, current_stream()))
+        return count, lagsum, zsum, (ndup if dev else int(ndup[0]))
+
+    @staticmethod
+    def variogram_fit_aniso(h, phi, gamma, count, kinds, nu=1.0, weighting=0, max_nugget_frac=1.0):
+        """gss_variogram_fit_aniso (host code of the library, no device): per-bin vectors -> (kind name, sill, nugget,
+        (r1, r2) or None when the fit is isotropic, theta, isotropic range, nu, objective per kind)."""
+        l = _lib.load()
+        h = np.ascontiguousarray(h, dtype=np.float64).reshape(-1)
+        p = np.ascontiguousarray(phi, dtype=np.float64).reshape(-1)
+        g = np.ascontiguousarray(gamma, dtype=np.float64).reshape(-1)
+        c = np.ascontiguousarray(count, dtype=np.int64).reshape(-1)
+        if not h.shape == p.shape == g.shape == c.shape:
+            raise ValueError("h, phi, gamma and count must have one length")
+        names = {v: k for k, v in _lib._KINDS.items()}
+        kk = np.ascontiguousarray([_lib._KINDS[k] for k in kinds], dtype=np.int32)
+        obj = np.empty(len(kk))
+        best = _lib.Variogram()
+        check(l.gss_variogram_fit_aniso(ptr(h), ptr(p), ptr(g), ptr(c), h.size, ptr(kk), len(kk), float(nu),
+                                        int(weighting), float(max_nugget_frac), C.byref(best), ptr(obj)))
+        if best.aniso == 0:
+            return names[best.kind], best.sill, best.nugget, None, 0.0, best.range, best.nu, obj
+        radii = (1.0 / best.inv_radii[0], 1.0 / best.inv_radii[1])
+        theta = float(np.arctan2(best.rotation[3], best.rotation[0]))
+        return names[best.kind], best.sill, best.nugget, radii, theta, best.range, best.nu, obj
+
 
 def default_engine():
     return HipEngine

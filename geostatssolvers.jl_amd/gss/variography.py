@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .engine import default_engine
-from .variograms import GAUSSIAN_NUGGET_EPS, VariogramModel
+from .variograms import GAUSSIAN_NUGGET_EPS, MetricBall, VariogramModel
 
 ESTIMATORS = {"matheron": 0, "cressie": 1}
 WEIGHTINGS = {"count": 0, "count/h2": 1, "uniform": 2}
@@ -137,4 +137,141 @@ def fit(kind_or_kinds, g, weighting="count", nu=1.0, max_nugget_frac=1.0, return
         else:
             regularize = False
     model = VariogramModel(kind, float(sill), float(nugget), float(rng), float(order), None, regularize)
+    return (model, dict(zip(names, obj))) if return_objectives else model
+
+
+# ---- varioplane: every direction sector in one pass (gss_variogram_plane) and the anisotropic fit --------------------
+@dataclass
+class EmpiricalVarioplaneResult:
+    """One variable's empirical variogram by direction sector: row s of the (nangs, nlags) arrays is the sector
+    [angles[s], angles[s + 1]) of directions modulo pi (the last one ends at angles[0] + pi).  The sectors partition
+    the half-circle: over s the counts add up to those of EmpiricalVariogram.  Empty bins hold NaN."""
+    angles: np.ndarray        # lower boundaries of the sectors, radians
+    midangles: np.ndarray
+    abscissa: np.ndarray
+    ordinate: np.ndarray
+    counts: np.ndarray
+    nduplicates: int
+    maxlag: float
+    estimator: str = "matheron"
+    var: str = ""
+
+    @property
+    def nangs(self):
+        return int(self.counts.shape[0])
+
+    @property
+    def nlags(self):
+        return int(self.counts.shape[1])
+
+    def sector(self, s):
+        """Sector s as an EmpiricalVariogramResult: what `fit` takes for one direction."""
+        return EmpiricalVariogramResult(self.abscissa[s].copy(), self.ordinate[s].copy(), self.counts[s].copy(),
+                                        self.nduplicates, self.maxlag, self.estimator, self.var)
+
+
+def plane_basis(normal):
+    """e1, e2, n (rows) for the plane with the given normal: n = normal / |normal|; e1 = the coordinate axis on which n
+    has its smallest absolute component (the first such axis), made orthogonal to n and normalised; e2 = n x e1, so
+    that (e1, e2, n) is right-handed.  For normal = z this is e1 = x, e2 = y: angles are those of the x-y plane."""
+    nrm = np.asarray(normal, dtype=np.float64).reshape(-1)
+    if nrm.size != 3 or not np.all(np.isfinite(nrm)) or not np.any(nrm != 0.0):
+        raise ValueError("normal must be a non-zero finite 3-vector")
+    nrm = nrm / np.sqrt((nrm * nrm).sum())
+    a = np.zeros(3)
+    a[int(np.argmin(np.abs(nrm)))] = 1.0
+    e1 = a - (a @ nrm) * nrm
+    e1 = e1 / np.sqrt((e1 * e1).sum())
+    e2 = np.cross(nrm, e1)
+    e2 = e2 / np.sqrt((e2 * e2).sum())
+    return np.ascontiguousarray(np.stack([e1, e2, nrm]))
+
+
+PLANE_MAX_COLUMNS = 4          # gss.h: value columns per gss_variogram_plane call
+PLANE_MAX_WORDS = 8192         # gss.h: nangles * nlags * (2 + nz)
+
+
+def EmpiricalVarioplane(data, var_or_vars, nangs=18, nlags=20, maxlag=None, offset=0.0, normal=None,
+                        ptol=float("inf"), estimator="matheron", engine=None):
+    """Empirical variogram of every one of `nangs` equal direction sectors of the half-circle, in one pass over the
+    pairs: sector s holds the directions [offset + s pi / nangs, offset + (s + 1) pi / nangs) modulo pi (angles in
+    radians, counter-clockwise from the first axis of the plane).  2-D tables: the plane of the samples (`normal` is
+    refused).  3-D tables: `normal` is required; the plane is spanned by `plane_basis(normal)` and only pairs whose
+    separation lies within `ptol` of the plane take part (inf: all, projected onto it).  One variable ->
+    EmpiricalVarioplaneResult, several -> dict.  Missing values are dropped per variable as in EmpiricalVariogram."""
+    if estimator not in ESTIMATORS:
+        raise ValueError(f"estimator {estimator!r}: 'matheron' or 'cressie'")
+    engine = engine or default_engine()
+    single = isinstance(var_or_vars, str)
+    names = [var_or_vars] if single else list(var_or_vars)
+    if not names:
+        raise ValueError("no variable given")
+    nangs, nlags = int(nangs), int(nlags)
+    if nangs < 2:
+        raise ValueError("a varioplane has at least 2 sectors")
+    x = np.ascontiguousarray(data.domain.centroids(), dtype=np.float64)
+    d = x.shape[1]
+    if d == 2:
+        if normal is not None:
+            raise ValueError("normal describes a plane in 3-D; 2-D samples lie in their own plane")
+        basis = None
+    elif d == 3:
+        if normal is None:
+            raise ValueError("3-D samples need the normal of the plane the directions are taken in")
+        basis = plane_basis(normal)
+    else:
+        raise ValueError(f"a varioplane needs 2-D or 3-D samples, these are {d}-D")
+    cols = [np.asarray(data[v], dtype=np.float64) for v in names]
+    if maxlag is None:
+        maxlag = _default_maxlag(x)
+    angles = float(offset) + np.arange(nangs) * (math.pi / nangs)
+    dirs = np.ascontiguousarray(np.stack([np.cos(angles), np.sin(angles)], axis=1))
+    percall = max(1, min(PLANE_MAX_COLUMNS, PLANE_MAX_WORDS // max(nangs * nlags, 1) - 2))
+    groups = {}                                    # finite mask -> variables that share it
+    for i, c in enumerate(cols):
+        groups.setdefault(np.isfinite(c).tobytes(), []).append(i)
+    out = [None] * len(names)
+    for members in groups.values():
+        keep = np.isfinite(cols[members[0]])
+        xs = x if keep.all() else np.ascontiguousarray(x[keep])
+        for lo in range(0, len(members), percall):
+            part = members[lo:lo + percall]
+            z = np.ascontiguousarray(np.stack([cols[i][keep] for i in part]))
+            count, lagsum, zsum, ndup = engine.variogram_plane(xs, z, nlags, maxlag, dirs, basis, ptol,
+                                                               ESTIMATORS[estimator])
+            with np.errstate(invalid="ignore", divide="ignore"):
+                absc = np.where(count > 0, lagsum / count, np.nan)
+            for r, i in enumerate(part):
+                out[i] = EmpiricalVarioplaneResult(angles.copy(), angles + 0.5 * math.pi / nangs, absc,
+                                                   _ordinate(estimator, zsum[r], count), count.copy(), int(ndup),
+                                                   float(maxlag), estimator, names[i])
+    return out[0] if single else dict(zip(names, out))
+
+
+def fit_anisotropic(kind_or_kinds, plane, weighting="count", nu=1.0, max_nugget_frac=1.0, return_objectives=False,
+                    engine=None):
+    """Weighted least-squares fit of 2-D geometric anisotropy to an EmpiricalVarioplaneResult
+    (gss_variogram_fit_aniso; every bin enters with the mid-angle of its sector).  Returns a VariogramModel with
+    `radii = (r1, r2)`, r1 >= r2, and `rotation` = the counter-clockwise rotation by the fitted azimuth theta of r1
+    (what `Kind(MetricBall((r1, r2), theta))` builds), or the isotropic model when the fitted ratio is 1.  The
+    Gaussian `nugget - 1e-6` rule is that of `fit`."""
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting {weighting!r}: one of {tuple(WEIGHTINGS)}")
+    engine = engine or default_engine()
+    kinds = [kind_or_kinds] if isinstance(kind_or_kinds, str) or callable(kind_or_kinds) else list(kind_or_kinds)
+    names = [_kind_name(k) for k in kinds]
+    phi = np.broadcast_to(np.asarray(plane.midangles, dtype=np.float64)[:, None], plane.counts.shape)
+    kind, sill, nugget, radii, theta, rng, order, obj = engine.variogram_fit_aniso(
+        plane.abscissa, phi, plane.ordinate, plane.counts, names, nu, WEIGHTINGS[weighting], max_nugget_frac)
+    regularize = True
+    if kind == "gaussian":
+        if nugget >= GAUSSIAN_NUGGET_EPS:
+            nugget -= GAUSSIAN_NUGGET_EPS
+        else:
+            regularize = False
+    if radii is None:
+        model = VariogramModel(kind, float(sill), float(nugget), float(rng), float(order), None, regularize)
+    else:
+        ball = MetricBall(radii, float(theta))
+        model = VariogramModel(kind, float(sill), float(nugget), 1.0, float(order), ball.radii, regularize, ball.rotation)
     return (model, dict(zip(names, obj))) if return_objectives else model

@@ -43,7 +43,7 @@ import GeoStatsBase: solve, preprocess, solvesingle
 
 export KrigingSolverHIP, IDWSolverHIP, LWRSolverHIP, ExpWeight, TricubeWeight, FFTGSHIP, LUGSHIP, SGSHIP
 export krig_fit, krig_predict_device!, fftgs_realize_device!, bind_device
-export empirical_variogram, fit_variogram
+export empirical_variogram, fit_variogram, empirical_varioplane, fit_anisotropic
 
 const libgss = get(ENV, "LIBGSS_HIP", "libgss_hip.so")
 
@@ -960,6 +960,97 @@ function fit_variogram(kinds, abscissa::Vector{Float64}, ordinate::Vector{Float6
   T = GAMMA_CONSTRUCTORS[b.kind+1]
   nug = T === GaussianVariogram ? max(b.nugget - GAUSSIAN_NUGGET_EPS[], 0.0) : b.nugget
   T === MaternVariogram ? T(sill=b.sill, nugget=nug, range=b.range, order=b.nu) : T(sill=b.sill, nugget=nug, range=b.range)
+end
+
+"""
+    empirical_varioplane(data, vars; nangs=18, nlags=20, maxlag=nothing, offset=0.0, normal=nothing, ptol=Inf,
+                         estimator=:matheron)
+
+Empirical variogram of every one of `nangs` equal direction sectors of the half-circle in ONE pass over the pairs
+(gss_variogram_plane): sector s holds the directions [offset + (s-1)π/nangs, offset + sπ/nangs) modulo π.  2-D data: the
+plane of the samples (`normal` is refused); 3-D data: `normal` is required, the in-plane axes are built as the twin's
+`plane_basis` builds them (e1 = the coordinate axis with the smallest |component| of the unit normal, made orthogonal to
+it; e2 = n × e1) and pairs farther than `ptol` from the plane are left out.  Up to 4 variables measured on the same
+samples with `nangs * nlags * (2 + length(vars)) <= 8192`.  Returns `(angles, midangles, abscissa, ordinate, counts,
+nduplicates)` with `nlags × nangs` matrices (sector s in column s); `ordinate` is a Dict for several variables.
+"""
+function empirical_varioplane(data, vars; nangs::Integer=18, nlags::Integer=20, maxlag=nothing, offset::Real=0.0,
+                              normal=nothing, ptol::Real=Inf, estimator::Symbol=:matheron)
+  names = vars isa Symbol ? [vars] : collect(Symbol, vars)
+  tab = Tables.columns(values(data))
+  cols = [Tables.getcolumn(tab, v) for v in names]
+  keep = [i for i in 1:nelements(domain(data)) if all(c -> !ismissing(c[i]) && isfinite(ustrip(c[i])), cols)]
+  X = coordmatrix(domain(data))[:, keep]
+  d, n = size(X)
+  d == 2 && !isnothing(normal) && throw(ArgumentError("normal describes a plane in 3-D; 2-D samples lie in their own plane"))
+  d == 3 && isnothing(normal) && throw(ArgumentError("3-D samples need the normal of the plane"))
+  basis = nothing
+  if d == 3
+    nrm = collect(Float64, normal) ./ sqrt(sum(abs2, normal))
+    a = zeros(3); a[argmin(abs.(nrm))] = 1.0
+    e1 = a .- sum(a .* nrm) .* nrm; e1 ./= sqrt(sum(abs2, e1))
+    e2 = [nrm[2] * e1[3] - nrm[3] * e1[2], nrm[3] * e1[1] - nrm[1] * e1[3], nrm[1] * e1[2] - nrm[2] * e1[1]]
+    e2 ./= sqrt(sum(abs2, e2))
+    basis = vcat(e1, e2, nrm)
+  end
+  Z = Matrix{Float64}(undef, n, length(names))
+  for (c, col) in enumerate(cols), (r, i) in enumerate(keep)
+    Z[r, c] = Float64(ustrip(col[i]))
+  end
+  lag = isnothing(maxlag) ? 0.1 * sqrt(sum(abs2, maximum(X, dims=2) .- minimum(X, dims=2))) : Float64(ustrip(maxlag))
+  angles = [Float64(offset) + (s - 1) * π / nangs for s in 1:nangs]
+  dirs = Matrix{Float64}(undef, 2, nangs)               # (cos, sin) of sector s at dirs + 2 (s - 1)
+  for s in 1:nangs
+    dirs[1, s] = cos(angles[s]); dirs[2, s] = sin(angles[s])
+  end
+  est = estimator == :cressie ? Int32(1) : Int32(0)
+  count = Matrix{Int64}(undef, nlags, nangs)
+  lagsum = Matrix{Float64}(undef, nlags, nangs)
+  zsum = Array{Float64,3}(undef, nlags, nangs, length(names))
+  ndup = Ref{Int64}(0)
+  GC.@preserve X Z dirs basis check(ccall((:gss_variogram_plane, libgss), Int32,
+    (Ptr{Float64}, Int64, Int32, Ptr{Float64}, Int32, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Int32,
+     Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int32, Ptr{Cvoid}),
+    X, Int64(n), Int32(d), Z, Int32(length(names)), Int32(nlags), lag, Int32(nangs), dirs,
+    isnothing(basis) ? C_NULL : pointer(basis), Float64(ptol), est, count, lagsum, zsum, ndup, GSS_MEM_HOST, C_NULL))
+  abscissa = [c > 0 ? s / c : NaN for (s, c) in zip(lagsum, count)]
+  gamma(m) = [c == 0 ? NaN : est == 0 ? s / 2c : (s / c)^4 / (2 * (0.457 + 0.494 / c)) for (s, c) in zip(m, count)]
+  ordinate = vars isa Symbol ? gamma(zsum[:, :, 1]) : Dict(v => gamma(zsum[:, :, c]) for (c, v) in enumerate(names))
+  (angles=angles, midangles=angles .+ π / (2nangs), abscissa=abscissa, ordinate=ordinate, counts=count, nduplicates=ndup[])
+end
+
+"""
+    fit_anisotropic(kinds, plane; var=nothing, weighting=:count, order=1.0, maxnuggetfrac=1.0)
+
+Fit of 2-D geometric anisotropy (gss_variogram_fit_aniso, host code of the library) to the result of
+`empirical_varioplane` (`var` selects the variable when it holds several): returns
+`Kind(MetricBall((r1, r2), Angle2d(θ)); sill, nugget)` with r1 >= r2, or the isotropic model when the fitted ratio is 1.
+The Gaussian nugget rule is that of `fit_variogram`.
+"""
+function fit_anisotropic(kinds, plane; var=nothing, weighting::Symbol=:count, order::Real=1.0, maxnuggetfrac::Real=1.0)
+  ks = kinds isa Type ? [kinds] : collect(kinds)
+  codes = Int32[something(findfirst(==(k), GAMMA_CONSTRUCTORS), 8) - 1 for k in ks]      # anything else: GSS_VG_POWER
+  w = weighting == :count ? Int32(0) : weighting == :uniform ? Int32(2) : Int32(1)
+  g = plane.ordinate isa Dict ? plane.ordinate[var] : plane.ordinate
+  h = vec(collect(Float64, plane.abscissa))
+  gam = vec(collect(Float64, g))
+  cnt = vec(collect(Int64, plane.counts))
+  phi = vec(Float64[plane.midangles[s] for _ in 1:size(plane.counts, 1), s in 1:size(plane.counts, 2)])
+  best = Ref(cvariogram(GaussianVariogram(), 1))
+  objective = Vector{Float64}(undef, length(codes))
+  check(ccall((:gss_variogram_fit_aniso, libgss), Int32,
+    (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int32, Ptr{Int32}, Int32, Float64, Int32, Float64,
+     Ptr{GssVariogram}, Ptr{Float64}), h, phi, gam, cnt, Int32(length(cnt)), codes, Int32(length(codes)), Float64(order),
+    w, Float64(maxnuggetfrac), best, objective))
+  b = best[]
+  T = GAMMA_CONSTRUCTORS[b.kind+1]
+  nug = T === GaussianVariogram ? max(b.nugget - GAUSSIAN_NUGGET_EPS[], 0.0) : b.nugget
+  if b.aniso == 0
+    return T === MaternVariogram ? T(sill=b.sill, nugget=nug, range=b.range, order=b.nu) : T(sill=b.sill, nugget=nug, range=b.range)
+  end
+  # [RECALL] Meshes exports Rotations' Angle2d (its docs write `Rotate(Angle2d(π/2))`); rotation[1], rotation[4] = cos, sin
+  ball = MetricBall((1 / b.inv_radii[1], 1 / b.inv_radii[2]), Angle2d(atan(b.rotation[4], b.rotation[1])))
+  T === MaternVariogram ? T(ball; sill=b.sill, nugget=nug, order=b.nu) : T(ball; sill=b.sill, nugget=nug)
 end
 
 # ---- several GPUs: one worker process per GPU ---------------------------------------------------------------------

@@ -147,8 +147,8 @@ int32_t gss_trim_pool(void);
  * single-launch factorisation left through its bounded wait and was repeated on the launch-per-block path),
  * "gemm_launches_128" / "gemm_launches_64" (FP64 matrix products launched so far on the 128 x 128 and on the 64 x 64
  * tile kernel: which of the two a given shape ran on),
- * "vario_tiles_total" / "vario_tiles_opened" (batch pairs of the last gss_variogram_empirical and how many of them its
- * box bound let through),
+ * "vario_tiles_total" / "vario_tiles_opened" (batch pairs of the last gss_variogram_empirical or gss_variogram_plane
+ * and how many of them its box bound let through),
  * "ipc_route" (how the last gss_state_ipc_import reached the owner's device: 0 same device, 1 visible peer, 2 not among
  * the visible devices, 3 refused -- visible but not peer-accessible). */
 int32_t gss_stat(const char* name, int64_t* value);
@@ -248,6 +248,61 @@ enum { GSS_FIT_W_COUNT = 0, GSS_FIT_W_COUNT_OVER_H2 = 1, GSS_FIT_W_UNIFORM = 2 }
 int32_t gss_variogram_fit(const double* h, const double* gamma, const int64_t* count, int32_t nlags,
                           const int32_t* kinds, int32_t nkinds, double nu, int32_t weighting,
                           double max_nugget_frac, gss_variogram_t* best, double* objective);
+
+/* gss_variogram_plane (varioplane): the same pass over the pairs, every kept pair binned by (direction sector, lag).
+ *   The sectors partition the half-circle of directions in a plane, so over the sectors the counts add up exactly to
+ *   those of the omnidirectional gss_variogram_empirical on the same inputs (in 3-D: when there is no slab).
+ *   Everything gss_variogram_empirical states above holds word for word: the pair key d2, the bin edges
+ *   edge2[k] = fl(fl(k delta)^2), the rule edge2[k] < d2 <= edge2[k + 1], duplicates counted apart, the finite-input
+ *   rule in both memory modes, the batch ordering (Morton below 32 768 samples, k-d from there), tile culling against
+ *   edge2[nlags] with the vario_tiles_* counters and GSS_VARIO_CULL, both estimators, Euclidean distance only.  The lag
+ *   bin always uses the full d2.
+ *   dirs       2 nangles doubles IN HOST MEMORY whatever `mem` is (a parameter, like `direction`):
+ *              (c_s, s_s) = (cos theta_s, sin theta_s), s = 0 .. nangles - 1, the LOWER boundaries of the sectors.  The
+ *              angles are strictly increasing with theta_{nangles-1} - theta_0 < pi and each (c_s, s_s) is a unit vector
+ *              to 1e-12; anything else is GSS_ERR_INVALID.  Sector s is [theta_s, theta_{s+1}), the last one
+ *              [theta_{nangles-1}, theta_0 + pi), directions taken modulo pi.
+ *   In-plane components (a1, a2) of the lag D = x_i - x_j:
+ *              dim = 2: `basis` must be NULL and (a1, a2) = (D0, D1).
+ *              dim = 3: `basis` is 9 host doubles e1, e2, nrm (three vectors, orthonormal to 1e-12):
+ *                       a1 = (D0 e1_0 + D1 e1_1) + D2 e1_2, a2 likewise with e2, w = D . nrm likewise; rounded operations
+ *                       in that order, no FMA.  The pair is kept iff fl(w w) <= fl(ptol^2); ptol = +inf: no slab, the
+ *                       lag is projected onto the plane.  (ptol is not read when dim = 2.)
+ *              dim = 1 is refused.
+ *   Sector of a kept pair:
+ *              1. p = fl(c_0 a2), q = fl(s_0 a1).
+ *              2. If p == q the sector is 0.
+ *              3. Otherwise, if p < q, negate (a1, a2) (exact).
+ *              4. The sector is the number of s in 1 .. nangles - 1 with fl(c_s a2) >= fl(s_s a1).
+ *              The rule is total, does not depend on which sample of a pair comes first, is closed at a sector's lower
+ *              boundary and open at its upper one, and equals floor(((atan2(a2, a1) - theta_0) mod pi) / Delta) for
+ *              uniform sectors up to pairs within rounding of a boundary.
+ *   Limits     nangles in 2 .. 180, nlags in 1 .. 256, nz in 1 .. 4 and nangles * nlags * (2 + nz) <= 8192 (the
+ *              histogram of a workgroup: 64 KiB of the 160 KiB of local memory, so that two workgroups share a compute
+ *              unit); beyond any of them GSS_ERR_INVALID with a message that names the limit.
+ *   Outputs    count[nangles x nlags] (sector s at count + s * nlags), lagsum likewise,
+ *              zsum[nz x nangles x nlags] (column c at zsum + c * nangles * nlags), *nduplicates (all pairs with
+ *              d2 == 0, whatever the slab).  Counts are exact and the same on every run. */
+int32_t gss_variogram_plane(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz, int32_t nlags,
+                            double maxlag, int32_t nangles, const double* dirs, const double* basis, double ptol,
+                            int32_t estimator, int64_t* count, double* lagsum, double* zsum, int64_t* nduplicates,
+                            int32_t mem, void* stream);
+/* gss_variogram_fit_aniso (host code, no device): 2-D geometric anisotropy fitted to a varioplane,
+ *   gamma(h, phi) = nugget + (sill - nugget) f(h sqrt(cos^2(phi - theta) / r1^2 + sin^2(phi - theta) / r2^2)),
+ *   r1 >= r2 > 0, theta in [0, pi), f as in gss_variogram_fit.  Per bin (nbins of them, any order): h (the abscissa
+ *   lagsum / count), phi (the caller's angle for the bin's sector, radians: the front-ends pass the mid-sector angle),
+ *   gamma and count; bins with count <= 0 are ignored.  kinds, nu, weighting, max_nugget_frac, objective as in
+ *   gss_variogram_fit.  For fixed (theta, r1, r2) the inner problem is that call's closed-form solve.  Outer search,
+ *   deterministic: a grid of 36 angles x 32 log-spaced r1 over [h_min / 4, 4 h_max] x 16 log-spaced ratios r2 / r1 in
+ *   [1/16, 1]; the best points of the grid are each refined by cyclic golden-section searches of (r1, ratio, theta) to a
+ *   relative width of 1e-8 and the best result is kept.
+ *   *best is filled as a MetricBall((r1, r2), Angle2d(theta)) model: aniso = 2, range = 1, inv_radii = (1/r1, 1/r2, 1),
+ *   rotation = the counter-clockwise rotation by theta (row-major 3 x 3, identity on the third axis); when the best
+ *   ratio is 1 the isotropic form is returned instead: aniso = 0, range = r1, identity rotation.  dim = 0 is left to the
+ *   caller.  GSS_VG_POWER -> GSS_ERR_UNSUPPORTED.  (A fit of the full 3-D ellipsoid is not offered.) */
+int32_t gss_variogram_fit_aniso(const double* h, const double* phi, const double* gamma, const int64_t* count,
+                                int32_t nbins, const int32_t* kinds, int32_t nkinds, double nu, int32_t weighting,
+                                double max_nugget_frac, gss_variogram_t* best, double* objective);
 
 /* ---- neighbour search: replaces `search!(neighbors, center, searcher)` krig.jl:210 and the
  *      KNearestSearch / KBallSearch construction ui.jl:27,30.  Exact; neighbours ordered by

@@ -9,7 +9,14 @@
 Method: warm-up, then `--reps` timed runs, each bracketed by events on the stream (the call includes the ordering of the
 samples and the reduction: what a user pays; both calls are bare ctypes calls on preallocated outputs); the median is
 reported.  One JSON line
-per row on stdout.  python tools/vario_sweep.py [--reps 7] [--max-n 1000000]"""
+per row on stdout.  python tools/vario_sweep.py [--reps 7] [--max-n 1000000]
+
+--plane: instead, the varioplane rows (gss_variogram_plane, 18 sectors x 20 lags, one value column, 2-D and 3-D with
+ptol = inf) at 2*10^4 and 10^5 samples with the full diameter and at 10^5 with lags to 5 % of the extent.  Beside each:
+the only way to the same table without that call -- 18 calls of gss_variogram_empirical with direction = the
+mid-sector unit vector and cos_atol = cos(pi / 36), timed as one block -- and the omnidirectional call.  The three are
+measured alternating.  (To time the 18 calls on another build of the library, run this with GSS_LIB_PATH set to it and
+--yardstick-only: that build need not have the plane call.)"""
 import argparse
 import ctypes as C
 import json
@@ -58,13 +65,93 @@ def bare_variogram(lib, x, z, nlags, maxlag):
     return run, (count, lagsum, zsum, ndup)
 
 
+def bare_directional(lib, x, z, nlags, maxlag, nangles):
+    """`nangles` directional calls (mid-sector direction, cone of half a sector) as one block of bare calls."""
+    n, d = x.shape
+    outs = (torch.empty(nlags, dtype=torch.int64, device="cuda"), torch.empty(nlags, dtype=torch.float64, device="cuda"),
+            torch.empty((z.shape[0], nlags), dtype=torch.float64, device="cuda"),
+            torch.empty(1, dtype=torch.int64, device="cuda"))
+    us = []
+    for s in range(nangles):
+        a = (s + 0.5) * np.pi / nangles
+        us.append(np.ascontiguousarray([np.cos(a), np.sin(a), 0.0][:d] if d == 3 else [np.cos(a), np.sin(a)]))
+    cos_atol = float(np.cos(np.pi / (2 * nangles)))
+
+    def run():
+        for u in us:
+            _lib.check(lib.gss_variogram_empirical(
+                C.c_void_p(x.data_ptr()), n, d, C.c_void_p(z.data_ptr()), z.shape[0], nlags, float(maxlag), _lib.ptr(u),
+                float("inf"), cos_atol, 0, *(C.c_void_p(o.data_ptr()) for o in outs), _lib.MEM_DEVICE,
+                _lib.current_stream()))
+    return run
+
+
+def bare_plane(lib, x, z, nlags, maxlag, nangles):
+    n, d = x.shape
+    ang = np.arange(nangles) * np.pi / nangles
+    dirs = np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=1))
+    basis = np.ascontiguousarray(np.eye(3)) if d == 3 else None
+    count = torch.empty((nangles, nlags), dtype=torch.int64, device="cuda")
+    outs = (count, torch.empty((nangles, nlags), dtype=torch.float64, device="cuda"),
+            torch.empty((z.shape[0], nangles, nlags), dtype=torch.float64, device="cuda"),
+            torch.empty(1, dtype=torch.int64, device="cuda"))
+
+    def run():
+        _lib.check(lib.gss_variogram_plane(
+            C.c_void_p(x.data_ptr()), n, d, C.c_void_p(z.data_ptr()), z.shape[0], nlags, float(maxlag), nangles,
+            _lib.ptr(dirs), _lib.ptr(basis), float("inf"), 0, *(C.c_void_p(o.data_ptr()) for o in outs), _lib.MEM_DEVICE,
+            _lib.current_stream()))
+    return run, outs
+
+
+def plane_rows(lib, reps, yardstick_only):
+    rng = np.random.default_rng(1)
+    nangles, nlags = 18, 20
+    for d in (2, 3):
+        for n, label in ((20_000, "full"), (100_000, "full"), (100_000, "5pct")):
+            x = torch.as_tensor(rng.uniform(0.0, 1000.0, (n, d)), device="cuda")
+            z = torch.as_tensor(rng.normal(size=(1, n)), device="cuda")
+            maxlag = 1000.0 * d ** 0.5 if label == "full" else 50.0
+            run_dir = bare_directional(lib, x, z, nlags, maxlag, nangles)
+            run_omni, _ = bare_variogram(lib, x, z, nlags, maxlag)
+            row = {"what": "varioplane", "n": n, "dim": d, "maxlag": label, "nangles": nangles, "nlags": nlags, "nz": 1}
+            if yardstick_only:
+                row["directional_x18_ms"] = round(timed(run_dir, reps, warm=1)[0], 4)
+                row["omnidirectional_ms"] = round(timed(run_omni, reps, warm=1)[0], 4)
+            else:
+                run_plane, outs = bare_plane(lib, x, z, nlags, maxlag, nangles)
+                tp, td, to = [], [], []
+                for _ in range(3):                      # alternating blocks
+                    tp.append(timed(run_plane, reps, warm=1)[0])
+                    td.append(timed(run_dir, reps, warm=1)[0])
+                    to.append(timed(run_omni, reps, warm=1)[0])
+                _lib.profile_enable(True)
+                _lib.profile_reset()
+                run_plane()
+                kms, launches = _lib.profile_read("vario_plane")
+                _lib.profile_enable(False)
+                p, dd, o = statistics.median(tp), statistics.median(td), statistics.median(to)
+                row.update({"plane_ms": round(p, 4), "directional_x18_ms": round(dd, 4), "omnidirectional_ms": round(o, 4),
+                            "plane_kernel_ms": round(kms / max(launches, 1), 4),
+                            "plane_over_directional": round(p / dd, 4), "plane_over_omnidirectional": round(p / o, 3),
+                            "pairs_binned": int(outs[0].sum().item()),
+                            "tiles_opened": _lib.stat("vario_tiles_opened"), "tiles_total": _lib.stat("vario_tiles_total")})
+            print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--max-n", type=int, default=1_000_000)
+    ap.add_argument("--plane", action="store_true", help="the varioplane rows instead")
+    ap.add_argument("--yardstick-only", action="store_true", help="with --plane: only the 18 directional calls and the "
+                    "omnidirectional one (for a build of the library without the plane call)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     lib = _lib.lib()
+    if args.plane:
+        plane_rows(lib, args.reps, args.yardstick_only)
+        return
     rng = np.random.default_rng(1)
     for n in (20_000, 100_000, 1_000_000):
         if n > args.max_n:
