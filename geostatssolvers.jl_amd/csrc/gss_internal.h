@@ -967,10 +967,19 @@ struct KnnIndex {
 };
 // The mask of sequential simulation (seq.jl:105): a sample qualifies only if its visiting rank lies below the query's.
 // rank: per sample; qrank: per query; bminrank: lowest rank inside each batch of 64 of the index (Searcher::index).
+// The mask of cross-validation (fold_mode; rank / qrank / bminrank are not read then): sample j qualifies for query p
+// only if fold[j] != qfold[p] and, when ex >= 0, its search key lies strictly above ex (leave-ball-out).  fold == NULL
+// is leave-one-out: a sample's fold is its own index and query p of the call is sample qoff + p.  No box can be skipped
+// by fold, so there is no per-batch array.  A caller that queries in chunks offsets qfold / qoff like the centres.
 struct KnnMask {
   const int* rank;
   const int* qrank;
   const int* bminrank;
+  bool fold_mode = false;
+  const int* fold = nullptr;
+  const int* qfold = nullptr;
+  int64_t qoff = 0;
+  double ex = -1.0;
 };
 
 // The k nearest samples of each centre under a metric / inside a ball: the one way to search.  It validates what the

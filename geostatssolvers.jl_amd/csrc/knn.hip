@@ -476,6 +476,125 @@ __global__ __launch_bounds__(256) void knn_pruned_kernel(const double* __restric
   if (lane == 0 && count_out) count_out[p] = cnt;
 }
 
+// Cross-validation search (KnnMask::fold_mode): the traversal, key arithmetic, (key, index) order, ball test and pass
+// restriction of knn_pruned_kernel, word for word -- a copy, so that the kernels of that family stay the code they
+// were -- with another qualification: sample j may be a neighbour of query p iff fold[j] != qfold[p] and, for a
+// leave-ball-out exclusion key ex >= 0, key(p, j) > ex (a sample exactly on the exclusion radius is excluded).
+// fold == NULL: leave-one-out, the fold of a sample is its own index and query p is sample qoff + p.  Eligibility is
+// not a property of a box, so every box the bound lets through is opened; a batch whose samples all share the query's
+// fold costs its 64 keys and inserts nothing.
+template <int DIM, int METRIC>
+__global__ __launch_bounds__(256) void knn_fold_kernel(const double* __restrict__ xs, const int* __restrict__ perm,
+                                                       const double* __restrict__ blo, const double* __restrict__ bhi,
+                                                       const double* __restrict__ blo1,
+                                                       const double* __restrict__ bhi1, int n, int nb, int nb1,
+                                                       const double* __restrict__ centers, int64_t m, int k, double r2,
+                                                       int use_ball, int aniso, double ir0, double ir1, double ir2,
+                                                       const int* __restrict__ fold, const int* __restrict__ qfold,
+                                                       int64_t qoff, double ex, int* __restrict__ idx_out,
+                                                       int* __restrict__ count_out, const double* __restrict__ lowd,
+                                                       const int* __restrict__ lowi) {
+  const int lane = threadIdx.x & 63;
+  const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= m) return;  // whole wave
+  const int myfold = qfold ? qfold[p] : (int)(qoff + p);
+  const double my_lowd = lowd ? lowd[p] : -1.0;
+  const int my_lowi = lowd ? lowi[p] : -1;
+  const double ir[3] = {ir0, ir1, ir2};
+  double qc[DIM];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) qc[a] = centers[p * DIM + a];
+  const double INF = __builtin_huge_val();
+  double ld = INF;   // lane l: l-th nearest so far (INF / INT_MAX = empty)
+  int li = INT_MAX;
+
+  for (int c1 = 0; c1 < nb1; c1 += 64) {
+    const int g = c1 + lane;
+    double d1 = INF;
+    if (g < nb1) {
+      double lo[DIM], hi[DIM];
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        lo[a] = blo1[g * DIM + a];
+        hi[a] = bhi1[g * DIM + a];
+      }
+      d1 = box_key<DIM, METRIC>(lo, hi, qc, ir, aniso != 0);
+    }
+    bool done1 = !(g < nb1);
+    while (true) {
+      const double tau1 = readlane_f64(ld, k - 1);
+      const bool cand1 = !done1 && d1 <= tau1 && (!use_ball || d1 <= r2);
+      if (!__ballot(cand1)) break;
+      const double mn1 = wave_min_f64(cand1 ? d1 : INF);
+      const int pick1 = __builtin_ctzll(__ballot(cand1 && d1 == mn1));
+      if (lane == pick1) done1 = true;
+      const int b = (c1 + pick1) * 64 + lane;
+      double dmin = INF;
+      bool done = !(b < nb);
+      if (!done) {
+        double lo[DIM], hi[DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+          lo[a] = blo[b * DIM + a];
+          hi[a] = bhi[b * DIM + a];
+        }
+        dmin = box_key<DIM, METRIC>(lo, hi, qc, ir, aniso != 0);
+      }
+      while (true) {
+        double tau_d = readlane_f64(ld, k - 1);
+        int tau_i = __builtin_amdgcn_readlane(li, k - 1);
+        const bool cand = !done && dmin <= tau_d && (!use_ball || dmin <= r2);
+        if (!__ballot(cand)) break;
+        const double mn = wave_min_f64(cand ? dmin : INF);
+        const int pick = __builtin_ctzll(__ballot(cand && dmin == mn));
+        if (lane == pick) done = true;
+        const int j = ((c1 + pick1) * 64 + pick) * 64 + lane;
+        const bool valid = j < n;
+        double c[DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) c[a] = valid ? xs[(int64_t)j * DIM + a] : 0.0;
+        const int oidx = valid ? perm[j] : INT_MAX;
+        const double d2 = metric_key<DIM, METRIC>(c, qc, ir, aniso != 0);
+        bool qual = valid && (!use_ball || d2 <= r2) && key_less(d2, oidx, tau_d, tau_i) &&
+                    key_less(my_lowd, my_lowi, d2, oidx);
+        // the fold id is only fetched for candidates that would enter the list (oidx < n whenever qual holds)
+        if (qual) qual = (fold ? fold[oidx] : oidx) != myfold && (ex < 0.0 || d2 > ex);
+        unsigned long long qm = __ballot(qual);
+        if ((k >= KNN_SORT_MIN_K || tau_i == INT_MAX) && __popcll(qm) >= KNN_SORT_MIN) {
+          double bd = qual ? d2 : INF;
+          int bi = qual ? oidx : INT_MAX;
+          bitonic_sort64(bd, bi, lane);
+          bitonic_merge64(ld, li, bd, bi, lane);
+          qm = 0;
+        }
+        while (qm) {
+          const int src = __builtin_ctzll(qm);
+          qm &= qm - 1;
+          const double cd = readlane_f64(d2, src);
+          const int ci = __builtin_amdgcn_readlane(oidx, src);
+          if (!key_less(cd, ci, tau_d, tau_i)) continue;
+          const int pos = __popcll(__ballot(key_less(ld, li, cd, ci)));
+          const double up_d = shfl_up1_f64(ld);
+          const int up_i = shfl_up1_b32(li);
+          if (lane > pos) {
+            ld = up_d;
+            li = up_i;
+          } else if (lane == pos) {
+            ld = cd;
+            li = ci;
+          }
+          tau_d = readlane_f64(ld, k - 1);
+          tau_i = __builtin_amdgcn_readlane(li, k - 1);
+        }
+      }
+    }
+  }
+  const bool has = lane < k && li != INT_MAX;
+  const int cnt = __popcll(__ballot(has));
+  if (lane < k) idx_out[p * k + lane] = has ? li : -1;
+  if (lane == 0 && count_out) count_out[p] = cnt;
+}
+
 // ---- more than 64 neighbours (ui.jl:16-23 accepts any maxneighbors <= n): passes of 64 -----------------------------
 __global__ __launch_bounds__(256) void knn_any_init_kernel(int64_t m, int* __restrict__ count, double* __restrict__ lowd,
                                                            int* __restrict__ lowi) {
@@ -654,6 +773,26 @@ int32_t Searcher::pass(const double* q, int64_t m, int kk, int* idx, int* count,
     return GSS_OK;
   }
   const KnnIndex& ix = ix_;
+  if (mask && mask->fold_mode) {   // cross-validation: samples outside the query's fold (and exclusion ball)
+    GSS_REQUIRE((mask->fold == nullptr) == (mask->qfold == nullptr), "fold search needs sample and query folds together");
+    const dim3 grid((unsigned)((m + 3) / 4));
+#define GSS_FOLD_ARGS ix.xs.as<double>(), ix.perm.as<int>(), ix.lo.as<double>(), ix.hi.as<double>(), \
+                      ix.lo1.as<double>(), ix.hi1.as<double>(), (int)ix.n, ix.nb, ix.nb1, q, m, kk, r2, use_ball, aniso, \
+                      ir[0], ir[1], ir[2], mask->fold, mask->qfold, mask->qoff, mask->ex, idx, count, lowd, lowi
+#define GSS_FOLD_LAUNCH(METRIC)                                                                               \
+  switch (ix.dim) {                                                                                            \
+    case 1: hipLaunchKernelGGL((knn_fold_kernel<1, METRIC>), grid, dim3(256), 0, s, GSS_FOLD_ARGS); break;     \
+    case 2: hipLaunchKernelGGL((knn_fold_kernel<2, METRIC>), grid, dim3(256), 0, s, GSS_FOLD_ARGS); break;     \
+    default: hipLaunchKernelGGL((knn_fold_kernel<3, METRIC>), grid, dim3(256), 0, s, GSS_FOLD_ARGS); break;    \
+  }
+    if (metric == GSS_METRIC_CITYBLOCK) { GSS_FOLD_LAUNCH(GSS_METRIC_CITYBLOCK) }
+    else if (metric == GSS_METRIC_CHEBYSHEV) { GSS_FOLD_LAUNCH(GSS_METRIC_CHEBYSHEV) }
+    else { GSS_FOLD_LAUNCH(GSS_METRIC_EUCLIDEAN) }
+#undef GSS_FOLD_LAUNCH
+#undef GSS_FOLD_ARGS
+    GSS_HIP(hipGetLastError());
+    return GSS_OK;
+  }
   const int *rank = mask ? mask->rank : nullptr, *qrank = mask ? mask->qrank : nullptr,
             *bminrank = mask ? mask->bminrank : nullptr;
   if (rank) GSS_REQUIRE(qrank && bminrank, "masked search needs query ranks and per-batch minimum ranks");

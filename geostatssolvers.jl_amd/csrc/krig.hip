@@ -469,6 +469,36 @@ __global__ void sub_scalar_kernel(double* z, int64_t n, double mu) {
   if (i < n) z[i] -= mu;
 }
 
+// Leave-one-out from the factor (gss_krig_cv_global; Dubrule 1983): K^-1 = W'^T D W' with D = +1 on the n data rows and
+// -1 on the nc constraint rows, so B_ii = (K^-1)_ii = sum_{k=i}^{N1-1} D_k W'(k, i)^2 -- W' is lower triangular and its
+// columns are contiguous.  Row N1 of W' holds the dual weights (wd_row_kernel): it is not part of the factor and the
+// sum stops in front of it.  One wave per column; lane l adds rows i + l, i + l + 64, ... in that order, the 64 lane
+// sums meet in a fixed butterfly: the same bits on every run.  pred_i = z_i - wd_i / B_ii (wd was formed from z - mean
+// for simple kriging, so the mean cancels), var_i = max(0, 1 / B_ii) = the Schur complement of the system without i.
+__global__ __launch_bounds__(256) void krig_loo_kernel(const double* __restrict__ Wp, int64_t ldw, int n, int N1,
+                                                       const double* __restrict__ wd, const double* __restrict__ z,
+                                                       double* __restrict__ pred, double* __restrict__ var,
+                                                       uint8_t* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;  // whole wave
+  const double* col = Wp + (int64_t)i * ldw;
+  double acc = 0.0;
+  for (int k = i + lane; k < N1; k += 64) {
+    const double w = col[k];
+    acc = k < n ? fma(w, w, acc) : fma(-w, w, acc);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+  if (lane != 0) return;
+  const double NaN = __longlong_as_double(0x7ff8000000000000LL);
+  const bool ok = acc > 0.0 && acc < __builtin_huge_val();
+  const double v = 1.0 / acc;
+  pred[i] = ok ? z[i] - wd[i] * v : NaN;
+  var[i] = ok ? (v > 0.0 ? v : 0.0) : NaN;
+  if (status) status[i] = ok ? GSS_PT_OK : GSS_PT_SINGULAR;
+}
+
 }  // namespace gss
 
 using namespace gss;
@@ -521,7 +551,8 @@ int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const sign
                        double sk_mean, Searcher& sr, const double* xdata, const double* z, const double* drift_data,
                        const double* x0, const double* x0_raw, const double* drift_dom, int64_t m, int k,
                        int minneighbors, double* mean, double* var, uint8_t* status, int* idx_out, int* count_out,
-                       hipStream_t s, HostPipe* pipe, int block_nsub, const double* block_cell, double block_cvv);
+                       hipStream_t s, HostPipe* pipe, int block_nsub, const double* block_cell, double block_cvv,
+                       const KnnMask* mask = nullptr);
 }
 
 
@@ -804,7 +835,16 @@ static int32_t krig_fit_enqueue(gss_krig* h, const FitPlan& fp, hipStream_t s) {
 static hipStream_t krig_fit_stream() { return helper_stream(HELPER_FIT); }
 
 // async: on the fit stream, behind everything `s` holds now; the caller's stream is joined by krig_join_device
+// The factor buffer ((n + nc + 1)^2 doubles) exists from the first use that needs one: a fit, or a caller that asks for
+// it to receive a broadcast.  A handle that only serves moving neighbourhoods (GSS_KRIG_NO_FACTOR: 10^5 - 10^6 samples)
+// never allocates it.
+static int32_t krig_factor_alloc(gss_krig* h) {
+  if (h->factor.p) return GSS_OK;
+  return h->factor.alloc(sizeof(double) * (size_t)(h->ldw * h->N1pad + h->N1pad));
+}
+
 static int32_t krig_factorize(gss_krig* h, hipStream_t s, bool async = false) {
+  GSS_TRY(krig_factor_alloc(h));
   hipStream_t fs = s;
   if (async) {
     fs = krig_fit_stream();
@@ -987,8 +1027,6 @@ int32_t gss_krig_create(gss_krig_t** out, const gss_variogram_t* vg, int32_t var
     GSS_HIP(hipMemcpyAsync(h->drift_data.p, drift_data, sizeof(double) * n * ndrift, hipMemcpyHostToDevice, s));
   }
   GSS_HIP(hipStreamSynchronize(s));
-  // the factor buffer always exists so that a broadcast can land in it
-  GSS_TRY(h->factor.alloc(sizeof(double) * (size_t)(h->ldw * h->N1pad + h->N1pad)));
   if ((flags & GSS_KRIG_NO_FACTOR) == 0) {
     const bool async = (flags & GSS_KRIG_ASYNC_FIT) != 0;
     GSS_TRY(krig_factorize(h, s, async));
@@ -1017,6 +1055,7 @@ int32_t gss_krig_factor_buffer(gss_krig_t* h, void** dev_ptr, int64_t* bytes) {
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr && dev_ptr != nullptr && bytes != nullptr, "NULL argument");
   GSS_TRY(krig_fit_wait(h));   // (an asynchronous fit: the buffer is handed out complete)
+  GSS_TRY(krig_factor_alloc(h));   // a GSS_KRIG_NO_FACTOR handle: the buffer a broadcast lands in
   *dev_ptr = h->factor.p;
   *bytes = (int64_t)(sizeof(double) * (size_t)(h->ldw * h->N1pad + h->N1pad));
   return GSS_OK;
@@ -1025,6 +1064,8 @@ int32_t gss_krig_factor_buffer(gss_krig_t* h, void** dev_ptr, int64_t* bytes) {
 int32_t gss_krig_adopt_factor(gss_krig_t* h) {
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(h->factor.p != nullptr, "gss_krig_adopt_factor: no factor has arrived (gss_krig_factor_buffer hands out "
+                                      "the buffer to fill)");
   h->factored = true;
   return GSS_OK;
 }
@@ -1320,6 +1361,97 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
   GSS_HIP(hipGetLastError());
   GSS_TRY(so.back(mean_out, sizeof(double) * (size_t)(nbatch * m), mem, s));
   GSS_HIP(hipStreamSynchronize(s));  // Zm / U / WD are freed on return
+  return GSS_OK;
+}
+
+// ---- cross-validation (gss.h): every sample predicted from samples outside its own fold ------------------------------
+int32_t gss_krig_cv_global(gss_krig_t* h, double* pred, double* var, uint8_t* status, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(h->factored, "gss_krig_cv_global: the handle has no factor (created with GSS_KRIG_NO_FACTOR and never "
+                           "adopted one); gss_krig_cv_knn works without");
+  GSS_REQUIRE(h->block_nsub == 0, "cross-validation is at point support: the handle has block support set");
+  GSS_REQUIRE(pred && var, "gss_krig_cv_global: NULL array");
+  hipStream_t s = to_stream(stream);
+  GSS_TRY(krig_join_device(h, s));
+  GSS_TRY(krig_fit_wait(h));   // an asynchronous fit: its status (GSS_ERR_NOT_POSDEF) is reported here
+  const int64_t n = h->n;
+  Staged sp, sv, sst;
+  GSS_TRY(sp.out(pred, sizeof(double) * (size_t)n, mem));
+  GSS_TRY(sv.out(var, sizeof(double) * (size_t)n, mem));
+  GSS_TRY(sst.out(status, (size_t)n, mem));
+  {
+    ProfScope ps("krig_loo", s);
+    hipLaunchKernelGGL(krig_loo_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, h->Wp(), h->ldw, (int)n,
+                       (int)h->N1, h->wd(), h->z.as<double>(), sp.as<double>(), sv.as<double>(), sst.as<uint8_t>());
+    GSS_HIP(hipGetLastError());
+  }
+  GSS_TRY(sp.back(pred, sizeof(double) * (size_t)n, mem, s));
+  GSS_TRY(sv.back(var, sizeof(double) * (size_t)n, mem, s));
+  GSS_TRY(sst.back(status, (size_t)n, mem, s));
+  return GSS_OK;
+}
+
+int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radius, int32_t k, int32_t minneighbors,
+                        double radius, const double* inv_radii, int32_t metric, double metric_param, double* pred,
+                        double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out, int32_t mem,
+                        void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  if (metric == GSS_METRIC_HAVERSINE) {
+    set_error("cross-validation under the haversine distance is not available: the fold search runs on the k-d index, "
+              "which that key has no box bounds for (DESIGN.md section 7)");
+    return GSS_ERR_UNSUPPORTED;
+  }
+  Searcher sr;
+  GSS_TRY(sr.init(metric, metric_param, radius, inv_radii, h->dim, &h->fr));
+  GSS_REQUIRE(h->block_nsub == 0, "cross-validation is at point support: the handle has block support set");
+  GSS_REQUIRE(pred && var, "gss_krig_cv_knn: NULL array");
+  const int64_t n = h->n;
+  GSS_REQUIRE(k >= 1 && k <= n - 1, "gss_krig_cv_knn: maxneighbors %d outside 1..n-1 = %lld (a sample is never its own "
+                                    "neighbour)", k, (long long)(n - 1));
+  GSS_REQUIRE(!(exclude_radius != exclude_radius), "gss_krig_cv_knn: exclude_radius is NaN");
+  hipStream_t s = to_stream(stream);
+  const int dim = h->dim;
+  Staged sf, smean, svar, sstat, sidx, scnt;
+  if (fold) {
+    std::vector<int32_t> fh;
+    const int32_t* fhost = fold;
+    if (mem != GSS_MEM_HOST) {   // the ids are checked before any kernel indexes by them
+      fh.resize((size_t)n);
+      GSS_HIP(hipMemcpyAsync(fh.data(), fold, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+      GSS_HIP(hipStreamSynchronize(s));
+      fhost = fh.data();
+    }
+    for (int64_t i = 0; i < n; ++i)
+      GSS_REQUIRE(fhost[i] >= 0, "gss_krig_cv_knn: fold id %d of sample %lld is negative", fhost[i], (long long)i);
+    GSS_TRY(sf.in(fold, sizeof(int32_t) * (size_t)n, mem, s));
+  }
+  GSS_TRY(smean.out(pred, sizeof(double) * (size_t)n, mem));
+  GSS_TRY(svar.out(var, sizeof(double) * (size_t)n, mem));
+  GSS_TRY(sstat.out(status, (size_t)n, mem));
+  GSS_TRY(sidx.out(idx_out, sizeof(int32_t) * (size_t)(n * k), mem));
+  GSS_TRY(scnt.out(count_out, sizeof(int32_t) * (size_t)n, mem));
+  GSS_TRY(sr.samples(h->xdata.as<double>(), h->xraw.as<double>(), n, s));
+  // the exclusion ball in the search key: squared (and scaled like the ball) for the Euclidean family, else as it is
+  KnnMask mask{nullptr, nullptr, nullptr};
+  mask.fold_mode = true;
+  mask.fold = mask.qfold = fold ? sf.as<int>() : nullptr;
+  mask.ex = exclude_radius < 0.0 ? -1.0 : (sr.metric == GSS_METRIC_EUCLIDEAN ? exclude_radius * exclude_radius
+                                                                               : exclude_radius);
+  // the queries are the samples themselves: covariance frame, raw frame for a search in a second one, own drift rows
+  // (xraw only exists beside a rotated variogram; without one xdata holds the coordinates as given)
+  const double* xq_raw = h->fr.on ? h->xraw.as<double>() : h->xdata.as<double>();
+  GSS_TRY(krig_local_dev(h->vg, h->variant, h->nc, dim, &h->ds.e[0][0], h->ds.inv_scale[0], h->sk_mean, sr,
+                         h->xdata.as<double>(), h->z.as<double>(), h->drift_data.as<double>(), h->xdata.as<double>(),
+                         sr.two_frames ? xq_raw : nullptr, h->drift_data.as<double>(), n, k, minneighbors,
+                         smean.as<double>(), svar.as<double>(), sstat.as<uint8_t>(), sidx.as<int>(), scnt.as<int>(), s,
+                         nullptr, 0, nullptr, 0.0, &mask));
+  GSS_TRY(smean.back(pred, sizeof(double) * (size_t)n, mem, s));
+  GSS_TRY(svar.back(var, sizeof(double) * (size_t)n, mem, s));
+  GSS_TRY(sstat.back(status, (size_t)n, mem, s));
+  GSS_TRY(sidx.back(idx_out, sizeof(int32_t) * (size_t)(n * k), mem, s));
+  GSS_TRY(scnt.back(count_out, sizeof(int32_t) * (size_t)n, mem, s));
   return GSS_OK;
 }
 

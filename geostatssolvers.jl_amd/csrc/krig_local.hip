@@ -542,7 +542,8 @@ int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const sign
                        double sk_mean, Searcher& sr, const double* xdata, const double* z, const double* drift_data,
                        const double* x0, const double* x0_raw, const double* drift_dom, int64_t m, int k,
                        int minneighbors, double* mean, double* var, uint8_t* status, int* idx_out, int* count_out,
-                       hipStream_t s, HostPipe* pipe, int block_nsub, const double* block_cell, double block_cvv) {
+                       hipStream_t s, HostPipe* pipe, int block_nsub, const double* block_cell, double block_cvv,
+                       const KnnMask* mask) {
   GSS_REQUIRE(nc <= LMAX_NC, "moving-neighbourhood kriging supports at most %d drift terms (got %d)", LMAX_NC, nc);
   GSS_REQUIRE(k >= 1 && k <= BIG_MAX_K, "maxneighbors = %d: moving neighbourhoods hold at most %d neighbours "
                                         "(use the global neighbourhood beyond that)", k, BIG_MAX_K);
@@ -574,7 +575,13 @@ int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const sign
     if (piped) GSS_TRY(pipe->fetch(off, mv, s));
     {
       ProfScope ps("knn", s);
-      GSS_TRY(sr.query(x0 + off * dim, x0_raw ? x0_raw + off * dim : nullptr, mv, k, idx, cnt, s));
+      KnnMask mk{nullptr, nullptr, nullptr};   // cross-validation: the query folds of this chunk
+      if (mask) {
+        mk = *mask;
+        if (mk.qfold) mk.qfold += off;
+        mk.qoff += off;
+      }
+      GSS_TRY(sr.query(x0 + off * dim, x0_raw ? x0_raw + off * dim : nullptr, mv, k, idx, cnt, s, mask ? &mk : nullptr));
     }
     const double* dd = drift_dom ? drift_dom + off * nc : nullptr;
     ProfScope pl("krig_local", s);

@@ -9,6 +9,8 @@ from .geo import (CartesianGrid, Composition, DomainView, Ensemble, GeoTable, Po
 from .problems import EstimationProblem, SimulationProblem
 from .solvers import (FFTGS, LUGS, SGS, ExpWeight, IDWSolver, KrigingSolver, LWRSolver, TricubeWeight, kriging_ui,
                       searcher_ui, simulate_with_generic_loop, solve)
+from .validation import (BlockValidation, CrossValidationResult, KFoldValidation, LeaveBallOut, LeaveOneOut,
+                         cross_validate, cverror)
 from .variograms import (CubicVariogram, ExponentialVariogram, GaussianVariogram, MaternVariogram, MetricBall,
                          NestedVariogram, PentasphericalVariogram, PowerVariogram, SineHoleVariogram,
                          SphericalVariogram)

@@ -49,6 +49,12 @@ class Variogram(C.Structure):
                 ("extra", VariogramExtra * 3), ("rotation", C.c_double * 9)]
 
 
+class CVSummary(C.Structure):
+    """gss_cv_summary_t (gss.h): counts and means over e = z - pred of a cross-validation."""
+    _fields_ = [(f, C.c_double) for f in ("n_ok", "n_missing", "n_singular", "me", "mae", "mse", "mse_std_n", "mean_std",
+                                          "msq_std", "cverror")]
+
+
 _p = C.c_void_p
 _i32, _i64, _u64, _f64 = C.c_int32, C.c_int64, C.c_uint64, C.c_double
 _VG = C.POINTER(Variogram)
@@ -89,6 +95,9 @@ SIGNATURES = {
     "gss_krig_set_block_support": [_p, _p, _i32, _p],
     "gss_krig_predict_knn": [_p, _p, _p, _i64, _i32, _i32, _f64, _p, _i32, _f64, _p, _p, _p, _p, _p, _i32, _p],
     "gss_krig_predict_global_batch": [_p, _p, _i64, _p, _i64, _p, _i32, _p],
+    "gss_krig_cv_global": [_p, _p, _p, _p, _i32, _p],
+    "gss_krig_cv_knn": [_p, _p, _f64, _i32, _i32, _f64, _p, _i32, _f64, _p, _p, _p, _p, _p, _i32, _p],
+    "gss_cv_summary": [_p, _p, _p, _p, _p, _i64, _i32, C.POINTER(CVSummary), _p, _i32, _p],
     "gss_idw_predict": [_p, _p, _i64, _i32, _p, _i64, _i32, _i32, _f64, _p, _i32, _f64, _f64, _p, _p, _p, _i32, _p],
     "gss_lwr_predict": [_p, _p, _i64, _i32, _p, _i64, _i32, _i32, _f64, _p, _i32, _f64, _i32, _f64, _f64, _p, _p, _p, _i32,
                         _p],

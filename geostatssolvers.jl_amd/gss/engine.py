@@ -219,6 +219,57 @@ class KrigHandle(_NativeState):
             return mean, var, status, idx, cnt
         return mean, var, status
 
+    def _cv_out(self, device, k=None):
+        """Output arrays of a cross-validation call: numpy, or CUDA tensors when `device`."""
+        if device:
+            import torch
+            dev = f"cuda:{torch.cuda.current_device()}"
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)   # noqa: E731
+            out = [mk((self.n,), torch.float64), mk((self.n,), torch.float64), mk((self.n,), torch.uint8)]
+            if k is not None:
+                out += [mk((self.n, k), torch.int32), mk((self.n,), torch.int32)]
+            return out
+        out = [np.empty(self.n), np.empty(self.n), np.empty(self.n, dtype=np.uint8)]
+        if k is not None:
+            out += [np.empty((self.n, k), dtype=np.int32), np.empty(self.n, dtype=np.int32)]
+        return out
+
+    def cv_global(self, device=False):
+        """Leave-one-out predictions of every sample under the global neighbourhood, from the factor of the handle
+        (gss.h, gss_krig_cv_global) -> (pred, variance, status)."""
+        pred, var, status = self._cv_out(device)
+        check(self._l.gss_krig_cv_global(self._h, ptr(pred), ptr(var), ptr(status),
+                                         MEM_DEVICE if device else MEM_HOST, current_stream()))
+        return pred, var, status
+
+    def cv_knn(self, k, fold=None, exclude_radius=None, minneighbors=1, radius=None, radii=None, return_idx=False,
+               distance=None, rotation=None, device=False):
+        """Every sample predicted from its k nearest samples outside its own fold (gss.h, gss_krig_cv_knn).  `fold`: n
+        ids >= 0 (numpy: host arrays out; CUDA int32 tensor, or `device=True` without folds: everything stays in HBM)
+        or None for leave-one-out; `exclude_radius`: leave-ball-out.  -> (pred, variance, status[, idx, count])."""
+        device = bool(device) or (is_torch(fold) and fold.is_cuda)
+        if device and fold is not None and not (is_torch(fold) and fold.is_cuda):
+            raise ValueError("device=True needs the fold ids as a CUDA tensor")
+        if fold is not None:
+            if device:
+                import torch
+                fold = fold.to(torch.int32).contiguous()
+            else:
+                fold = np.ascontiguousarray(fold, dtype=np.int32)
+            if fold.shape != (self.n,):
+                raise ValueError(f"fold must hold one id per sample ({self.n}), got shape {tuple(fold.shape)}")
+        out = self._cv_out(device, int(k) if return_idx else None)
+        pred, var, status = out[:3]
+        idx, cnt = (out[3], out[4]) if return_idx else (None, None)
+        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
+        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
+        met, mpar = _lib.metric_spec(distance)
+        met, ir = _ball_metric(met, ir, radii, rotation)
+        check(self._l.gss_krig_cv_knn(self._h, ptr(fold), -1.0 if exclude_radius is None else float(exclude_radius),
+                                      int(k), int(minneighbors), r, ptr(ir), met, mpar, ptr(pred), ptr(var), ptr(status),
+                                      ptr(idx), ptr(cnt), MEM_DEVICE if device else MEM_HOST, current_stream()))
+        return tuple(out)
+
     def predict_global_batch(self, xdom, zbatch):
         xdom = _prep_in(xdom)
         zb = _prep_in(zbatch)
@@ -724,6 +775,34 @@ class HipEngine:
         radii = (1.0 / best.inv_radii[0], 1.0 / best.inv_radii[1])
         theta = float(np.arctan2(best.rotation[3], best.rotation[0]))
         return names[best.kind], best.sill, best.nugget, radii, theta, best.range, best.nu, obj
+
+    @staticmethod
+    def cv_summary(z, pred, var, status=None, fold=None, nfolds=0):
+        """gss_cv_summary: the error summary of a cross-validation, reduced on the device in a fixed order -> (dict of
+        the fields of gss_cv_summary_t, per-fold mean squared errors or None).  numpy arrays or CUDA tensors, all in
+        one memory space."""
+        l = _lib.lib()
+        dev = is_torch(z) and z.is_cuda
+        if dev:
+            import torch
+            z, pred, var = (a.to(torch.float64).contiguous() for a in (z, pred, var))
+            status = None if status is None else status.to(torch.uint8).contiguous()
+            fold = None if fold is None else fold.to(torch.int32).contiguous()
+        else:
+            z, pred, var = (np.ascontiguousarray(a, dtype=np.float64) for a in (z, pred, var))
+            status = None if status is None else np.ascontiguousarray(status, dtype=np.uint8)
+            fold = None if fold is None else np.ascontiguousarray(fold, dtype=np.int32)
+        n = z.shape[0]
+        if any(a is not None and tuple(a.shape) != (n,) for a in (pred, var, status, fold)):
+            raise ValueError("z, pred, var, status and fold must have one length")
+        nf = int(nfolds) if fold is not None else 0
+        fmse = None
+        if nf > 0:
+            fmse = _empty_like_space(z, (nf,), np.float64) if dev else np.empty(nf)
+        out = _lib.CVSummary()
+        check(l.gss_cv_summary(ptr(z), ptr(pred), ptr(var), ptr(status), ptr(fold), n, nf, C.byref(out), ptr(fmse),
+                               MEM_DEVICE if dev else MEM_HOST, current_stream()))
+        return {f: getattr(out, f) for f, _ in _lib.CVSummary._fields_}, fmse
 
 
 def default_engine():

@@ -1,0 +1,164 @@
+"""Cross-validation of a kriging model on the samples it was fitted to ([DEP] GeoStatsBase `cverror` with LeaveOneOut /
+KFoldValidation / BlockValidation / LeaveBallOut -- a dependency of the reference, not in its tree; the conventions here
+are this library's own and are stated in include/gss.h).
+
+    res = cross_validate(problem, KrigingSolver(z=dict(variogram=g, maxneighbors=16)), KFoldValidation(10))
+    res["z"].summary.cverror          # == cverror(solver, problem, KFoldValidation(10))["z"]
+
+Host logic only: the folds are built here, every prediction and the error summary come from the engine (the global
+neighbourhood reads leave-one-out off the factor of the fitted system, gss_krig_cv_global; a moving neighbourhood
+searches each sample's neighbours outside its own fold, gss_krig_cv_knn; gss_cv_summary reduces the errors)."""
+from __future__ import annotations
+
+from types import SimpleNamespace
+
+import numpy as np
+
+from .engine import EDK
+from .geo import GeoTable, PointSet
+from .problems import EstimationProblem
+from .solvers import KrigingSolver, _ball, _distance, _rot_kw, kriging_ui, searcher_ui
+
+
+class LeaveOneOut:
+    """Every sample is its own fold."""
+    exclude_radius = None
+
+    def folds(self, coords):
+        return None, 0
+
+
+class LeaveBallOut(LeaveOneOut):
+    """Leave-one-out that also leaves out every sample within `radius` (search distance) of the one predicted; a sample
+    exactly on the radius is left out."""
+
+    def __init__(self, radius):
+        if not float(radius) >= 0.0:
+            raise ValueError("LeaveBallOut needs a radius >= 0")
+        self.exclude_radius = float(radius)
+
+
+class KFoldValidation:
+    """k folds whose sizes differ by at most one; `shuffle` assigns the samples at random (`rng`: seed or Generator),
+    otherwise sample i belongs to fold i mod k."""
+    exclude_radius = None
+
+    def __init__(self, k, shuffle=True, rng=None):
+        if int(k) < 2:
+            raise ValueError("KFoldValidation needs at least 2 folds")
+        self.k, self.shuffle, self.rng = int(k), bool(shuffle), rng
+
+    def folds(self, coords):
+        n = coords.shape[0]
+        if self.k > n:
+            raise ValueError(f"{self.k} folds for {n} samples")
+        ids = (np.arange(n) % self.k).astype(np.int32)
+        if self.shuffle:
+            rng = self.rng if isinstance(self.rng, np.random.Generator) else np.random.default_rng(self.rng)
+            ids = ids[rng.permutation(n)]
+        return np.ascontiguousarray(ids), self.k
+
+
+class BlockValidation:
+    """fold = the axis-aligned block of side lengths `sides` a sample falls in, counted from the corner of the samples'
+    bounding box: cell index floor((x - xmin) / side) per axis (a sample on a block edge belongs to the upper block), the
+    occupied blocks numbered 0, 1, ... in ascending order of their cell index."""
+    exclude_radius = None
+
+    def __init__(self, sides):
+        self.sides = np.atleast_1d(np.asarray(sides, dtype=np.float64))
+        if not np.all(self.sides > 0.0):
+            raise ValueError("BlockValidation needs positive side lengths")
+
+    def folds(self, coords):
+        d = coords.shape[1]
+        sides = np.broadcast_to(self.sides, (d,)) if self.sides.size == 1 else self.sides
+        if sides.size != d:
+            raise ValueError(f"{sides.size} block sides for {d}-D samples")
+        cell = np.floor((coords - coords.min(axis=0)) / sides).astype(np.int64)
+        _, ids = np.unique(cell, axis=0, return_inverse=True)
+        ids = np.ascontiguousarray(ids.reshape(-1), dtype=np.int32)
+        return ids, int(ids.max()) + 1
+
+
+class CrossValidationResult:
+    """Per variable: `pred`, `variance`, `residual` (z - pred), `status` (0 ok, 1 missing, 2 singular) and `fold` (ids;
+    None for leave-one-out) of the non-missing samples `indices`, and `summary` (the fields of gss_cv_summary_t plus
+    `fold_mse`)."""
+
+    def __init__(self, indices, z, pred, variance, status, fold, summary):
+        self.indices, self.z, self.pred, self.variance, self.status, self.fold = indices, z, pred, variance, status, fold
+        self.residual = z - pred
+        self.summary = summary
+
+    def __repr__(self):
+        s = self.summary
+        return f"CrossValidationResult(n_ok={int(s.n_ok)}, me={s.me:.4g}, mse={s.mse:.4g}, cverror={s.cverror:.4g})"
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a)
+
+
+def cross_validate(problem_or_geotable, solver, method=None, engine=None):
+    """{variable: CrossValidationResult}.  Of an EstimationProblem only the data are used.  The dispatch follows the
+    KrigingSolver's own parameters: the kriging variant by `kriging_ui`; `maxneighbors`, `minneighbors`, `neighborhood`
+    and `distance` by `searcher_ui`.  `maxneighbors=None` is the global neighbourhood, which offers leave-one-out only."""
+    method = LeaveOneOut() if method is None else method
+    if not isinstance(solver, KrigingSolver):
+        raise TypeError(f"cross-validation is available for KrigingSolver, not {type(solver).__name__}")
+    if isinstance(problem_or_geotable, EstimationProblem):
+        data, variables = problem_or_geotable.data, problem_or_geotable.variables
+    elif isinstance(problem_or_geotable, GeoTable):
+        data = problem_or_geotable
+        variables = tuple(v for v in solver.vparams if v in data.table) or tuple(data.table)
+    else:
+        raise TypeError("cross_validate needs an EstimationProblem or a GeoTable")
+    eng = engine or solver.engine
+    coords = data.domain.centroids()
+    out = {}
+    for var in variables:
+        p = solver.params(var)
+        z = np.asarray(data[var], dtype=np.float64)
+        inds = np.flatnonzero(~np.isnan(z))
+        if inds.size < 2:
+            raise AssertionError(f"cross-validation of {var} needs at least two non-missing samples")
+        if p.get("support", "point") != "point":
+            raise ValueError("cross-validation predicts the samples, at point support: support='point' only")
+        x, zv = np.ascontiguousarray(coords[inds]), np.ascontiguousarray(z[inds])
+        n = x.shape[0]
+        vdom = PointSet(x)
+        variant = kriging_ui(vdom, p["variogram"], p["mean"], p["degree"], p["drifts"])
+        drift = None
+        if variant == EDK:
+            drift = np.stack([[f(c) for f in p["drifts"]] for c in x]).astype(np.float64)
+        exact = p["maxneighbors"] is None
+        fold, nfolds = None, 0
+        if exact:
+            if type(method) is not LeaveOneOut:
+                raise ValueError(f"{type(method).__name__} under the global neighbourhood (maxneighbors=None) is not "
+                                 "available: the factor of the system gives leave-one-out only; set maxneighbors")
+        else:
+            fold, nfolds = method.folds(x)
+        h = eng.Krig(p["variogram"], variant, x, zv, mean=p["mean"], degree=p["degree"], drift_data=drift, factor=exact)
+        try:
+            if exact:
+                pred, var_, st = h.cv_global()
+            else:
+                _, nmax = searcher_ui(vdom, p["maxneighbors"], p["distance"], p["neighborhood"])
+                radius, radii = _ball(p["neighborhood"])
+                pred, var_, st = h.cv_knn(min(nmax, n - 1), fold=fold, exclude_radius=method.exclude_radius,
+                                          minneighbors=p["minneighbors"], radius=radius, radii=radii,
+                                          distance=_distance(p), **_rot_kw(p["neighborhood"]))[:3]
+        finally:
+            h.close()
+        pred, var_, st = _host(pred), _host(var_), _host(st)
+        fields, fmse = eng.cv_summary(zv, pred, var_, st, fold, nfolds)
+        summary = SimpleNamespace(**fields, fold_mse=None if fmse is None else _host(fmse))
+        out[var] = CrossValidationResult(inds, zv, pred, var_, st, fold, summary)
+    return out
+
+
+def cverror(solver, problem, method=None):
+    """{variable: cross-validation error}: the mean over the folds of the folds' mean squared errors."""
+    return {v: r.summary.cverror for v, r in cross_validate(problem, solver, method).items()}

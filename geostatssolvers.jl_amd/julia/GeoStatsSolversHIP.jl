@@ -44,6 +44,7 @@ import GeoStatsBase: solve, preprocess, solvesingle
 export KrigingSolverHIP, IDWSolverHIP, LWRSolverHIP, ExpWeight, TricubeWeight, FFTGSHIP, LUGSHIP, SGSHIP
 export krig_fit, krig_predict_device!, fftgs_realize_device!, bind_device
 export empirical_variogram, fit_variogram, empirical_varioplane, fit_anisotropic
+export cverror, krig_cv_global, cv_summary, CVSummary
 
 const libgss = get(ENV, "LIBGSS_HIP", "libgss_hip.so")
 
@@ -875,6 +876,119 @@ function krig_predict_device!(μ::Ptr{Float64}, σ²::Ptr{Float64}, status::Ptr{
   check(ccall((:gss_krig_predict_global, libgss), Int32,
               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Ptr{Cvoid}),
               fit.handle, X0, C_NULL, Int64(m), μ, σ², status, GSS_MEM_DEVICE, stream))
+end
+
+# ---- cross-validation (gss.h: gss_krig_cv_global, gss_krig_cv_knn, gss_cv_summary) ------------------------------
+struct CVSummary
+  n_ok::Float64
+  n_missing::Float64
+  n_singular::Float64
+  me::Float64
+  mae::Float64
+  mse::Float64
+  mse_std_n::Float64
+  mean_std::Float64
+  msq_std::Float64
+  cverror::Float64
+end
+
+"""
+    krig_cv_global(fit) -> (pred, σ², status)
+
+Leave-one-out prediction of every sample of `fit = krig_fit(...)` under the global neighbourhood, read off the factor.
+"""
+function krig_cv_global(fit::KrigingFit)
+  pred = Vector{Float64}(undef, fit.n); σ² = similar(pred); status = Vector{UInt8}(undef, fit.n)
+  GC.@preserve pred σ² status check(ccall((:gss_krig_cv_global, libgss), Int32,
+    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Ptr{Cvoid}), fit.handle, pred, σ², status, GSS_MEM_HOST,
+    C_NULL))
+  pred, σ², status
+end
+
+"""
+    cv_summary(z, pred, σ², status; folds=nothing, nfolds=0) -> (CVSummary, per-fold mean squared errors or nothing)
+
+`folds`: 0-based fold ids (Int32) of the samples, `nothing` for leave-one-out.
+"""
+function cv_summary(z::Vector{Float64}, pred::Vector{Float64}, σ²::Vector{Float64}, status::Vector{UInt8};
+                    folds::Union{Nothing,Vector{Int32}}=nothing, nfolds::Integer=0)
+  out = Ref(CVSummary(0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+  nf = isnothing(folds) ? 0 : Int(nfolds)
+  fmse = nf > 0 ? Vector{Float64}(undef, nf) : nothing
+  GC.@preserve z pred σ² status folds fmse check(ccall((:gss_cv_summary, libgss), Int32,
+    (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int32}, Int64, Int32, Ptr{Cvoid}, Ptr{Float64}, Int32,
+     Ptr{Cvoid}), z, pred, σ², status, isnothing(folds) ? C_NULL : folds, Int64(length(z)), Int32(nf), out,
+    isnothing(fmse) ? C_NULL : fmse, GSS_MEM_HOST, C_NULL))
+  out[], fmse
+end
+
+"""
+    cverror(solver::KrigingSolverHIP, problem; folds=nothing, excluderadius=nothing) -> Dict(var => error)
+
+Cross-validation error of every variable of `problem` on its own samples (the domain is not used): the mean over the
+folds of the folds' mean squared errors.  `folds`: 0-based fold id per non-missing sample (`nothing`: leave-one-out);
+`excluderadius`: leave-ball-out.  `maxneighbors = nothing` is the global neighbourhood, which offers leave-one-out only.
+"""
+function cverror(solver::KrigingSolverHIP, problem::EstimationProblem; folds=nothing, excluderadius=nothing)
+  pdata = data(problem)
+  dtable = values(pdata)
+  ddomain = domain(pdata)
+  errs = Dict{Symbol,Float64}()
+  for covars in covariables(problem, solver), var in covars.names
+    p = covars.params[Set([var])]
+    zcol = Tables.getcolumn(Tables.columns(dtable), var)
+    inds = findall(!ismissing, zcol)
+    z, u = stripunits(zcol)
+    X = coordmatrix(view(ddomain, inds))
+    d, n = size(X)
+    variant, degree, ndrift, Fd, skmean = Int32(1), Int32(0), Int32(0), C_NULL, 0.0
+    if !isnothing(p.drifts)
+      variant, ndrift = Int32(3), Int32(length(p.drifts))
+      Fd = Float64[f(Point(X[:, i]...)) for f in p.drifts, i in 1:n]
+    elseif !isnothing(p.degree)
+      variant, degree = Int32(2), Int32(p.degree)
+    elseif !isnothing(p.mean)
+      variant, skmean = Int32(0), (p.mean isa Quantity ? Float64(ustrip(u, p.mean)) : Float64(p.mean))
+    end
+    exact = isnothing(p.maxneighbors)
+    exact && !(isnothing(folds) && isnothing(excluderadius)) &&
+      throw(ArgumentError("the global neighbourhood (maxneighbors = nothing) offers leave-one-out only"))
+    p.support === :point || throw(ArgumentError("cross-validation is at point support"))
+    extent = sqrt(sum(abs2, maximum(X, dims=2) .- minimum(X, dims=2)))
+    vg = Ref(cvariogram(p.variogram, d; extent))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    pred = Vector{Float64}(undef, n); σ² = similar(pred); status = Vector{UInt8}(undef, n)
+    fold = isnothing(folds) ? nothing : Vector{Int32}(folds)
+    GC.@preserve X z Fd pred σ² status fold begin
+      check(ccall((:gss_krig_create, libgss), Int32,
+                  (Ptr{Ptr{Cvoid}}, Ptr{GssVariogram}, Int32, Float64, Int32, Int32, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}, Int64, Int32, Ptr{Cvoid}),
+                  h, vg, variant, skmean, degree, ndrift, X, z, Fd, n, exact ? Int32(0) : GSS_KRIG_NO_FACTOR, C_NULL))
+      try
+        if exact
+          check(ccall((:gss_krig_cv_global, libgss), Int32,
+                      (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Ptr{Cvoid}),
+                      h[], pred, σ², status, GSS_MEM_HOST, C_NULL))
+        else
+          radius, ir = ballspec(p.neighborhood)
+          met, mpar = searchmetric(p)
+          k = clamp(p.maxneighbors, 1, n - 1)
+          check(ccall((:gss_krig_cv_knn, libgss), Int32,
+                      (Ptr{Cvoid}, Ptr{Int32}, Float64, Int32, Int32, Float64, Ptr{Float64}, Int32, Float64, Ptr{Float64},
+                       Ptr{Float64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Cvoid}),
+                      h[], isnothing(fold) ? C_NULL : fold, isnothing(excluderadius) ? -1.0 : Float64(excluderadius),
+                      Int32(k), Int32(p.minneighbors), radius, ir, met, mpar, pred, σ², status, C_NULL, C_NULL,
+                      GSS_MEM_HOST, C_NULL))
+        end
+      finally
+        ccall((:gss_krig_destroy, libgss), Int32, (Ptr{Cvoid},), h[])
+      end
+    end
+    nf = isnothing(fold) ? 0 : Int(maximum(fold)) + 1
+    s, _ = cv_summary(Vector{Float64}(z), pred, σ², status; folds=fold, nfolds=nf)
+    errs[var] = s.cverror
+  end
+  errs
 end
 
 """

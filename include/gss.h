@@ -385,6 +385,51 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
 int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t m, const double* zbatch,
                                       int64_t nbatch, double* mean_out, int32_t mem, void* stream);
 
+/* ---- cross-validation: does the model predict the samples it was given?  ([DEP] GeoStatsBase `cverror` with
+ *      LeaveOneOut / KFoldValidation / BlockValidation / LeaveBallOut; not in the reference tree.)  Every sample of the
+ *      handle is predicted, at point support, from samples outside its own fold.  Handles with block support set are
+ *      refused (GSS_ERR_INVALID).
+ *
+ * gss_krig_cv_global: leave-one-out under the global neighbourhood from the factor the handle already holds, no
+ *   refit: with B = K^-1 = W'^T D W' (D = +1 on the n data rows, -1 on the nc constraint rows) and the dual weights
+ *   wd = K^-1 [z - mean; 0], pred_i = z_i - wd_i / B_ii and var_i = max(0, 1 / B_ii) (Dubrule 1983), for simple,
+ *   ordinary, universal and external-drift kriging alike.  B_ii is one fixed-order sum per column of W': the results are
+ *   the same bits on every run.  B_ii <= 0 or not finite: GSS_PT_SINGULAR, pred = var = NaN.  Needs a factor
+ *   (GSS_ERR_INVALID on a GSS_KRIG_NO_FACTOR handle that never adopted one); an asynchronous fit is waited for and its
+ *   status (GSS_ERR_NOT_POSDEF) reported here.  pred, var (n doubles) and status (n bytes, may be NULL) live in `mem`.
+ *
+ * gss_krig_cv_knn: moving neighbourhood.  Sample p is predicted from its k nearest samples j that satisfy
+ *   fold[j] != fold[p] and, when exclude_radius >= 0, search distance(p, j) > exclude_radius (leave-ball-out: a sample
+ *   exactly on the radius is left out), besides what gss_krig_predict_knn requires (the ball radius / inv_radii, the
+ *   order by (key, index)).  fold: n ids >= 0 in `mem` (a negative id: GSS_ERR_INVALID; ids in device memory are copied
+ *   to the host for that check, which waits for the stream); NULL: leave-one-out.  Coordinates duplicated across folds
+ *   are ordinary zero-distance neighbours.  k in 1 .. n - 1; minneighbors, radius, inv_radii, metric, metric_param as
+ *   gss_krig_predict_knn; GSS_METRIC_HAVERSINE has no indexed search: GSS_ERR_UNSUPPORTED.  Fewer than minneighbors
+ *   eligible samples: GSS_PT_MISSING, pred = var = NaN.  External drifts at the queries are the handle's own rows.
+ *   Works on GSS_KRIG_NO_FACTOR handles.  pred, var, status, idx_out (n x k) / count_out (may be NULL) live in `mem`.
+ *
+ * gss_cv_summary: one deterministic reduction (per-workgroup partial sums in a fixed order, then one workgroup; no
+ *   floating-point atomics: the same bits on every run) over e_i = z_i - pred_i.
+ *   Over the points with GSS_PT_OK: n_ok, me = mean e, mae = mean |e|, mse = mean e^2.  Over those with var > 0
+ *   (mse_std_n of them): mean_std = mean e / sigma, msq_std = mean e^2 / sigma^2.  n_missing, n_singular: counts.
+ *   cverror: the mean over the non-empty folds of the fold's mean squared error (the default squared loss of the
+ *   GeoStats family); fold == NULL (leave-one-out): the mse.  fold: n ids in 0 .. nfolds - 1; fold_mse (nfolds doubles
+ *   in `mem`, or NULL) receives the per-fold mean squared errors, NaN for a fold without an OK point.  Means over an
+ *   empty set are NaN.  One wave per fold reads all n ids: meant for tens to thousands of folds.
+ *   z, pred, var, status (NULL: all OK), fold, fold_mse live in `mem`; `out` is host memory and the call returns when it
+ *   is filled. */
+int32_t gss_krig_cv_global(gss_krig_t* h, double* pred, double* var, uint8_t* status, int32_t mem, void* stream);
+int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radius, int32_t k, int32_t minneighbors,
+                        double radius, const double* inv_radii, int32_t metric, double metric_param,
+                        double* pred, double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out,
+                        int32_t mem, void* stream);
+typedef struct gss_cv_summary {
+  double n_ok, n_missing, n_singular, me, mae, mse, mse_std_n, mean_std, msq_std, cverror;
+} gss_cv_summary_t;
+int32_t gss_cv_summary(const double* z, const double* pred, const double* var, const uint8_t* status,
+                       const int32_t* fold, int64_t n, int32_t nfolds, gss_cv_summary_t* out, double* fold_mse,
+                       int32_t mem, void* stream);
+
 /* ---- IDWSolver / LWRSolver on the neighbour-search kernel -------------
  * gss_idw_predict replaces the estimation loop idw.jl:111-142: neighbours by gss_knn_search's rule,
  *   w_i = 1 / d_i^exponent, mean = sum w_i z_i / sum w_i, dist = min d_i; a zero distance copies that

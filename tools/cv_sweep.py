@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Timing of the cross-validation calls on device arrays, each beside the call of the library it shares its work with.
+
+  * gss_krig_cv_knn (ordinary kriging, Matern-3/2, uniform 3-D samples; leave-one-out and 10 block folds) at n = 10^5
+    and 10^6 samples with k = 16 and 64, beside gss_krig_predict_knn on the same handle at n query points -- the samples
+    shifted by a fraction of their spacing -- and the same k: the same kriging work per point, an unmasked search.  The
+    two are measured alternating; the search / solve split of each is read from gss_profile_read ("knn", "krig_local").
+  * gss_krig_cv_global at n = 1 000 and 4 000 beside gss_krig_create, the fit whose factor it reads.
+
+Method: warm-up, then `--reps` timed runs bracketed by events on the stream; the median is reported.  One JSON line per
+row on stdout.  python tools/cv_sweep.py [--reps 5] [--max-n 1000000]"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "geostatssolvers.jl_amd")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from gss import _lib  # noqa: E402
+from gss.engine import OK, KrigHandle  # noqa: E402
+import gss  # noqa: E402
+
+
+def timed(fn, reps, warm=1):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def split(fn):
+    """(search ms, solve ms) of one call from the library's own event timers."""
+    _lib.profile_enable(True)
+    _lib.profile_reset()
+    fn()
+    torch.cuda.synchronize()
+    knn, solve = _lib.profile_read("knn")[0], _lib.profile_read("krig_local")[0]
+    _lib.profile_enable(False)
+    return round(knn, 3), round(solve, 3)
+
+
+def knn_rows(lib, reps, max_n):
+    rng = np.random.default_rng(1)
+    for n in (100_000, 1_000_000):
+        if n > max_n:
+            continue
+        x = rng.uniform(0.0, 1000.0, (n, 3))
+        h = KrigHandle(gss.MaternVariogram(range=60.0, order=1.5), OK, x, rng.normal(size=n), factor=False)
+        spacing = 1000.0 / n ** (1.0 / 3.0)
+        xq = torch.as_tensor(x + rng.uniform(-0.25, 0.25, x.shape) * spacing, device="cuda")
+        block, nblocks = gss.BlockValidation((500.0, 200.0, 1001.0)).folds(x)              # 2 x 5 x 1 blocks
+        assert nblocks == 10
+        folds = {"loo": None, "10 block folds": torch.as_tensor(block, device="cuda")}
+        out = [torch.empty(n, dtype=torch.float64, device="cuda"), torch.empty(n, dtype=torch.float64, device="cuda"),
+               torch.empty(n, dtype=torch.uint8, device="cuda")]
+        po = [C.c_void_p(o.data_ptr()) for o in out]
+        for k in (16, 64):
+            def predict():
+                _lib.check(lib.gss_krig_predict_knn(h._h, C.c_void_p(xq.data_ptr()), None, n, k, 1, -1.0, None, 0, 0.0,
+                                                    *po, None, None, _lib.MEM_DEVICE, _lib.current_stream()))
+            for name, fold in folds.items():
+                fp = None if fold is None else C.c_void_p(fold.data_ptr())
+
+                def cv():
+                    _lib.check(lib.gss_krig_cv_knn(h._h, fp, -1.0, k, 1, -1.0, None, 0, 0.0, *po, None, None,
+                                                   _lib.MEM_DEVICE, _lib.current_stream()))
+                tc, tp = [], []
+                for _ in range(3):                      # alternating blocks
+                    tc.append(timed(cv, reps))
+                    tp.append(timed(predict, reps))
+                c, p = statistics.median(tc), statistics.median(tp)
+                cs, ps = split(cv), split(predict)
+                print(json.dumps({"what": "cv_knn", "n": n, "k": k, "folds": name, "cv_ms": round(c, 3),
+                                  "predict_knn_ms": round(p, 3), "cv_over_predict": round(c / p, 3),
+                                  "cv_search_ms": cs[0], "cv_solve_ms": cs[1], "predict_search_ms": ps[0],
+                                  "predict_solve_ms": ps[1], "points_per_s": round(n / (c * 1e-3), 1)}), flush=True)
+        h.close()
+
+
+def global_rows(lib, reps):
+    rng = np.random.default_rng(2)
+    for n in (1000, 4000):
+        x = rng.uniform(0.0, 1000.0, (n, 3))
+        z = rng.normal(size=n)
+        g = gss.MaternVariogram(range=60.0, order=1.5)
+        fits = []
+        for _ in range(reps + 1):                       # the fit it reuses: create returns when the factor is there
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            h = KrigHandle(g, OK, x, z)
+            fits.append((time.perf_counter() - t0) * 1e3)
+            if _ < reps:
+                h.close()
+        out = [torch.empty(n, dtype=torch.float64, device="cuda"), torch.empty(n, dtype=torch.float64, device="cuda"),
+               torch.empty(n, dtype=torch.uint8, device="cuda")]
+        po = [C.c_void_p(o.data_ptr()) for o in out]
+
+        def cv():
+            _lib.check(lib.gss_krig_cv_global(h._h, *po, _lib.MEM_DEVICE, _lib.current_stream()))
+        t = timed(cv, reps)
+        h.close()
+        fit = statistics.median(fits[1:])
+        print(json.dumps({"what": "cv_global", "n": n, "cv_global_ms": round(t, 4), "fit_ms": round(fit, 3),
+                          "cv_over_fit": round(t / fit, 5)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--max-n", type=int, default=1_000_000)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    lib = _lib.lib()
+    global_rows(lib, args.reps)
+    knn_rows(lib, args.reps, args.max_n)
+
+
+if __name__ == "__main__":
+    main()
