@@ -965,21 +965,33 @@ struct KnnIndex {
   int64_t n = 0;
   int nb = 0, nb1 = 0, dim = 0;
 };
-// The mask of sequential simulation (seq.jl:105): a sample qualifies only if its visiting rank lies below the query's.
+// Which samples a query may take, beyond the ball: all of them (no mask), or one of two masks.
+// Rank, sequential simulation (seq.jl:105): a sample qualifies only if its visiting rank lies below the query's.
 // rank: per sample; qrank: per query; bminrank: lowest rank inside each batch of 64 of the index (Searcher::index).
-// The mask of cross-validation (fold_mode; rank / qrank / bminrank are not read then): sample j qualifies for query p
-// only if fold[j] != qfold[p] and, when ex >= 0, its search key lies strictly above ex (leave-ball-out).  fold == NULL
-// is leave-one-out: a sample's fold is its own index and query p of the call is sample qoff + p.  No box can be skipped
-// by fold, so there is no per-batch array.  A caller that queries in chunks offsets qfold / qoff like the centres.
+// Fold, cross-validation: sample j qualifies for query p only if fold[j] != qfold[p] and, when ex >= 0, its search key
+// lies strictly above ex (leave-ball-out).  fold == NULL (then qfold == NULL) is leave-one-out: a sample's fold is its own
+// index and query p of the call is sample qoff + p.  No box can be skipped by fold, so there is no per-batch array.
+// A caller that queries in chunks passes from(off), the fold mask of queries off, off + 1, ... of the call (a rank mask
+// is only ever used whole and is returned as it is).
 struct KnnMask {
-  const int* rank;
-  const int* qrank;
-  const int* bminrank;
-  bool fold_mode = false;
-  const int* fold = nullptr;
-  const int* qfold = nullptr;
-  int64_t qoff = 0;
-  double ex = -1.0;
+  struct Rank { const int *rank, *qrank, *bminrank; };
+  struct Fold { const int *fold, *qfold; int64_t qoff; double ex; };
+  enum Kind { NONE, RANK, FOLD } kind = NONE;
+  union {   // the one `kind` names
+    Rank r;
+    Fold f;
+  };
+  KnnMask() : f{} {}
+  KnnMask(const Rank& m) : kind(RANK), r(m) {}
+  KnnMask(const Fold& m) : kind(FOLD), f(m) {}
+  KnnMask from(int64_t off) const {
+    KnnMask k = *this;
+    if (kind == FOLD) {
+      if (k.f.qfold) k.f.qfold += off;
+      k.f.qoff += off;
+    }
+    return k;
+  }
 };
 
 // The k nearest samples of each centre under a metric / inside a ball: the one way to search.  It validates what the

@@ -17,6 +17,7 @@
 #include <future>
 #include <climits>
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -106,6 +107,37 @@ __device__ __forceinline__ void bitonic_merge64(double& ld, int& li, double bd, 
   for (int stride = 32; stride >= 1; stride >>= 1) bitonic_cx(ld, li, lane, stride, true);
 }
 
+// Inserts (cd, ci) into the ascending list (LD, LI) -- lane l holds the l-th key, the last lane's key falls off -- and
+// re-reads the k-th key into (TAU_D, TAU_I); uses `lane` and `k` of the kernel.  A macro and not a function: a function
+// is optimised on its own before it is inlined, and every knn_kernel then compiles to other code than with the
+// statements in place (moving neighbourhood).
+#define KNN_LIST_INSERT(LD, LI, cd, ci, TAU_D, TAU_I)                \
+  do {                                                               \
+    const int pos = __popcll(__ballot(key_less(LD, LI, cd, ci)));    \
+    const double up_d = shfl_up1_f64(LD);                            \
+    const int up_i = shfl_up1_b32(LI);                               \
+    if (lane > pos) {                                                \
+      LD = up_d;                                                     \
+      LI = up_i;                                                     \
+    } else if (lane == pos) {                                        \
+      LD = cd;                                                       \
+      LI = ci;                                                       \
+    }                                                                \
+    TAU_D = readlane_f64(LD, k - 1);                                 \
+    TAU_I = __builtin_amdgcn_readlane(LI, k - 1);                    \
+  } while (0)
+
+// the finished list of query p: its first k indices (-1 where the list is empty) and their number; every lane calls
+__device__ __forceinline__ void list_store(int li, int lane, int k, int64_t p, bool store, int* __restrict__ idx_out,
+                                           int* __restrict__ count_out) {
+  const bool has = lane < k && li != INT_MAX;
+  const int cnt = __popcll(__ballot(has));
+  if (store) {
+    if (lane < k) idx_out[p * k + lane] = has ? li : -1;
+    if (lane == 0 && count_out) count_out[p] = cnt;
+  }
+}
+
 template <int DIM, int METRIC>
 __global__ __launch_bounds__(256) void knn_kernel(const double* __restrict__ xdata, int n,
                                                   const double* __restrict__ centers, int64_t m, int k, double r2,
@@ -169,33 +201,14 @@ __global__ __launch_bounds__(256) void knn_kernel(const double* __restrict__ xda
           const double cd = readlane_f64(d2, src);
           const int ci = __builtin_amdgcn_readlane(gidx, src);
           if (!key_less(cd, ci, tau_d[q], tau_i[q])) continue;  // an earlier insertion tightened tau
-          const int pos = __popcll(__ballot(key_less(ld[q], li[q], cd, ci)));
-          const double up_d = shfl_up1_f64(ld[q]);
-          const int up_i = shfl_up1_b32(li[q]);
-          if (lane > pos) {
-            ld[q] = up_d;
-            li[q] = up_i;
-          } else if (lane == pos) {
-            ld[q] = cd;
-            li[q] = ci;
-          }
-          tau_d[q] = readlane_f64(ld[q], k - 1);
-          tau_i[q] = __builtin_amdgcn_readlane(li[q], k - 1);
+          KNN_LIST_INSERT(ld[q], li[q], cd, ci, tau_d[q], tau_i[q]);
         }
       }
     }
   }
 
 #pragma unroll
-  for (int q = 0; q < KNN_Q; ++q) {
-    const int64_t p = qbase + q;
-    const bool has = lane < k && li[q] != INT_MAX;
-    const int cnt = __popcll(__ballot(has));
-    if (p < m) {
-      if (lane < k) idx_out[p * k + lane] = has ? li[q] : -1;
-      if (lane == 0 && count_out) count_out[p] = cnt;
-    }
-  }
+  for (int q = 0; q < KNN_Q; ++q) list_store(li[q], lane, k, qbase + q, qbase + q < m, idx_out, count_out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -351,26 +364,26 @@ __device__ __forceinline__ double box_key(const double* lo, const double* hi, co
   return acc;
 }
 
-// MASKED (sequential simulation, seq.jl:105 `search!(..., mask=simulated)`): a sample qualifies only if its
-// visiting rank is lower than the query's (rank[] per original index, qrank[] per query, bminrank[] = lowest
-// rank inside each batch so that batches with nothing simulated yet are skipped).
-template <int DIM, bool MASKED, int METRIC = GSS_METRIC_EUCLIDEAN>
-__global__ __launch_bounds__(256) void knn_pruned_kernel(const double* __restrict__ xs, const int* __restrict__ perm,
-                                                         const double* __restrict__ blo, const double* __restrict__ bhi,
-                                                         const double* __restrict__ blo1,
-                                                         const double* __restrict__ bhi1, int n, int nb, int nb1,
-                                                         const double* __restrict__ centers, int64_t m, int k,
-                                                         double r2, int use_ball, int aniso, double ir0, double ir1,
-                                                         double ir2, const int* __restrict__ rank,
-                                                         const int* __restrict__ qrank,
-                                                         const int* __restrict__ bminrank, int* __restrict__ idx_out,
-                                                         int* __restrict__ count_out,
-                                                         const double* __restrict__ lowd,
-                                                         const int* __restrict__ lowi) {
+// Which samples may be neighbours of a query is the traversal's one open question, answered by a qualifier: a small
+// struct passed by value whose three members are inlined.  of_query(p): what the query is compared by; batch(b, mine):
+// may batch b hold an eligible sample; admits(qual, valid, oidx, d2, mine): `qual` refined for the candidate of this
+// lane (sample oidx at key d2; valid: the lane holds a sample).
+
+// The traversal of the pruned search (described before the index build), one wave per query and 4 queries per workgroup,
+// over the samples a qualifier lets through.
+template <int DIM, int METRIC, class Qualifier>
+__device__ __forceinline__ void knn_traverse(const double* __restrict__ xs, const int* __restrict__ perm,
+                                             const double* __restrict__ blo, const double* __restrict__ bhi,
+                                             const double* __restrict__ blo1, const double* __restrict__ bhi1, int n,
+                                             int nb, int nb1, const double* __restrict__ centers, int64_t m, int k,
+                                             double r2, int use_ball, int aniso, double ir0, double ir1, double ir2,
+                                             const Qualifier ql, int* __restrict__ idx_out,
+                                             int* __restrict__ count_out, const double* __restrict__ lowd,
+                                             const int* __restrict__ lowi) {
   const int lane = threadIdx.x & 63;
   const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= m) return;  // whole wave
-  const int myrank = MASKED ? qrank[p] : 0;
+  const int mine = ql.of_query(p);
   // more than 64 neighbours are found 64 at a time: a later pass only accepts keys above the last key of the pass
   // before it (keys are >= 0, so (-1, -1) accepts everything)
   const double my_lowd = lowd ? lowd[p] : -1.0;
@@ -416,7 +429,7 @@ __global__ __launch_bounds__(256) void knn_pruned_kernel(const double* __restric
           hi[a] = bhi[b * DIM + a];
         }
         dmin = box_key<DIM, METRIC>(lo, hi, qc, ir, aniso != 0);
-        if (MASKED && !(bminrank[b] < myrank)) done = true;
+        if (!ql.batch(b, mine)) done = true;
       }
       while (true) {
         // current k-th best key, re-read from the list (lane k - 1) whenever it may have changed
@@ -436,7 +449,7 @@ __global__ __launch_bounds__(256) void knn_pruned_kernel(const double* __restric
         const double d2 = metric_key<DIM, METRIC>(c, qc, ir, aniso != 0);
         bool qual = valid && (!use_ball || d2 <= r2) && key_less(d2, oidx, tau_d, tau_i) &&
                     key_less(my_lowd, my_lowi, d2, oidx);
-        if (MASKED) qual = qual && rank[valid ? oidx : 0] < myrank;
+        qual = ql.admits(qual, valid, oidx, d2, mine);
         unsigned long long qm = __ballot(qual);
         // (short lists take the sort too while they are not full: the first batch would otherwise be 64 insertions)
         if ((k >= KNN_SORT_MIN_K || tau_i == INT_MAX) && __popcll(qm) >= KNN_SORT_MIN) {
@@ -454,35 +467,61 @@ __global__ __launch_bounds__(256) void knn_pruned_kernel(const double* __restric
           const double cd = readlane_f64(d2, src);
           const int ci = __builtin_amdgcn_readlane(oidx, src);
           if (!key_less(cd, ci, tau_d, tau_i)) continue;
-          const int pos = __popcll(__ballot(key_less(ld, li, cd, ci)));
-          const double up_d = shfl_up1_f64(ld);
-          const int up_i = shfl_up1_b32(li);
-          if (lane > pos) {
-            ld = up_d;
-            li = up_i;
-          } else if (lane == pos) {
-            ld = cd;
-            li = ci;
-          }
-          tau_d = readlane_f64(ld, k - 1);
-          tau_i = __builtin_amdgcn_readlane(li, k - 1);
+          KNN_LIST_INSERT(ld, li, cd, ci, tau_d, tau_i);
         }
       }
     }
   }
-  const bool has = lane < k && li != INT_MAX;
-  const int cnt = __popcll(__ballot(has));
-  if (lane < k) idx_out[p * k + lane] = has ? li : -1;
-  if (lane == 0 && count_out) count_out[p] = cnt;
+  list_store(li, lane, k, p, true, idx_out, count_out);
 }
 
-// Cross-validation search (KnnMask::fold_mode): the traversal, key arithmetic, (key, index) order, ball test and pass
-// restriction of knn_pruned_kernel, word for word -- a copy, so that the kernels of that family stay the code they
-// were -- with another qualification: sample j may be a neighbour of query p iff fold[j] != qfold[p] and, for a
-// leave-ball-out exclusion key ex >= 0, key(p, j) > ex (a sample exactly on the exclusion radius is excluded).
-// fold == NULL: leave-one-out, the fold of a sample is its own index and query p is sample qoff + p.  Eligibility is
-// not a property of a box, so every box the bound lets through is opened; a batch whose samples all share the query's
-// fold costs its 64 keys and inserts nothing.
+// every sample
+struct QualAll {
+  __device__ __forceinline__ int of_query(int64_t) const { return 0; }
+  __device__ __forceinline__ bool batch(int, int) const { return true; }
+  __device__ __forceinline__ bool admits(bool qual, bool, int, double, int) const { return qual; }
+};
+
+// Sequential simulation (seq.jl:105 `search!(..., mask=simulated)`): a sample qualifies only if its visiting rank is
+// lower than the query's (rank[] per original index, qrank[] per query, bminrank[] = lowest rank inside each batch so
+// that batches with nothing simulated yet are skipped).  The rank is loaded for every lane, eligible or not.
+struct QualRank {
+  const int *rank, *qrank, *bminrank;
+  __device__ __forceinline__ int of_query(int64_t p) const { return qrank[p]; }
+  __device__ __forceinline__ bool batch(int b, int mine) const { return bminrank[b] < mine; }
+  __device__ __forceinline__ bool admits(bool qual, bool valid, int oidx, double, int mine) const {
+    return qual && rank[valid ? oidx : 0] < mine;
+  }
+};
+
+// The kernel of the plain and the masked search: the traversal with the qualifier its arguments make.
+template <int DIM, bool MASKED, int METRIC = GSS_METRIC_EUCLIDEAN>
+__global__ __launch_bounds__(256) void knn_pruned_kernel(const double* __restrict__ xs, const int* __restrict__ perm,
+                                                         const double* __restrict__ blo, const double* __restrict__ bhi,
+                                                         const double* __restrict__ blo1,
+                                                         const double* __restrict__ bhi1, int n, int nb, int nb1,
+                                                         const double* __restrict__ centers, int64_t m, int k,
+                                                         double r2, int use_ball, int aniso, double ir0, double ir1,
+                                                         double ir2, const int* __restrict__ rank,
+                                                         const int* __restrict__ qrank,
+                                                         const int* __restrict__ bminrank, int* __restrict__ idx_out,
+                                                         int* __restrict__ count_out,
+                                                         const double* __restrict__ lowd,
+                                                         const int* __restrict__ lowi) {
+  if (MASKED)
+    knn_traverse<DIM, METRIC>(xs, perm, blo, bhi, blo1, bhi1, n, nb, nb1, centers, m, k, r2, use_ball, aniso, ir0, ir1,
+                              ir2, QualRank{rank, qrank, bminrank}, idx_out, count_out, lowd, lowi);
+  else
+    knn_traverse<DIM, METRIC>(xs, perm, blo, bhi, blo1, bhi1, n, nb, nb1, centers, m, k, r2, use_ball, aniso, ir0, ir1,
+                              ir2, QualAll{}, idx_out, count_out, lowd, lowi);
+}
+
+// Cross-validation search: the traversal of knn_traverse with its own qualification, kept as a body of its own because
+// merged into knn_traverse it was measurably slower (moving neighbourhood): sample j may be a neighbour of
+// query p iff fold[j] != qfold[p] and, for a leave-ball-out exclusion key ex >= 0, key(p, j) > ex (a sample exactly on the
+// exclusion radius is excluded).  fold == NULL: leave-one-out, the fold of a sample is its own index and query p is sample
+// qoff + p.  Eligibility is not a property of a box, so every box the bound lets through is opened; a batch whose samples
+// all share the query's fold costs its 64 keys and inserts nothing.  A change to knn_traverse is made here too.
 template <int DIM, int METRIC>
 __global__ __launch_bounds__(256) void knn_fold_kernel(const double* __restrict__ xs, const int* __restrict__ perm,
                                                        const double* __restrict__ blo, const double* __restrict__ bhi,
@@ -573,26 +612,12 @@ __global__ __launch_bounds__(256) void knn_fold_kernel(const double* __restrict_
           const double cd = readlane_f64(d2, src);
           const int ci = __builtin_amdgcn_readlane(oidx, src);
           if (!key_less(cd, ci, tau_d, tau_i)) continue;
-          const int pos = __popcll(__ballot(key_less(ld, li, cd, ci)));
-          const double up_d = shfl_up1_f64(ld);
-          const int up_i = shfl_up1_b32(li);
-          if (lane > pos) {
-            ld = up_d;
-            li = up_i;
-          } else if (lane == pos) {
-            ld = cd;
-            li = ci;
-          }
-          tau_d = readlane_f64(ld, k - 1);
-          tau_i = __builtin_amdgcn_readlane(li, k - 1);
+          KNN_LIST_INSERT(ld, li, cd, ci, tau_d, tau_i);
         }
       }
     }
   }
-  const bool has = lane < k && li != INT_MAX;
-  const int cnt = __popcll(__ballot(has));
-  if (lane < k) idx_out[p * k + lane] = has ? li : -1;
-  if (lane == 0 && count_out) count_out[p] = cnt;
+  list_store(li, lane, k, p, true, idx_out, count_out);
 }
 
 // ---- more than 64 neighbours (ui.jl:16-23 accepts any maxneighbors <= n): passes of 64 -----------------------------
@@ -745,78 +770,66 @@ int32_t Searcher::index(hipStream_t s, const KnnIndex** out) {
   return GSS_OK;
 }
 
+// Run-time (dim in 1..3, metric) to compile-time arguments: f(integral_constant dim[, integral_constant metric]).
+// Only the exhaustive kernel has a Haversine copy; without HAVERSINE that metric is not instantiated.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <class F>
+static void with_dim(int dim, F&& f) {
+  switch (dim) {
+    case 1: f(Int<1>{}); break;
+    case 2: f(Int<2>{}); break;
+    default: f(Int<3>{}); break;
+  }
+}
+template <bool HAVERSINE, class F>
+static void with_dim_metric(int dim, int metric, F&& f) {
+  with_dim(dim, [&](auto D) {
+    if constexpr (HAVERSINE) {
+      if (metric == GSS_METRIC_HAVERSINE) return f(D, Int<GSS_METRIC_HAVERSINE>{});
+    }
+    if (metric == GSS_METRIC_CITYBLOCK) f(D, Int<GSS_METRIC_CITYBLOCK>{});
+    else if (metric == GSS_METRIC_CHEBYSHEV) f(D, Int<GSS_METRIC_CHEBYSHEV>{});
+    else f(D, Int<GSS_METRIC_EUCLIDEAN>{});
+  });
+}
+
 // one pass: the kk <= 64 nearest whose key lies above (lowd, lowi) where given
 int32_t Searcher::pass(const double* q, int64_t m, int kk, int* idx, int* count, hipStream_t s, const KnnMask* mask,
                        bool indexed, const double* lowd, const int* lowi) {
   if (!indexed) {
     const dim3 grid((unsigned)((m + 4 * KNN_Q - 1) / (4 * KNN_Q)));
-#define GSS_BRUTE_ARGS xs, (int)n, q, m, kk, r2, use_ball, aniso, ir[0], ir[1], ir[2], idx, count, lowd, lowi
-#define GSS_BRUTE_LAUNCH(D)                                                                                             \
-  switch (metric) {                                                                                                     \
-    case GSS_METRIC_CITYBLOCK:                                                                                          \
-      hipLaunchKernelGGL((knn_kernel<D, GSS_METRIC_CITYBLOCK>), grid, dim3(256), 0, s, GSS_BRUTE_ARGS); break;          \
-    case GSS_METRIC_CHEBYSHEV:                                                                                          \
-      hipLaunchKernelGGL((knn_kernel<D, GSS_METRIC_CHEBYSHEV>), grid, dim3(256), 0, s, GSS_BRUTE_ARGS); break;          \
-    case GSS_METRIC_HAVERSINE:                                                                                          \
-      hipLaunchKernelGGL((knn_kernel<D, GSS_METRIC_HAVERSINE>), grid, dim3(256), 0, s, GSS_BRUTE_ARGS); break;          \
-    default:                                                                                                            \
-      hipLaunchKernelGGL((knn_kernel<D, GSS_METRIC_EUCLIDEAN>), grid, dim3(256), 0, s, GSS_BRUTE_ARGS); break;          \
-  }
-    switch (dim) {
-      case 1: GSS_BRUTE_LAUNCH(1) break;
-      case 2: GSS_BRUTE_LAUNCH(2) break;
-      default: GSS_BRUTE_LAUNCH(3) break;
-    }
-#undef GSS_BRUTE_LAUNCH
-#undef GSS_BRUTE_ARGS
+    with_dim_metric<true>(dim, metric, [&](auto D, auto M) {
+      hipLaunchKernelGGL((knn_kernel<decltype(D)::value, decltype(M)::value>), grid, dim3(256), 0, s, xs, (int)n, q, m,
+                         kk, r2, use_ball, aniso, ir[0], ir[1], ir[2], idx, count, lowd, lowi);
+    });
     GSS_HIP(hipGetLastError());
     return GSS_OK;
   }
+  const KnnMask::Kind kind = mask ? mask->kind : KnnMask::NONE;
+  if (kind == KnnMask::RANK)
+    GSS_REQUIRE(mask->r.rank && mask->r.qrank && mask->r.bminrank,
+                "masked search needs query ranks and per-batch minimum ranks");
+  if (kind == KnnMask::FOLD)
+    GSS_REQUIRE((mask->f.fold == nullptr) == (mask->f.qfold == nullptr),
+                "fold search needs sample and query folds together");
   const KnnIndex& ix = ix_;
-  if (mask && mask->fold_mode) {   // cross-validation: samples outside the query's fold (and exclusion ball)
-    GSS_REQUIRE((mask->fold == nullptr) == (mask->qfold == nullptr), "fold search needs sample and query folds together");
-    const dim3 grid((unsigned)((m + 3) / 4));
-#define GSS_FOLD_ARGS ix.xs.as<double>(), ix.perm.as<int>(), ix.lo.as<double>(), ix.hi.as<double>(), \
-                      ix.lo1.as<double>(), ix.hi1.as<double>(), (int)ix.n, ix.nb, ix.nb1, q, m, kk, r2, use_ball, aniso, \
-                      ir[0], ir[1], ir[2], mask->fold, mask->qfold, mask->qoff, mask->ex, idx, count, lowd, lowi
-#define GSS_FOLD_LAUNCH(METRIC)                                                                               \
-  switch (ix.dim) {                                                                                            \
-    case 1: hipLaunchKernelGGL((knn_fold_kernel<1, METRIC>), grid, dim3(256), 0, s, GSS_FOLD_ARGS); break;     \
-    case 2: hipLaunchKernelGGL((knn_fold_kernel<2, METRIC>), grid, dim3(256), 0, s, GSS_FOLD_ARGS); break;     \
-    default: hipLaunchKernelGGL((knn_fold_kernel<3, METRIC>), grid, dim3(256), 0, s, GSS_FOLD_ARGS); break;    \
-  }
-    if (metric == GSS_METRIC_CITYBLOCK) { GSS_FOLD_LAUNCH(GSS_METRIC_CITYBLOCK) }
-    else if (metric == GSS_METRIC_CHEBYSHEV) { GSS_FOLD_LAUNCH(GSS_METRIC_CHEBYSHEV) }
-    else { GSS_FOLD_LAUNCH(GSS_METRIC_EUCLIDEAN) }
-#undef GSS_FOLD_LAUNCH
-#undef GSS_FOLD_ARGS
-    GSS_HIP(hipGetLastError());
-    return GSS_OK;
-  }
-  const int *rank = mask ? mask->rank : nullptr, *qrank = mask ? mask->qrank : nullptr,
-            *bminrank = mask ? mask->bminrank : nullptr;
-  if (rank) GSS_REQUIRE(qrank && bminrank, "masked search needs query ranks and per-batch minimum ranks");
   const dim3 grid((unsigned)((m + 3) / 4));
-#define GSS_KNN_ARGS ix.xs.as<double>(), ix.perm.as<int>(), ix.lo.as<double>(), ix.hi.as<double>(), \
-                     ix.lo1.as<double>(), ix.hi1.as<double>(), (int)ix.n, ix.nb, ix.nb1, \
-                     q, m, kk, r2, use_ball, aniso, ir[0], ir[1], ir[2], rank, qrank, bminrank, idx, count, lowd, lowi
-#define GSS_KNN_LAUNCH(MASKED, METRIC)                                                                               \
-  switch (ix.dim) {                                                                                                   \
-    case 1: hipLaunchKernelGGL((knn_pruned_kernel<1, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;   \
-    case 2: hipLaunchKernelGGL((knn_pruned_kernel<2, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;   \
-    default: hipLaunchKernelGGL((knn_pruned_kernel<3, MASKED, METRIC>), grid, dim3(256), 0, s, GSS_KNN_ARGS); break;  \
-  }
-  if (rank) {   // SGS: candidates whose rank lies below the query's
-    if (metric == GSS_METRIC_CITYBLOCK) { GSS_KNN_LAUNCH(true, GSS_METRIC_CITYBLOCK) }
-    else if (metric == GSS_METRIC_CHEBYSHEV) { GSS_KNN_LAUNCH(true, GSS_METRIC_CHEBYSHEV) }
-    else { GSS_KNN_LAUNCH(true, GSS_METRIC_EUCLIDEAN) }
-  } else {
-    if (metric == GSS_METRIC_CITYBLOCK) { GSS_KNN_LAUNCH(false, GSS_METRIC_CITYBLOCK) }
-    else if (metric == GSS_METRIC_CHEBYSHEV) { GSS_KNN_LAUNCH(false, GSS_METRIC_CHEBYSHEV) }
-    else { GSS_KNN_LAUNCH(false, GSS_METRIC_EUCLIDEAN) }
-  }
-#undef GSS_KNN_LAUNCH
-#undef GSS_KNN_ARGS
+  with_dim_metric<false>(ix.dim, metric, [&](auto D, auto M) {
+    constexpr int DIM = decltype(D)::value, METRIC = decltype(M)::value;
+    // every indexed kernel takes the index, the queries and the ball, then its qualifier's fields, then the outputs
+    auto launch = [&](auto kernel, auto... qualifier) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ix.xs.as<double>(), ix.perm.as<int>(), ix.lo.as<double>(),
+                         ix.hi.as<double>(), ix.lo1.as<double>(), ix.hi1.as<double>(), (int)ix.n, ix.nb, ix.nb1, q, m, kk,
+                         r2, use_ball, aniso, ir[0], ir[1], ir[2], qualifier..., idx, count, lowd, lowi);
+    };
+    if (kind == KnnMask::FOLD)   // cross-validation: samples outside the query's fold (and exclusion ball)
+      launch(knn_fold_kernel<DIM, METRIC>, mask->f.fold, mask->f.qfold, mask->f.qoff, mask->f.ex);
+    else if (kind == KnnMask::RANK)   // SGS: candidates whose rank lies below the query's
+      launch(knn_pruned_kernel<DIM, true, METRIC>, mask->r.rank, mask->r.qrank, mask->r.bminrank);
+    else
+      launch(knn_pruned_kernel<DIM, false, METRIC>, nullptr, nullptr, nullptr);
+  });
   GSS_HIP(hipGetLastError());
   return GSS_OK;
 }
@@ -871,15 +884,11 @@ int32_t Searcher::query(const double* c, const double* c_raw, int64_t m, int k, 
   for (int base = 0; base < k; base += 64) {
     const int kk = (k - base) < 64 ? (k - base) : 64;
     GSS_TRY(pass(q, m, kk, tidx.as<int>(), tcnt.as<int>(), s, mask, indexed, lowd.as<double>(), lowi.as<int>()));
-#define GSS_APPEND(D)                                                                                                  \
-  hipLaunchKernelGGL(knn_any_append_kernel<D>, grid, dim3(256), 0, s, xs, q, m, k, base, kk, tidx.as<int>(),           \
-                     tcnt.as<int>(), metric, aniso, ir[0], ir[1], ir[2], idx, count, lowd.as<double>(), lowi.as<int>())
-    switch (dim) {
-      case 1: GSS_APPEND(1); break;
-      case 2: GSS_APPEND(2); break;
-      default: GSS_APPEND(3); break;
-    }
-#undef GSS_APPEND
+    with_dim(dim, [&](auto D) {
+      hipLaunchKernelGGL(knn_any_append_kernel<decltype(D)::value>, grid, dim3(256), 0, s, xs, q, m, k, base, kk,
+                         tidx.as<int>(), tcnt.as<int>(), metric, aniso, ir[0], ir[1], ir[2], idx, count,
+                         lowd.as<double>(), lowi.as<int>());
+    });
     GSS_HIP(hipGetLastError());
   }
   GSS_HIP(hipStreamSynchronize(s));  // the pass buffers are released on return

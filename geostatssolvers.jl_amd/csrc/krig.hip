@@ -1434,11 +1434,10 @@ int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radiu
   GSS_TRY(scnt.out(count_out, sizeof(int32_t) * (size_t)n, mem));
   GSS_TRY(sr.samples(h->xdata.as<double>(), h->xraw.as<double>(), n, s));
   // the exclusion ball in the search key: squared (and scaled like the ball) for the Euclidean family, else as it is
-  KnnMask mask{nullptr, nullptr, nullptr};
-  mask.fold_mode = true;
-  mask.fold = mask.qfold = fold ? sf.as<int>() : nullptr;
-  mask.ex = exclude_radius < 0.0 ? -1.0 : (sr.metric == GSS_METRIC_EUCLIDEAN ? exclude_radius * exclude_radius
-                                                                               : exclude_radius);
+  const double ex = exclude_radius < 0.0 ? -1.0 : (sr.metric == GSS_METRIC_EUCLIDEAN ? exclude_radius * exclude_radius
+                                                                                     : exclude_radius);
+  const int* fold_dev = fold ? sf.as<int>() : nullptr;   // the samples are the queries: one array serves both
+  const KnnMask mask(KnnMask::Fold{fold_dev, fold_dev, 0, ex});
   // the queries are the samples themselves: covariance frame, raw frame for a search in a second one, own drift rows
   // (xraw only exists beside a rotated variogram; without one xdata holds the coordinates as given)
   const double* xq_raw = h->fr.on ? h->xraw.as<double>() : h->xdata.as<double>();

@@ -575,12 +575,7 @@ int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const sign
     if (piped) GSS_TRY(pipe->fetch(off, mv, s));
     {
       ProfScope ps("knn", s);
-      KnnMask mk{nullptr, nullptr, nullptr};   // cross-validation: the query folds of this chunk
-      if (mask) {
-        mk = *mask;
-        if (mk.qfold) mk.qfold += off;
-        mk.qoff += off;
-      }
+      const KnnMask mk = mask ? mask->from(off) : KnnMask();   // cross-validation: the query folds of this chunk
       GSS_TRY(sr.query(x0 + off * dim, x0_raw ? x0_raw + off * dim : nullptr, mv, k, idx, cnt, s, mask ? &mk : nullptr));
     }
     const double* dd = drift_dom ? drift_dom + off * nc : nullptr;

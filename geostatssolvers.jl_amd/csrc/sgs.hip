@@ -1171,7 +1171,7 @@ int32_t gss_sgs_create_paths(gss_sgs_t** out, const gss_variogram_t* vg, double 
     GSS_HIP(hipGetLastError());
     {
       ProfScope ps("sgs_search", s);
-      const KnnMask mask{rk, rk, bmin.as<int>()};
+      const KnnMask mask(KnnMask::Rank{rk, rk, bmin.as<int>()});
       if (h->filter_after) {   // one unmasked search serves every path: k nearest cells of the whole domain
         if (pp == 0) {
           GSS_TRY(rawidx.alloc(sizeof(int) * (size_t)(N * h->k)));
