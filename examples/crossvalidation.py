@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Does the fitted model predict the samples it was fitted to?  Empirical variogram -> fit -> cross-validation of
-candidate models on the samples themselves, under the global neighbourhood (leave-one-out off the factor of the fitted
-system) and under a moving neighbourhood (ten random folds, blocks, leave-ball-out).
+candidate models on the samples themselves, under the global neighbourhood (leave-one-out and ten random folds, both off
+the factor of the fitted system) and under a moving neighbourhood (ten random folds, blocks, leave-ball-out).
 python examples/crossvalidation.py   (needs the built library and an MI355X)"""
 import os
 import sys
@@ -36,7 +36,15 @@ for name, model in models.items():
     out["loo"][name] = s
     print("%-15s leave-one-out  me %+.4f  mse %.4f  mean e/s %+.4f  mean (e/s)^2 %.3f" % (name, s.me, s.mse, s.mean_std, s.msq_std))
 
-# 3. moving neighbourhood: folds, blocks, leave-ball-out
+# 3. global neighbourhood, ten random folds of 60 samples: still the one factor, not ten refits
+out["global folds"] = {}
+for name, model in models.items():
+    e = gss.cverror(gss.KrigingSolver(z=dict(variogram=model)), gss.EstimationProblem(data, gss.PointSet(x[:1]), "z"),
+                    gss.KFoldValidation(10, rng=1))["z"]
+    out["global folds"][name] = e
+    print("%-15s global neighbourhood, 10 folds  cverror %.4f" % (name, e))
+
+# 4. moving neighbourhood: folds, blocks, leave-ball-out
 problem = gss.EstimationProblem(data, gss.PointSet(x[:1]), "z")       # the domain of the problem is not used
 out["cverror"] = {}
 for name, model in models.items():

@@ -946,6 +946,11 @@ int32_t trsm_right_lt_f64(double* X, int64_t m, int64_t n, int64_t ldx, const do
 // Fill / copy kernels used instead of hipMemsetAsync / hipMemcpyAsync inside sequences that may be captured into a
 // hipGraph: with ROCm 7.2 a graph's memset nodes running next to plain memsets of another stream were observed to
 // write a stale fill pattern (0x24242424 into a word that was cleared with 0).
+// crossval_folds.hip: cross-validation by folds off the factor W' of a fitted global system (gss_krig_cv_global_folds).
+// fold: n ids >= 0 on the host; every other array on the device (status may be NULL).  Synchronous.
+int32_t cv_global_folds_dev(const double* Wp, int64_t ldw, int64_t n, int64_t N1, int nc, bool simple,
+                            const double* wd, const double* z, const int32_t* fold, double* pred, double* var,
+                            uint8_t* status, hipStream_t s);
 int32_t dev_zero_bytes(void* p, size_t bytes, hipStream_t s);             // p 4-byte aligned, bytes multiple of 4
 int32_t dev_copy_f64(double* dst, const double* src, int64_t n, hipStream_t s);
 

@@ -1392,6 +1392,42 @@ int32_t gss_krig_cv_global(gss_krig_t* h, double* pred, double* var, uint8_t* st
   return GSS_OK;
 }
 
+// Folds under the global neighbourhood: the block form of the identity above, e_F = (B_FF)^-1 wd_F (crossval_folds.hip)
+int32_t gss_krig_cv_global_folds(gss_krig_t* h, const int32_t* fold, double* pred, double* var, uint8_t* status,
+                                 int32_t mem, void* stream) {
+  GSS_ENTRY();
+  if (fold == nullptr) return gss_krig_cv_global(h, pred, var, status, mem, stream);
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(h->factored, "gss_krig_cv_global_folds: the handle has no factor (created with GSS_KRIG_NO_FACTOR and "
+                           "never adopted one); gss_krig_cv_knn works without");
+  GSS_REQUIRE(h->block_nsub == 0, "cross-validation is at point support: the handle has block support set");
+  GSS_REQUIRE(pred && var, "gss_krig_cv_global_folds: NULL array");
+  hipStream_t s = to_stream(stream);
+  GSS_TRY(krig_join_device(h, s));
+  GSS_TRY(krig_fit_wait(h));   // an asynchronous fit: its status (GSS_ERR_NOT_POSDEF) is reported here
+  const int64_t n = h->n;
+  std::vector<int32_t> fh;
+  const int32_t* fhost = fold;
+  if (mem != GSS_MEM_HOST) {   // the samples are grouped by fold on the host
+    fh.resize((size_t)n);
+    GSS_HIP(hipMemcpyAsync(fh.data(), fold, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipStreamSynchronize(s));
+    fhost = fh.data();
+  }
+  for (int64_t i = 0; i < n; ++i)
+    GSS_REQUIRE(fhost[i] >= 0, "gss_krig_cv_global_folds: fold id %d of sample %lld is negative", fhost[i], (long long)i);
+  Staged sp, sv, sst;
+  GSS_TRY(sp.out(pred, sizeof(double) * (size_t)n, mem));
+  GSS_TRY(sv.out(var, sizeof(double) * (size_t)n, mem));
+  GSS_TRY(sst.out(status, (size_t)n, mem));
+  GSS_TRY(cv_global_folds_dev(h->Wp(), h->ldw, n, h->N1, h->nc, h->variant == GSS_KRIG_SIMPLE, h->wd(),
+                              h->z.as<double>(), fhost, sp.as<double>(), sv.as<double>(), sst.as<uint8_t>(), s));
+  GSS_TRY(sp.back(pred, sizeof(double) * (size_t)n, mem, s));
+  GSS_TRY(sv.back(var, sizeof(double) * (size_t)n, mem, s));
+  GSS_TRY(sst.back(status, (size_t)n, mem, s));
+  return GSS_OK;
+}
+
 int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radius, int32_t k, int32_t minneighbors,
                         double radius, const double* inv_radii, int32_t metric, double metric_param, double* pred,
                         double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out, int32_t mem,

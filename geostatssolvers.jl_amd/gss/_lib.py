@@ -96,6 +96,7 @@ SIGNATURES = {
     "gss_krig_predict_knn": [_p, _p, _p, _i64, _i32, _i32, _f64, _p, _i32, _f64, _p, _p, _p, _p, _p, _i32, _p],
     "gss_krig_predict_global_batch": [_p, _p, _i64, _p, _i64, _p, _i32, _p],
     "gss_krig_cv_global": [_p, _p, _p, _p, _i32, _p],
+    "gss_krig_cv_global_folds": [_p, _p, _p, _p, _p, _i32, _p],
     "gss_krig_cv_knn": [_p, _p, _f64, _i32, _i32, _f64, _p, _i32, _f64, _p, _p, _p, _p, _p, _i32, _p],
     "gss_cv_summary": [_p, _p, _p, _p, _p, _i64, _i32, C.POINTER(CVSummary), _p, _i32, _p],
     "gss_idw_predict": [_p, _p, _i64, _i32, _p, _i64, _i32, _i32, _f64, _p, _i32, _f64, _f64, _p, _p, _p, _i32, _p],

@@ -242,6 +242,26 @@ class KrigHandle(_NativeState):
                                          MEM_DEVICE if device else MEM_HOST, current_stream()))
         return pred, var, status
 
+    def cv_global_folds(self, fold, device=False):
+        """Every sample predicted from all samples outside its own fold under the global neighbourhood, from the factor
+        of the handle (gss.h, gss_krig_cv_global_folds).  `fold`: n ids >= 0, arbitrary (numpy: host arrays out; CUDA
+        int32 tensor: everything stays in HBM) or None for leave-one-out (`cv_global`).  -> (pred, variance, status)."""
+        device = bool(device) or (is_torch(fold) and fold.is_cuda)
+        if device and fold is not None and not (is_torch(fold) and fold.is_cuda):
+            raise ValueError("device=True needs the fold ids as a CUDA tensor")
+        if fold is not None:
+            if device:
+                import torch
+                fold = fold.to(torch.int32).contiguous()
+            else:
+                fold = np.ascontiguousarray(fold, dtype=np.int32)
+            if fold.shape != (self.n,):
+                raise ValueError(f"fold must hold one id per sample ({self.n}), got shape {tuple(fold.shape)}")
+        pred, var, status = self._cv_out(device)
+        check(self._l.gss_krig_cv_global_folds(self._h, ptr(fold), ptr(pred), ptr(var), ptr(status),
+                                               MEM_DEVICE if device else MEM_HOST, current_stream()))
+        return pred, var, status
+
     def cv_knn(self, k, fold=None, exclude_radius=None, minneighbors=1, radius=None, radii=None, return_idx=False,
                distance=None, rotation=None, device=False):
         """Every sample predicted from its k nearest samples outside its own fold (gss.h, gss_krig_cv_knn).  `fold`: n

@@ -6,8 +6,9 @@ are this library's own and are stated in include/gss.h).
     res["z"].summary.cverror          # == cverror(solver, problem, KFoldValidation(10))["z"]
 
 Host logic only: the folds are built here, every prediction and the error summary come from the engine (the global
-neighbourhood reads leave-one-out off the factor of the fitted system, gss_krig_cv_global; a moving neighbourhood
-searches each sample's neighbours outside its own fold, gss_krig_cv_knn; gss_cv_summary reduces the errors)."""
+neighbourhood reads leave-one-out, gss_krig_cv_global, and folds, gss_krig_cv_global_folds, off the factor of the fitted
+system; a moving neighbourhood searches each sample's neighbours outside its own fold, gss_krig_cv_knn; gss_cv_summary
+reduces the errors)."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -103,7 +104,9 @@ def _host(a):
 def cross_validate(problem_or_geotable, solver, method=None, engine=None):
     """{variable: CrossValidationResult}.  Of an EstimationProblem only the data are used.  The dispatch follows the
     KrigingSolver's own parameters: the kriging variant by `kriging_ui`; `maxneighbors`, `minneighbors`, `neighborhood`
-    and `distance` by `searcher_ui`.  `maxneighbors=None` is the global neighbourhood, which offers leave-one-out only."""
+    and `distance` by `searcher_ui`.  `maxneighbors=None` is the global neighbourhood: leave-one-out and the methods that
+    partition the samples into folds (KFoldValidation, BlockValidation) are read off the factor of the one fitted system;
+    LeaveBallOut, whose sets overlap, needs a moving neighbourhood."""
     method = LeaveOneOut() if method is None else method
     if not isinstance(solver, KrigingSolver):
         raise TypeError(f"cross-validation is available for KrigingSolver, not {type(solver).__name__}")
@@ -135,15 +138,17 @@ def cross_validate(problem_or_geotable, solver, method=None, engine=None):
         exact = p["maxneighbors"] is None
         fold, nfolds = None, 0
         if exact:
-            if type(method) is not LeaveOneOut:
+            # folds need the block form of the identity (handle.cv_global_folds); a ball is no partition
+            if type(method) is not LeaveOneOut and (method.exclude_radius is not None
+                                                    or not hasattr(eng.Krig, "cv_global_folds")):
                 raise ValueError(f"{type(method).__name__} under the global neighbourhood (maxneighbors=None) is not "
                                  "available: the factor of the system gives leave-one-out only; set maxneighbors")
-        else:
+        if not exact or type(method) is not LeaveOneOut:
             fold, nfolds = method.folds(x)
         h = eng.Krig(p["variogram"], variant, x, zv, mean=p["mean"], degree=p["degree"], drift_data=drift, factor=exact)
         try:
             if exact:
-                pred, var_, st = h.cv_global()
+                pred, var_, st = h.cv_global() if fold is None else h.cv_global_folds(fold)
             else:
                 _, nmax = searcher_ui(vdom, p["maxneighbors"], p["distance"], p["neighborhood"])
                 radius, radii = _ball(p["neighborhood"])

@@ -878,7 +878,7 @@ function krig_predict_device!(μ::Ptr{Float64}, σ²::Ptr{Float64}, status::Ptr{
               fit.handle, X0, C_NULL, Int64(m), μ, σ², status, GSS_MEM_DEVICE, stream))
 end
 
-# ---- cross-validation (gss.h: gss_krig_cv_global, gss_krig_cv_knn, gss_cv_summary) ------------------------------
+# ---- cross-validation (gss.h: gss_krig_cv_global, gss_krig_cv_global_folds, gss_krig_cv_knn, gss_cv_summary) ----
 struct CVSummary
   n_ok::Float64
   n_missing::Float64
@@ -927,7 +927,9 @@ end
 
 Cross-validation error of every variable of `problem` on its own samples (the domain is not used): the mean over the
 folds of the folds' mean squared errors.  `folds`: 0-based fold id per non-missing sample (`nothing`: leave-one-out);
-`excluderadius`: leave-ball-out.  `maxneighbors = nothing` is the global neighbourhood, which offers leave-one-out only.
+`excluderadius`: leave-ball-out.  `maxneighbors = nothing` is the global neighbourhood: leave-one-out and `folds` are both
+read off the factor of the one fitted system (no refit per fold); `excluderadius` there throws, a ball is no partition
+of the samples.
 """
 function cverror(solver::KrigingSolverHIP, problem::EstimationProblem; folds=nothing, excluderadius=nothing)
   pdata = data(problem)
@@ -951,8 +953,8 @@ function cverror(solver::KrigingSolverHIP, problem::EstimationProblem; folds=not
       variant, skmean = Int32(0), (p.mean isa Quantity ? Float64(ustrip(u, p.mean)) : Float64(p.mean))
     end
     exact = isnothing(p.maxneighbors)
-    exact && !(isnothing(folds) && isnothing(excluderadius)) &&
-      throw(ArgumentError("the global neighbourhood (maxneighbors = nothing) offers leave-one-out only"))
+    exact && !isnothing(excluderadius) &&
+      throw(ArgumentError("the global neighbourhood (maxneighbors = nothing) offers leave-one-out and folds only"))
     p.support === :point || throw(ArgumentError("cross-validation is at point support"))
     extent = sqrt(sum(abs2, maximum(X, dims=2) .- minimum(X, dims=2)))
     vg = Ref(cvariogram(p.variogram, d; extent))
@@ -965,10 +967,14 @@ function cverror(solver::KrigingSolverHIP, problem::EstimationProblem; folds=not
                    Ptr{Float64}, Int64, Int32, Ptr{Cvoid}),
                   h, vg, variant, skmean, degree, ndrift, X, z, Fd, n, exact ? Int32(0) : GSS_KRIG_NO_FACTOR, C_NULL))
       try
-        if exact
+        if exact && isnothing(fold)
           check(ccall((:gss_krig_cv_global, libgss), Int32,
                       (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Ptr{Cvoid}),
                       h[], pred, σ², status, GSS_MEM_HOST, C_NULL))
+        elseif exact
+          check(ccall((:gss_krig_cv_global_folds, libgss), Int32,
+                      (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Ptr{Cvoid}),
+                      h[], fold, pred, σ², status, GSS_MEM_HOST, C_NULL))
         else
           radius, ir = ballspec(p.neighborhood)
           met, mpar = searchmetric(p)

@@ -398,6 +398,24 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
  *   (GSS_ERR_INVALID on a GSS_KRIG_NO_FACTOR handle that never adopted one); an asynchronous fit is waited for and its
  *   status (GSS_ERR_NOT_POSDEF) reported here.  pred, var (n doubles) and status (n bytes, may be NULL) live in `mem`.
  *
+ * gss_krig_cv_global_folds: folds under the global neighbourhood, from the same factor and again without a refit.
+ *   fold: n ids >= 0 in `mem`, arbitrary and not necessarily compact; equal ids form a fold (a negative id:
+ *   GSS_ERR_INVALID; the ids are grouped on the host, device ids are copied there, which waits for the stream).  Every
+ *   sample is predicted from all samples outside its own fold F by the block form of the identity above:
+ *   z_F - pred_F = (B_FF)^-1 wd_F and var_F = diag((B_FF)^-1), where B_FF = W'[:, F]^T D W'[:, F] is a signed Gram
+ *   product of the gathered columns of W' (FP64 MFMA), factorised per fold as L L^T -- in LDS, one workgroup per fold,
+ *   for folds of up to 128 samples; larger folds one after the other on the factor-and-inverse routine of the fit.
+ *   The constraint rows enter through D alone, so simple, ordinary, universal and external-drift kriging share one
+ *   path.  fold == NULL is gss_krig_cv_global, bit for bit.  A fold whose remainder cannot determine the system,
+ *   n - |F| < max(1, nc), is decided from the sizes (simple kriging is exempt: an empty remainder predicts the mean
+ *   with variance C(0)); a fold whose Cholesky meets a non-positive or non-finite pivot is singular.  In both cases
+ *   every sample of the fold gets GSS_PT_SINGULAR and pred = var = NaN, and the other folds are unaffected.  Limit: a
+ *   remainder that passes the count but is geometrically degenerate (say, collinear samples under a planar drift) is
+ *   caught by the pivot test only, and rounding may let a pivot that is zero in exact arithmetic pass as a tiny
+ *   positive one.  No floating-point atomics, every sum in a fixed order: the same bits on every run.  Refusals and
+ *   the asynchronous fit as gss_krig_cv_global.  pred, var, status (may be NULL) live in `mem`; the call returns when
+ *   they are complete.
+ *
  * gss_krig_cv_knn: moving neighbourhood.  Sample p is predicted from its k nearest samples j that satisfy
  *   fold[j] != fold[p] and, when exclude_radius >= 0, search distance(p, j) > exclude_radius (leave-ball-out: a sample
  *   exactly on the radius is left out), besides what gss_krig_predict_knn requires (the ball radius / inv_radii, the
@@ -419,6 +437,8 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
  *   z, pred, var, status (NULL: all OK), fold, fold_mse live in `mem`; `out` is host memory and the call returns when it
  *   is filled. */
 int32_t gss_krig_cv_global(gss_krig_t* h, double* pred, double* var, uint8_t* status, int32_t mem, void* stream);
+int32_t gss_krig_cv_global_folds(gss_krig_t* h, const int32_t* fold, double* pred, double* var, uint8_t* status,
+                                 int32_t mem, void* stream);
 int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radius, int32_t k, int32_t minneighbors,
                         double radius, const double* inv_radii, int32_t metric, double metric_param,
                         double* pred, double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out,

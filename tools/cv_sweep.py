@@ -6,6 +6,10 @@
     shifted by a fraction of their spacing -- and the same k: the same kriging work per point, an unmasked search.  The
     two are measured alternating; the search / solve split of each is read from gss_profile_read ("knn", "krig_local").
   * gss_krig_cv_global at n = 1 000 and 4 000 beside gss_krig_create, the fit whose factor it reads.
+  * gss_krig_cv_global_folds at n = 1 000 and 4 000 with 10 shuffled folds, and at n = 4 000 with a few hundred block
+    folds, beside what a user does without it: per fold gss_krig_create on the other samples and
+    gss_krig_predict_global at the fold's samples.  The two alternate; the Gram kernel's share and its fraction of the
+    FP64 matrix peak (--fp64-peak-tflops, 78.6 for the MI355X) come from gss_profile_read ("cv_fold_gram").
 
 Method: warm-up, then `--reps` timed runs bracketed by events on the stream; the median is reported.  One JSON line per
 row on stdout.  python tools/cv_sweep.py [--reps 5] [--max-n 1000000]"""
@@ -118,13 +122,77 @@ def global_rows(lib, reps):
                           "cv_over_fit": round(t / fit, 5)}), flush=True)
 
 
+def fold_rows(lib, reps, peak_tflops):
+    rng = np.random.default_rng(3)
+    g = gss.MaternVariogram(range=60.0, order=1.5)
+    for n, kind in ((1000, "10 shuffled folds"), (4000, "10 shuffled folds"), (4000, "block folds")):
+        x = rng.uniform(0.0, 1000.0, (n, 3))
+        z = rng.normal(size=n)
+        if kind == "block folds":
+            fold, nfolds = gss.BlockValidation(125.0).folds(x)                             # up to 8^3 occupied blocks
+        else:
+            fold, nfolds = gss.KFoldValidation(10, rng=1).folds(x)
+        sizes = np.bincount(fold)
+        groups = [np.flatnonzero(fold == f) for f in range(nfolds)]
+        rest = [np.flatnonzero(fold != f) for f in range(nfolds)]
+        xin = [torch.as_tensor(x[gi], device="cuda") for gi in groups]
+        h = KrigHandle(g, OK, x, z)
+        dfold = torch.as_tensor(fold, device="cuda")
+        out = [torch.empty(n, dtype=torch.float64, device="cuda"), torch.empty(n, dtype=torch.float64, device="cuda"),
+               torch.empty(n, dtype=torch.uint8, device="cuda")]
+        po = [C.c_void_p(o.data_ptr()) for o in out]
+
+        def cv():
+            _lib.check(lib.gss_krig_cv_global_folds(h._h, C.c_void_p(dfold.data_ptr()), *po, _lib.MEM_DEVICE,
+                                                    _lib.current_stream()))
+
+        def refits():
+            for f in range(nfolds):
+                hf = KrigHandle(g, OK, x[rest[f]], z[rest[f]])
+                hf.predict_global(xin[f])
+                hf.close()
+        tc, tr = [], []
+        for _ in range(3):                              # alternating blocks
+            tc.append(timed(cv, reps))
+            tr.append(timed(refits, 1 if kind == "block folds" else reps))
+        c, r = statistics.median(tc), statistics.median(tr)
+        _lib.profile_enable(True)
+        _lib.profile_reset()
+        cv()
+        torch.cuda.synchronize()
+        parts = {k: round(_lib.profile_read("cv_fold_" + k)[0], 4) for k in ("gram", "solve", "large")}
+        _lib.profile_enable(False)
+        pred = out[0].cpu().numpy().copy()
+        refits_pred = np.empty(n)
+        for f in range(min(nfolds, 3)):                 # the two routes agree (first folds only: this is a timing tool)
+            hf = KrigHandle(g, OK, x[rest[f]], z[rest[f]])
+            refits_pred[groups[f]] = hf.predict_global(xin[f])[0].cpu().numpy()
+            hf.close()
+            assert np.max(np.abs(refits_pred[groups[f]] - pred[groups[f]])) < 1e-8
+        h.close()
+        # useful work: the lower triangle of every B_FF, N1 s^2 / 2 multiply-adds per fold, two flops each (the kernel
+        # issues whole 16 x 16 tiles and skips the k below the first column of a row block)
+        flops = (n + 1) * float(np.sum(sizes.astype(np.float64) ** 2))
+        gram_tflops = flops / (parts["gram"] * 1e-3) / 1e12 if parts["gram"] > 0 else float("nan")
+        print(json.dumps({"what": "cv_global_folds", "n": n, "folds": kind, "nfolds": int(nfolds),
+                          "largest_fold": int(sizes.max()), "cv_folds_ms": round(c, 3), "refits_ms": round(r, 3),
+                          "refits_over_cv": round(r / c, 2), "gram_ms": parts["gram"], "solve_ms": parts["solve"],
+                          "large_ms": parts["large"], "gram_nominal_tflops": round(gram_tflops, 3),
+                          "gram_fraction_of_fp64_matrix_peak": round(gram_tflops / peak_tflops, 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--fp64-peak-tflops", type=float, default=78.6)
+    ap.add_argument("--only-folds", action="store_true", help="the gss_krig_cv_global_folds rows only")
     ap.add_argument("--max-n", type=int, default=1_000_000)
     args = ap.parse_args()
     torch.cuda.set_device(0)
     lib = _lib.lib()
+    fold_rows(lib, args.reps, args.fp64_peak_tflops)
+    if args.only_folds:
+        return
     global_rows(lib, args.reps)
     knn_rows(lib, args.reps, args.max_n)
 
