@@ -29,6 +29,15 @@
 // the workgroup's nangles x nlags histogram in LDS, one atomic per quantity, when the bin changes and after the tile.
 // Plain LDS atomics for every pair lost to this by up to 3 x ("Varioplane").  Ordering, check, gather,
 // batches, unit drawing, culling and the reduction are the code of the omnidirectional pass.
+//
+// Cross-variograms (gss_variogram_cross).  vario_cross_kernel bins every kept pair once and adds the NZ (NZ + 1) / 2
+// products dz_a dz_b of its value differences.  A window of VW bins times 36 products does not fit the register file
+// (288 VGPRs at VW = 4), so the kernel takes the run form of the plane path for every NZ: a lane keeps one current bin
+// (count, sum of h, NP products: NP + 2 accumulators) and sends it to the workgroup's histogram in LDS when the bin
+// changes.  The bin is a lag, the same for a lane's whole life, so a run is carried across tiles and units and flushed
+// last at the end of the kernel.  Everything else -- ordering, check, gather, batches, unit drawing, culling, reduction
+// -- is the code of the omnidirectional pass; the histogram is (2 + NP) nlags + 2 words (78 KiB at NZ = 8, 256 lags:
+// room for two workgroups per compute unit; the registers of that instantiation admit one).  Registers and times: DESIGN.md, "Cross-variograms".
 #include "gss_internal.h"
 
 #include <hipcub/hipcub.hpp>
@@ -357,6 +366,158 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
   for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) out[t] = s_cnt[t];
 }
 
+// Cross-variograms: bins by lag like the omnidirectional instantiations above, sums mul_rounded(dz_a, dz_b) for every
+// a <= b (row a NZ - a (a - 1) / 2 + (b - a)).  Run form: see the head of this file.
+template <int DIM, int NZ>
+__global__ __launch_bounds__(VARIO_THREADS) void vario_cross_kernel(
+    const double* __restrict__ xs,      // n x DIM, k-d order
+    const double* __restrict__ zs,      // NZ columns of n, k-d order
+    const double* __restrict__ blo,     // nb x DIM batch boxes
+    const double* __restrict__ bhi,
+    VarioArgs A, unsigned long long* __restrict__ unit_counter,
+    unsigned long long* __restrict__ partial) {   // per workgroup: cnt[nlags], ndup, opened, hsum[nlags], csum[NP nlags]
+  constexpr int NP = NZ * (NZ + 1) / 2;
+  extern __shared__ double smem[];
+  const int nlags = A.nlags;
+  double* s_edge = smem;                                                  // nlags + 1
+  unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + nlags + 1);   // nlags + 2 (ndup, opened)
+  double* s_h = smem + nlags + 1 + nlags + 2;                             // nlags
+  double* s_z = s_h + nlags;                                              // NP * nlags
+  const int nwords = (nlags + 2) + nlags + NP * nlags;                    // what is flushed: s_cnt onwards
+  for (int t = threadIdx.x; t <= nlags; t += VARIO_THREADS) {
+    const double e = mul_rounded((double)t, A.delta);
+    s_edge[t] = mul_rounded(e, e);
+  }
+  for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) s_cnt[t] = 0ull;   // +0.0 is all-zero bits
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const double emax2 = s_edge[nlags];
+  const int64_t n = A.n;
+  const unsigned long long nunits = (unsigned long long)A.nb * (unsigned long long)A.nchunks;
+  unsigned long long ndup = 0ull, opened = 0ull;
+
+  int rb = 0;   // the lane's current run: its bin (valid while rc > 0), its pairs, its sums
+  unsigned int rc = 0u;
+  double rh = 0.0, rz[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) rz[p] = 0.0;
+
+  unsigned long long unext = 0ull, uend = 0ull;
+  while (true) {
+    if (unext == uend) {
+      unsigned long long u0 = 0ull;
+      if (lane == 0) u0 = atomicAdd(unit_counter, (unsigned long long)A.grab);
+      unext = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u0 >> 32)) << 32) |
+              (unsigned)__builtin_amdgcn_readfirstlane((int)u0);
+      if (unext >= nunits) break;
+      uend = unext + (unsigned long long)A.grab < nunits ? unext + (unsigned long long)A.grab : nunits;
+    }
+    const unsigned long long u = unext++;
+    const int I = (int)(u / (unsigned)A.nchunks);
+    const int J0 = (int)(u % (unsigned)A.nchunks) * A.jw;
+    if (J0 + A.jw - 1 < I) continue;   // the empty half of the triangle
+
+    // lanes 0..15: bound of tile (I, J0 + lane)
+    const int Jl = J0 + lane;
+    bool cand = lane < A.jw && Jl >= I && Jl < A.nb;
+    if (cand) {
+      double loa[DIM], hia[DIM], lob[DIM], hib[DIM];
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        loa[a] = blo[(int64_t)I * DIM + a];
+        hia[a] = bhi[(int64_t)I * DIM + a];
+        lob[a] = blo[(int64_t)Jl * DIM + a];
+        hib[a] = bhi[(int64_t)Jl * DIM + a];
+      }
+      cand = A.nocull || vario_box_d2<DIM>(loa, hia, lob, hib) <= emax2;
+    }
+    unsigned long long open = __ballot(cand);
+    opened += (unsigned long long)__popcll(open);
+
+    const int ni = (int64_t)I * 64 + 64 <= n ? 64 : (int)(n - (int64_t)I * 64);
+    while (open) {
+      const int pick = __builtin_ctzll(open);
+      open &= open - 1;
+      const int J = J0 + pick;
+      const bool diag = I == J;
+
+      const int64_t j = (int64_t)J * 64 + lane;
+      const bool vj = j < n;
+      const int64_t jc = vj ? j : n - 1;
+      double xj[DIM], zj[NZ];
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) xj[a] = xs[jc * DIM + a];
+#pragma unroll
+      for (int c = 0; c < NZ; ++c) zj[c] = zs[(int64_t)c * n + jc];
+
+#pragma unroll 2
+      for (int ii = 0; ii < ni; ++ii) {
+        const int64_t i = (int64_t)I * 64 + ii;   // wave uniform: scalar loads
+        double xi[DIM], dl[DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) xi[a] = xs[i * DIM + a];
+        const double d2 = vario_d2<DIM>(xi, xj, dl);
+        const bool pairok = vj && (!diag || ii < lane);
+        ndup += (pairok && d2 == 0.0) ? 1ull : 0ull;
+        bool keep = pairok && d2 > 0.0 && d2 <= emax2;
+        if (A.directional) {
+#pragma clang fp contract(off)
+          double t = dl[0] * A.u[0];
+          if (DIM > 1) t = t + dl[1] * A.u[1];
+          if (DIM > 2) t = t + dl[2] * A.u[2];
+          const double tt = t * t;
+          const double p2 = d2 - tt;
+          const double cd = A.cos2 * d2;
+          keep = keep && p2 <= A.dtol2 && tt >= cd;
+        }
+        const double h = gss_sqrt(d2);
+        const int k = vario_bin(s_edge, nlags, d2, h, A.inv_delta);   // in 0 .. nlags - 1 for every pair
+        // The run is updated without a branch that writes registers (such a branch makes the compiler keep copies of
+        // all NP sums): exact 0 / 1 factors select instead.  mf masks the pair: a dropped pair contributes products
+        // that are exactly zero; fma(rz, 1, v) = rz + v rounded once.  kf clears the run after it has been sent.
+        const bool flush = keep && k != rb && rc != 0u;
+        if (flush) {   // the bin changes: the run goes to the histogram
+          atomicAdd(&s_cnt[rb], (unsigned long long)rc);
+          lds_add_f64(&s_h[rb], rh);
+#pragma unroll
+          for (int p = 0; p < NP; ++p) lds_add_f64(&s_z[p * nlags + rb], rz[p]);
+        }
+        const double mf = keep ? 1.0 : 0.0, kf = flush ? 0.0 : 1.0;
+        double dz[NZ], dm[NZ];
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) {
+          dz[c] = zs[(int64_t)c * n + i] - zj[c];
+          dm[c] = mul_rounded(dz[c], mf);
+        }
+        rb = keep ? k : rb;
+        rc = (flush ? 0u : rc) + (keep ? 1u : 0u);
+        rh = fma(rh, kf, keep ? h : 0.0);
+        int p = 0;
+#pragma unroll
+        for (int a = 0; a < NZ; ++a) {
+#pragma unroll
+          for (int b = a; b < NZ; ++b) {
+            rz[p] = fma(rz[p], kf, mul_rounded(dm[a], dz[b]));
+            ++p;
+          }
+        }
+      }
+    }
+  }
+  if (rc != 0u) {   // the last run of the lane
+    atomicAdd(&s_cnt[rb], (unsigned long long)rc);
+    lds_add_f64(&s_h[rb], rh);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) lds_add_f64(&s_z[p * nlags + rb], rz[p]);
+  }
+  if (ndup) atomicAdd(&s_cnt[nlags], ndup);
+  if (lane == 0 && opened) atomicAdd(&s_cnt[nlags + 1], opened);
+  __syncthreads();
+  unsigned long long* out = partial + (size_t)blockIdx.x * nwords;
+  for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) out[t] = s_cnt[t];
+}
+
 // Sum of the workgroup slices, one workgroup per output word: thread j adds the slices j, j + 256, ... in ascending
 // order, then the 256 partial sums are folded pairwise in a fixed pattern -- the integer totals are exact and the
 // floating-point ones depend only on which pairs each workgroup of the pair kernel drew.
@@ -615,6 +776,47 @@ int32_t vario_launch_any(bool plane, int dim, const VarioPtrs& P, const VarioArg
   }
 }
 
+// the cross kernel: same protocol (nwg == 0: residency only).  Its histogram passes 64 KiB from NP nlags > ~7 900.
+template <int DIM, int NZ>
+int32_t vario_launch_cross_one(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds, hipStream_t s,
+                               int* resident) {
+  auto kernel = vario_cross_kernel<DIM, NZ>;
+  if (nwg == 0) {
+    GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds));
+    GSS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, kernel, VARIO_THREADS, lds));
+    return GSS_OK;
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(VARIO_THREADS), lds, s, P.xs, P.zs, P.lo, P.hi, A,
+                     P.unit_counter, P.partial);
+  GSS_HIP(hipGetLastError());
+  return GSS_OK;
+}
+
+template <int DIM>
+int32_t vario_launch_cross_nz(const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
+                              int* resident) {
+  switch (nz) {
+    case 1: return vario_launch_cross_one<DIM, 1>(P, A, nwg, lds, s, resident);
+    case 2: return vario_launch_cross_one<DIM, 2>(P, A, nwg, lds, s, resident);
+    case 3: return vario_launch_cross_one<DIM, 3>(P, A, nwg, lds, s, resident);
+    case 4: return vario_launch_cross_one<DIM, 4>(P, A, nwg, lds, s, resident);
+    case 5: return vario_launch_cross_one<DIM, 5>(P, A, nwg, lds, s, resident);
+    case 6: return vario_launch_cross_one<DIM, 6>(P, A, nwg, lds, s, resident);
+    case 7: return vario_launch_cross_one<DIM, 7>(P, A, nwg, lds, s, resident);
+    default: return vario_launch_cross_one<DIM, 8>(P, A, nwg, lds, s, resident);
+  }
+}
+
+int32_t vario_launch_cross(int dim, const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
+                           int* resident) {
+  switch (dim) {
+    case 1: return vario_launch_cross_nz<1>(P, A, nz, nwg, lds, s, resident);
+    case 2: return vario_launch_cross_nz<2>(P, A, nz, nwg, lds, s, resident);
+    default: return vario_launch_cross_nz<3>(P, A, nz, nwg, lds, s, resident);
+  }
+}
+
 // tile counters of the last call: written by the reduction into page-locked memory, read after the event
 int64_t* g_vario_stats = nullptr;   // [0] tiles opened
 hipEvent_t g_vario_event = nullptr;
@@ -801,6 +1003,189 @@ double fit_kind(const FitData& D, int kind, double nu, double* nugget, double* s
   return obest;
 }
 
+// ---- linear model of coregionalisation (gss_variogram_fit_lmc) -------------------------------------------------------
+// Gamma_k (nz x nz, symmetric) ~ B0 + B1 f_k with B0, B1 positive semidefinite.  Matrices are row-major nz x nz.
+constexpr int LMC_MAX_NZ = 8;
+
+// P+: the nearest positive semidefinite matrix in the Frobenius norm.  Cyclic Jacobi, rotations in the fixed order
+// (0,1), (0,2), .., (nz-2,nz-1), until the off-diagonal part is below 1e-34 of the whole or 64 sweeps; negative
+// eigenvalues are set to 0.  A matrix without a negative eigenvalue is returned as it came (no rounding added).
+void lmc_project(int nz, double* M) {
+  double A[LMC_MAX_NZ * LMC_MAX_NZ], V[LMC_MAX_NZ * LMC_MAX_NZ];
+  for (int i = 0; i < nz; ++i) {
+    for (int j = 0; j < nz; ++j) {
+      A[i * nz + j] = 0.5 * (M[i * nz + j] + M[j * nz + i]);
+      V[i * nz + j] = i == j ? 1.0 : 0.0;
+    }
+  }
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0, all = 0.0;
+    for (int i = 0; i < nz; ++i) {
+      for (int j = 0; j < nz; ++j) {
+        all += A[i * nz + j] * A[i * nz + j];
+        if (i != j) off += A[i * nz + j] * A[i * nz + j];
+      }
+    }
+    if (off <= 1e-34 * all) break;
+    for (int p = 0; p < nz - 1; ++p) {
+      for (int q = p + 1; q < nz; ++q) {
+        const double apq = A[p * nz + q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q * nz + q] - A[p * nz + p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < nz; ++k) {   // columns p, q
+          const double akp = A[k * nz + p], akq = A[k * nz + q];
+          A[k * nz + p] = c * akp - sn * akq;
+          A[k * nz + q] = sn * akp + c * akq;
+        }
+        for (int k = 0; k < nz; ++k) {   // rows p, q
+          const double apk = A[p * nz + k], aqk = A[q * nz + k];
+          A[p * nz + k] = c * apk - sn * aqk;
+          A[q * nz + k] = sn * apk + c * aqk;
+        }
+        A[p * nz + q] = A[q * nz + p] = 0.0;
+        for (int k = 0; k < nz; ++k) {
+          const double vkp = V[k * nz + p], vkq = V[k * nz + q];
+          V[k * nz + p] = c * vkp - sn * vkq;
+          V[k * nz + q] = sn * vkp + c * vkq;
+        }
+      }
+    }
+  }
+  bool negative = false;
+  for (int i = 0; i < nz; ++i) negative = negative || A[i * nz + i] < 0.0;
+  if (!negative) return;
+  for (int i = 0; i < nz; ++i) {
+    for (int j = i; j < nz; ++j) {
+      double v = 0.0;
+      for (int k = 0; k < nz; ++k) {
+        const double ev = A[k * nz + k];
+        if (ev > 0.0) v += V[i * nz + k] * ev * V[j * nz + k];
+      }
+      M[i * nz + j] = M[j * nz + i] = v;
+    }
+  }
+}
+
+struct LmcData {
+  int nz;
+  std::vector<double> h, w;
+  std::vector<double> G;   // per usable bin: the full nz x nz matrix
+};
+
+double lmc_objective(const LmcData& D, const std::vector<double>& f, const double* B0, const double* B1) {
+  const int nn = D.nz * D.nz;
+  double s = 0.0;
+  for (size_t k = 0; k < f.size(); ++k) {
+    double r2 = 0.0;
+    for (int e = 0; e < nn; ++e) {
+      const double r = D.G[k * nn + e] - B0[e] - B1[e] * f[k];
+      r2 += r * r;
+    }
+    s += D.w[k] * r2;
+  }
+  return s;
+}
+
+// Goulard-Voltz sweeps for given shape values f_k, from the unconstrained least-squares solution of every entry.
+double lmc_inner(const LmcData& D, const std::vector<double>& f, double* B0, double* B1) {
+  const int nz = D.nz, nn = nz * nz;
+  const size_t m = f.size();
+  double sw = 0.0, swf = 0.0, swff = 0.0;
+  for (size_t k = 0; k < m; ++k) {
+    sw += D.w[k];
+    swf += D.w[k] * f[k];
+    swff += D.w[k] * f[k] * f[k];
+  }
+  const double fb = swf / sw;
+  double sff = 0.0;
+  for (size_t k = 0; k < m; ++k) sff += D.w[k] * (f[k] - fb) * (f[k] - fb);
+  double SG[LMC_MAX_NZ * LMC_MAX_NZ], SFG[LMC_MAX_NZ * LMC_MAX_NZ];
+  for (int e = 0; e < nn; ++e) {
+    double sg = 0.0, sfg = 0.0;
+    for (size_t k = 0; k < m; ++k) {
+      sg += D.w[k] * D.G[k * nn + e];
+      sfg += D.w[k] * f[k] * D.G[k * nn + e];
+    }
+    SG[e] = sg;
+    SFG[e] = sfg;
+    const double gb = sg / sw;
+    double c = 0.0;
+    for (size_t k = 0; k < m; ++k) c += D.w[k] * (f[k] - fb) * (D.G[k * nn + e] - gb);
+    B1[e] = sff > 0.0 ? c / sff : 0.0;
+    B0[e] = gb - B1[e] * fb;
+  }
+  for (int sweep = 0; sweep < 1000; ++sweep) {
+    double N0[LMC_MAX_NZ * LMC_MAX_NZ], N1[LMC_MAX_NZ * LMC_MAX_NZ];
+    for (int e = 0; e < nn; ++e) N0[e] = (SG[e] - B1[e] * swf) / sw;
+    lmc_project(nz, N0);
+    for (int e = 0; e < nn; ++e) N1[e] = swff > 0.0 ? (SFG[e] - N0[e] * swf) / swff : 0.0;
+    lmc_project(nz, N1);
+    double d0 = 0.0, d1 = 0.0, n0 = 0.0, n1 = 0.0;
+    for (int e = 0; e < nn; ++e) {
+      d0 += (N0[e] - B0[e]) * (N0[e] - B0[e]);
+      d1 += (N1[e] - B1[e]) * (N1[e] - B1[e]);
+      n0 += N0[e] * N0[e];
+      n1 += N1[e] * N1[e];
+      B0[e] = N0[e];
+      B1[e] = N1[e];
+    }
+    const double tol = 1e-12 * (std::sqrt(n0) + std::sqrt(n1));
+    if (std::sqrt(d0) <= tol && std::sqrt(d1) <= tol) break;
+  }
+  return lmc_objective(D, f, B0, B1);
+}
+
+double lmc_at(const LmcData& D, int kind, double nu, double range, double* B0, double* B1) {
+  std::vector<double> f(D.h.size());
+  for (size_t k = 0; k < f.size(); ++k) f[k] = fit_shape(kind, D.h[k] / range, nu);
+  return lmc_inner(D, f, B0, B1);
+}
+
+// the range search of fit_kind with the sweeps as the inner solve
+double lmc_kind(const LmcData& D, int kind, double nu, double* range, double* B0, double* B1) {
+  double hmin = D.h[0], hmax = D.h[0];
+  for (double v : D.h) {
+    hmin = v < hmin ? v : hmin;
+    hmax = v > hmax ? v : hmax;
+  }
+  const double r0 = 0.25 * hmin, r1 = 4.0 * hmax;
+  std::vector<double> rg(FIT_GRID), og(FIT_GRID);
+  int ib = 0;
+  for (int i = 0; i < FIT_GRID; ++i) {
+    rg[i] = r0 * std::pow(r1 / r0, (double)i / (double)(FIT_GRID - 1));
+    og[i] = lmc_at(D, kind, nu, rg[i], B0, B1);
+    if (og[i] < og[ib]) ib = i;
+  }
+  double lo = rg[ib > 0 ? ib - 1 : 0], hi = rg[ib < FIT_GRID - 1 ? ib + 1 : FIT_GRID - 1];
+  double rbest = rg[ib], obest = og[ib];
+  const double gr = 0.6180339887498949;
+  double x1 = hi - gr * (hi - lo), x2 = lo + gr * (hi - lo);
+  double o1 = lmc_at(D, kind, nu, x1, B0, B1), o2 = lmc_at(D, kind, nu, x2, B0, B1);
+  for (int it = 0; it < 200 && (hi - lo) > 1e-8 * 0.5 * (hi + lo); ++it) {
+    if (o1 < obest) { obest = o1; rbest = x1; }
+    if (o2 < obest) { obest = o2; rbest = x2; }
+    if (o1 <= o2) {
+      hi = x2;
+      x2 = x1;
+      o2 = o1;
+      x1 = hi - gr * (hi - lo);
+      o1 = lmc_at(D, kind, nu, x1, B0, B1);
+    } else {
+      lo = x1;
+      x1 = x2;
+      o1 = o2;
+      x2 = lo + gr * (hi - lo);
+      o2 = lmc_at(D, kind, nu, x2, B0, B1);
+    }
+  }
+  if (o1 < obest) { obest = o1; rbest = x1; }
+  if (o2 < obest) { obest = o2; rbest = x2; }
+  *range = rbest;
+  return lmc_at(D, kind, nu, rbest, B0, B1);
+}
+
 // ---- geometric anisotropy in the plane (gss_variogram_fit_aniso) -----------------------------------------------------
 // Outer parameters u = (log r1, log(r2 / r1) <= 0, theta); for fixed u the scaled lag of bin k is
 // h_k sqrt(cos^2(phi_k - theta) / r1^2 + sin^2(phi_k - theta) / r2^2) and the rest is the cone solve above.
@@ -985,10 +1370,13 @@ namespace {
 // The pass over the pairs that gss_variogram_empirical and gss_variogram_plane share: checks of the common arguments,
 // staging, the finite-input check, the ordering, the gather, the grid, the pair kernel, the reduction and the way home.
 // A: what the caller has filled in of the kernel's arguments (direction or sectors); nbins: bins of the histogram
-// (nlags, or nangles nlags); dirs: the plane's sector boundaries (host), else NULL.
+// (nlags, or nangles nlags); dirs: the plane's sector boundaries (host), else NULL.  nsum: rows of value sums per bin
+// (nz, or nz (nz + 1) / 2 products when `cross`: gss_variogram_cross).
 int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, const double* z, int32_t nz, int32_t nlags, double maxlag, int32_t estimator, VarioArgs& A, int64_t nbins, const double* dirs,
-                  int64_t* count, double* lagsum, double* zsum, int64_t* nduplicates, int32_t mem, void* stream) {
+                  int64_t* count, double* lagsum, double* zsum, int64_t* nduplicates, int32_t mem, void* stream,
+                  bool cross = false, int32_t nsum = 0) {
   const bool plane = dirs != nullptr;
+  if (!cross) nsum = nz;
   // squared bin edges edge2[k] = fl(fl(k delta)^2): the kernel forms the same doubles; only the ends are checked here
   const double delta = maxlag / (double)nlags;
   {
@@ -1053,13 +1441,14 @@ int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, cons
   A.delta = delta;
   A.inv_delta = 1.0 / delta;
   P.unit_counter = d_flags;
-  const size_t nwords = (size_t)(nbins + 2) + nbins + (size_t)nz * nbins;
+  const size_t nwords = (size_t)(nbins + 2) + nbins + (size_t)nsum * nbins;
   const size_t lds = sizeof(double) * ((size_t)nlags + 1 + nwords + (plane ? 2 * (size_t)A.nangles : 0));
   // the grid: as many workgroups as are resident at a time for this instantiation (registers and LDS decide: 6 per CU
   // for one value column, 2 for eight), fewer when there are not two units per wave; a workgroup beyond that would only
   // start once the others have emptied the counter
   int resident = 0;
-  GSS_TRY(vario_launch_any(plane, dim, P, A, nz, 0, lds, s, &resident));
+  if (cross) GSS_TRY(vario_launch_cross(dim, P, A, nz, 0, lds, s, &resident));
+  else GSS_TRY(vario_launch_any(plane, dim, P, A, nz, 0, lds, s, &resident));
   if (resident < 1) resident = 1;
   const int64_t nunits = (int64_t)A.nb * A.nchunks;
   const int64_t want = (nunits + 7) / 8, cap = (int64_t)ncu * resident;
@@ -1073,7 +1462,7 @@ int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, cons
 
   GSS_TRY(scount.out(count, sizeof(int64_t) * nbins, mem));
   GSS_TRY(slag.out(lagsum, sizeof(double) * nbins, mem));
-  GSS_TRY(szsum.out(zsum, sizeof(double) * nbins * nz, mem));
+  GSS_TRY(szsum.out(zsum, sizeof(double) * nbins * nsum, mem));
   GSS_TRY(sdup.out(nduplicates, sizeof(int64_t), mem));
   if (!g_vario_stats) {
     GSS_HIP(hipHostMalloc(reinterpret_cast<void**>(&g_vario_stats), 2 * sizeof(int64_t), hipHostMallocDefault));
@@ -1081,12 +1470,13 @@ int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, cons
     GSS_HIP(hipEventCreateWithFlags(&g_vario_event, hipEventDisableTiming));
   }
   {
-    ProfScope prof(plane ? "vario_plane" : "vario_pairs", s);
-    GSS_TRY(vario_launch_any(plane, dim, P, A, nz, nwg, lds, s, nullptr));
+    ProfScope prof(cross ? "vario_cross" : (plane ? "vario_plane" : "vario_pairs"), s);
+    if (cross) GSS_TRY(vario_launch_cross(dim, P, A, nz, nwg, lds, s, nullptr));
+    else GSS_TRY(vario_launch_any(plane, dim, P, A, nz, nwg, lds, s, nullptr));
   }
   // (a histogram of nbins bins is reduced as one of nbins lags: sector s of the plane at s * nlags)
   hipLaunchKernelGGL(vario_reduce_kernel, dim3((unsigned)nwords), dim3(256), 0, s, P.partial, nwg,
-                     (int)nbins, (int)nz, scount.as<int64_t>(), slag.as<double>(), szsum.as<double>(),
+                     (int)nbins, (int)nsum, scount.as<int64_t>(), slag.as<double>(), szsum.as<double>(),
                      sdup.as<int64_t>(), g_vario_stats, d_bad);
   GSS_HIP(hipGetLastError());
   GSS_HIP(hipEventRecord(g_vario_event, s));
@@ -1097,7 +1487,7 @@ int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, cons
   if (mem == GSS_MEM_HOST) {
     GSS_HIP(hipMemcpyAsync(count, scount.p, sizeof(int64_t) * nbins, hipMemcpyDeviceToHost, s));
     GSS_HIP(hipMemcpyAsync(lagsum, slag.p, sizeof(double) * nbins, hipMemcpyDeviceToHost, s));
-    GSS_HIP(hipMemcpyAsync(zsum, szsum.p, sizeof(double) * nbins * nz, hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(zsum, szsum.p, sizeof(double) * nbins * nsum, hipMemcpyDeviceToHost, s));
     GSS_HIP(hipMemcpyAsync(nduplicates, sdup.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     GSS_HIP(hipStreamSynchronize(s));
     // a non-finite input is found on the device and reported through the outputs (gss.h); here they have arrived
@@ -1125,6 +1515,29 @@ int32_t vario_check_args(const char* who, const double* x, int64_t n, int32_t di
   return GSS_OK;
 }
 
+// the direction test of gss_variogram_empirical and gss_variogram_cross into the kernel's arguments (A is cleared first)
+int32_t vario_direction(const char* who, int32_t dim, const double* direction, double dtol, double cos_atol,
+                        VarioArgs& A) {
+  std::memset(&A, 0, sizeof(A));
+  A.dtol2 = __builtin_huge_val();
+  if (direction == nullptr) return GSS_OK;
+  // the direction is a HOST array of `dim` doubles in both memory modes (it is a parameter, not data)
+  double nn = 0.0;
+  for (int a = 0; a < dim; ++a) {
+    GSS_REQUIRE(std::isfinite(direction[a]), "%s: direction is not finite", who);
+    nn += direction[a] * direction[a];
+    A.u[a] = direction[a];
+  }
+  GSS_REQUIRE(std::fabs(std::sqrt(nn) - 1.0) <= 1e-12, "%s: direction is not a unit vector (norm %.17g)", who,
+              std::sqrt(nn));
+  GSS_REQUIRE(dtol > 0.0 && !std::isnan(dtol), "%s: dtol must be positive (+inf: no band)", who);
+  GSS_REQUIRE(cos_atol >= 0.0 && cos_atol <= 1.0, "%s: cos_atol outside [0, 1]", who);
+  A.directional = 1;
+  A.dtol2 = dtol * dtol;
+  A.cos2 = cos_atol * cos_atol;
+  return GSS_OK;
+}
+
 }  // namespace
 
 extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
@@ -1135,26 +1548,22 @@ extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t d
   GSS_TRY(vario_check_args("gss_variogram_empirical", x, n, dim, 1, z, nz, VARIO_MAX_NZ, nlags, maxlag, estimator, count,
                            lagsum, zsum, nduplicates, mem));
   VarioArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.dtol2 = __builtin_huge_val();
-  if (direction != nullptr) {
-    // the direction is a HOST array of `dim` doubles in both memory modes (it is a parameter, not data)
-    double nn = 0.0;
-    for (int a = 0; a < dim; ++a) {
-      GSS_REQUIRE(std::isfinite(direction[a]), "gss_variogram_empirical: direction is not finite");
-      nn += direction[a] * direction[a];
-      A.u[a] = direction[a];
-    }
-    GSS_REQUIRE(std::fabs(std::sqrt(nn) - 1.0) <= 1e-12, "gss_variogram_empirical: direction is not a unit vector "
-                "(norm %.17g)", std::sqrt(nn));
-    GSS_REQUIRE(dtol > 0.0 && !std::isnan(dtol), "gss_variogram_empirical: dtol must be positive (+inf: no band)");
-    GSS_REQUIRE(cos_atol >= 0.0 && cos_atol <= 1.0, "gss_variogram_empirical: cos_atol outside [0, 1]");
-    A.directional = 1;
-    A.dtol2 = dtol * dtol;
-    A.cos2 = cos_atol * cos_atol;
-  }
+  GSS_TRY(vario_direction("gss_variogram_empirical", dim, direction, dtol, cos_atol, A));
   return vario_run("gss_variogram_empirical", x, n, dim, z, nz, nlags, maxlag, estimator, A, nlags, nullptr,
                    count, lagsum, zsum, nduplicates, mem, stream);
+}
+
+extern "C" int32_t gss_variogram_cross(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
+                                       int32_t nlags, double maxlag, const double* direction, double dtol,
+                                       double cos_atol, int64_t* count, double* lagsum, double* csum,
+                                       int64_t* nduplicates, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_TRY(vario_check_args("gss_variogram_cross", x, n, dim, 1, z, nz, VARIO_MAX_NZ, nlags, maxlag, GSS_VARIO_MATHERON,
+                           count, lagsum, csum, nduplicates, mem));
+  VarioArgs A;
+  GSS_TRY(vario_direction("gss_variogram_cross", dim, direction, dtol, cos_atol, A));
+  return vario_run("gss_variogram_cross", x, n, dim, z, nz, nlags, maxlag, GSS_VARIO_MATHERON, A, nlags, nullptr, count,
+                   lagsum, csum, nduplicates, mem, stream, true, nz * (nz + 1) / 2);
 }
 
 extern "C" int32_t gss_variogram_plane(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
@@ -1372,5 +1781,89 @@ extern "C" int32_t gss_variogram_fit_aniso(const double* h, const double* phi, c
   best->rotation[1] = -sn;
   best->rotation[3] = sn;
   best->rotation[4] = c;
+  return GSS_OK;
+}
+
+extern "C" int32_t gss_variogram_fit_lmc(const double* h, const double* gamma, const int64_t* count, int32_t nlags,
+                                         int32_t nz, const int32_t* kinds, int32_t nkinds, double nu,
+                                         int32_t weighting, int32_t* kind, double* range, double* b0, double* b1,
+                                         double* objective) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr && gamma != nullptr && count != nullptr && kinds != nullptr && kind != nullptr &&
+                  range != nullptr && b0 != nullptr && b1 != nullptr && objective != nullptr,
+              "gss_variogram_fit_lmc: NULL argument");
+  GSS_REQUIRE(nz >= 1 && nz <= LMC_MAX_NZ, "gss_variogram_fit_lmc: nz %d outside 1..%d", nz, LMC_MAX_NZ);
+  GSS_REQUIRE(nlags >= 1 && nlags <= 65536, "gss_variogram_fit_lmc: nlags %d outside 1..65536", nlags);
+  GSS_REQUIRE(nkinds >= 1 && nkinds <= 64, "gss_variogram_fit_lmc: nkinds %d outside 1..64", nkinds);
+  GSS_REQUIRE(weighting >= GSS_FIT_W_COUNT && weighting <= GSS_FIT_W_UNIFORM,
+              "gss_variogram_fit_lmc: unknown weighting %d", weighting);
+  bool matern = false;
+  for (int i = 0; i < nkinds; ++i) {
+    if (kinds[i] == GSS_VG_POWER) {
+      set_error("gss_variogram_fit_lmc: the power model has no sill and no range to search; only the stationary kinds "
+                "are fitted");
+      return GSS_ERR_UNSUPPORTED;
+    }
+    GSS_REQUIRE(kinds[i] >= GSS_VG_GAUSSIAN && kinds[i] <= GSS_VG_SINEHOLE, "gss_variogram_fit_lmc: unknown kind %d",
+                kinds[i]);
+    matern = matern || kinds[i] == GSS_VG_MATERN;
+  }
+  if (matern) GSS_REQUIRE(nu > 0.0 && nu <= 50.0, "gss_variogram_fit_lmc: Matern order must lie in (0, 50]");
+  const int nn = nz * nz;
+  LmcData D;
+  D.nz = nz;
+  for (int k = 0; k < nlags; ++k) {
+    if (count[k] <= 0) continue;
+    GSS_REQUIRE(std::isfinite(h[k]) && h[k] > 0.0, "gss_variogram_fit_lmc: bin %d has pairs but no finite positive lag",
+                k);
+    const double c = (double)count[k];
+    D.h.push_back(h[k]);
+    D.w.push_back(weighting == GSS_FIT_W_COUNT ? c : (weighting == GSS_FIT_W_COUNT_OVER_H2 ? c / (h[k] * h[k]) : 1.0));
+    const size_t at = D.G.size();
+    D.G.resize(at + nn);
+    for (int a = 0; a < nz; ++a) {
+      for (int b = a; b < nz; ++b) {
+        const double g = gamma[(size_t)(a * nz - a * (a - 1) / 2 + (b - a)) * nlags + k];
+        GSS_REQUIRE(std::isfinite(g), "gss_variogram_fit_lmc: bin %d has pairs but no finite ordinate (%d, %d)", k, a, b);
+        D.G[at + a * nz + b] = D.G[at + b * nz + a] = g;
+      }
+    }
+  }
+  GSS_REQUIRE(D.h.size() >= 2, "gss_variogram_fit_lmc: fewer than two bins hold pairs");
+  int ibest = -1;
+  double B0[LMC_MAX_NZ * LMC_MAX_NZ], B1[LMC_MAX_NZ * LMC_MAX_NZ];
+  for (int i = 0; i < nkinds; ++i) {
+    double rg = 0.0;
+    bool positive = true;
+    if (nz == 1) {   // one variable: the positive semidefinite cone is nugget >= 0, sill - nugget >= 0 -- the
+      FitData F;     // closed form of gss_variogram_fit with max_nugget_frac = 1, and its very numbers
+      F.h = D.h;
+      F.g = D.G;
+      F.w = D.w;
+      F.frac = 1.0;
+      double ng, sl;
+      objective[i] = fit_kind(F, kinds[i], nu, &ng, &sl, &rg);
+      B0[0] = ng;
+      B1[0] = sl - ng;
+      positive = sl > 0.0;
+    } else {
+      objective[i] = lmc_kind(D, kinds[i], nu, &rg, B0, B1);
+      for (int a = 0; a < nz; ++a) positive = positive && B0[a * nz + a] + B1[a * nz + a] > 0.0;
+    }
+    if (!positive) {   // a variable without a positive sill: no model of this kind
+      objective[i] = std::nan("");
+      continue;
+    }
+    if (ibest < 0 || objective[i] < objective[ibest]) {
+      ibest = i;
+      *range = rg;
+      for (int e = 0; e < nn; ++e) {
+        b0[e] = B0[e];
+        b1[e] = B1[e];
+      }
+    }
+  }
+  GSS_REQUIRE(ibest >= 0, "gss_variogram_fit_lmc: no kind fits these ordinates with a positive sill for every variable");
+  *kind = kinds[ibest];
   return GSS_OK;
 }

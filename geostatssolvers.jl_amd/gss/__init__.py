@@ -14,7 +14,8 @@ from .validation import (BlockValidation, CrossValidationResult, KFoldValidation
 from .variograms import (CubicVariogram, ExponentialVariogram, GaussianVariogram, MaternVariogram, MetricBall,
                          NestedVariogram, PentasphericalVariogram, PowerVariogram, SineHoleVariogram,
                          SphericalVariogram)
-from .variography import (DirectionalVariogram, EmpiricalVariogram, EmpiricalVariogramResult, EmpiricalVarioplane,
-                          EmpiricalVarioplaneResult, fit, fit_anisotropic)
+from .variography import (DirectionalVariogram, EmpiricalCrossVariogram, EmpiricalCrossVariogramResult,
+                          EmpiricalVariogram, EmpiricalVariogramResult, EmpiricalVarioplane, EmpiricalVarioplaneResult,
+                          LMCModel, fit, fit_anisotropic, fit_lmc)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

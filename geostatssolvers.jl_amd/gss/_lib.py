@@ -85,6 +85,8 @@ SIGNATURES = {
     "gss_variogram_fit": [_p, _p, _p, _i32, _p, _i32, _f64, _i32, _f64, _VG, _p],
     "gss_variogram_plane": [_p, _i64, _i32, _p, _i32, _i32, _f64, _i32, _p, _p, _f64, _i32, _p, _p, _p, _p, _i32, _p],
     "gss_variogram_fit_aniso": [_p, _p, _p, _p, _i32, _p, _i32, _f64, _i32, _f64, _VG, _p],
+    "gss_variogram_cross": [_p, _i64, _i32, _p, _i32, _i32, _f64, _p, _f64, _f64, _p, _p, _p, _p, _i32, _p],
+    "gss_variogram_fit_lmc": [_p, _p, _p, _i32, _i32, _p, _i32, _f64, _i32, _p, _p, _p, _p, _p],
     "gss_knn_search": [_p, _i64, _i32, _p, _i64, _i32, _f64, _p, _i32, _f64, _p, _p, _i32, _p],
     "gss_krig_create": [C.POINTER(_p), _VG, _i32, _f64, _i32, _i32, _p, _p, _p, _i64, _i32, _p],
     "gss_krig_destroy": [_p],

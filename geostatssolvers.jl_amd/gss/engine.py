@@ -797,6 +797,66 @@ class HipEngine:
         return names[best.kind], best.sill, best.nugget, radii, theta, best.range, best.nu, obj
 
     @staticmethod
+    def variogram_cross(x, z, nlags, maxlag, direction=None, dtol=float("inf"), cos_atol=0.0):
+        """gss_variogram_cross: x (n, d), z (nz, n) -> count (nlags,) int64, lagsum (nlags,), csum (nz (nz + 1) / 2,
+        nlags) -- row a nz - a (a - 1) / 2 + (b - a) holds the pair (a, b), a <= b -- and nduplicates.  Memory as in
+        variogram_empirical."""
+        l = _lib.lib()
+        dev = is_torch(x) and x.is_cuda
+        if dev != (is_torch(z) and z.is_cuda):
+            raise ValueError("x and z must live in the same memory space")
+        x = _prep_in(x)
+        z = _prep_in(z)
+        if x.ndim == 1:
+            x = x[:, None]
+        n, d = x.shape
+        z = z.reshape(-1, n)
+        nz = z.shape[0]
+        nlags = int(nlags)
+        shape = (nz * (nz + 1) // 2, max(nlags, 0))
+        if dev:
+            import torch
+            count = torch.empty(shape[1], dtype=torch.int64, device=x.device)
+            lagsum = torch.empty(shape[1], dtype=torch.float64, device=x.device)
+            csum = torch.empty(shape, dtype=torch.float64, device=x.device)
+            ndup = torch.empty(1, dtype=torch.int64, device=x.device)
+        else:
+            count = np.empty(shape[1], dtype=np.int64)
+            lagsum = np.empty(shape[1])
+            csum = np.empty(shape)
+            ndup = np.zeros(1, dtype=np.int64)
+        u = None if direction is None else np.ascontiguousarray(direction, dtype=np.float64).reshape(-1)
+        if u is not None and u.size != d:
+            raise ValueError(f"direction has {u.size} components for {d}-D samples")
+        check(l.gss_variogram_cross(ptr(x), n, d, ptr(z), nz, nlags, float(maxlag), ptr(u), float(dtol), float(cos_atol),
+                                    ptr(count), ptr(lagsum), ptr(csum), ptr(ndup), MEM_DEVICE if dev else MEM_HOST,
+                                    current_stream()))
+        return count, lagsum, csum, (ndup if dev else int(ndup[0]))
+
+    @staticmethod
+    def variogram_fit_lmc(h, gamma, count, kinds, nu=1.0, weighting=0):
+        """gss_variogram_fit_lmc (host code of the library, no device): h, count (nlags,), gamma (nz (nz + 1) / 2,
+        nlags) in the row order of variogram_cross -> (kind name, range, B0 (nz, nz), B1 (nz, nz), objective per
+        kind)."""
+        l = _lib.load()
+        h = np.ascontiguousarray(h, dtype=np.float64).reshape(-1)
+        g = np.ascontiguousarray(gamma, dtype=np.float64).reshape(-1, h.size)
+        c = np.ascontiguousarray(count, dtype=np.int64).reshape(-1)
+        if c.shape != h.shape:
+            raise ValueError("h and count must be vectors of one length")
+        nz = int(round((np.sqrt(8.0 * g.shape[0] + 1.0) - 1.0) / 2.0))
+        if nz * (nz + 1) // 2 != g.shape[0]:
+            raise ValueError("gamma has nz (nz + 1) / 2 rows: one per pair of variables (a, b), a <= b")
+        names = {v: k for k, v in _lib._KINDS.items()}
+        kk = np.ascontiguousarray([_lib._KINDS[k] for k in kinds], dtype=np.int32)
+        obj = np.empty(len(kk))
+        kind, rng = C.c_int32(0), C.c_double(0.0)
+        b0, b1 = np.zeros((max(nz, 1), max(nz, 1))), np.zeros((max(nz, 1), max(nz, 1)))
+        check(l.gss_variogram_fit_lmc(ptr(h), ptr(g), ptr(c), h.size, nz, ptr(kk), len(kk), float(nu), int(weighting),
+                                      C.byref(kind), C.byref(rng), ptr(b0), ptr(b1), ptr(obj)))
+        return names[kind.value], rng.value, b0, b1, obj
+
+    @staticmethod
     def cv_summary(z, pred, var, status=None, fold=None, nfolds=0):
         """gss_cv_summary: the error summary of a cross-validation, reduced on the device in a fixed order -> (dict of
         the fields of gss_cv_summary_t, per-fold mean squared errors or None).  numpy arrays or CUDA tensors, all in

@@ -275,3 +275,123 @@ def fit_anisotropic(kind_or_kinds, plane, weighting="count", nu=1.0, max_nugget_
         ball = MetricBall(radii, float(theta))
         model = VariogramModel(kind, float(sill), float(nugget), 1.0, float(order), ball.radii, regularize, ball.rotation)
     return (model, dict(zip(names, obj))) if return_objectives else model
+
+
+# ---- cross-variograms in one pass (gss_variogram_cross) and the linear model of coregionalisation -------------------
+def _pair_row(nz, a, b):
+    a, b = (a, b) if a <= b else (b, a)
+    return a * nz - a * (a - 1) // 2 + (b - a)
+
+
+@dataclass
+class EmpiricalCrossVariogramResult:
+    """Direct and cross variograms of several variables measured on the same samples, from one pass over the pairs.
+    `ordinate` has one row per pair of variables (a, b), a <= b, in the row order of gss_variogram_cross; bins
+    without pairs hold NaN.  Variables are addressed by name or by position."""
+    names: tuple
+    abscissa: np.ndarray
+    ordinate: np.ndarray      # (nz (nz + 1) / 2, nlags): gamma_ab = csum / (2 count)
+    count: np.ndarray
+    nduplicates: int
+    maxlag: float
+
+    def _index(self, v):
+        return self.names.index(v) if isinstance(v, str) else int(v)
+
+    @property
+    def nlags(self):
+        return int(self.count.size)
+
+    def gamma(self, a, b):
+        """The cross-variogram of variables a and b (symmetric in them); gamma(a, a) is the direct one."""
+        return self.ordinate[_pair_row(len(self.names), self._index(a), self._index(b))]
+
+    def direct(self, a):
+        """Variable a's direct variogram as an EmpiricalVariogramResult: what `fit` takes."""
+        i = self._index(a)
+        return EmpiricalVariogramResult(self.abscissa.copy(), self.gamma(i, i).copy(), self.count.copy(),
+                                        self.nduplicates, self.maxlag, "matheron", self.names[i])
+
+
+def EmpiricalCrossVariogram(data, names, nlags=20, maxlag=None, direction=None, dtol=float("inf"), atol=math.pi / 8,
+                            engine=None):
+    """Direct and cross variograms (Matheron) of up to 8 variables of one table in ONE pass over the pairs.  A sample
+    takes part only if every one of the variables exists there (a cross-variogram needs both values at both ends).
+    `direction`, `dtol`, `atol` as in DirectionalVariogram; None: omnidirectional."""
+    engine = engine or default_engine()
+    names = tuple(names)
+    if not 1 <= len(names) <= 8:
+        raise ValueError("between 1 and 8 variables (gss.h: value columns per gss_variogram_cross call)")
+    x = np.ascontiguousarray(data.domain.centroids(), dtype=np.float64)
+    cols = np.stack([np.asarray(data[v], dtype=np.float64) for v in names])
+    keep = np.isfinite(cols).all(axis=0)
+    if not keep.all():
+        x, cols = np.ascontiguousarray(x[keep]), cols[:, keep]
+    if maxlag is None:
+        maxlag = _default_maxlag(x)
+    u, cos_atol = None, 0.0
+    if direction is not None:
+        u = np.asarray(direction, dtype=np.float64).reshape(-1)
+        nrm = float(np.sqrt((u * u).sum()))
+        if not (nrm > 0.0 and np.isfinite(nrm)):
+            raise ValueError("direction must be a non-zero finite vector")
+        if atol is not None and not 0.0 <= atol <= math.pi / 2:
+            raise ValueError("atol is an angle in [0, pi / 2] radians")
+        u = u / nrm
+        cos_atol = 0.0 if atol is None or atol >= math.pi / 2 else math.cos(atol)
+    count, lagsum, csum, ndup = engine.variogram_cross(x, np.ascontiguousarray(cols), nlags, maxlag, u, dtol, cos_atol)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        absc = np.where(count > 0, lagsum / count, np.nan)
+        gam = np.where(count > 0, csum / (2.0 * count.astype(np.float64)), np.nan)
+    return EmpiricalCrossVariogramResult(names, absc, gam, count, int(ndup), float(maxlag))
+
+
+@dataclass
+class LMCModel:
+    """Linear model of coregionalisation Gamma(h) = B0 + B1 f(h / range): nugget matrix B0 and partial sills B1, both
+    positive semidefinite, one structure and one range for all variables."""
+    names: tuple
+    kind: str
+    range: float
+    order: float
+    B0: np.ndarray
+    B1: np.ndarray
+    objective: float
+
+    def _index(self, v):
+        return self.names.index(v) if isinstance(v, str) else int(v)
+
+    def variogram(self, a):
+        """Variable a's direct model, as every solver takes it: sill = B0_aa + B1_aa, nugget = B0_aa and the shared
+        range.  A Gaussian model follows the `nugget - 1e-6` rule of `fit`."""
+        i = self._index(a)
+        sill, nugget, regularize = float(self.B0[i, i] + self.B1[i, i]), float(self.B0[i, i]), True
+        if self.kind == "gaussian":
+            if nugget >= GAUSSIAN_NUGGET_EPS:
+                nugget -= GAUSSIAN_NUGGET_EPS
+            else:
+                regularize = False
+        return VariogramModel(self.kind, sill, nugget, float(self.range), float(self.order), None, regularize)
+
+    def correlation(self, a, b):
+        """(B0_ab + B1_ab) / sqrt(sill_a sill_b): the correlation of the two variables at one location under this
+        model.  This is the number the LUGS solver takes as its joint parameter `correlation` when it co-simulates a
+        and b."""
+        i, j = self._index(a), self._index(b)
+        s = self.B0 + self.B1
+        return float(s[i, j] / math.sqrt(s[i, i] * s[j, j]))
+
+
+def fit_lmc(kind_or_kinds, cross, weighting="count", nu=1.0, return_objectives=False, engine=None):
+    """Fit of the linear model of coregionalisation to an EmpiricalCrossVariogramResult (gss_variogram_fit_lmc, host
+    code of the library): the best of the given kinds -> LMCModel."""
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting {weighting!r}: one of {tuple(WEIGHTINGS)}")
+    engine = engine or default_engine()
+    kinds = [kind_or_kinds] if isinstance(kind_or_kinds, str) or callable(kind_or_kinds) else list(kind_or_kinds)
+    knames = [_kind_name(k) for k in kinds]
+    kind, rng, b0, b1, obj = engine.variogram_fit_lmc(cross.abscissa, cross.ordinate, cross.count, knames, nu,
+                                                      WEIGHTINGS[weighting])
+    model = LMCModel(tuple(cross.names), kind, float(rng), float(nu) if kind == "matern" else 1.0, b0, b1,
+                     float(obj[knames.index(kind)]))
+    return (model, dict(zip(knames, obj))) if return_objectives else model

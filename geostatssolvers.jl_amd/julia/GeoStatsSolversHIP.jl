@@ -44,6 +44,7 @@ import GeoStatsBase: solve, preprocess, solvesingle
 export KrigingSolverHIP, IDWSolverHIP, LWRSolverHIP, ExpWeight, TricubeWeight, FFTGSHIP, LUGSHIP, SGSHIP
 export krig_fit, krig_predict_device!, fftgs_realize_device!, bind_device
 export empirical_variogram, fit_variogram, empirical_varioplane, fit_anisotropic
+export empirical_cross_variogram, fit_lmc, pairindex
 export cverror, krig_cv_global, cv_summary, CVSummary
 
 const libgss = get(ENV, "LIBGSS_HIP", "libgss_hip.so")
@@ -1171,6 +1172,85 @@ function fit_anisotropic(kinds, plane; var=nothing, weighting::Symbol=:count, or
   # [RECALL] Meshes exports Rotations' Angle2d (its docs write `Rotate(Angle2d(π/2))`); rotation[1], rotation[4] = cos, sin
   ball = MetricBall((1 / b.inv_radii[1], 1 / b.inv_radii[2]), Angle2d(atan(b.rotation[4], b.rotation[1])))
   T === MaternVariogram ? T(ball; sill=b.sill, nugget=nug, order=b.nu) : T(ball; sill=b.sill, nugget=nug)
+end
+
+"""
+    empirical_cross_variogram(data, vars; nlags=20, maxlag=nothing, direction=nothing, dtol=Inf, atol=π/8)
+
+Direct and cross variograms (Matheron) of up to 8 variables measured on the same samples in ONE pass over the pairs
+(gss_variogram_cross).  Rows with a missing value in any of `vars` are dropped.  Returns `(vars, abscissa, ordinate,
+counts, nduplicates)`; `ordinate` is an `nlags × nz(nz+1)/2` matrix whose column `pairindex(nz, a, b)` holds
+γ_ab = csum / 2count for the variables a ≤ b (1-based positions in `vars`); the columns (a, a) are the direct variograms.
+"""
+function empirical_cross_variogram(data, vars; nlags::Integer=20, maxlag=nothing, direction=nothing, dtol::Real=Inf,
+                                   atol::Real=π / 8)
+  names = collect(Symbol, vars)
+  tab = Tables.columns(values(data))
+  cols = [Tables.getcolumn(tab, v) for v in names]
+  keep = [i for i in 1:nelements(domain(data)) if all(c -> !ismissing(c[i]) && isfinite(ustrip(c[i])), cols)]
+  X = coordmatrix(domain(data))[:, keep]
+  d, n = size(X)
+  nz = length(names)
+  Z = Matrix{Float64}(undef, n, nz)          # column c at Z + c * n
+  for (c, col) in enumerate(cols), (r, i) in enumerate(keep)
+    Z[r, c] = Float64(ustrip(col[i]))
+  end
+  lag = isnothing(maxlag) ? 0.1 * sqrt(sum(abs2, maximum(X, dims=2) .- minimum(X, dims=2))) : Float64(ustrip(maxlag))
+  u = isnothing(direction) ? nothing : collect(Float64, direction) ./ sqrt(sum(abs2, direction))
+  cosatol = isnothing(direction) || atol >= π / 2 ? 0.0 : cos(Float64(atol))
+  count = Vector{Int64}(undef, nlags)
+  lagsum = Vector{Float64}(undef, nlags)
+  csum = Matrix{Float64}(undef, nlags, nz * (nz + 1) ÷ 2)
+  ndup = Ref{Int64}(0)
+  GC.@preserve X Z u check(ccall((:gss_variogram_cross, libgss), Int32,
+    (Ptr{Float64}, Int64, Int32, Ptr{Float64}, Int32, Int32, Float64, Ptr{Float64}, Float64, Float64, Ptr{Int64},
+     Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int32, Ptr{Cvoid}),
+    X, Int64(n), Int32(d), Z, Int32(nz), Int32(nlags), lag, isnothing(u) ? C_NULL : pointer(u), Float64(dtol), cosatol,
+    count, lagsum, csum, ndup, GSS_MEM_HOST, C_NULL))
+  abscissa = [c > 0 ? s / c : NaN for (s, c) in zip(lagsum, count)]
+  ordinate = [count[k] == 0 ? NaN : csum[k, p] / 2count[k] for k in 1:nlags, p in 1:size(csum, 2)]
+  (vars=names, abscissa=abscissa, ordinate=ordinate, counts=count, nduplicates=ndup[])
+end
+
+"column of the pair (a, b) of 1-based variable positions in the `ordinate` of `empirical_cross_variogram`"
+pairindex(nz::Integer, a::Integer, b::Integer) = (a > b ? pairindex(nz, b, a) : (a - 1) * nz - (a - 1) * (a - 2) ÷ 2 + (b - a) + 1)
+
+"""
+    fit_lmc(kinds, cross; weighting=:count, order=1.0)
+
+Linear model of coregionalisation Γ(h) = B0 + B1 f(h / range) fitted to the result of `empirical_cross_variogram`
+(gss_variogram_fit_lmc, host code of the library).  Returns `(variograms, correlation, B0, B1, range)`: `variograms[v]`
+is the direct model of variable `v` (sill B0_vv + B1_vv, nugget B0_vv, the shared range; the Gaussian nugget rule is that
+of `fit_variogram`) and `correlation[(a, b)]` = (B0_ab + B1_ab) / sqrt(sill_a sill_b) is the number the LUGS solver takes as
+the joint parameter `correlation` of `(a, b)`.
+"""
+function fit_lmc(kinds, cross; weighting::Symbol=:count, order::Real=1.0)
+  ks = kinds isa Type ? [kinds] : collect(kinds)
+  codes = Int32[something(findfirst(==(k), GAMMA_CONSTRUCTORS), 8) - 1 for k in ks]      # anything else: GSS_VG_POWER
+  w = weighting == :count ? Int32(0) : weighting == :uniform ? Int32(2) : Int32(1)
+  nz = length(cross.vars)
+  h = collect(Float64, cross.abscissa)
+  gam = Matrix{Float64}(cross.ordinate)             # pair p at gam + (p - 1) * nlags
+  cnt = collect(Int64, cross.counts)
+  kind = Ref{Int32}(0)
+  range = Ref{Float64}(0.0)
+  B0 = Matrix{Float64}(undef, nz, nz)
+  B1 = Matrix{Float64}(undef, nz, nz)               # symmetric: row-major and column-major agree
+  objective = Vector{Float64}(undef, length(codes))
+  check(ccall((:gss_variogram_fit_lmc, libgss), Int32,
+    (Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int32, Int32, Ptr{Int32}, Int32, Float64, Int32, Ptr{Int32}, Ptr{Float64},
+     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, gam, cnt, Int32(length(cnt)), Int32(nz), codes, Int32(length(codes)),
+    Float64(order), w, kind, range, B0, B1, objective))
+  T = GAMMA_CONSTRUCTORS[kind[]+1]
+  function direct(a)
+    sill, nug = B0[a, a] + B1[a, a], B0[a, a]
+    nug = T === GaussianVariogram ? max(nug - GAUSSIAN_NUGGET_EPS[], 0.0) : nug
+    T === MaternVariogram ? T(sill=sill, nugget=nug, range=range[], order=Float64(order)) : T(sill=sill, nugget=nug, range=range[])
+  end
+  S = B0 .+ B1
+  variograms = Dict(v => direct(a) for (a, v) in enumerate(cross.vars))
+  correlation = Dict((cross.vars[a], cross.vars[b]) => S[a, b] / sqrt(S[a, a] * S[b, b]) for a in 1:nz for b in a+1:nz)
+  (variograms=variograms, correlation=correlation, B0=B0, B1=B1, range=range[])
 end
 
 # ---- several GPUs: one worker process per GPU ---------------------------------------------------------------------

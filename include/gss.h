@@ -304,6 +304,46 @@ int32_t gss_variogram_fit_aniso(const double* h, const double* phi, const double
                                 int32_t nbins, const int32_t* kinds, int32_t nkinds, double nu, int32_t weighting,
                                 double max_nugget_frac, gss_variogram_t* best, double* objective);
 
+/* gss_variogram_cross: direct AND cross variograms of nz variables in one pass over the pairs -- the pair geometry
+ *   (key, bin, cull) does not depend on the column and is paid once.  Everything gss_variogram_empirical states above
+ *   holds word for word: the pair key d2, the bin edges edge2[k] = fl(fl(k delta)^2), the rule
+ *   edge2[k] < d2 <= edge2[k + 1], duplicates counted apart, the direction test (host unit vector, dtol, cos_atol), the
+ *   finite-input rule in both memory modes, the batch ordering (Morton below 32 768 samples, k-d from there), tile
+ *   culling with the vario_tiles_* counters and GSS_VARIO_CULL, Euclidean distance only, the limits of n, nlags and nz
+ *   (1 .. 8; nz = 1 is the direct call).  count, lagsum and *nduplicates are the values that call returns on the same
+ *   inputs.  Matheron only: the Cressie-Hawkins estimator has no cross form, so there is no `estimator`.  There is no
+ *   cross form of gss_variogram_plane.
+ *   csum       nz (nz + 1) / 2 rows of nlags: the pair (a, b), a <= b, at row a nz - a (a - 1) / 2 + (b - a) holds
+ *              sum fl((z_a,i - z_a,j) (z_b,i - z_b,j)) over the kept pairs of the bin (one rounded product per pair, no
+ *              FMA).  The product does not depend on which sample of a pair comes first.  The front-ends form
+ *              gamma_ab = csum / (2 count); the rows (a, a) are the direct variograms (the zsum of
+ *              gss_variogram_empirical up to the order of addition).  The counts are exact and the same on every run;
+ *              a sum differs from the exact one by at most count 2^-53 sum |products|.
+ *   Local memory: the histogram of a workgroup is (2 + nz (nz + 1) / 2) nlags + 2 words, 78 KiB at nz = 8 and
+ *   nlags = 256 of the 160 KiB of a compute unit: two workgroups could share it there.  That is accepted and the
+ *   product is not capped: the registers of the nz = 8 instantiation (one wave per SIMD, one workgroup per compute
+ *   unit) bind before the local memory does. */
+int32_t gss_variogram_cross(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz, int32_t nlags,
+                            double maxlag, const double* direction, double dtol, double cos_atol, int64_t* count,
+                            double* lagsum, double* csum, int64_t* nduplicates, int32_t mem, void* stream);
+/* gss_variogram_fit_lmc (host code, no device): the linear model of coregionalisation
+ *   Gamma(h) = B0 + B1 f(h / range) fitted to the bins with count > 0.  Gamma is the nz x nz matrix of direct and cross
+ *   variograms, given as `gamma`: nz (nz + 1) / 2 rows of nlags in the row order of csum above.  B0 (nugget matrix) and
+ *   B1 (partial sills) are symmetric positive semidefinite; one structure f (a kind of gss_variogram_fit, Matern at
+ *   order nu; GSS_VG_POWER -> GSS_ERR_UNSUPPORTED) and one range are shared by all pairs.  Objective
+ *   sum_k w_k || Gamma_k - B0 - B1 f_k ||_F^2 over the full matrices (off-diagonals count twice), w as in
+ *   gss_variogram_fit.  For a fixed range, Goulard-Voltz sweeps from the unconstrained least squares of every entry:
+ *   B0 <- P+(sum w (Gamma - B1 f) / sum w), B1 <- P+(sum w f (Gamma - B0) / sum w f^2), until neither moves by more than
+ *   1e-12 (||B0||_F + ||B1||_F) or 1 000 sweeps; P+ clips the negative eigenvalues of a cyclic Jacobi decomposition
+ *   (fixed rotation order).  The range is searched as in gss_variogram_fit (256-point log grid over
+ *   [h_min / 4, 4 h_max], golden section to 1e-8).  Deterministic.  nz = 1 returns the numbers of gss_variogram_fit
+ *   with max_nugget_frac = 1.  Outputs: *kind (the best of kinds), *range, b0 and b1 (nz x nz, row-major),
+ *   objective[nkinds] (NaN where some variable gets no positive sill B0_aa + B1_aa).  The Gaussian kind is the bare
+ *   formula, as in gss_variogram_fit.  GSS_ERR_INVALID: nz outside 1 .. 8, fewer than two usable bins. */
+int32_t gss_variogram_fit_lmc(const double* h, const double* gamma, const int64_t* count, int32_t nlags, int32_t nz,
+                              const int32_t* kinds, int32_t nkinds, double nu, int32_t weighting, int32_t* kind,
+                              double* range, double* b0, double* b1, double* objective);
+
 /* ---- neighbour search: replaces `search!(neighbors, center, searcher)` krig.jl:210 and the
  *      KNearestSearch / KBallSearch construction ui.jl:27,30.  Exact; neighbours ordered by
  *      ascending (FP64 squared distance accumulated in dimension order without FMA, index).

@@ -16,7 +16,12 @@ ptol = inf) at 2*10^4 and 10^5 samples with the full diameter and at 10^5 with l
 the only way to the same table without that call -- 18 calls of gss_variogram_empirical with direction = the
 mid-sector unit vector and cos_atol = cos(pi / 36), timed as one block -- and the omnidirectional call.  The three are
 measured alternating.  (To time the 18 calls on another build of the library, run this with GSS_LIB_PATH set to it and
---yardstick-only: that build need not have the plane call.)"""
+--yardstick-only: that build need not have the plane call.)
+
+--cross: 10^5 samples in 3-D, all pairs, 20 lags, nz = 2 and 8: gss_variogram_cross against the polarisation route on the
+same library -- gss_variogram_empirical on the nz (nz + 1) / 2 columns z_a and z_a + z_b, in as many calls as its limit
+of 8 columns needs.  The two alternate, every run in a fresh process (one warm-up call, one timed call between events),
+five runs each; the medians are compared."""
 import argparse
 import ctypes as C
 import json
@@ -139,8 +144,57 @@ def plane_rows(lib, reps, yardstick_only):
             print(json.dumps(row), flush=True)
 
 
+def cross_child(route, nz):
+    """one timed call of one route in this process -> milliseconds on stdout"""
+    lib = _lib.lib()
+    rng = np.random.default_rng(1)
+    n, nlags, maxlag = 100_000, 20, 1000.0 * 3 ** 0.5
+    x = torch.as_tensor(rng.uniform(0.0, 1000.0, (n, 3)), device="cuda")
+    zh = rng.normal(size=(nz, n))
+    if route == "cross":
+        z = torch.as_tensor(zh, device="cuda")
+        outs = (torch.empty(nlags, dtype=torch.int64, device="cuda"), torch.empty(nlags, dtype=torch.float64, device="cuda"),
+                torch.empty((nz * (nz + 1) // 2, nlags), dtype=torch.float64, device="cuda"),
+                torch.empty(1, dtype=torch.int64, device="cuda"))
+
+        def run():
+            _lib.check(lib.gss_variogram_cross(
+                C.c_void_p(x.data_ptr()), n, 3, C.c_void_p(z.data_ptr()), nz, nlags, maxlag, None, float("inf"), 0.0,
+                *(C.c_void_p(o.data_ptr()) for o in outs), _lib.MEM_DEVICE, _lib.current_stream()))
+    else:
+        cols = [zh[a] for a in range(nz)] + [zh[a] + zh[b] for a in range(nz) for b in range(a + 1, nz)]
+        runs = [bare_variogram(lib, x, torch.as_tensor(np.stack(cols[lo:lo + 8]), device="cuda"), nlags, maxlag)[0]
+                for lo in range(0, len(cols), 8)]
+
+        def run():
+            for r in runs:
+                r()
+    med, _ = timed(run, 1, warm=1)
+    print(json.dumps({"route": route, "nz": nz, "ms": med}), flush=True)
+
+
+def cross_rows(runs=5):
+    import subprocess
+    for nz in (2, 8):
+        times = {"cross": [], "polarisation": []}
+        for _ in range(runs):
+            for route in ("cross", "polarisation"):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cross-child", route, str(nz)],
+                                   capture_output=True, text=True, timeout=600, check=True)
+                times[route].append(json.loads(r.stdout.strip().splitlines()[-1])["ms"])
+        c, p = statistics.median(times["cross"]), statistics.median(times["polarisation"])
+        print(json.dumps({"what": "cross-variogram", "n": 100_000, "dim": 3, "maxlag": "full", "nlags": 20, "nz": nz,
+                          "columns_polarisation": nz * (nz + 1) // 2, "calls_polarisation": (nz * (nz + 1) // 2 + 7) // 8,
+                          "cross_ms": [round(t, 4) for t in times["cross"]],
+                          "polarisation_ms": [round(t, 4) for t in times["polarisation"]],
+                          "cross_median_ms": round(c, 4), "polarisation_median_ms": round(p, 4),
+                          "cross_over_polarisation": round(c / p, 4), "cross_not_slower": c <= p}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cross", action="store_true", help="the cross-variogram rows instead")
+    ap.add_argument("--cross-child", nargs=2, metavar=("ROUTE", "NZ"), help=argparse.SUPPRESS)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--max-n", type=int, default=1_000_000)
     ap.add_argument("--plane", action="store_true", help="the varioplane rows instead")
@@ -148,6 +202,12 @@ def main():
                     "omnidirectional one (for a build of the library without the plane call)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.cross_child:
+        cross_child(args.cross_child[0], int(args.cross_child[1]))
+        return
+    if args.cross:
+        cross_rows()
+        return
     lib = _lib.lib()
     if args.plane:
         plane_rows(lib, args.reps, args.yardstick_only)
