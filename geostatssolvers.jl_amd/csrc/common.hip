@@ -315,7 +315,7 @@ void HostPipe::add_in(const void* host, void* dev, size_t stride) {
 }
 
 void HostPipe::add_out(void* host, void* dev, size_t stride) {
-  if (!host || !dev || nout >= 6) return;
+  if (!host || !dev || nout >= 24) return;
   outs[nout++] = Arr{nullptr, static_cast<char*>(host), static_cast<char*>(dev), stride};
 }
 

@@ -176,7 +176,7 @@ struct HostPipe {
     char* dev;
     size_t stride;
   };
-  Arr ins[4], outs[6];
+  Arr ins[4], outs[24];   // (outs: mean, variance and status of each of up to 8 cokriging targets)
   int nin = 0, nout = 0;
   hipStream_t cin = nullptr, cout = nullptr;
   hipEvent_t ev_in = nullptr, ev_done = nullptr;

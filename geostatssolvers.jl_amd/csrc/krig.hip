@@ -15,6 +15,12 @@
 //   krig_rhs2_kernel      K1+K2: assembles R = [c0; f0] for a chunk of points (coalesced HBM stores)
 //                         and accumulates the dual-form mean on the fly
 //   krig_quadform_kernel  K3: FP64 MFMA triangular GEMM W' * R fused with the signed column norms
+//
+// Cokriging (gss.h, gss_cokrig_create): the same system over the stacked samples of nz variables
+// under C_ab(h) = b1[a][b] rho(h) (+ b0[a][b] at a zero key), with the per-variable indicators as constraint columns.
+//   cokrig_system_kernel  the n x n block of the system, replacing the pairwise covariances of the fit
+//   cokrig_rhs_kernel     the right-hand sides of all nz targets from one evaluation of rho per (sample, point)
+// The factorisation, K3 and the cross-validation identities are those of the single-variable handle.
 #include "gss_internal.h"
 
 #include <mutex>
@@ -152,6 +158,151 @@ static int32_t launch_krig_rhs(hipStream_t s, const VgDev& vg, const double* xd,
     default: GSS_K1W_LAUNCH(-1); break;
   }
 #undef GSS_K1W_LAUNCH
+  return GSS_OK;
+}
+
+// ---- cokriging -------------------------------------------------------------------------------------------------------
+// Coefficient table of a cokriging handle in device memory (CO_TAB doubles): b1[a * CO_MAXZ + b] (symmetrised), then
+// c0 = b0 + b1 in the same layout (the value at a zero key), then means[CO_MAXZ].
+constexpr int CO_MAXZ = 8;
+constexpr int CO_C0 = CO_MAXZ * CO_MAXZ, CO_MEANS = 2 * CO_MAXZ * CO_MAXZ, CO_TAB = CO_MEANS + CO_MAXZ;
+
+// rho(a, b) of the structure (sill 1, no nugget) and whether the key is zero.  The key and the shape are those of
+// cov_pair / cov_d2_select: KIND >= 0 folds the model switch away, KIND < 0 reads it from vg.  The shape is evaluated on
+// max(d2, 1e-300) for every lane; the caller selects the zero-key value afterwards.
+template <int DIM, int KIND>
+__device__ __forceinline__ double co_rho(const VgDev& vg, const double* a, const double* b, bool* zero) {
+  const double d2 = KIND < 0 ? sqdist_nofma<DIM>(a, b, vg.ir, vg.aniso != 0) : sqdist_nofma<DIM>(a, b, vg.ir, true);
+  *zero = d2 <= 0.0;
+  return vg_shape(KIND < 0 ? vg.kind : KIND, fmax(d2, 1e-300), vg.inv_range, vg.mscale, vg.pw);
+}
+
+// M[i * ldw + j] = C_{var_i var_j}(x_i, x_j) for i, j < n (the block is symmetric: the table is, and so is the key).
+// Lane = column sample j, the row sample i is wave-uniform (cov_pairwise_kernel's layout).
+template <int DIM>
+__global__ __launch_bounds__(256) void cokrig_system_kernel(VgDev vg, const double* __restrict__ xd,
+                                                            const int* __restrict__ var,
+                                                            const double* __restrict__ tab, int n,
+                                                            double* __restrict__ M, int64_t ldw) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const int i0 = blockIdx.y * 64;
+  const int i1 = i0 + 64 < n ? i0 + 64 : n;
+  if (j >= n) return;
+  double c[DIM];
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) c[k] = xd[(int64_t)j * DIM + k];
+  const int vj = var[j];
+  for (int i = i0; i < i1; ++i) {
+    double x[DIM];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) x[k] = xd[(int64_t)i * DIM + k];
+    bool zero;
+    const double rho = co_rho<DIM, -1>(vg, x, c, &zero);
+    const int e = var[i] * CO_MAXZ + vj;
+    M[(int64_t)i * ldw + j] = zero ? tab[CO_C0 + e] : tab[e] * rho;
+  }
+}
+
+// Fd[c * n + i] = [var_i == c]: the unbiasedness columns of ordinary cokriging
+__global__ __launch_bounds__(256) void cokrig_indicator_kernel(const int* __restrict__ var, int n, int nc,
+                                                               double* __restrict__ Fd) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int v = var[i];
+  for (int c = 0; c < nc; ++c) Fd[(int64_t)c * n + i] = v == c ? 1.0 : 0.0;
+}
+
+// z_i -= means[var_i] (simple cokriging kriges the residuals)
+__global__ __launch_bounds__(256) void cokrig_center_kernel(double* __restrict__ z, const int* __restrict__ var,
+                                                            const double* __restrict__ tab, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) z[i] -= tab[CO_MEANS + var[i]];
+}
+
+// Right-hand sides of all targets: block t of R (blk = N1pad * ldr doubles apart) gets, in row j < n,
+// b1[var_j][t] rho(x_j, x0_p), or c0[var_j][t] when the key is zero.  The unit walk, the two adjacent points per thread
+// and the 16-B stores are those of krig_rhs2_kernel; rho is evaluated once per (sample, point) and scaled nz times.  j is
+// wave-uniform, so x_j, var_j and row var_j of the two tables come through the scalar cache and the scale is a scalar
+// operand of the multiply.
+// nz is a run-time loop bound: the loop body keeps two products and two selects live whatever nz is, so the kernel
+// needs no more registers than krig_rhs2_kernel plus the two key flags (DESIGN.md section 4 has the counts), and one
+// instantiation per (DIM, KIND) serves nz = 1 .. 8.  Unrolling over a compile-time nz would only let the compiler
+// hoist the nz scalar loads in front of the shape, which the scalar cache already hides behind the sqrt / exp chain.
+template <int DIM, int KIND>
+__global__ __launch_bounds__(256) void cokrig_rhs_kernel(VgDev vg, const double* __restrict__ xd,
+                                                         const int* __restrict__ var, const double* __restrict__ tab,
+                                                         int nz, int n, const double* __restrict__ x0, int64_t m_valid,
+                                                         double* __restrict__ R, int64_t ldr, int64_t blk, int seg_len,
+                                                         int nblk, int64_t ncols) {
+  for (int unit = blockIdx.x; unit < nblk * NSEG; unit += gridDim.x) {
+    const int seg = unit % NSEG;
+    const int64_t p = (int64_t)(unit / NSEG) * 512 + 2 * threadIdx.x;
+    if (p >= ncols) continue;
+    const int64_t pa = p < m_valid ? p : m_valid - 1, pb = p + 1 < m_valid ? p + 1 : m_valid - 1;
+    double ca[DIM], cb[DIM];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+      ca[k] = x0[pa * DIM + k];
+      cb[k] = x0[pb * DIM + k];
+    }
+    const int j0 = seg * seg_len;
+    const int j1 = j0 + seg_len < n ? j0 + seg_len : n;
+    double2* rp = reinterpret_cast<double2*>(R + (int64_t)j0 * ldr + p);
+    const int64_t ld2 = ldr >> 1, blk2 = blk >> 1;
+#pragma unroll 2
+    for (int j = j0; j < j1; ++j) {
+      double x[DIM];
+#pragma unroll
+      for (int k = 0; k < DIM; ++k) x[k] = xd[j * DIM + k];
+      bool za, zb;
+      const double ra = co_rho<DIM, KIND>(vg, x, ca, &za);
+      const double rb = co_rho<DIM, KIND>(vg, x, cb, &zb);
+      const double* row = tab + var[j] * CO_MAXZ;
+      double2* rt = rp;
+      for (int t = 0; t < nz; ++t) {
+        const double b = row[t], c = row[CO_C0 + t];
+        double2 v;
+        v.x = za ? c : b * ra;
+        v.y = zb ? c : b * rb;
+        *rt = v;
+        rt += blk2;
+      }
+      rp += ld2;
+    }
+  }
+}
+
+// rows n .. n + nrows - 1 of every block: the indicator [c == t] in row n + c (c < nc), zero rows up to N1pad
+__global__ __launch_bounds__(256) void cokrig_tail_rows_kernel(double* __restrict__ R, int64_t ldr, int64_t blk, int n,
+                                                               int nc, int nrows, int nz, int64_t ncols) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= ncols) return;
+  for (int t = 0; t < nz; ++t)
+    for (int r = 0; r < nrows; ++r) R[t * blk + (int64_t)(n + r) * ldr + p] = (r < nc && r == t) ? 1.0 : 0.0;
+}
+
+template <int DIM>
+static int32_t launch_cokrig_rhs(hipStream_t s, const VgDev& vg, const double* xd, const int* var, const double* tab,
+                                 int nz, int n, const double* x0, int64_t m_valid, double* R, int64_t ldr, int64_t blk,
+                                 int seg_len, int nblk) {
+  GSS_REQUIRE((ldr & 1) == 0 && (blk & 1) == 0, "launch_cokrig_rhs: odd leading dimension %lld (16-B stores need an "
+              "even one)", (long long)ldr);
+  const int64_t ncols = (int64_t)nblk * 256;
+  const int nblk2 = (int)((ncols + 511) / 512);
+  const dim3 g2((unsigned)(nblk2 * NSEG));
+#define GSS_CK_LAUNCH(KIND)                                                                                          \
+  hipLaunchKernelGGL((cokrig_rhs_kernel<DIM, KIND>), g2, dim3(256), 0, s, vg, xd, var, tab, nz, n, x0, m_valid, R,   \
+                     ldr, blk, seg_len, nblk2, ncols)
+  switch (vg.kind) {
+    case GSS_VG_GAUSSIAN: GSS_CK_LAUNCH(GSS_VG_GAUSSIAN); break;
+    case GSS_VG_EXPONENTIAL: GSS_CK_LAUNCH(GSS_VG_EXPONENTIAL); break;
+    case GSS_VG_SPHERICAL: GSS_CK_LAUNCH(GSS_VG_SPHERICAL); break;
+    case VG_MATERN12: GSS_CK_LAUNCH(VG_MATERN12); break;
+    case VG_MATERN32: GSS_CK_LAUNCH(VG_MATERN32); break;
+    case VG_MATERN52: GSS_CK_LAUNCH(VG_MATERN52); break;
+    default: GSS_CK_LAUNCH(-1); break;
+  }
+#undef GSS_CK_LAUNCH
   return GSS_OK;
 }
 
@@ -542,6 +693,12 @@ struct gss_krig {
   int block_nsub = 0;
   double block_cell[3] = {0.0, 0.0, 0.0};
   double block_cvv = 0.0;
+  // cokriging (gss_cokrig_create): nz > 0, the system is over the stacked samples of nz variables.  covar: the
+  // variable id of every stacked sample; cotab: the coefficient table the kernels read (CO_TAB doubles); c00 / means:
+  // host copies of C_tt(0) = b0[t][t] + b1[t][t] and of the known means (zero under the ordinary variant)
+  int nz = 0;
+  DevBuf covar, cotab;
+  double c00[CO_MAXZ] = {}, means[CO_MAXZ] = {};
   double* Wp() const { return factor.as<double>(); }
   double* wd() const { return factor.as<double>() + ldw * N1pad; }
 };
@@ -793,7 +950,17 @@ static int32_t krig_fit_enqueue(gss_krig* h, const FitPlan& fp, hipStream_t s) {
   GSS_TRY(dev_zero_bytes(M, sizeof(double) * (size_t)szM, s));
   GSS_TRY(dev_zero_bytes(h->factor.p, h->factor.bytes, s));
   GSS_TRY(dev_zero_bytes(info2, sizeof(int), s));
-  GSS_TRY(cov_pairwise_dev(h->vg, h->xdata.as<double>(), n, h->xdata.as<double>(), n, M, ldw, s));
+  if (h->nz > 0) {
+    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)((n + 63) / 64));
+    switch (h->dim) {
+      case 1: hipLaunchKernelGGL(cokrig_system_kernel<1>, grid, dim3(256), 0, s, h->vg, h->xdata.as<double>(), h->covar.as<int>(), h->cotab.as<double>(), (int)n, M, ldw); break;
+      case 2: hipLaunchKernelGGL(cokrig_system_kernel<2>, grid, dim3(256), 0, s, h->vg, h->xdata.as<double>(), h->covar.as<int>(), h->cotab.as<double>(), (int)n, M, ldw); break;
+      default: hipLaunchKernelGGL(cokrig_system_kernel<3>, grid, dim3(256), 0, s, h->vg, h->xdata.as<double>(), h->covar.as<int>(), h->cotab.as<double>(), (int)n, M, ldw); break;
+    }
+    GSS_HIP(hipGetLastError());
+  } else {
+    GSS_TRY(cov_pairwise_dev(h->vg, h->xdata.as<double>(), n, h->xdata.as<double>(), n, M, ldw, s));
+  }
   double* Wp = h->Wp();
   // M and W' are zero outside the n x n blocks and reach past the next multiple of 16 (N1pad, ldw): the padded contract
   GSS_TRY(potrf_inverse_f64(M, n, ldw, Wp, ldw, T, info, false, s, true));
@@ -801,7 +968,13 @@ static int32_t krig_fit_enqueue(gss_krig* h, const FitPlan& fp, hipStream_t s) {
   if (nc > 0) {
     GSS_TRY(dev_zero_bytes(S, sizeof(double) * (size_t)szS, s));
     // Fd (n x nc, column-major): drift functions at the data locations
-    GSS_TRY(launch_drift_rows(h, h->xdata.as<double>(), h->drift_data.as<double>(), n, n, Fd, n, nc, s));
+    if (h->nz > 0) {   // cokriging: one indicator column per variable
+      hipLaunchKernelGGL(cokrig_indicator_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                         h->covar.as<int>(), (int)n, nc, Fd);
+      GSS_HIP(hipGetLastError());
+    } else {
+      GSS_TRY(launch_drift_rows(h, h->xdata.as<double>(), h->drift_data.as<double>(), n, n, Fd, n, nc, s));
+    }
     // Bm[c] = W F[:, c]   (row c of B = (L^-1 F)')
     for (int c = 0; c < nc; ++c) GSS_TRY(gemv_f64(false, n, n, Wp, ldw, Fd + (int64_t)c * n, Bm + (int64_t)c * n, gwork, s));
     hipLaunchKernelGGL(small_gram_kernel, dim3(nc, nc), dim3(64), 0, s, Bm, nc, n, S, MAX_NC);
@@ -819,7 +992,11 @@ static int32_t krig_fit_enqueue(gss_krig* h, const FitPlan& fp, hipStream_t s) {
   // dual weights wd = W'' D W' [z - mean; 0]
   GSS_TRY(dev_zero_bytes(zz, sizeof(double) * (size_t)(2 * ldw), s));
   GSS_TRY(dev_copy_f64(zz, h->z.as<double>(), n, s));
-  if (h->variant == GSS_KRIG_SIMPLE && h->sk_mean != 0.0) {
+  if (h->nz > 0) {
+    if (h->variant == GSS_KRIG_SIMPLE)
+      hipLaunchKernelGGL(cokrig_center_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, zz,
+                         h->covar.as<int>(), h->cotab.as<double>(), (int)n);
+  } else if (h->variant == GSS_KRIG_SIMPLE && h->sk_mean != 0.0) {
     hipLaunchKernelGGL(sub_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, zz, n, h->sk_mean);
   }
   GSS_TRY(gemv_f64(false, N1, N1, Wp, ldw, zz, u, gwork, s));
@@ -921,6 +1098,53 @@ static int32_t krig_fit_wait(gss_krig* h) {
     set_error("drift functions are linearly dependent on the sample locations (constraint %d)", hinfo[1] - 1);
     return GSS_ERR_NOT_POSDEF;
   }
+  return GSS_OK;
+}
+
+// K3 over one chunk: mean, variance and status of points 0 .. mv - 1 from the right-hand sides R (N1pad x ldr, cols =
+// mv rounded up to 256 columns assembled).  Whole rounds of 512 resident workgroups (2 per CU) run one workgroup per
+// strip; the remainder strips would occupy a full extra round, so they run as (strip, row block) units, which pack ~3x
+// tighter.
+static void launch_krig_quadform(const gss_krig* h, const double* Rws, int64_t ldr, double c00, double mean0,
+                                 int64_t mv, int64_t cols, double* mean_out, double* var_out, uint8_t* stp,
+                                 double* qpart, hipStream_t s) {
+  const int nstrips = (int)(cols / BN);
+  const int nI = (int)((h->N1 + BM) / BM);  // row blocks of rows 0..N1 (row N1 = dual weights)
+#define GSS_K3_ARGS(S0, NS) h->Wp(), h->ldw, (int)h->N1pad, (int)h->n, (int)h->N1, Rws, ldr, c00, mean0, mv, \
+                            mean_out, var_out, stp, qpart, (S0), (NS)
+  const int nmain = (nstrips / 512) * 512;
+  const int nrem = nstrips - nmain;
+  if (nmain > 0)
+    hipLaunchKernelGGL((krig_quadform_kernel<false>), dim3((unsigned)nmain), dim3(256), QUADFORM_LDS_BYTES, s,
+                       GSS_K3_ARGS(0, nmain));
+  if (nrem > 0) {
+    const unsigned grid = (unsigned)(8 * ((nrem + 7) / 8) * nI);
+    hipLaunchKernelGGL((krig_quadform_kernel<true>), dim3(grid), dim3(256), QUADFORM_LDS_BYTES, s,
+                       GSS_K3_ARGS(nmain, nrem));
+    const int64_t pbeg = (int64_t)nmain * BN;
+    if (mv > pbeg)
+      hipLaunchKernelGGL(krig_finish_kernel, dim3((unsigned)((mv - pbeg + 255) / 256)), dim3(256), 0, s, qpart + pbeg,
+                         nI, ldr, c00, mv - pbeg, var_out + pbeg, stp ? stp + pbeg : nullptr);
+  }
+#undef GSS_K3_ARGS
+}
+
+// the quadratic form keeps 4 LDS stages: above the default limit of a launch, raised once per device
+static int32_t krig_quadform_attrs() {
+  static uint64_t attr_set = 0;
+  if (first_on_this_device(attr_set)) {
+    GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(krig_quadform_kernel<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)QUADFORM_LDS_BYTES));
+    GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(krig_quadform_kernel<true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)QUADFORM_LDS_BYTES));
+  }
+  return GSS_OK;
+}
+
+// entry points that know one variable only
+static int32_t krig_refuse_cokrig(const gss_krig* h, const char* who) {
+  GSS_REQUIRE(h->nz == 0, "%s: the handle is a cokriging system over %d variables; its estimates come from "
+              "gss_cokrig_predict_global (cross-validation: gss_krig_cv_global, gss_krig_cv_global_folds)", who, h->nz);
   return GSS_OK;
 }
 
@@ -1074,6 +1298,7 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
                                 double* mean, double* var, uint8_t* status, int32_t mem, void* stream) {
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_TRY(krig_refuse_cokrig(h, "gss_krig_predict_global"));
   GSS_REQUIRE(h->factored, "handle has no factor (created with GSS_KRIG_NO_FACTOR and never adopted one)");
   GSS_REQUIRE(m >= 0 && (m == 0 || (xdom && mean && var)), "gss_krig_predict_global: NULL array");
   GSS_REQUIRE(h->variant != GSS_KRIG_EXTDRIFT || drift_dom != nullptr, "external drift values missing");
@@ -1081,13 +1306,7 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
   hipStream_t s = to_stream(stream);
   const int dim = h->dim;
 
-  static uint64_t attr_set = 0;
-  if (first_on_this_device(attr_set)) {
-    GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(krig_quadform_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)QUADFORM_LDS_BYTES));
-    GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(krig_quadform_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)QUADFORM_LDS_BYTES));
-  }
+  GSS_TRY(krig_quadform_attrs());
 
   int64_t mc = krig_chunk_points(h->N1pad, m);
   // host arrays: pieces of the call (two rounds of resident workgroups of the quadratic form each) overlap their
@@ -1158,31 +1377,11 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
     GSS_TRY(krig_join_device(h, s));   // an asynchronous fit ran beside the assembly; the quadratic form needs it
     ProfScope pq("krig_quadform", s);
     {
-      const int nstrips = (int)(cols / BN);
-      const int nI = (int)((h->N1 + BM) / BM);  // row blocks of rows 0..N1 (row N1 = dual weights)
-      double* qpart = mpart;
       const double mean0 = h->variant == GSS_KRIG_SIMPLE ? h->sk_mean : 0.0;
       uint8_t* stp = status ? sstat.as<uint8_t>() + off : nullptr;
       const double c00 = h->block_nsub > 0 ? h->block_cvv : h->vg.sill;   // variance = C(V, V) - rhs . weights
-#define GSS_K3_ARGS(S0, NS) h->Wp(), h->ldw, (int)h->N1pad, (int)h->n, (int)h->N1, Rws, ldr, c00, mean0, mv, \
-                            smean.as<double>() + off, svar.as<double>() + off, stp, qpart, (S0), (NS)
-      // Whole rounds of 512 resident workgroups (2 per CU) run one workgroup per strip; the remainder strips
-      // would occupy a full extra round, so they run as (strip, row block) units, which pack ~3x tighter.
-      const int nmain = (nstrips / 512) * 512;
-      const int nrem = nstrips - nmain;
-      if (nmain > 0)
-        hipLaunchKernelGGL((krig_quadform_kernel<false>), dim3((unsigned)nmain), dim3(256), QUADFORM_LDS_BYTES, s,
-                           GSS_K3_ARGS(0, nmain));
-      if (nrem > 0) {
-        const unsigned grid = (unsigned)(8 * ((nrem + 7) / 8) * nI);
-        hipLaunchKernelGGL((krig_quadform_kernel<true>), dim3(grid), dim3(256), QUADFORM_LDS_BYTES, s,
-                           GSS_K3_ARGS(nmain, nrem));
-        const int64_t pbeg = (int64_t)nmain * BN;
-        if (mv > pbeg)
-          hipLaunchKernelGGL(krig_finish_kernel, dim3((unsigned)((mv - pbeg + 255) / 256)), dim3(256), 0, s, qpart + pbeg,
-                             nI, ldr, c00, mv - pbeg, svar.as<double>() + off + pbeg, stp ? stp + pbeg : nullptr);
-      }
-#undef GSS_K3_ARGS
+      launch_krig_quadform(h, Rws, ldr, c00, mean0, mv, cols, smean.as<double>() + off, svar.as<double>() + off, stp,
+                           mpart, s);
     }
     GSS_HIP(hipGetLastError());
     GSS_TRY(pipe.deliver(off, mv, s));
@@ -1198,9 +1397,229 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
 }
 
 
+// ---- cokriging (gss.h) -----------------------------------------------------------------------------------------------
+// Points per chunk of a cokriging call: the workspace holds nz blocks of N1pad rows.  GSS_COKRIG_CHUNK_POINTS caps it
+// (tests: a chunk loop that runs more than once at a small size).
+static int64_t cokrig_chunk_points(int64_t N1pad, int nz, int64_t m) {
+  int64_t mc = krig_chunk_points(N1pad * nz, m);
+  if (const char* e = std::getenv("GSS_COKRIG_CHUNK_POINTS")) {
+    int64_t cap = std::atoll(e) / 256 * 256;
+    if (cap > 0 && cap < mc) mc = cap;
+  }
+  return mc;
+}
+
+int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
+                          const double* b1, int32_t variant, const double* means, const double* xdata,
+                          const double* z, const int32_t* var, int64_t n, int32_t flags, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(out != nullptr, "gss_cokrig_create: out is NULL");
+  *out = nullptr;
+  GSS_REQUIRE(structure != nullptr, "gss_cokrig_create: structure is NULL");
+  GSS_REQUIRE(nz >= 1 && nz <= CO_MAXZ, "gss_cokrig_create: nz = %d outside 1 .. %d", nz, CO_MAXZ);
+  GSS_REQUIRE(b0 != nullptr && b1 != nullptr, "gss_cokrig_create: b0 or b1 is NULL");
+  if (structure->kind == GSS_VG_POWER) {
+    set_error("gss_cokrig_create: a power structure has no sill, the coregionalisation model needs one");
+    return GSS_ERR_UNSUPPORTED;
+  }
+  GSS_REQUIRE(structure->nextra == 0, "gss_cokrig_create: one structure plus nugget (nextra = %d)", structure->nextra);
+  if (variant == GSS_KRIG_UNIVERSAL || variant == GSS_KRIG_EXTDRIFT) {
+    set_error("gss_cokrig_create: cokriging with a drift is not available (simple and ordinary only)");
+    return GSS_ERR_UNSUPPORTED;
+  }
+  GSS_REQUIRE(variant == GSS_KRIG_SIMPLE || variant == GSS_KRIG_ORDINARY, "unknown kriging variant %d", variant);
+  GSS_REQUIRE((flags & GSS_KRIG_NO_FACTOR) == 0, "gss_cokrig_create: GSS_KRIG_NO_FACTOR is refused: there is no "
+              "moving-neighbourhood cokriging, the handle serves the global neighbourhood only");
+  GSS_REQUIRE(variant != GSS_KRIG_SIMPLE || means != nullptr, "gss_cokrig_create: simple cokriging needs means[nz]");
+  GSS_REQUIRE(xdata != nullptr && z != nullptr && var != nullptr, "gss_cokrig_create: NULL data");
+  GSS_REQUIRE(n >= 1, "all samples are missing, aborting...");
+  GSS_REQUIRE(n < (1 << 30), "too many samples");
+
+  // the coefficient table: b1 symmetrised (so that the system block and the right-hand sides read the same numbers
+  // whichever index comes first), c0 = b0 + b1, the means
+  double tab[CO_TAB] = {};
+  double big = 0.0;
+  for (int e = 0; e < nz * nz; ++e) {
+    GSS_REQUIRE(std::isfinite(b0[e]) && std::isfinite(b1[e]), "gss_cokrig_create: b0 / b1 entry [%d][%d] is not finite",
+                e / nz, e % nz);
+    big = std::fmax(big, std::fmax(std::fabs(b0[e]), std::fabs(b1[e])));
+  }
+  for (int a = 0; a < nz; ++a)
+    for (int b = 0; b < nz; ++b) {
+      GSS_REQUIRE(std::fabs(b0[a * nz + b] - b0[b * nz + a]) <= 1e-12 * big,
+                  "gss_cokrig_create: b0 is not symmetric at [%d][%d]", a, b);
+      GSS_REQUIRE(std::fabs(b1[a * nz + b] - b1[b * nz + a]) <= 1e-12 * big,
+                  "gss_cokrig_create: b1 is not symmetric at [%d][%d]", a, b);
+      const double s1 = 0.5 * (b1[a * nz + b] + b1[b * nz + a]), s0 = 0.5 * (b0[a * nz + b] + b0[b * nz + a]);
+      tab[a * CO_MAXZ + b] = s1;
+      tab[CO_C0 + a * CO_MAXZ + b] = s0 + s1;
+    }
+  for (int a = 0; a < nz; ++a)
+    GSS_REQUIRE(tab[CO_C0 + a * CO_MAXZ + a] > 0.0, "gss_cokrig_create: variable %d has no positive sill "
+                "b0[%d][%d] + b1[%d][%d]", a, a, a, a, a);
+  if (variant == GSS_KRIG_SIMPLE)
+    for (int a = 0; a < nz; ++a) {
+      GSS_REQUIRE(std::isfinite(means[a]), "gss_cokrig_create: means[%d] is not finite", a);
+      tab[CO_MEANS + a] = means[a];
+    }
+
+  gss_krig* h = new (std::nothrow) gss_krig();
+  if (!h) return GSS_ERR_ALLOC;
+  struct Guard {
+    gss_krig* h;
+    ~Guard() { delete h; }
+  } guard{h};
+  gss_variogram_t unit = *structure, plain;   // rho: sill 1, no nugget
+  unit.sill = 1.0;
+  unit.nugget = 0.0;
+  GSS_TRY(vg_frame_split(&unit, &plain, &h->fr));
+  GSS_TRY(make_vgdev(&plain, &h->vg));
+  const int dim = h->vg.dim;
+  int64_t per[CO_MAXZ] = {};
+  for (int64_t i = 0; i < n; ++i) {
+    GSS_REQUIRE(var[i] >= 0 && var[i] < nz, "gss_cokrig_create: variable id %d of sample %lld outside 0 .. %d", var[i],
+                (long long)i, nz - 1);
+    GSS_REQUIRE(std::isfinite(z[i]), "gss_cokrig_create: value of sample %lld is not finite", (long long)i);
+    for (int k = 0; k < dim; ++k)
+      GSS_REQUIRE(std::isfinite(xdata[i * dim + k]), "gss_cokrig_create: coordinate %d of sample %lld is not finite", k,
+                  (long long)i);
+    ++per[var[i]];
+  }
+  if (variant == GSS_KRIG_ORDINARY)
+    for (int a = 0; a < nz; ++a)
+      GSS_REQUIRE(per[a] >= 1, "gss_cokrig_create: variable %d has no sample (ordinary cokriging needs one "
+                  "unbiasedness row per variable)", a);
+
+  GSS_TRY(frame_origin(&h->fr, xdata, GSS_MEM_HOST, nullptr));
+  h->variant = variant;
+  h->dim = dim;
+  h->n = n;
+  h->nz = nz;
+  for (int a = 0; a < nz; ++a) {
+    h->c00[a] = tab[CO_C0 + a * CO_MAXZ + a];
+    h->means[a] = tab[CO_MEANS + a];
+  }
+  std::memset(&h->ds, 0, sizeof(h->ds));
+  h->ds.variant = variant;
+  h->ds.dim = dim;
+  for (int k = 0; k < 3; ++k) h->ds.inv_scale[k] = 1.0;
+  h->nc = variant == GSS_KRIG_ORDINARY ? nz : 0;
+  h->ds.nc = h->nc;
+  h->N1 = n + h->nc;
+  h->N1pad = round_up(h->N1 + 1, BK);   // (the spare row of the dual weights: gss_krig_create)
+  h->ldw = round_up(h->N1 + 1, BM);
+
+  hipStream_t s = to_stream(stream);
+  GSS_TRY(h->xdata.alloc(sizeof(double) * (size_t)(n * dim)));
+  GSS_TRY(h->z.alloc(sizeof(double) * (size_t)n));
+  GSS_TRY(h->covar.alloc(sizeof(int32_t) * (size_t)n));
+  GSS_TRY(h->cotab.alloc(sizeof(tab)));
+  if (h->fr.on) {
+    GSS_TRY(h->xraw.alloc(sizeof(double) * (size_t)(n * dim)));
+    GSS_HIP(hipMemcpyAsync(h->xraw.p, xdata, sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
+    GSS_TRY(frame_apply_dev(h->fr, h->xraw.as<double>(), n, h->xdata.as<double>(), s));
+  } else {
+    GSS_HIP(hipMemcpyAsync(h->xdata.p, xdata, sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
+  }
+  GSS_HIP(hipMemcpyAsync(h->z.p, z, sizeof(double) * n, hipMemcpyHostToDevice, s));
+  GSS_HIP(hipMemcpyAsync(h->covar.p, var, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+  GSS_HIP(hipMemcpyAsync(h->cotab.p, tab, sizeof(tab), hipMemcpyHostToDevice, s));
+  GSS_HIP(hipStreamSynchronize(s));   // tab lives on this frame
+  const bool async = (flags & GSS_KRIG_ASYNC_FIT) != 0;
+  GSS_TRY(krig_factorize(h, s, async));
+  if (!async) GSS_TRY(krig_fit_wait(h));   // otherwise joined by the first call that needs the factor
+  guard.h = nullptr;
+  *out = h;
+  return GSS_OK;
+}
+
+int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, double* mean, double* variance,
+                                  uint8_t* status, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(h->nz > 0, "gss_cokrig_predict_global: the handle is not a cokriging system (gss_cokrig_create makes one)");
+  GSS_REQUIRE(h->factored, "handle has no factor");
+  GSS_REQUIRE(m >= 0 && (m == 0 || (xdom && mean && variance)), "gss_cokrig_predict_global: NULL array");
+  if (m == 0) return GSS_OK;
+  hipStream_t s = to_stream(stream);
+  const int dim = h->dim, nz = h->nz;
+  GSS_TRY(krig_quadform_attrs());
+
+  int64_t mc = cokrig_chunk_points(h->N1pad, nz, m);
+  HostPipe pipe;   // host arrays: pieces of the call overlap their transfers with the computation of their neighbours
+  GSS_TRY(pipe.begin(mem, m, s));
+  const bool piped = pipe.on;
+  if (piped && mc > HostPipe::PIECE) mc = HostPipe::PIECE;
+  double *Rws = nullptr, *mpart = nullptr;
+  GSS_TRY(krig_workspace(h->N1pad * nz, mc, s, &Rws, &mpart));
+  const int64_t ldr = mc, blk = h->N1pad * ldr;
+  const int seg_len = (int)((h->n + NSEG - 1) / NSEG);
+
+  Staged sx, smean, svar, sstat;
+  if (piped) GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
+  else GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
+  GSS_TRY(smean.out(mean, sizeof(double) * (size_t)(nz * m), mem));
+  GSS_TRY(svar.out(variance, sizeof(double) * (size_t)(nz * m), mem));
+  GSS_TRY(sstat.out(status, (size_t)(nz * m), mem));
+  if (piped) {
+    pipe.add_in(xdom, sx.p, sizeof(double) * dim);
+    for (int t = 0; t < nz; ++t) {   // column t of every output is an array of its own to the pipe
+      pipe.add_out(mean + t * m, smean.as<double>() + t * m, sizeof(double));
+      pipe.add_out(variance + t * m, svar.as<double>() + t * m, sizeof(double));
+      if (status) pipe.add_out(status + t * m, sstat.as<uint8_t>() + t * m, 1);
+    }
+    pipe.frame = &h->fr;   // rotated structure: each piece moves into the frame where it lands
+  }
+  FrameCopy xfr;
+  if (!piped) GSS_TRY(xfr.of(h->fr, &sx, m, s));
+
+  for (int64_t off = 0; off < m; off += mc) {
+    const int64_t mv = (m - off) < mc ? (m - off) : mc;
+    const int64_t cols = round_up(mv, 256);  // multiple of BN as well
+    const double* x0 = sx.as<double>() + off * dim;
+    GSS_TRY(pipe.fetch(off, mv, s));
+    const int nblk = (int)(cols / 256);
+    const int nrows = (int)(h->N1pad - h->n);
+    {
+      ProfScope ps("cokrig_rhs", s);
+      const double* xd = h->xdata.as<double>();
+      const int* cv = h->covar.as<int>();
+      const double* tab = h->cotab.as<double>();
+      switch (dim) {
+        case 1: GSS_TRY(launch_cokrig_rhs<1>(s, h->vg, xd, cv, tab, nz, (int)h->n, x0, mv, Rws, ldr, blk, seg_len, nblk)); break;
+        case 2: GSS_TRY(launch_cokrig_rhs<2>(s, h->vg, xd, cv, tab, nz, (int)h->n, x0, mv, Rws, ldr, blk, seg_len, nblk)); break;
+        default: GSS_TRY(launch_cokrig_rhs<3>(s, h->vg, xd, cv, tab, nz, (int)h->n, x0, mv, Rws, ldr, blk, seg_len, nblk)); break;
+      }
+      hipLaunchKernelGGL(cokrig_tail_rows_kernel, dim3((unsigned)(cols / 256)), dim3(256), 0, s, Rws, ldr, blk,
+                         (int)h->n, h->nc, nrows, nz, cols);
+      GSS_HIP(hipGetLastError());
+    }
+    GSS_TRY(krig_join_device(h, s));   // an asynchronous fit ran beside the assembly; the quadratic form needs it
+    {
+      ProfScope pq("krig_quadform", s);
+      for (int t = 0; t < nz; ++t) {
+        uint8_t* stp = status ? sstat.as<uint8_t>() + t * m + off : nullptr;
+        launch_krig_quadform(h, Rws + t * blk, ldr, h->c00[t], h->means[t], mv, cols,
+                             smean.as<double>() + t * m + off, svar.as<double>() + t * m + off, stp, mpart, s);
+      }
+    }
+    GSS_HIP(hipGetLastError());
+    GSS_TRY(pipe.deliver(off, mv, s));
+  }
+  if (piped) {
+    GSS_TRY(pipe.finish(s));
+  } else {
+    GSS_TRY(smean.back(mean, sizeof(double) * (size_t)(nz * m), mem, s));
+    GSS_TRY(svar.back(variance, sizeof(double) * (size_t)(nz * m), mem, s));
+    GSS_TRY(sstat.back(status, (size_t)(nz * m), mem, s));
+  }
+  return krig_fit_wait(h);   // status of an asynchronous fit (it finished while the assembly ran)
+}
+
 int32_t gss_krig_set_block_support(gss_krig_t* h, const double* cell, int32_t nsub, void* stream) {
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_TRY(krig_refuse_cokrig(h, "gss_krig_set_block_support"));
   if (nsub <= 0 || cell == nullptr) {   // back to point support
     h->block_nsub = 0;
     return GSS_OK;
@@ -1240,6 +1659,7 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
                              int32_t* count_out, int32_t mem, void* stream) {
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_TRY(krig_refuse_cokrig(h, "gss_krig_predict_knn"));
 
   Searcher sr;
   GSS_TRY(sr.init(metric, metric_param, radius, inv_radii, h->dim, &h->fr));
@@ -1302,6 +1722,7 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
                                       int64_t nbatch, double* mean_out, int32_t mem, void* stream) {
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_TRY(krig_refuse_cokrig(h, "gss_krig_predict_global_batch"));
   GSS_REQUIRE(h->factored, "handle has no factor");
   GSS_REQUIRE(m >= 0 && nbatch >= 0, "negative sizes");
   GSS_REQUIRE(h->variant != GSS_KRIG_EXTDRIFT, "batched prediction is not available with external drifts");
@@ -1434,6 +1855,7 @@ int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radiu
                         void* stream) {
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_TRY(krig_refuse_cokrig(h, "gss_krig_cv_knn"));
   if (metric == GSS_METRIC_HAVERSINE) {
     set_error("cross-validation under the haversine distance is not available: the fold search runs on the k-d index, "
               "which that key has no box bounds for (DESIGN.md section 7)");

@@ -7,8 +7,8 @@ solver front-ends (`solvers`) that mirror the reference's `solve(problem, solver
 from .geo import (CartesianGrid, Composition, DomainView, Ensemble, GeoTable, PointSet, aitchison, asarray, domain,
                   georef, parent, parentindices, view)
 from .problems import EstimationProblem, SimulationProblem
-from .solvers import (FFTGS, LUGS, SGS, ExpWeight, IDWSolver, KrigingSolver, LWRSolver, TricubeWeight, kriging_ui,
-                      searcher_ui, simulate_with_generic_loop, solve)
+from .solvers import (FFTGS, LUGS, SGS, CoKrigingSolver, ExpWeight, IDWSolver, KrigingSolver, LWRSolver, TricubeWeight,
+                      kriging_ui, searcher_ui, simulate_with_generic_loop, solve)
 from .validation import (BlockValidation, CrossValidationResult, KFoldValidation, LeaveBallOut, LeaveOneOut,
                          cross_validate, cverror)
 from .variograms import (CubicVariogram, ExponentialVariogram, GaussianVariogram, MaternVariogram, MetricBall,

@@ -303,6 +303,54 @@ class KrigHandle(_NativeState):
         return out
 
 
+class CoKrigHandle(KrigHandle):
+    """gss_krig_t* of a cokriging system (gss.h, gss_cokrig_create): the stacked samples of nz variables under
+    C_ab(h) = B1[a, b] rho(h) (+ B0[a, b] at a zero lag).  `structure` is a single variogram model of which only the
+    shape is read (kind, range or ball, order).  `cv_global` and `cv_global_folds` are those of the kriging handle;
+    every other method of it is refused by the library."""
+
+    def __init__(self, structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False):
+        self._l = _lib.lib()
+        x = np.ascontiguousarray(xdata, dtype=np.float64)
+        if x.ndim == 1:
+            x = x[:, None]
+        self.n, self.dim = x.shape
+        zz = np.ascontiguousarray(z, dtype=np.float64)
+        vv = np.ascontiguousarray(var, dtype=np.int32)
+        if zz.shape != (self.n,) or vv.shape != (self.n,):
+            raise ValueError(f"z and var must hold one entry per stacked sample ({self.n})")
+        b0 = np.ascontiguousarray(np.atleast_2d(np.asarray(B0, dtype=np.float64)))
+        b1 = np.ascontiguousarray(np.atleast_2d(np.asarray(B1, dtype=np.float64)))
+        self.nz = b1.shape[0]
+        if b0.shape != (self.nz, self.nz) or b1.shape != (self.nz, self.nz):
+            raise ValueError(f"B0 and B1 must be square matrices of one size (got {b0.shape}, {b1.shape})")
+        mm = None
+        if variant == SK:
+            mm = np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if means is None else means, dtype=np.float64),
+                                                      (self.nz,)))
+        self.variant, self.ndrift = variant, 0
+        if getattr(structure, "kind", None) in ("power", "nested"):
+            raise ValueError("cokriging takes one stationary structure (the LMC has one structure plus nugget)")
+        v = make_variogram(structure.kind, self.dim, 1.0, 0.0, structure.range, structure.nu, structure.radii,
+                           rotation=getattr(structure, "rotation", None))
+        h = C.c_void_p()
+        check(self._l.gss_cokrig_create(C.byref(h), C.byref(v), self.nz, ptr(b0), ptr(b1), variant, ptr(mm), ptr(x),
+                                        ptr(zz), ptr(vv), self.n, _lib.KRIG_ASYNC_FIT if async_fit else 0,
+                                        current_stream()))
+        self._h = h
+
+    def predict_global(self, xdom):
+        """-> (mean[nz, m], variance[nz, m], status[nz, m]); numpy in, numpy out; CUDA tensors stay in HBM."""
+        xdom = _prep_in(xdom)
+        m = xdom.shape[0]
+        mean = _empty_like_space(xdom, (self.nz, m), np.float64)
+        var = _empty_like_space(xdom, (self.nz, m), np.float64)
+        status = _empty_like_space(xdom, (self.nz, m), np.uint8)
+        check(self._l.gss_cokrig_predict_global(self._h, ptr(xdom), m, ptr(mean), ptr(var), ptr(status), _space(xdom),
+                                                current_stream()))
+        return mean, var, status
+
+
 class FFTGSHandle(_NativeState):
     _STATE_KIND = _lib.STATE_FFTGS
 
@@ -511,9 +559,15 @@ class HipEngine:
     name = "hip"
     device_resident = True     # handles accept / return CUDA tensors, so solvers may keep intermediates in HBM
     Krig = KrigHandle
+    CoKrig = CoKrigHandle
     FFTGS = FFTGSHandle
     LUGS = LUGSHandle
     SGS = SGSHandle
+
+    @staticmethod
+    def cokrig(structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False):
+        """A fitted cokriging system (CoKrigHandle): `predict_global(xdom)`, `cv_global()`, `cv_global_folds(fold)`."""
+        return CoKrigHandle(structure, B0, B1, variant, xdata, z, var, means=means, async_fit=async_fit)
 
     @staticmethod
     def cov_pairwise(vg, a, b=None):

@@ -24,7 +24,7 @@ from . import parallel
 from .engine import EDK, OK, SK, UK, default_engine
 from .geo import Composition, Ensemble, GeoTable, PointSet, georef, parent, parentindices
 from .problems import EstimationProblem, SimulationProblem
-from .variograms import GaussianVariogram, MetricBall
+from .variograms import GaussianVariogram, MetricBall, VariogramModel
 
 _GLOBAL_KEYS = {"rng", "threads", "init", "engine", "share", "mask"}
 
@@ -433,6 +433,124 @@ class KrigingSolver(_Solver):
             h0.close()
         if gather or ws == 1:
             return georef(cols, pdom)                                  # krig.jl:163
+        return georef(cols, PointSet(_host(xdom)))
+
+
+# ------------------------------------------------------------------------------------------
+# CoKrigingSolver (not in the reference: the estimation step behind fit_lmc)
+# ------------------------------------------------------------------------------------------
+class CoKrigingSolver(_Solver):
+    """Ordinary or simple cokriging of jointly modelled variables under a fitted linear model of coregionalisation,
+    global neighbourhood: `CoKrigingSolver((("cu", "zn"), dict(model=lmc, variant="ordinary")))`.
+
+    `model`: an LMCModel whose `names` contain the listed variables; the sub-matrices of B0 / B1 are taken in the
+    listed order.  `variant`: "ordinary" (one unbiasedness constraint per variable) or "simple" with `mean` = the known
+    means (a scalar or one per variable; None: 0).  A Gaussian structure gets the `nugget + 1e-6` rule of the package
+    on the diagonal of B0 unless `regularize=False`.  Each variable's missing (NaN) rows are dropped separately, so
+    variables measured at different locations of one table are the normal case."""
+    JPARAMS = dict(model=None, variant="ordinary", mean=None, regularize=True)
+    VARIANTS = {"ordinary": OK, "simple": SK}
+
+    def __init__(self, *pairs, **kw):
+        super().__init__(*pairs, **kw)
+        if self.vparams:
+            raise ValueError(f"CoKrigingSolver takes joint parameters only, e.g. ((\"a\", \"b\"), dict(model=...)); "
+                             f"got per-variable parameters for {sorted(self.vparams)}")
+        self._spec = {}
+        for key, p in self.jparams.items():
+            names = self._jorder[key]
+            model = p["model"]
+            if model is None or not hasattr(model, "B1"):
+                raise ValueError(f"variables {names}: `model` must be an LMCModel (fit_lmc)")
+            missing = [v for v in names if v not in model.names]
+            if missing:
+                raise ValueError(f"variables {missing} are not in the coregionalisation model (it has {model.names})")
+            if not 1 <= len(names) <= 8:
+                raise ValueError("between 1 and 8 variables per cokriging system (gss.h, gss_cokrig_create)")
+            if p["variant"] not in self.VARIANTS:
+                raise ValueError(f"variant {p['variant']!r}: one of {tuple(self.VARIANTS)}")
+            idx = [model.names.index(v) for v in names]
+            B0 = np.array(np.asarray(model.B0, dtype=np.float64)[np.ix_(idx, idx)])
+            B1 = np.array(np.asarray(model.B1, dtype=np.float64)[np.ix_(idx, idx)])
+            for name, B in (("B0", B0), ("B1", B1)):
+                if not np.all(np.isfinite(B)):
+                    raise ValueError(f"{name} has a non-finite entry")
+                if np.max(np.abs(B - B.T)) > 1e-12 * max(np.max(np.abs(B)), 1e-300):
+                    raise ValueError(f"{name} is not symmetric")
+                ev = np.linalg.eigvalsh(0.5 * (B + B.T))
+                if ev[0] < -1e-12 * max(np.trace(B), 0.0):
+                    raise ValueError(f"{name} is not positive semidefinite for {names} (smallest eigenvalue {ev[0]:.3g}): "
+                                     f"not an admissible coregionalisation model")
+            if np.any(np.diag(B0) + np.diag(B1) <= 0.0):
+                raise ValueError("every variable needs a positive sill B0_aa + B1_aa")
+            if model.kind == "gaussian" and p["regularize"]:
+                B0 = B0 + 1e-6 * np.eye(len(names))
+            means = None
+            if p["variant"] == "simple":
+                means = np.array(np.broadcast_to(np.asarray(0.0 if p["mean"] is None else p["mean"], dtype=np.float64),
+                                                 (len(names),)))
+            elif p["mean"] is not None:
+                raise ValueError("`mean` belongs to variant=\"simple\" (ordinary cokriging estimates the means)")
+            structure = VariogramModel(model.kind, 1.0, 0.0, float(model.range), float(model.order), None, False)
+            self._spec[names] = dict(structure=structure, B0=B0, B1=B1, variant=self.VARIANTS[p["variant"]], means=means)
+
+    def preprocess(self, problem: EstimationProblem):
+        """Per joint group: the non-missing rows of each variable, stacked in the listed order.  Host logic only."""
+        names = list(problem.variables)
+        covered = {v for grp in self._spec for v in grp}
+        loose = [v for v in names if v not in covered]
+        if loose:
+            raise ValueError(f"variables {loose} have no joint parameters: CoKrigingSolver((({', '.join(map(repr, loose))}, "
+                             f"...), dict(model=...)))")
+        coords = problem.data.domain.centroids()
+        pre = {}
+        for grp, spec in self._spec.items():
+            if not all(v in names for v in grp):
+                if any(v in names for v in grp):
+                    raise ValueError(f"the cokriging group {grp} is only partly among the problem's variables {names}")
+                continue
+            xs, zs, vs = [], [], []
+            for a, v in enumerate(grp):
+                z = np.asarray(problem.data[v], dtype=np.float64)
+                inds = np.flatnonzero(~np.isnan(z))
+                if inds.size == 0:
+                    raise AssertionError(f"all samples of {v} are missing, aborting...")
+                xs.append(coords[inds])
+                zs.append(z[inds])
+                vs.append(np.full(inds.size, a, dtype=np.int32))
+            pre[grp] = dict(x=np.ascontiguousarray(np.concatenate(xs)), z=np.concatenate(zs), var=np.concatenate(vs), **spec)
+        return pre
+
+    def solve(self, problem: EstimationProblem, gather: bool = True):
+        """`<var>` and `<var>_variance` over the domain for every variable of every group; the domain points are sharded
+        over ranks as in KrigingSolver.solve."""
+        pre = self.preprocess(problem)
+        pdom = problem.domain
+        m = pdom.nelements()
+        rank, ws = parallel.world()
+        lo, hi = parallel.shard_range(m, rank, ws)
+        xdom = _domain_points(self.engine, pdom, lo, hi)
+        cols = {}
+        for grp, q in pre.items():
+            nz = len(grp)
+            if hi > lo:
+                h = self.engine.cokrig(q["structure"], q["B0"], q["B1"], q["variant"], q["x"], q["z"], q["var"],
+                                       means=q["means"], async_fit=True)
+                try:
+                    mu, var_, st = h.predict_global(xdom)
+                    mu, var_, st = _host(mu), _host(var_), _host(st)
+                finally:
+                    h.close()
+            else:
+                mu, var_, st = np.empty((nz, 0)), np.empty((nz, 0)), np.empty((nz, 0), dtype=np.uint8)
+            for a, v in enumerate(grp):
+                ma, va = _mask_missing(mu[a], st[a]), _mask_missing(var_[a], st[a])
+                if gather and ws > 1:
+                    ma, va = parallel.all_gather_concat(ma, m), parallel.all_gather_concat(va, m)
+                cols[v], cols[f"{v}_variance"] = ma, va
+        cols = {k: cols[k] for v in problem.variables for k in (v, f"{v}_variance")}
+        if gather or ws == 1:
+            return georef(cols, pdom)
         return georef(cols, PointSet(_host(xdom)))
 
 

@@ -184,7 +184,7 @@ int32_t gss_state_ipc_import(int32_t kind, void* handle, const uint8_t* token, v
 /* ---- kernel timing (bench.py's roofline leg): when enabled every launch of a named hot kernel is
  *      bracketed by HIP events on the stream it is launched on; gss_profile_read synchronises
  *      those events and returns the summed duration and the launch count for `name`
- *      ("krig_rhs", "krig_quadform", "fftgs_noise", "fftgs_fwd", "fftgs_phase", "fftgs_inv", ...). */
+ *      ("krig_rhs", "cokrig_rhs", "krig_quadform", "fftgs_noise", "fftgs_fwd", "fftgs_phase", "fftgs_inv", ...). */
 int32_t gss_profile_enable(int32_t on);
 int32_t gss_profile_reset(void);
 int32_t gss_profile_read(const char* name, double* total_ms, int64_t* launches);
@@ -424,6 +424,57 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
  * zbatch is nbatch x n; mean_out nbatch x m (row per batch).  No variances. */
 int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t m, const double* zbatch,
                                       int64_t nbatch, double* mean_out, int32_t mem, void* stream);
+
+/* ---- cokriging under a linear model of coregionalisation: the estimation step behind gss_variogram_cross and
+ *      gss_variogram_fit_lmc.  (The reference has no cokriging solver; the conventions are this library's own.)
+ *
+ * gss_cokrig_create: the global-neighbourhood system over the stacked samples of nz variables (1 .. 8, the limit of
+ *   gss_variogram_cross), fitted like gss_krig_create fits one variable.
+ *   Samples    x (n x dim, point-major), z (n), var (n ids in 0 .. nz - 1), HOST arrays in any order; the system keeps
+ *              the caller's row order.  Heterotopic sampling is the normal case: any number >= 1 of samples per
+ *              variable, at the same or at different locations.
+ *   Model      C_ab(h) = b1[a][b] rho(h) for h != 0 and C_ab(0) = b0[a][b] + b1[a][b]; rho is the covariance of
+ *              `structure` with sill 1 and nugget 0.  Of `structure` only kind, dim, range, nu, aniso, inv_radii and
+ *              rotation are read; nextra must be 0; GSS_VG_POWER -> GSS_ERR_UNSUPPORTED.  A rotated ball is evaluated
+ *              on frame coordinates, data and domain alike (gss_variogram_t::rotation).  b0, b1: nz x nz, row-major.
+ *   h = 0      is decided as the nugget of every covariance of this library is: on the squared-distance key in frame
+ *              coordinates, accumulated without FMA, being zero.  Two variables measured at one location therefore get
+ *              the cross nugget b0[a][b]; so does a domain point placed on a sample.
+ *   Variants   GSS_KRIG_ORDINARY: traditional ordinary cokriging, nc = nz, one unbiasedness row per variable (the
+ *              weights of the target variable sum to 1, those of every other variable to 0); `means` is not read.
+ *              GSS_KRIG_SIMPLE: nc = 0, means[nz] known; the residuals z_i - means[var_i] are kriged and means[t] is
+ *              added back.  GSS_KRIG_UNIVERSAL / GSS_KRIG_EXTDRIFT -> GSS_ERR_UNSUPPORTED.
+ *   Checks     GSS_ERR_INVALID, the message names the entry: nz outside 1 .. 8; b0 or b1 not symmetric to
+ *              1e-12 max |entry| (the library then works with (B + B') / 2); a diagonal b0[a][a] + b1[a][a] <= 0; a
+ *              variable id outside 0 .. nz - 1; under the ordinary variant a variable without a sample; a non-finite
+ *              coefficient, mean, coordinate or value.  Semidefiniteness of b0 and b1 is NOT checked: a model that is
+ *              not admissible, or collocated samples under a rank-deficient b1 without nugget, surface as
+ *              GSS_ERR_NOT_POSDEF from the fit, as duplicates do for one variable.  The Gaussian kind is the bare
+ *              formula: a front-end that applies the `nugget + 1e-6` rule adds it to the diagonal of b0.
+ *   flags      GSS_KRIG_ASYNC_FIT as gss_krig_create.  GSS_KRIG_NO_FACTOR -> GSS_ERR_INVALID: there is no
+ *              moving-neighbourhood cokriging.
+ *   The handle is a gss_krig_t: gss_krig_destroy, gss_krig_info (n stacked samples, nc) and gss_krig_factor_buffer
+ *   apply.  gss_krig_cv_global and gss_krig_cv_global_folds work on it unchanged -- the identities do not care what
+ *   the blocks of the system mean: pred_i predicts sample i of variable var_i from all other stacked samples, or from
+ *   those outside its fold; a caller removes a whole location by giving its collocated samples one fold id.  (Under
+ *   the ordinary variant a fold that holds every sample of some variable leaves that variable's constraint without
+ *   support: it is caught by the pivot test of the fold only.)  Every other entry point that takes a gss_krig_t
+ *   (gss_krig_predict_global, _predict_global_batch, _predict_knn, _cv_knn, _set_block_support) refuses such a handle
+ *   with GSS_ERR_INVALID.
+ *
+ * gss_cokrig_predict_global: every target variable at every domain point in one call.  xdom m x dim point-major;
+ *   mean and variance: nz columns of m (column t at + t * m); status: nz x m bytes (may be NULL).
+ *   variance_t = b0[t][t] + b1[t][t] - the quadratic form, clamped at 0 as gss_krig_predict_global clamps.  rho is
+ *   evaluated once per (sample, point) and serves the right-hand sides of all nz targets.  `mem`: host arrays travel
+ *   piece by piece beside the computation, as in gss_krig_predict_global.  The right-hand-side workspace holds nz
+ *   blocks, so a chunk is 1 / nz of that call's; the environment variable GSS_COKRIG_CHUNK_POINTS caps the points per
+ *   chunk (rounded down to a multiple of 256), for tests, like GSS_VARIO_CULL above: the results are the same.
+ *   gss_profile_read names: "cokrig_rhs" (assembly), "krig_quadform" (the nz quadratic forms). */
+int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
+                          const double* b1, int32_t variant, const double* means, const double* xdata,
+                          const double* z, const int32_t* var, int64_t n, int32_t flags, void* stream);
+int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, double* mean, double* variance,
+                                  uint8_t* status, int32_t mem, void* stream);
 
 /* ---- cross-validation: does the model predict the samples it was given?  ([DEP] GeoStatsBase `cverror` with
  *      LeaveOneOut / KFoldValidation / BlockValidation / LeaveBallOut; not in the reference tree.)  Every sample of the
