@@ -1,0 +1,118 @@
+// Moving-neighbourhood cokriging (gss.h, gss_cokrig_predict_knn): one search per variable over that variable's samples
+// (knn.hip, the unmasked query), then one system per domain point on the lists of all variables
+// (cokrig_local_kernel.h).  This unit holds the driver, the general instantiations (any model, 1-D) and the dispatch;
+// the compile-time kinds of 2-D and 3-D have units of their own (cokrig_local_2d.hip, cokrig_local_3d.hip).
+#include "cokrig_local_kernel.h"
+
+#include <cstdlib>
+#include <cstring>
+
+namespace gss {
+
+// idx_out (m x ksum, the caller's rows, -1 beyond a variable's count) and count_out (m x nz) from the lists of the
+// searches; one thread per entry of idx_out, the first nz threads of a point write its counts
+__global__ __launch_bounds__(256) void cokrig_lists_kernel(CoLocalSpec sp, const int* __restrict__ idx,
+                                                           const int* __restrict__ cnt, const int* __restrict__ row,
+                                                           int64_t m, int* __restrict__ idx_out,
+                                                           int* __restrict__ count_out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= m * sp.ksum) return;
+  const int64_t p = e / sp.ksum;
+  const int col = (int)(e - p * sp.ksum);
+  int a = 0, kk = sp.k[0], ko = sp.koff[0], go = sp.off[0];
+#pragma unroll
+  for (int b = 1; b < COL_MAXZ; ++b) {
+    if (b < sp.nz && col >= sp.koff[b]) {
+      a = b;
+      kk = sp.k[b];
+      ko = sp.koff[b];
+      go = sp.off[b];
+    }
+  }
+  const int jj = col - ko;
+  int c = cnt[(int64_t)a * m + p];
+  c = c < 0 ? 0 : (c > kk ? kk : c);
+  if (idx_out) idx_out[e] = jj < c ? row[go + idx[m * ko + p * kk + jj]] : -1;
+  if (count_out && jj == 0) count_out[p * sp.nz + a] = c;
+}
+
+int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped& g, Searcher* sr, const int* k,
+                         int minneighbors, const double* x0, const double* x0_raw, int64_t m, double* mean, double* var,
+                         uint8_t* status, int64_t ldo, int* idx_out, int* count_out, hipStream_t s, HostPipe* pipe) {
+  const int nz = g.nz;
+  GSS_REQUIRE(nz >= 1 && nz <= COL_MAXZ, "cokrig_local_dev: %d variables outside 1 .. %d", nz, COL_MAXZ);
+  CoLocalSpec sp;
+  std::memset(&sp, 0, sizeof(sp));
+  sp.nz = nz;
+  sp.ordinary = variant == GSS_KRIG_ORDINARY ? 1 : 0;
+  sp.minneighbors = minneighbors;
+  for (int a = 0; a < nz; ++a) {
+    sp.k[a] = k[a];
+    sp.koff[a] = sp.ksum;
+    sp.off[a] = (int)g.off[a];
+    sp.ksum += k[a];
+  }
+  GSS_REQUIRE(sp.ksum >= 1 && sp.ksum <= LMAX_K, "cokrig_local_dev: %d neighbours in total outside 1 .. %d", sp.ksum,
+              LMAX_K);
+
+  const bool piped = pipe && pipe->on;
+  int64_t chunk = piped ? HostPipe::PIECE : (1 << 20);
+  if (const char* e = std::getenv("GSS_COKRIG_CHUNK_POINTS")) {   // tests: the chunk loop past its first turn
+    const int64_t cap = std::atoll(e) / 256 * 256;
+    if (cap > 0 && cap < chunk) chunk = cap;
+  }
+  const int64_t mc = m < chunk ? m : chunk;
+  DevBuf idx_s, cnt_s;
+  GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)(mc * sp.ksum)));
+  GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(mc * nz)));
+  const int kind = vg.nextra == 0 ? vg.kind : -1;
+  for (int64_t off = 0; off < m; off += chunk) {
+    const int64_t mv = (m - off) < chunk ? (m - off) : chunk;
+    if (piped) GSS_TRY(pipe->fetch(off, mv, s));
+    int* idx = idx_s.as<int>();
+    int* cnt = cnt_s.as<int>();
+    {
+      ProfScope ps("knn", s);
+      for (int a = 0; a < nz; ++a)
+        GSS_TRY(sr[a].query(x0 + off * dim, x0_raw ? x0_raw + off * dim : nullptr, mv, k[a], idx + mv * sp.koff[a],
+                            cnt + (int64_t)a * mv, s));
+    }
+    {
+      ProfScope pl("cokrig_local", s);
+      CoLocalLaunch a;
+      a.vg = &vg;
+      a.sp = sp;
+      a.xg = g.x;
+      a.zres = g.zres;
+      a.cotab = g.tab;
+      a.x0 = x0 + off * dim;
+      a.m = mv;
+      a.idx = idx;
+      a.cnt = cnt;
+      a.mean = mean + off;
+      a.var = var + off;
+      a.status = status ? status + off : nullptr;
+      a.ldo = ldo;
+      a.s = s;
+      const bool fixed = kind == GSS_VG_GAUSSIAN || kind == GSS_VG_EXPONENTIAL || kind == GSS_VG_SPHERICAL ||
+                         kind == VG_MATERN12 || kind == VG_MATERN32 || kind == VG_MATERN52;
+      int32_t rc;
+      if (dim == 3) rc = fixed ? cokrig_local_launch_3d(kind, a) : cokrig_local_launch<3, -1>(a);
+      else if (dim == 2) rc = fixed ? cokrig_local_launch_2d(kind, a) : cokrig_local_launch<2, -1>(a);
+      else rc = cokrig_local_launch<1, -1>(a);
+      GSS_TRY(rc);
+    }
+    if (idx_out || count_out) {
+      const int64_t ne = mv * sp.ksum;
+      hipLaunchKernelGGL(cokrig_lists_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, sp, idx, cnt, g.row, mv,
+                         idx_out ? idx_out + off * sp.ksum : nullptr, count_out ? count_out + off * nz : nullptr);
+      GSS_HIP(hipGetLastError());
+    }
+    if (piped) GSS_TRY(pipe->deliver(off, mv, s));
+  }
+  if (piped) GSS_TRY(pipe->finish(s));
+  GSS_HIP(hipStreamSynchronize(s));   // the lists are released on return
+  return GSS_OK;
+}
+
+}  // namespace gss

@@ -21,7 +21,10 @@
 //   cokrig_system_kernel  the n x n block of the system, replacing the pairwise covariances of the fit
 //   cokrig_rhs_kernel     the right-hand sides of all nz targets from one evaluation of rho per (sample, point)
 // The factorisation, K3 and the cross-validation identities are those of the single-variable handle.
+// The moving neighbourhood of cokriging (gss_cokrig_predict_knn) has its entry point here and its kernel and driver in
+// cokrig_local.hip.
 #include "gss_internal.h"
+#include "cokrig.h"
 
 #include <mutex>
 #include "mfma_f64.h"
@@ -162,20 +165,7 @@ static int32_t launch_krig_rhs(hipStream_t s, const VgDev& vg, const double* xd,
 }
 
 // ---- cokriging -------------------------------------------------------------------------------------------------------
-// Coefficient table of a cokriging handle in device memory (CO_TAB doubles): b1[a * CO_MAXZ + b] (symmetrised), then
-// c0 = b0 + b1 in the same layout (the value at a zero key), then means[CO_MAXZ].
-constexpr int CO_MAXZ = 8;
-constexpr int CO_C0 = CO_MAXZ * CO_MAXZ, CO_MEANS = 2 * CO_MAXZ * CO_MAXZ, CO_TAB = CO_MEANS + CO_MAXZ;
-
-// rho(a, b) of the structure (sill 1, no nugget) and whether the key is zero.  The key and the shape are those of
-// cov_pair / cov_d2_select: KIND >= 0 folds the model switch away, KIND < 0 reads it from vg.  The shape is evaluated on
-// max(d2, 1e-300) for every lane; the caller selects the zero-key value afterwards.
-template <int DIM, int KIND>
-__device__ __forceinline__ double co_rho(const VgDev& vg, const double* a, const double* b, bool* zero) {
-  const double d2 = KIND < 0 ? sqdist_nofma<DIM>(a, b, vg.ir, vg.aniso != 0) : sqdist_nofma<DIM>(a, b, vg.ir, true);
-  *zero = d2 <= 0.0;
-  return vg_shape(KIND < 0 ? vg.kind : KIND, fmax(d2, 1e-300), vg.inv_range, vg.mscale, vg.pw);
-}
+// (the coefficient table CO_* and co_rho: cokrig.h, shared with the moving neighbourhood)
 
 // M[i * ldw + j] = C_{var_i var_j}(x_i, x_j) for i, j < n (the block is symmetric: the table is, and so is the key).
 // Lane = column sample j, the row sample i is wave-uniform (cov_pairwise_kernel's layout).
@@ -699,6 +689,11 @@ struct gss_krig {
   int nz = 0;
   DevBuf covar, cotab;
   double c00[CO_MAXZ] = {}, means[CO_MAXZ] = {};
+  // the same samples grouped by variable for the per-variable searches of gss_cokrig_predict_knn (cokrig.h, CoGrouped):
+  // coordinates on the covariance frame / as given (only with a frame), residuals z - means[var], the caller's row of
+  // every grouped sample, and where each variable starts
+  DevBuf co_xg, co_xg_raw, co_zres, co_row;
+  int64_t co_off[CO_MAXZ + 1] = {};
   double* Wp() const { return factor.as<double>(); }
   double* wd() const { return factor.as<double>() + ldw * N1pad; }
 };
@@ -1409,29 +1404,36 @@ static int64_t cokrig_chunk_points(int64_t N1pad, int nz, int64_t m) {
   return mc;
 }
 
-int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
-                          const double* b1, int32_t variant, const double* means, const double* xdata,
-                          const double* z, const int32_t* var, int64_t n, int32_t flags, void* stream) {
-  GSS_ENTRY();
-  GSS_REQUIRE(out != nullptr, "gss_cokrig_create: out is NULL");
+// The body of both creators.  factor: fit the global system (gss_cokrig_create) or keep the samples only
+// (gss_cokrig_create_local); who: the entry point the messages name.
+static int32_t cokrig_create_impl(const char* who, bool factor, gss_krig_t** out, const gss_variogram_t* structure,
+                                  int32_t nz, const double* b0, const double* b1, int32_t variant, const double* means,
+                                  const double* xdata, const double* z, const int32_t* var, int64_t n, int32_t flags,
+                                  void* stream) {
+  GSS_REQUIRE(out != nullptr, "%s: out is NULL", who);
   *out = nullptr;
-  GSS_REQUIRE(structure != nullptr, "gss_cokrig_create: structure is NULL");
-  GSS_REQUIRE(nz >= 1 && nz <= CO_MAXZ, "gss_cokrig_create: nz = %d outside 1 .. %d", nz, CO_MAXZ);
-  GSS_REQUIRE(b0 != nullptr && b1 != nullptr, "gss_cokrig_create: b0 or b1 is NULL");
+  GSS_REQUIRE(structure != nullptr, "%s: structure is NULL", who);
+  GSS_REQUIRE(nz >= 1 && nz <= CO_MAXZ, "%s: nz = %d outside 1 .. %d", who, nz, CO_MAXZ);
+  GSS_REQUIRE(b0 != nullptr && b1 != nullptr, "%s: b0 or b1 is NULL", who);
   if (structure->kind == GSS_VG_POWER) {
-    set_error("gss_cokrig_create: a power structure has no sill, the coregionalisation model needs one");
+    set_error("%s: a power structure has no sill, the coregionalisation model needs one", who);
     return GSS_ERR_UNSUPPORTED;
   }
-  GSS_REQUIRE(structure->nextra == 0, "gss_cokrig_create: one structure plus nugget (nextra = %d)", structure->nextra);
+  GSS_REQUIRE(structure->nextra == 0, "%s: one structure plus nugget (nextra = %d)", who, structure->nextra);
   if (variant == GSS_KRIG_UNIVERSAL || variant == GSS_KRIG_EXTDRIFT) {
-    set_error("gss_cokrig_create: cokriging with a drift is not available (simple and ordinary only)");
+    set_error("%s: cokriging with a drift is not available (simple and ordinary only)", who);
     return GSS_ERR_UNSUPPORTED;
   }
   GSS_REQUIRE(variant == GSS_KRIG_SIMPLE || variant == GSS_KRIG_ORDINARY, "unknown kriging variant %d", variant);
-  GSS_REQUIRE((flags & GSS_KRIG_NO_FACTOR) == 0, "gss_cokrig_create: GSS_KRIG_NO_FACTOR is refused: there is no "
-              "moving-neighbourhood cokriging, the handle serves the global neighbourhood only");
-  GSS_REQUIRE(variant != GSS_KRIG_SIMPLE || means != nullptr, "gss_cokrig_create: simple cokriging needs means[nz]");
-  GSS_REQUIRE(xdata != nullptr && z != nullptr && var != nullptr, "gss_cokrig_create: NULL data");
+  GSS_REQUIRE((flags & GSS_KRIG_NO_FACTOR) == 0, "%s: GSS_KRIG_NO_FACTOR is refused: a handle without a factor, for the "
+              "moving neighbourhood only, comes from gss_cokrig_create_local", who);
+  if (!factor && nz > COL_MAXZ) {
+    set_error("%s: nz = %d: the moving neighbourhood takes at most %d variables (2 nz + 1 right-hand-side columns ride "
+              "along in one 16-column tile)", who, nz, COL_MAXZ);
+    return GSS_ERR_UNSUPPORTED;
+  }
+  GSS_REQUIRE(variant != GSS_KRIG_SIMPLE || means != nullptr, "%s: simple cokriging needs means[nz]", who);
+  GSS_REQUIRE(xdata != nullptr && z != nullptr && var != nullptr, "%s: NULL data", who);
   GSS_REQUIRE(n >= 1, "all samples are missing, aborting...");
   GSS_REQUIRE(n < (1 << 30), "too many samples");
 
@@ -1440,26 +1442,26 @@ int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, in
   double tab[CO_TAB] = {};
   double big = 0.0;
   for (int e = 0; e < nz * nz; ++e) {
-    GSS_REQUIRE(std::isfinite(b0[e]) && std::isfinite(b1[e]), "gss_cokrig_create: b0 / b1 entry [%d][%d] is not finite",
+    GSS_REQUIRE(std::isfinite(b0[e]) && std::isfinite(b1[e]), "%s: b0 / b1 entry [%d][%d] is not finite", who,
                 e / nz, e % nz);
     big = std::fmax(big, std::fmax(std::fabs(b0[e]), std::fabs(b1[e])));
   }
   for (int a = 0; a < nz; ++a)
     for (int b = 0; b < nz; ++b) {
       GSS_REQUIRE(std::fabs(b0[a * nz + b] - b0[b * nz + a]) <= 1e-12 * big,
-                  "gss_cokrig_create: b0 is not symmetric at [%d][%d]", a, b);
+                  "%s: b0 is not symmetric at [%d][%d]", who, a, b);
       GSS_REQUIRE(std::fabs(b1[a * nz + b] - b1[b * nz + a]) <= 1e-12 * big,
-                  "gss_cokrig_create: b1 is not symmetric at [%d][%d]", a, b);
+                  "%s: b1 is not symmetric at [%d][%d]", who, a, b);
       const double s1 = 0.5 * (b1[a * nz + b] + b1[b * nz + a]), s0 = 0.5 * (b0[a * nz + b] + b0[b * nz + a]);
       tab[a * CO_MAXZ + b] = s1;
       tab[CO_C0 + a * CO_MAXZ + b] = s0 + s1;
     }
   for (int a = 0; a < nz; ++a)
-    GSS_REQUIRE(tab[CO_C0 + a * CO_MAXZ + a] > 0.0, "gss_cokrig_create: variable %d has no positive sill "
-                "b0[%d][%d] + b1[%d][%d]", a, a, a, a, a);
+    GSS_REQUIRE(tab[CO_C0 + a * CO_MAXZ + a] > 0.0, "%s: variable %d has no positive sill "
+                "b0[%d][%d] + b1[%d][%d]", who, a, a, a, a, a);
   if (variant == GSS_KRIG_SIMPLE)
     for (int a = 0; a < nz; ++a) {
-      GSS_REQUIRE(std::isfinite(means[a]), "gss_cokrig_create: means[%d] is not finite", a);
+      GSS_REQUIRE(std::isfinite(means[a]), "%s: means[%d] is not finite", who, a);
       tab[CO_MEANS + a] = means[a];
     }
 
@@ -1477,18 +1479,18 @@ int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, in
   const int dim = h->vg.dim;
   int64_t per[CO_MAXZ] = {};
   for (int64_t i = 0; i < n; ++i) {
-    GSS_REQUIRE(var[i] >= 0 && var[i] < nz, "gss_cokrig_create: variable id %d of sample %lld outside 0 .. %d", var[i],
+    GSS_REQUIRE(var[i] >= 0 && var[i] < nz, "%s: variable id %d of sample %lld outside 0 .. %d", who, var[i],
                 (long long)i, nz - 1);
-    GSS_REQUIRE(std::isfinite(z[i]), "gss_cokrig_create: value of sample %lld is not finite", (long long)i);
+    GSS_REQUIRE(std::isfinite(z[i]), "%s: value of sample %lld is not finite", who, (long long)i);
     for (int k = 0; k < dim; ++k)
-      GSS_REQUIRE(std::isfinite(xdata[i * dim + k]), "gss_cokrig_create: coordinate %d of sample %lld is not finite", k,
+      GSS_REQUIRE(std::isfinite(xdata[i * dim + k]), "%s: coordinate %d of sample %lld is not finite", who, k,
                   (long long)i);
     ++per[var[i]];
   }
   if (variant == GSS_KRIG_ORDINARY)
     for (int a = 0; a < nz; ++a)
-      GSS_REQUIRE(per[a] >= 1, "gss_cokrig_create: variable %d has no sample (ordinary cokriging needs one "
-                  "unbiasedness row per variable)", a);
+      GSS_REQUIRE(per[a] >= 1, "%s: variable %d has no sample (ordinary cokriging needs one "
+                  "unbiasedness row per variable)", who, a);
 
   GSS_TRY(frame_origin(&h->fr, xdata, GSS_MEM_HOST, nullptr));
   h->variant = variant;
@@ -1524,13 +1526,60 @@ int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, in
   GSS_HIP(hipMemcpyAsync(h->z.p, z, sizeof(double) * n, hipMemcpyHostToDevice, s));
   GSS_HIP(hipMemcpyAsync(h->covar.p, var, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
   GSS_HIP(hipMemcpyAsync(h->cotab.p, tab, sizeof(tab), hipMemcpyHostToDevice, s));
-  GSS_HIP(hipStreamSynchronize(s));   // tab lives on this frame
-  const bool async = (flags & GSS_KRIG_ASYNC_FIT) != 0;
-  GSS_TRY(krig_factorize(h, s, async));
-  if (!async) GSS_TRY(krig_fit_wait(h));   // otherwise joined by the first call that needs the factor
+  // grouped by variable, the caller's order inside a variable: what the per-variable searches index
+  {
+    std::vector<double> xg((size_t)(n * dim)), zr((size_t)n);
+    std::vector<int32_t> row((size_t)n);
+    int64_t at[CO_MAXZ];
+    h->co_off[0] = 0;
+    for (int a = 0; a < CO_MAXZ; ++a) {
+      at[a] = h->co_off[a];
+      h->co_off[a + 1] = h->co_off[a] + per[a];
+    }
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t j = at[var[i]]++;
+      for (int k = 0; k < dim; ++k) xg[(size_t)(j * dim + k)] = xdata[i * dim + k];
+      zr[(size_t)j] = z[i] - tab[CO_MEANS + var[i]];
+      row[(size_t)j] = (int32_t)i;
+    }
+    GSS_TRY(h->co_xg.alloc(sizeof(double) * (size_t)(n * dim)));
+    GSS_TRY(h->co_zres.alloc(sizeof(double) * (size_t)n));
+    GSS_TRY(h->co_row.alloc(sizeof(int32_t) * (size_t)n));
+    if (h->fr.on) {
+      GSS_TRY(h->co_xg_raw.alloc(sizeof(double) * (size_t)(n * dim)));
+      GSS_HIP(hipMemcpyAsync(h->co_xg_raw.p, xg.data(), sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
+      GSS_TRY(frame_apply_dev(h->fr, h->co_xg_raw.as<double>(), n, h->co_xg.as<double>(), s));
+    } else {
+      GSS_HIP(hipMemcpyAsync(h->co_xg.p, xg.data(), sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
+    }
+    GSS_HIP(hipMemcpyAsync(h->co_zres.p, zr.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
+    GSS_HIP(hipMemcpyAsync(h->co_row.p, row.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+    GSS_HIP(hipStreamSynchronize(s));   // tab and the grouped copies live on this frame
+  }
+  if (factor) {
+    const bool async = (flags & GSS_KRIG_ASYNC_FIT) != 0;
+    GSS_TRY(krig_factorize(h, s, async));
+    if (!async) GSS_TRY(krig_fit_wait(h));   // otherwise joined by the first call that needs the factor
+  }
   guard.h = nullptr;
   *out = h;
   return GSS_OK;
+}
+
+int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
+                          const double* b1, int32_t variant, const double* means, const double* xdata,
+                          const double* z, const int32_t* var, int64_t n, int32_t flags, void* stream) {
+  GSS_ENTRY();
+  return cokrig_create_impl("gss_cokrig_create", true, out, structure, nz, b0, b1, variant, means, xdata, z, var, n,
+                            flags, stream);
+}
+
+int32_t gss_cokrig_create_local(gss_krig_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
+                                const double* b1, int32_t variant, const double* means, const double* xdata,
+                                const double* z, const int32_t* var, int64_t n, void* stream) {
+  GSS_ENTRY();
+  return cokrig_create_impl("gss_cokrig_create_local", false, out, structure, nz, b0, b1, variant, means, xdata, z, var,
+                            n, 0, stream);
 }
 
 int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, double* mean, double* variance,
@@ -1614,6 +1663,85 @@ int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, 
     GSS_TRY(sstat.back(status, (size_t)(nz * m), mem, s));
   }
   return krig_fit_wait(h);   // status of an asynchronous fit (it finished while the assembly ran)
+}
+
+int32_t gss_cokrig_predict_knn(gss_krig_t* h, const double* xdom, int64_t m, const int32_t* k, int32_t minneighbors,
+                               double radius, const double* inv_radii, int32_t metric, double metric_param,
+                               double* mean, double* variance, uint8_t* status, int32_t* idx_out, int32_t* count_out,
+                               int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(h->nz > 0, "gss_cokrig_predict_knn: the handle is not a cokriging system (gss_cokrig_create and "
+              "gss_cokrig_create_local make one)");
+  const int nz = h->nz, dim = h->dim;
+  if (nz > COL_MAXZ) {
+    set_error("gss_cokrig_predict_knn: the handle holds %d variables, the moving neighbourhood takes at most %d", nz,
+              COL_MAXZ);
+    return GSS_ERR_UNSUPPORTED;
+  }
+  GSS_REQUIRE(k != nullptr, "gss_cokrig_predict_knn: k is NULL (one neighbour count per variable)");
+  int ksum = 0;
+  for (int a = 0; a < nz; ++a) {
+    const int64_t na = h->co_off[a + 1] - h->co_off[a];
+    GSS_REQUIRE(k[a] >= 1 && k[a] <= na, "gss_cokrig_predict_knn: k[%d] = %d outside 1 .. %lld, the sample count of "
+                "variable %d (a front-end clamps it; gss_cokrig_predict_global uses every sample)", a, k[a],
+                (long long)na, a);
+    ksum += k[a];
+  }
+  if (ksum > 64) {
+    set_error("gss_cokrig_predict_knn: %d neighbours in total, the tile kernel holds at most 64", ksum);
+    return GSS_ERR_UNSUPPORTED;
+  }
+  GSS_REQUIRE(m >= 0 && (m == 0 || (xdom && mean && variance)), "gss_cokrig_predict_knn: NULL array");
+
+  Searcher sr[COL_MAXZ];   // one per variable, over that variable's samples; all in the same frame
+  for (int a = 0; a < nz; ++a) GSS_TRY(sr[a].init(metric, metric_param, radius, inv_radii, dim, &h->fr));
+  if (m == 0) return GSS_OK;
+  hipStream_t s = to_stream(stream);
+  Staged sx, smean, svar, sstat, sidx, scnt;
+  HostPipe pipe;   // host arrays: in and out piece by piece beside the computation (gss_internal.h)
+  if (!sr[0].two_frames) GSS_TRY(pipe.begin(mem, m, s));   // two frames: the domain is needed twice, it comes in whole
+  if (pipe.on) GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
+  else GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
+  GSS_TRY(smean.out(mean, sizeof(double) * (size_t)(nz * m), mem));
+  GSS_TRY(svar.out(variance, sizeof(double) * (size_t)(nz * m), mem));
+  GSS_TRY(sstat.out(status, (size_t)(nz * m), mem));
+  GSS_TRY(sidx.out(idx_out, sizeof(int32_t) * (size_t)(m * ksum), mem));
+  GSS_TRY(scnt.out(count_out, sizeof(int32_t) * (size_t)(m * nz), mem));
+  if (pipe.on) {
+    pipe.add_in(xdom, sx.p, sizeof(double) * dim);
+    for (int t = 0; t < nz; ++t) {   // column t of every output is an array of its own to the pipe
+      pipe.add_out(mean + t * m, smean.as<double>() + t * m, sizeof(double));
+      pipe.add_out(variance + t * m, svar.as<double>() + t * m, sizeof(double));
+      if (status) pipe.add_out(status + t * m, sstat.as<uint8_t>() + t * m, 1);
+    }
+    pipe.add_out(idx_out, sidx.p, sizeof(int32_t) * (size_t)ksum);
+    pipe.add_out(count_out, scnt.p, sizeof(int32_t) * (size_t)nz);
+    pipe.frame = &h->fr;
+  }
+  CoGrouped g;
+  g.x = h->co_xg.as<double>();
+  g.x_raw = h->co_xg_raw.as<double>();
+  g.zres = h->co_zres.as<double>();
+  g.row = h->co_row.as<int>();
+  g.tab = h->cotab.as<double>();
+  g.nz = nz;
+  for (int a = 0; a <= CO_MAXZ; ++a) g.off[a] = h->co_off[a];
+  for (int a = 0; a < nz; ++a)
+    GSS_TRY(sr[a].samples(g.x + g.off[a] * dim, g.x_raw ? g.x_raw + g.off[a] * dim : nullptr, g.off[a + 1] - g.off[a], s));
+  const double* x0_raw = sx.as<double>();   // as staged; the covariance-frame copy follows
+  FrameCopy xfr;
+  if (!pipe.on) GSS_TRY(xfr.of(h->fr, &sx, m, s));
+  GSS_TRY(cokrig_local_dev(h->vg, h->variant, dim, g, sr, k, minneighbors, sx.as<double>(),
+                           sr[0].two_frames ? x0_raw : nullptr, m, smean.as<double>(), svar.as<double>(),
+                           status ? sstat.as<uint8_t>() : nullptr, m, sidx.as<int>(), scnt.as<int>(), s, &pipe));
+  if (pipe.on) return GSS_OK;   // everything is home (cokrig_local_dev ends with pipe.finish)
+  GSS_TRY(smean.back(mean, sizeof(double) * (size_t)(nz * m), mem, s));
+  GSS_TRY(svar.back(variance, sizeof(double) * (size_t)(nz * m), mem, s));
+  GSS_TRY(sstat.back(status, (size_t)(nz * m), mem, s));
+  GSS_TRY(sidx.back(idx_out, sizeof(int32_t) * (size_t)(m * ksum), mem, s));
+  GSS_TRY(scnt.back(count_out, sizeof(int32_t) * (size_t)(m * nz), mem, s));
+  return GSS_OK;
 }
 
 int32_t gss_krig_set_block_support(gss_krig_t* h, const double* cell, int32_t nsub, void* stream) {

@@ -51,6 +51,26 @@ __device__ __forceinline__ double c0_entry(const VgDev& vg, const LocalSpec& sp,
 }
 
 
+// Step KK of the tile factorisation of the moving-neighbourhood kernels (krig_local.hip, cokrig_local_kernel.h), after V = U_KK^-1 is known: U_KK,j = V' A_KK,j; Y_KK = V' B_KK; trailing updates
+template <int KK, int NT = 4>
+__device__ __forceinline__ void k5_block_step(d4_t (&T)[10], d4_t (&B)[4], const d4_t& V, int nt) {
+  const d4_t zero4 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int j = KK + 1; j < NT; ++j)
+    if (j < nt) T[tile_id(KK, j)] = xty(V, T[tile_id(KK, j)], zero4);
+  B[KK] = xty(V, B[KK], zero4);
+#pragma unroll
+  for (int i = KK + 1; i < NT; ++i) {
+    if (i < nt) {
+      const d4_t N = -T[tile_id(KK, i)];
+#pragma unroll
+      for (int j = i; j < NT; ++j)
+        if (j < nt) T[tile_id(i, j)] = xty(N, T[tile_id(KK, j)], T[tile_id(i, j)]);
+      B[i] = xty(N, B[KK], B[i]);
+    }
+  }
+}
+
 // Block elimination on the (2 + nc) x (2 + nc) Gram matrix G = Y'Y of the forward-substituted right-hand sides
 // [c0 | z | F] (one wave; lane i = drift term i, everything in registers; lanes 16..63 shadow lanes 0..15):
 // S = Y_F'Y_F = L L', u = L^-1 (Y_F'y_c - f0), v = L^-1 Y_F'y_z, r'S^-1 r = |u|^2, t'S^-1 r = u.v, then

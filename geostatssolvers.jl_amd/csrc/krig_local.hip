@@ -256,26 +256,6 @@ __global__ __launch_bounds__(BIG_NT) void krig_local_big_kernel(VgDev vg, LocalS
 // Rows beyond the neighbour count are padded with the identity.
 // ---------------------------------------------------------------------------------------------
 
-// step KK of the tile factorisation, after V = U_KK^-1 is known: U_KK,j = V' A_KK,j; Y_KK = V' B_KK; trailing updates
-template <int KK, int NT = 4>
-__device__ __forceinline__ void k5_block_step(d4_t (&T)[10], d4_t (&B)[4], const d4_t& V, int nt) {
-  const d4_t zero4 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int j = KK + 1; j < NT; ++j)
-    if (j < nt) T[tile_id(KK, j)] = xty(V, T[tile_id(KK, j)], zero4);
-  B[KK] = xty(V, B[KK], zero4);
-#pragma unroll
-  for (int i = KK + 1; i < NT; ++i) {
-    if (i < nt) {
-      const d4_t N = -T[tile_id(KK, i)];
-#pragma unroll
-      for (int j = i; j < NT; ++j)
-        if (j < nt) T[tile_id(i, j)] = xty(N, T[tile_id(KK, j)], T[tile_id(i, j)]);
-      B[i] = xty(N, B[KK], B[i]);
-    }
-  }
-}
-
 // Four domain points per workgroup, one per wave.  The waves only meet for the diagonal tiles: the row broadcasts of
 // the 16 x 16 factorisation are local to a 16-lane row (tile16.h), so ONE wave factors the four waves' diagonal tiles
 // in its four lane rows for the issue cost of one, and the duty rotates with the block step (wave kk does step kk)

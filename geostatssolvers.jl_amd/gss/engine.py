@@ -306,10 +306,13 @@ class KrigHandle(_NativeState):
 class CoKrigHandle(KrigHandle):
     """gss_krig_t* of a cokriging system (gss.h, gss_cokrig_create): the stacked samples of nz variables under
     C_ab(h) = B1[a, b] rho(h) (+ B0[a, b] at a zero lag).  `structure` is a single variogram model of which only the
-    shape is read (kind, range or ball, order).  `cv_global` and `cv_global_folds` are those of the kriging handle;
-    every other method of it is refused by the library."""
+    shape is read (kind, range or ball, order).  `cv_global` and `cv_global_folds` are those of the kriging handle,
+    `predict_knn` is the moving neighbourhood of cokriging; every other method of the kriging handle is refused by the
+    library."""
 
-    def __init__(self, structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False):
+    def __init__(self, structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False, factor=True):
+        """`factor=False`: gss_cokrig_create_local -- no system, no factor; the handle serves `predict_knn` only (at most
+        four variables)."""
         self._l = _lib.lib()
         x = np.ascontiguousarray(xdata, dtype=np.float64)
         if x.ndim == 1:
@@ -334,9 +337,13 @@ class CoKrigHandle(KrigHandle):
         v = make_variogram(structure.kind, self.dim, 1.0, 0.0, structure.range, structure.nu, structure.radii,
                            rotation=getattr(structure, "rotation", None))
         h = C.c_void_p()
-        check(self._l.gss_cokrig_create(C.byref(h), C.byref(v), self.nz, ptr(b0), ptr(b1), variant, ptr(mm), ptr(x),
-                                        ptr(zz), ptr(vv), self.n, _lib.KRIG_ASYNC_FIT if async_fit else 0,
-                                        current_stream()))
+        if factor:
+            check(self._l.gss_cokrig_create(C.byref(h), C.byref(v), self.nz, ptr(b0), ptr(b1), variant, ptr(mm), ptr(x),
+                                            ptr(zz), ptr(vv), self.n, _lib.KRIG_ASYNC_FIT if async_fit else 0,
+                                            current_stream()))
+        else:
+            check(self._l.gss_cokrig_create_local(C.byref(h), C.byref(v), self.nz, ptr(b0), ptr(b1), variant, ptr(mm),
+                                                  ptr(x), ptr(zz), ptr(vv), self.n, current_stream()))
         self._h = h
 
     def predict_global(self, xdom):
@@ -348,6 +355,29 @@ class CoKrigHandle(KrigHandle):
         status = _empty_like_space(xdom, (self.nz, m), np.uint8)
         check(self._l.gss_cokrig_predict_global(self._h, ptr(xdom), m, ptr(mean), ptr(var), ptr(status), _space(xdom),
                                                 current_stream()))
+        return mean, var, status
+
+    def predict_knn(self, xdom, k, minneighbors=1, radius=None, radii=None, return_idx=False, rotation=None):
+        """Moving neighbourhood (gss.h, gss_cokrig_predict_knn): the `k[a]` nearest samples of every variable a, each
+        variable searched on its own.  `k`: one count per variable, or an int for all of them.
+        -> (mean[nz, m], variance[nz, m], status[nz, m][, idx[m, sum k], count[m, nz]])."""
+        xdom = _prep_in(xdom)
+        m = xdom.shape[0]
+        kk = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.int32), (self.nz,)))
+        ksum = int(kk.sum())
+        mean = _empty_like_space(xdom, (self.nz, m), np.float64)
+        var = _empty_like_space(xdom, (self.nz, m), np.float64)
+        status = _empty_like_space(xdom, (self.nz, m), np.uint8)
+        idx = _empty_like_space(xdom, (m, max(ksum, 0)), np.int32) if return_idx else None
+        cnt = _empty_like_space(xdom, (m, self.nz), np.int32) if return_idx else None
+        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
+        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
+        met, ir = _ball_metric(0, ir, radii, rotation)
+        check(self._l.gss_cokrig_predict_knn(self._h, ptr(xdom), m, ptr(kk), int(minneighbors), r, ptr(ir), met, 0.0,
+                                             ptr(mean), ptr(var), ptr(status), ptr(idx), ptr(cnt), _space(xdom),
+                                             current_stream()))
+        if return_idx:
+            return mean, var, status, idx, cnt
         return mean, var, status
 
 
@@ -565,9 +595,11 @@ class HipEngine:
     SGS = SGSHandle
 
     @staticmethod
-    def cokrig(structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False):
-        """A fitted cokriging system (CoKrigHandle): `predict_global(xdom)`, `cv_global()`, `cv_global_folds(fold)`."""
-        return CoKrigHandle(structure, B0, B1, variant, xdata, z, var, means=means, async_fit=async_fit)
+    def cokrig(structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False, factor=True):
+        """A cokriging handle (CoKrigHandle).  `factor=True`: the fitted global system -- `predict_global(xdom)`,
+        `cv_global()`, `cv_global_folds(fold)`, `predict_knn(xdom, k)`; `factor=False`: the samples only, for
+        `predict_knn` (moving neighbourhood)."""
+        return CoKrigHandle(structure, B0, B1, variant, xdata, z, var, means=means, async_fit=async_fit, factor=factor)
 
     @staticmethod
     def cov_pairwise(vg, a, b=None):

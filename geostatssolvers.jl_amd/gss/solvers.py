@@ -440,16 +440,42 @@ class KrigingSolver(_Solver):
 # CoKrigingSolver (not in the reference: the estimation step behind fit_lmc)
 # ------------------------------------------------------------------------------------------
 class CoKrigingSolver(_Solver):
-    """Ordinary or simple cokriging of jointly modelled variables under a fitted linear model of coregionalisation,
-    global neighbourhood: `CoKrigingSolver((("cu", "zn"), dict(model=lmc, variant="ordinary")))`.
+    """Ordinary or simple cokriging of jointly modelled variables under a fitted linear model of coregionalisation:
+    `CoKrigingSolver((("cu", "zn"), dict(model=lmc, variant="ordinary")))` under the global neighbourhood, or with
+    `maxneighbors=` (an int, one count per variable, or a dict by name; `minneighbors`, `neighborhood` as in
+    KrigingSolver) from the nearest samples of every variable, each searched on its own.
 
     `model`: an LMCModel whose `names` contain the listed variables; the sub-matrices of B0 / B1 are taken in the
     listed order.  `variant`: "ordinary" (one unbiasedness constraint per variable) or "simple" with `mean` = the known
     means (a scalar or one per variable; None: 0).  A Gaussian structure gets the `nugget + 1e-6` rule of the package
     on the diagonal of B0 unless `regularize=False`.  Each variable's missing (NaN) rows are dropped separately, so
     variables measured at different locations of one table are the normal case."""
-    JPARAMS = dict(model=None, variant="ordinary", mean=None, regularize=True)
+    JPARAMS = dict(model=None, variant="ordinary", mean=None, regularize=True,
+                   # moving neighbourhood (gss.h, gss_cokrig_predict_knn): None keeps the global one; an int asks that
+                   # many neighbours of every variable, a sequence (listed order) or a dict by name one count per
+                   # variable; `neighborhood`: a MetricBall every variable's search is confined to
+                   maxneighbors=None, minneighbors=1, neighborhood=None)
     VARIANTS = {"ordinary": OK, "simple": SK}
+
+    @staticmethod
+    def _counts(names, maxneighbors):
+        """maxneighbors -> one count per listed variable (None: the global neighbourhood)."""
+        if maxneighbors is None:
+            return None
+        if isinstance(maxneighbors, dict):
+            unknown = [v for v in maxneighbors if v not in names]
+            if unknown:
+                raise ValueError(f"maxneighbors names {unknown}, which are not among the variables {names}")
+            absent = [v for v in names if v not in maxneighbors]
+            if absent:
+                raise ValueError(f"maxneighbors gives no count for {absent}")
+            return [int(maxneighbors[v]) for v in names]
+        if isinstance(maxneighbors, (int, np.integer)):
+            return [int(maxneighbors)] * len(names)
+        counts = [int(c) for c in maxneighbors]
+        if len(counts) != len(names):
+            raise ValueError(f"maxneighbors holds {len(counts)} counts for the {len(names)} variables {names}")
+        return counts
 
     def __init__(self, *pairs, **kw):
         super().__init__(*pairs, **kw)
@@ -467,6 +493,11 @@ class CoKrigingSolver(_Solver):
                 raise ValueError(f"variables {missing} are not in the coregionalisation model (it has {model.names})")
             if not 1 <= len(names) <= 8:
                 raise ValueError("between 1 and 8 variables per cokriging system (gss.h, gss_cokrig_create)")
+            counts = self._counts(names, p["maxneighbors"])
+            if counts is not None and len(names) > 4:
+                raise ValueError("the moving neighbourhood takes at most 4 variables (gss.h, gss_cokrig_predict_knn)")
+            if p["neighborhood"] is not None and not isinstance(p["neighborhood"], MetricBall):
+                raise TypeError("neighborhood must be a MetricBall")
             if p["variant"] not in self.VARIANTS:
                 raise ValueError(f"variant {p['variant']!r}: one of {tuple(self.VARIANTS)}")
             idx = [model.names.index(v) for v in names]
@@ -492,7 +523,9 @@ class CoKrigingSolver(_Solver):
             elif p["mean"] is not None:
                 raise ValueError("`mean` belongs to variant=\"simple\" (ordinary cokriging estimates the means)")
             structure = VariogramModel(model.kind, 1.0, 0.0, float(model.range), float(model.order), None, False)
-            self._spec[names] = dict(structure=structure, B0=B0, B1=B1, variant=self.VARIANTS[p["variant"]], means=means)
+            self._spec[names] = dict(structure=structure, B0=B0, B1=B1, variant=self.VARIANTS[p["variant"]], means=means,
+                                     maxneighbors=counts, minneighbors=int(p["minneighbors"]),
+                                     neighborhood=p["neighborhood"])
 
     def preprocess(self, problem: EstimationProblem):
         """Per joint group: the non-missing rows of each variable, stacked in the listed order.  Host logic only."""
@@ -518,7 +551,12 @@ class CoKrigingSolver(_Solver):
                 xs.append(coords[inds])
                 zs.append(z[inds])
                 vs.append(np.full(inds.size, a, dtype=np.int32))
-            pre[grp] = dict(x=np.ascontiguousarray(np.concatenate(xs)), z=np.concatenate(zs), var=np.concatenate(vs), **spec)
+            nmax = None
+            if spec["maxneighbors"] is not None:   # searcher_ui (ui.jl:16-23), per variable
+                nmax = [searcher_ui(PointSet(xa), ka, None, spec["neighborhood"])[1]
+                        for xa, ka in zip(xs, spec["maxneighbors"])]
+            pre[grp] = dict(x=np.ascontiguousarray(np.concatenate(xs)), z=np.concatenate(zs), var=np.concatenate(vs),
+                            nmax=nmax, **spec)
         return pre
 
     def solve(self, problem: EstimationProblem, gather: bool = True):
@@ -534,10 +572,20 @@ class CoKrigingSolver(_Solver):
         for grp, q in pre.items():
             nz = len(grp)
             if hi > lo:
+                local = q["nmax"] is not None
+                if local and sum(q["nmax"]) > 64:
+                    raise ValueError(f"maxneighbors: {sum(q['nmax'])} neighbours in total for {grp}, the moving "
+                                     f"neighbourhood of cokriging holds at most 64")
+                kw = dict(factor=False) if local else dict(async_fit=True)
                 h = self.engine.cokrig(q["structure"], q["B0"], q["B1"], q["variant"], q["x"], q["z"], q["var"],
-                                       means=q["means"], async_fit=True)
+                                       means=q["means"], **kw)
                 try:
-                    mu, var_, st = h.predict_global(xdom)
+                    if local:
+                        radius, radii = _ball(q["neighborhood"])
+                        mu, var_, st = h.predict_knn(xdom, q["nmax"], q["minneighbors"], radius, radii,
+                                                     **_rot_kw(q["neighborhood"]))
+                    else:
+                        mu, var_, st = h.predict_global(xdom)
                     mu, var_, st = _host(mu), _host(var_), _host(st)
                 finally:
                     h.close()

@@ -451,8 +451,8 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
  *              not admissible, or collocated samples under a rank-deficient b1 without nugget, surface as
  *              GSS_ERR_NOT_POSDEF from the fit, as duplicates do for one variable.  The Gaussian kind is the bare
  *              formula: a front-end that applies the `nugget + 1e-6` rule adds it to the diagonal of b0.
- *   flags      GSS_KRIG_ASYNC_FIT as gss_krig_create.  GSS_KRIG_NO_FACTOR -> GSS_ERR_INVALID: there is no
- *              moving-neighbourhood cokriging.
+ *   flags      GSS_KRIG_ASYNC_FIT as gss_krig_create.  GSS_KRIG_NO_FACTOR -> GSS_ERR_INVALID: the handle without a
+ *              factor has a creator of its own, gss_cokrig_create_local.
  *   The handle is a gss_krig_t: gss_krig_destroy, gss_krig_info (n stacked samples, nc) and gss_krig_factor_buffer
  *   apply.  gss_krig_cv_global and gss_krig_cv_global_folds work on it unchanged -- the identities do not care what
  *   the blocks of the system mean: pred_i predicts sample i of variable var_i from all other stacked samples, or from
@@ -460,7 +460,7 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
  *   the ordinary variant a fold that holds every sample of some variable leaves that variable's constraint without
  *   support: it is caught by the pivot test of the fold only.)  Every other entry point that takes a gss_krig_t
  *   (gss_krig_predict_global, _predict_global_batch, _predict_knn, _cv_knn, _set_block_support) refuses such a handle
- *   with GSS_ERR_INVALID.
+ *   with GSS_ERR_INVALID; the moving neighbourhood of cokriging is gss_cokrig_predict_knn below.
  *
  * gss_cokrig_predict_global: every target variable at every domain point in one call.  xdom m x dim point-major;
  *   mean and variance: nz columns of m (column t at + t * m); status: nz x m bytes (may be NULL).
@@ -475,6 +475,56 @@ int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, in
                           const double* z, const int32_t* var, int64_t n, int32_t flags, void* stream);
 int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, double* mean, double* variance,
                                   uint8_t* status, int32_t mem, void* stream);
+
+/* ---- moving-neighbourhood cokriging: per-variable search, one small system per domain point.
+ *
+ * gss_cokrig_create_local: a cokriging handle without a system and without a factor, for gss_cokrig_predict_knn only
+ *   (a sparse primary variable beside a dense secondary one: sample counts beyond what the O(n^3) fit of
+ *   gss_cokrig_create and its n^2 factor allow).  Arguments, checks, frame, coefficient table and row order are those
+ *   of gss_cokrig_create, with one difference: nz is 1 .. 4 here; 5 .. 8 -> GSS_ERR_UNSUPPORTED (the right-hand sides
+ *   of a point -- nz covariance columns, one data column, nz indicator columns -- ride along in one 16-column tile
+ *   whose per-wave storage holds twelve).  gss_krig_info (n stacked samples, nc) and gss_krig_destroy apply.  Every
+ *   entry point that needs a factor (gss_cokrig_predict_global, gss_krig_cv_global, gss_krig_cv_global_folds) refuses
+ *   the handle with GSS_ERR_INVALID, as it refuses a GSS_KRIG_NO_FACTOR handle.  Both creators keep a copy of the
+ *   samples grouped by variable on the device, with the map back to the caller's rows, so that each variable is
+ *   searched on its own.
+ *
+ * gss_cokrig_predict_knn: every target variable at every domain point from a per-variable moving neighbourhood; on
+ *   handles of either creator (nz <= 4; more -> GSS_ERR_UNSUPPORTED).
+ *   Neighbourhood  for every domain point the k[a] nearest samples of variable a, each variable searched separately
+ *              among its own samples (one joint search would let a dense secondary variable crowd the primary out).
+ *              k: nz counts, 1 <= k[a] <= the sample count of variable a (GSS_ERR_INVALID otherwise; a front-end
+ *              clamps); sum k[a] <= 64, more -> GSS_ERR_UNSUPPORTED.  radius / inv_radii / metric / metric_param:
+ *              the ball, the metric and the order by ascending (key, index) of gss_knn_search, the index being the
+ *              caller's row; the same ball applies to every variable.
+ *   Outputs    mean and variance: nz columns of m (column t at + t * m); status: nz x m bytes (may be NULL).  idx_out:
+ *              m x sum k, rows of the caller's arrays; variable a occupies columns off[a] .. off[a] + k[a] - 1 with
+ *              off[a] = k[0] + .. + k[a - 1], nearest first, -1 beyond the number found.  count_out: m x nz, the
+ *              number found per variable.  idx_out and count_out may be NULL.  `mem` as gss_krig_predict_knn.
+ *   Per point  with c_a neighbours found of variable a and K = sum c_a:
+ *              K < max(minneighbors, 1): every target GSS_PT_MISSING, mean = variance = NaN.
+ *              GSS_KRIG_ORDINARY: the unbiasedness constraint of a variable with c_a = 0 is dropped (it is not
+ *              reported as singular); a target t with c_t = 0 has no unbiased estimator and gets GSS_PT_MISSING and
+ *              NaN, the other targets are estimated.  GSS_KRIG_SIMPLE: every target is estimated from whatever was
+ *              found.  A non-positive pivot in the covariance block of the K neighbours, or in the constraint block
+ *              of the present variables: GSS_PT_SINGULAR and NaN for all targets.
+ *              variance_t = b0[t][t] + b1[t][t] - q_t + r_t' S^-1 r_t, clamped at 0 (q_t: the quadratic form of the
+ *              covariance block, S and r_t: the Schur complement and residual of the constraints; S is absent under
+ *              the simple variant).  The zero-key rule and the symmetrised coefficient table are those of
+ *              gss_cokrig_create: collocated samples of two variables meet through the cross nugget inside the
+ *              neighbourhood, and a domain point on a sample of variable t reproduces that datum.
+ *   Not here   block support and the drift variants (refused by the creators and by gss_krig_set_block_support);
+ *              gss_krig_predict_knn and gss_krig_cv_knn keep refusing cokriging handles.
+ *   Chunks     the domain is walked in chunks of 2^20 points (131 072 for host arrays, which travel piece by piece);
+ *              GSS_COKRIG_CHUNK_POINTS caps them as it caps gss_cokrig_predict_global's, for tests: the results are the
+ *              same.  gss_profile_read names: "knn" (the nz searches), "cokrig_local" (the systems). */
+int32_t gss_cokrig_create_local(gss_krig_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
+                                const double* b1, int32_t variant, const double* means, const double* xdata,
+                                const double* z, const int32_t* var, int64_t n, void* stream);
+int32_t gss_cokrig_predict_knn(gss_krig_t* h, const double* xdom, int64_t m, const int32_t* k, int32_t minneighbors,
+                               double radius, const double* inv_radii, int32_t metric, double metric_param,
+                               double* mean, double* variance, uint8_t* status, int32_t* idx_out, int32_t* count_out,
+                               int32_t mem, void* stream);
 
 /* ---- cross-validation: does the model predict the samples it was given?  ([DEP] GeoStatsBase `cverror` with
  *      LeaveOneOut / KFoldValidation / BlockValidation / LeaveBallOut; not in the reference tree.)  Every sample of the

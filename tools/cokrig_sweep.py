@@ -11,7 +11,13 @@
   compared against; it does not compute a cokriging estimate.  The two alternate.
 
 Method: warm-up, then `--reps` timed runs bracketed by events on the stream; the median is reported.  One JSON line on
-stdout.  python tools/cokrig_sweep.py [--reps 3] [--points 1000000]"""
+stdout.  python tools/cokrig_sweep.py [--reps 3] [--points 1000000]
+
+--local: the moving neighbourhood on the same inputs, gss_cokrig_predict_knn with 16 neighbours per variable, split into
+  the per-variable searches ("knn") and the system kernel ("cokrig_local"); beside it, in the same session, the global
+  call, and single-variable ordinary gss_krig_predict_knn with k = 32 over the same 5 000 locations and points, split
+  into its one search ("knn") and K5 ("krig_local").  The three alternate.  Written to
+  profiles/cokrig_local_sweep.json as well."""
 import argparse
 import json
 import os
@@ -59,6 +65,8 @@ def main():
     ap.add_argument("--points", type=int, default=1_000_000)
     ap.add_argument("--primary", type=int, default=1000)
     ap.add_argument("--secondary", type=int, default=4000)
+    ap.add_argument("--local", action="store_true", help="the moving neighbourhood beside the global call and K5")
+    ap.add_argument("--neighbors", type=int, default=16, help="--local: neighbours per variable")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     _lib.lib()
@@ -72,6 +80,8 @@ def main():
     xdom = torch.as_tensor(rng.uniform(0.0, 1000.0, (args.points, 3)), device="cuda")
     g = gss.SphericalVariogram(range=120.0)
 
+    if args.local:
+        return local(args, g, B0, B1, x, z, var, xdom)
     co = HipEngine.cokrig(g, B0, B1, OK, x, z, var)
     single = KrigHandle(gss.SphericalVariogram(range=120.0, sill=1.0, nugget=0.1), OK, x, z)
 
@@ -98,6 +108,43 @@ def main():
                       "rhs_separate_over_cokrig": round(ss["krig_rhs"][0] / cs["cokrig_rhs"][0], 3),
                       "total_separate_over_cokrig": round(s / c, 3),
                       "points_per_s": round(args.points / (c * 1e-3), 1)}), flush=True)
+
+
+def local(args, g, B0, B1, x, z, var, xdom):
+    k = args.neighbors
+    co = HipEngine.cokrig(g, B0, B1, OK, x, z, var)                      # with the factor: serves both calls
+    single = KrigHandle(gss.SphericalVariogram(range=120.0, sill=1.0, nugget=0.1), OK, x, z, factor=False)
+
+    def co_local():
+        co.predict_knn(xdom, k)
+
+    def co_global():
+        co.predict_global(xdom)
+
+    def k5():
+        single.predict_knn(xdom, 2 * k)
+    tl, tg, tk = [], [], []
+    for _ in range(2):                                      # alternating blocks
+        tl.append(timed(co_local, args.reps))
+        tg.append(timed(co_global, args.reps))
+        tk.append(timed(k5, args.reps))
+    l, gl, kk = statistics.median(tl), statistics.median(tg), statistics.median(tk)
+    ls = split(co_local, ("knn", "cokrig_local"))
+    ks = split(k5, ("knn", "krig_local"))
+    co.close()
+    single.close()
+    res = {"what": "cokrig_predict_knn", "primary": args.primary, "secondary": args.secondary, "nz": 2,
+           "points": args.points, "neighbors_per_variable": k, "local_ms": round(l, 3),
+           "local_search_ms": ls["knn"][0], "local_kernel_ms": ls["cokrig_local"][0], "global_ms": round(gl, 2),
+           "global_over_local": round(gl / l, 1), "krig_knn_k": 2 * k, "krig_knn_ms": round(kk, 3),
+           "krig_knn_search_ms": ks["knn"][0], "krig_knn_kernel_ms": ks["krig_local"][0],
+           "kernel_cokrig_over_krig": round(ls["cokrig_local"][0] / ks["krig_local"][0], 3),
+           "search_cokrig_over_krig": round(ls["knn"][0] / ks["knn"][0], 3),
+           "points_per_s": round(args.points / (l * 1e-3), 1)}
+    line = json.dumps(res)
+    print(line, flush=True)
+    with open(os.path.join(ROOT, "profiles", "cokrig_local_sweep.json"), "w") as f:
+        f.write(line + "\n")
 
 
 if __name__ == "__main__":
