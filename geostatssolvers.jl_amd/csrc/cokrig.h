@@ -1,6 +1,6 @@
-// Shared by the cokriging paths (krig.hip: the global neighbourhood; cokrig_local*.hip: the moving neighbourhood): the
-// layout of the coefficient table, the correlation with its zero-key flag, and the interface of the moving-neighbourhood
-// driver.
+// Shared by the cokriging paths (krig.hip: the global neighbourhood; cokrig_local*.hip: the moving neighbourhood;
+// cokrig_cv.hip: its cross-validation): the layout of the coefficient table, the correlation with its zero-key flag, and
+// the interfaces of the moving-neighbourhood drivers.
 #pragma once
 
 #include "gss_internal.h"
@@ -45,5 +45,13 @@ struct CoGrouped {
 int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped& g, Searcher* sr, const int* k,
                          int minneighbors, const double* x0, const double* x0_raw, int64_t m, double* mean, double* var,
                          uint8_t* status, int64_t ldo, int* idx_out, int* count_out, hipStream_t s, HostPipe* pipe);
+
+// Cross-validation on the same searchers and grouped samples (cokrig_cv.hip; gss.h, gss_cokrig_cv_knn): every grouped
+// sample is predicted as its own variable from the k[a] nearest samples of every variable a outside its fold and, for
+// ex >= 0, beyond the exclusion key ex.  fold: one id per caller's row (device) or NULL for one fold per sample.  pred,
+// var, status (may be NULL), idx_out (n x sum k) and count_out (n x nz; both may be NULL) are indexed by caller's rows.
+int32_t cokrig_cv_dev(const VgDev& vg, int variant, int dim, const CoGrouped& g, Searcher* sr, const int* k,
+                      int minneighbors, const int* fold, double ex, double* pred, double* var, uint8_t* status,
+                      int* idx_out, int* count_out, hipStream_t s);
 
 }  // namespace gss

@@ -1,7 +1,8 @@
 // Moving-neighbourhood cokriging (gss.h, gss_cokrig_predict_knn): one search per variable over that variable's samples
 // (knn.hip, the unmasked query), then one system per domain point on the lists of all variables
-// (cokrig_local_kernel.h).  This unit holds the driver, the general instantiations (any model, 1-D) and the dispatch;
-// the compile-time kinds of 2-D and 3-D have units of their own (cokrig_local_2d.hip, cokrig_local_3d.hip).
+// (cokrig_local_kernel.h).  This unit holds the driver, the general instantiations (any model, 1-D) and what the
+// cross-validation driver (cokrig_cv.hip) shares with it; the compile-time kinds of 2-D and 3-D have units of their own
+// (cokrig_local_2d.hip, cokrig_local_3d.hip).
 #include "cokrig_local_kernel.h"
 
 #include <cstdlib>
@@ -10,11 +11,12 @@
 namespace gss {
 
 // idx_out (m x ksum, the caller's rows, -1 beyond a variable's count) and count_out (m x nz) from the lists of the
-// searches; one thread per entry of idx_out, the first nz threads of a point write its counts
+// searches; one thread per entry of idx_out, the first nz threads of a point write its counts.  qrow: the output row of
+// every point (NULL: point p at row p)
 __global__ __launch_bounds__(256) void cokrig_lists_kernel(CoLocalSpec sp, const int* __restrict__ idx,
                                                            const int* __restrict__ cnt, const int* __restrict__ row,
-                                                           int64_t m, int* __restrict__ idx_out,
-                                                           int* __restrict__ count_out) {
+                                                           const int* __restrict__ qrow, int64_t m,
+                                                           int* __restrict__ idx_out, int* __restrict__ count_out) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= m * sp.ksum) return;
   const int64_t p = e / sp.ksum;
@@ -32,15 +34,23 @@ __global__ __launch_bounds__(256) void cokrig_lists_kernel(CoLocalSpec sp, const
   const int jj = col - ko;
   int c = cnt[(int64_t)a * m + p];
   c = c < 0 ? 0 : (c > kk ? kk : c);
-  if (idx_out) idx_out[e] = jj < c ? row[go + idx[m * ko + p * kk + jj]] : -1;
-  if (count_out && jj == 0) count_out[p * sp.nz + a] = c;
+  const int64_t po = qrow ? qrow[p] : p;
+  if (idx_out) idx_out[po * sp.ksum + col] = jj < c ? row[go + idx[m * ko + p * kk + jj]] : -1;
+  if (count_out && jj == 0) count_out[po * sp.nz + a] = c;
 }
 
-int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped& g, Searcher* sr, const int* k,
-                         int minneighbors, const double* x0, const double* x0_raw, int64_t m, double* mean, double* var,
-                         uint8_t* status, int64_t ldo, int* idx_out, int* count_out, hipStream_t s, HostPipe* pipe) {
+int32_t cokrig_lists_dev(const CoLocalSpec& sp, const int* idx, const int* cnt, const int* row, const int* qrow,
+                         int64_t m, int* idx_out, int* count_out, hipStream_t s) {
+  const int64_t ne = m * sp.ksum;
+  hipLaunchKernelGGL(cokrig_lists_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, sp, idx, cnt, row, qrow, m,
+                     idx_out, count_out);
+  GSS_HIP(hipGetLastError());
+  return GSS_OK;
+}
+
+int32_t cokrig_spec(const CoGrouped& g, int variant, const int* k, int minneighbors, CoLocalSpec* out) {
   const int nz = g.nz;
-  GSS_REQUIRE(nz >= 1 && nz <= COL_MAXZ, "cokrig_local_dev: %d variables outside 1 .. %d", nz, COL_MAXZ);
+  GSS_REQUIRE(nz >= 1 && nz <= COL_MAXZ, "moving-neighbourhood cokriging: %d variables outside 1 .. %d", nz, COL_MAXZ);
   CoLocalSpec sp;
   std::memset(&sp, 0, sizeof(sp));
   sp.nz = nz;
@@ -52,8 +62,18 @@ int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped&
     sp.off[a] = (int)g.off[a];
     sp.ksum += k[a];
   }
-  GSS_REQUIRE(sp.ksum >= 1 && sp.ksum <= LMAX_K, "cokrig_local_dev: %d neighbours in total outside 1 .. %d", sp.ksum,
-              LMAX_K);
+  GSS_REQUIRE(sp.ksum >= 1 && sp.ksum <= LMAX_K, "moving-neighbourhood cokriging: %d neighbours in total outside 1 .. %d",
+              sp.ksum, LMAX_K);
+  *out = sp;
+  return GSS_OK;
+}
+
+int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped& g, Searcher* sr, const int* k,
+                         int minneighbors, const double* x0, const double* x0_raw, int64_t m, double* mean, double* var,
+                         uint8_t* status, int64_t ldo, int* idx_out, int* count_out, hipStream_t s, HostPipe* pipe) {
+  const int nz = g.nz;
+  CoLocalSpec sp;
+  GSS_TRY(cokrig_spec(g, variant, k, minneighbors, &sp));
 
   const bool piped = pipe && pipe->on;
   int64_t chunk = piped ? HostPipe::PIECE : (1 << 20);
@@ -94,19 +114,11 @@ int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped&
       a.status = status ? status + off : nullptr;
       a.ldo = ldo;
       a.s = s;
-      const bool fixed = kind == GSS_VG_GAUSSIAN || kind == GSS_VG_EXPONENTIAL || kind == GSS_VG_SPHERICAL ||
-                         kind == VG_MATERN12 || kind == VG_MATERN32 || kind == VG_MATERN52;
-      int32_t rc;
-      if (dim == 3) rc = fixed ? cokrig_local_launch_3d(kind, a) : cokrig_local_launch<3, -1>(a);
-      else if (dim == 2) rc = fixed ? cokrig_local_launch_2d(kind, a) : cokrig_local_launch<2, -1>(a);
-      else rc = cokrig_local_launch<1, -1>(a);
-      GSS_TRY(rc);
+      GSS_TRY(cokrig_local_dispatch<false>(dim, kind, a));
     }
     if (idx_out || count_out) {
-      const int64_t ne = mv * sp.ksum;
-      hipLaunchKernelGGL(cokrig_lists_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, sp, idx, cnt, g.row, mv,
-                         idx_out ? idx_out + off * sp.ksum : nullptr, count_out ? count_out + off * nz : nullptr);
-      GSS_HIP(hipGetLastError());
+      GSS_TRY(cokrig_lists_dev(sp, idx, cnt, g.row, nullptr, mv, idx_out ? idx_out + off * sp.ksum : nullptr,
+                               count_out ? count_out + off * nz : nullptr, s));
     }
     if (piped) GSS_TRY(pipe->deliver(off, mv, s));
   }

@@ -72,14 +72,20 @@ __device__ __forceinline__ double co_entry(const double* tab, int vi, int vj, do
   return tab[zero ? COL_MAXZ * COL_MAXZ + e : e] * (zero ? 1.0 : rho);
 }
 
+// The per-point system of both kernels of this header: cokrig_local_kernel (CV = false: a domain point, every variable
+// a target) and cokrig_cv_kernel (CV = true: a sample of the handle as the query, its own variable the one target).
+// Neighbour gather, tile assembly, block steps and the Gram matrix are the same code; CV chooses the columns
+//   [c0_t | z - means[v] | 1[v = 0] .. 1[v = nz-1]]   (t = the query's variable, wave-uniform; at most nz + 2 columns)
+// and the finish for that one target, stored at the caller's row of the query.
 // NT = tiles of 16 neighbours the instantiation holds (1, 2 or 4: sum k <= 16 NT), as in K5.
 // idx: the lists of the searches, variable a at idx + mv * koff[a], row p of it k[a] wide; cnt[a * mv + p] its length.
-template <int DIM, int KIND, int NT>
-__global__ __launch_bounds__(64 * COL_WAVES) __attribute__((amdgpu_waves_per_eu(NT == 1 ? 4 : 3, NT == 1 ? 5 : (NT == 2 ? 4 : 3))))
-void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg, const double* __restrict__ zres,
-                         const double* __restrict__ cotab, const double* __restrict__ x0, int64_t m,
-                         const int* __restrict__ idx, const int* __restrict__ cnt, double* __restrict__ mean_out,
-                         double* __restrict__ var_out, uint8_t* __restrict__ status_out, int64_t ldo) {
+// x0: the m centres.  CV: they are grouped samples q0 .. q0 + m - 1 (x0 = xg + q0 DIM), qrow = row + q0 their rows in
+// the caller's arrays, and mean_out / var_out / status_out are indexed by those rows (ldo is not read).
+template <int DIM, int KIND, int NT, bool CV>
+__device__ __forceinline__ void cokrig_point(const VgDev& vg, const CoLocalSpec& sp, const double* xg, const double* zres,
+                                             const double* cotab, const double* x0, int64_t m, const int* idx,
+                                             const int* cnt, double* mean_out, double* var_out, uint8_t* status_out,
+                                             int64_t ldo, int64_t q0, const int* qrow) {
   __shared__ double nxs_[COL_WAVES][LMAX_K][3];   // neighbour coordinates
   __shared__ int nvs_[COL_WAVES][LMAX_K];         // and variable ids
   __shared__ double tab[COL_TAB];
@@ -104,6 +110,13 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
   const int64_t p = inrange ? pw : m - 1;
   const double NaN = __longlong_as_double(0x7ff8000000000000LL);
   const int nz = sp.nz;
+  int tq = 0;   // CV: the variable of the query, from its place among the grouped samples (wave-uniform)
+  if constexpr (CV) {
+#pragma unroll
+    for (int a = 1; a < COL_MAXZ; ++a)
+      if (a < nz && q0 + p >= sp.off[a]) tq = a;
+    tq = __builtin_amdgcn_readfirstlane(tq);
+  }
 
   // the tables: 36 doubles out of the handle's table (stride CO_MAXZ), once per workgroup
   if (threadIdx.x < COL_TAB) {
@@ -152,13 +165,16 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
     int jj = lane, kk = sp.k[0], ko = sp.koff[0], go = sp.off[0];
 #pragma unroll
     for (int a = 1; a < COL_MAXZ; ++a) {
-      if (lane >= base[a]) {
-        myv = a;
-        jj = lane - base[a];
-        kk = sp.k[a];
-        ko = sp.koff[a];
-        go = sp.off[a];
-      }
+      // (the fields are pinned as wave-uniform values before the choice: choosing between their addresses instead, as
+      //  the optimiser otherwise does, would force a copy of sp into private memory)
+      const int ka = __builtin_amdgcn_readfirstlane(sp.k[a]), koa = __builtin_amdgcn_readfirstlane(sp.koff[a]),
+                goa = __builtin_amdgcn_readfirstlane(sp.off[a]);
+      const bool in = lane >= base[a];
+      myv = in ? a : myv;
+      jj = in ? lane - base[a] : jj;
+      kk = in ? ka : kk;
+      ko = in ? koa : ko;
+      go = in ? goa : go;
     }
     const int loc = act ? idx[m * ko + p * kk + jj] : 0;
     const int64_t gj = act ? (int64_t)go + loc : 0;
@@ -176,14 +192,24 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
   __syncthreads();   // tab, and every wave's coordinates are in place
   {
     // the columns, lane = neighbour
+    if constexpr (CV) {
+      rhs_col(0)[lane] = act ? co_entry(tab, myv, tq, myrho, myzero) : 0.0;
+      rhs_col(1)[lane] = act ? myz : 0.0;
+      if (sp.ordinary) {
 #pragma unroll
-    for (int t = 0; t < COL_MAXZ; ++t)
-      if (t < nz) rhs_col(t)[lane] = act ? co_entry(tab, myv, t, myrho, myzero) : 0.0;
-    rhs_col(nz)[lane] = act ? myz : 0.0;
-    if (sp.ordinary) {
+        for (int t = 0; t < COL_MAXZ; ++t)
+          if (t < nz) rhs_col(2 + t)[lane] = (act && myv == t) ? 1.0 : 0.0;
+      }
+    } else {
 #pragma unroll
       for (int t = 0; t < COL_MAXZ; ++t)
-        if (t < nz) rhs_col(nz + 1 + t)[lane] = (act && myv == t) ? 1.0 : 0.0;
+        if (t < nz) rhs_col(t)[lane] = act ? co_entry(tab, myv, t, myrho, myzero) : 0.0;
+      rhs_col(nz)[lane] = act ? myz : 0.0;
+      if (sp.ordinary) {
+#pragma unroll
+        for (int t = 0; t < COL_MAXZ; ++t)
+          if (t < nz) rhs_col(nz + 1 + t)[lane] = (act && myv == t) ? 1.0 : 0.0;
+      }
     }
   }
   tile_sync<true>();   // the columns are read back by other lanes of this wave only
@@ -274,7 +300,7 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
     }
   }
   // right-hand sides into tile layout; columns beyond the ones in use and rows beyond the neighbour count are zero
-  const int ncols = nz + 1 + (sp.ordinary ? nz : 0);
+  const int ncols = (CV ? 2 : nz + 1) + (sp.ordinary ? nz : 0);
   d4_t B[4];
   {
     const double* colc = rhs_col(c < LMAX_RHS ? c : 0);
@@ -331,13 +357,15 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
   for (int r = 0; r < 4; ++r) G[g + 4 * r][c] = Gt[r];
   __syncthreads();
 
-  // ---- finish: lane t = target t (the lanes beyond shadow target 0); S is at most 4 x 4 and every lane factors it
-  const int t = lane < nz ? lane : 0;
+  // ---- finish: lane t = target t (the lanes beyond shadow target 0), CV: every lane the one target; S is at most
+  // 4 x 4 and every lane factors it.  Columns of G: the target's covariances, the data, the first indicator.
+  const int t = CV ? tq : (lane < nz ? lane : 0);
+  const int ccol = CV ? 0 : t, zcol = CV ? 1 : nz, ind0 = zcol + 1;
   int ct = ca[0];
 #pragma unroll
   for (int a = 1; a < COL_MAXZ; ++a)
     if (t == a) ct = ca[a];
-  const double qf = G[t][t], af = G[nz][t];
+  const double qf = G[ccol][ccol], af = G[zcol][ccol];
   double rsr = 0.0, tsr = 0.0;
   bool okS = true;
   if (sp.ordinary) {
@@ -346,10 +374,10 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
     for (int j = 0; j < COL_MAXZ; ++j) {
       if (j < nz) {
         const bool here = ca[j] > 0;   // wave-uniform
-        const int fj = nz + 1 + j;
+        const int fj = ind0 + j;
         double d = here ? G[fj][fj] : 1.0;
-        double ru = here ? G[fj][t] - (j == t ? 1.0 : 0.0) : 0.0;
-        double rw = here ? G[fj][nz] : 0.0;
+        double ru = here ? G[fj][ccol] - (j == t ? 1.0 : 0.0) : 0.0;
+        double rw = here ? G[fj][zcol] : 0.0;
 #pragma unroll
         for (int cc = 0; cc < j; ++cc) {
           d = fma(-L[j][cc], L[j][cc], d);
@@ -369,7 +397,7 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
 #pragma unroll
         for (int i = j + 1; i < COL_MAXZ; ++i) {
           if (i < nz) {
-            double s = (here && ca[i] > 0) ? G[nz + 1 + i][fj] : 0.0;
+            double s = (here && ca[i] > 0) ? G[ind0 + i][fj] : 0.0;
 #pragma unroll
             for (int cc = 0; cc < j; ++cc) s = fma(-L[i][cc], L[j][cc], s);
             L[i][j] = s * inv;
@@ -378,16 +406,16 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
       }
     }
   }
-  if (inrange && lane < nz) {
-    const int64_t o = (int64_t)lane * ldo + p;
+  if (inrange && (CV ? lane == 0 : lane < nz)) {
+    const int64_t o = CV ? (int64_t)qrow[p] : (int64_t)lane * ldo + p;
     uint8_t st = GSS_PT_OK;
     if (missing) st = GSS_PT_MISSING;
     else if (bad || !okS) st = GSS_PT_SINGULAR;
     else if (sp.ordinary && ct == 0) st = GSS_PT_MISSING;   // no neighbour of the target's own variable
     double mu = NaN, vv = NaN;
     if (st == GSS_PT_OK) {
-      mu = tab[2 * COL_MAXZ * COL_MAXZ + lane] + af - tsr;
-      vv = tab[COL_MAXZ * COL_MAXZ + lane * (COL_MAXZ + 1)] - qf + rsr;
+      mu = tab[2 * COL_MAXZ * COL_MAXZ + t] + af - tsr;
+      vv = tab[COL_MAXZ * COL_MAXZ + t * (COL_MAXZ + 1)] - qf + rsr;
       vv = vv > 0.0 ? vv : 0.0;
     }
     mean_out[o] = mu;
@@ -396,6 +424,34 @@ void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg
   }
 }
 
+#define GSS_COL_KERNEL_ATTRS(NT)        \
+  __launch_bounds__(64 * COL_WAVES)     \
+      __attribute__((amdgpu_waves_per_eu(NT == 1 ? 4 : 3, NT == 1 ? 5 : (NT == 2 ? 4 : 3))))
+
+template <int DIM, int KIND, int NT>
+__global__ GSS_COL_KERNEL_ATTRS(NT)
+void cokrig_local_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg, const double* __restrict__ zres,
+                         const double* __restrict__ cotab, const double* __restrict__ x0, int64_t m,
+                         const int* __restrict__ idx, const int* __restrict__ cnt, double* __restrict__ mean_out,
+                         double* __restrict__ var_out, uint8_t* __restrict__ status_out, int64_t ldo) {
+  cokrig_point<DIM, KIND, NT, false>(vg, sp, xg, zres, cotab, x0, m, idx, cnt, mean_out, var_out, status_out, ldo, 0,
+                                     nullptr);
+}
+
+// The one-target form (gss.h, gss_cokrig_cv_knn): the m queries are grouped samples q0 .. q0 + m - 1 of the handle; pred,
+// var and status are indexed by the caller's row of the query (row: the map of the grouped copy).
+template <int DIM, int KIND, int NT>
+__global__ GSS_COL_KERNEL_ATTRS(NT)
+void cokrig_cv_kernel(VgDev vg, CoLocalSpec sp, const double* __restrict__ xg, const double* __restrict__ zres,
+                      const double* __restrict__ cotab, const int* __restrict__ row, int64_t q0, int64_t m,
+                      const int* __restrict__ idx, const int* __restrict__ cnt, double* __restrict__ pred,
+                      double* __restrict__ var_out, uint8_t* __restrict__ status_out) {
+  cokrig_point<DIM, KIND, NT, true>(vg, sp, xg, zres, cotab, xg + q0 * DIM, m, idx, cnt, pred, var_out, status_out, 0, q0,
+                                    row + q0);
+}
+
+// One launch of either kernel.  CV = false: x0 are the m domain points, mean / var / status have nz columns ldo apart.
+// CV = true: the queries are grouped samples q0 .. q0 + m - 1, row is the map to the caller's rows (x0, ldo not read).
 struct CoLocalLaunch {
   const VgDev* vg;
   CoLocalSpec sp;
@@ -406,14 +462,22 @@ struct CoLocalLaunch {
   uint8_t* status;
   int64_t ldo;
   hipStream_t s;
+  const int* row = nullptr;
+  int64_t q0 = 0;
 };
 
-template <int DIM, int KIND>
+template <int DIM, int KIND, bool CV = false>
 int32_t cokrig_local_launch(const CoLocalLaunch& a) {
   const dim3 grid((unsigned)((a.m + COL_WAVES - 1) / COL_WAVES)), block(64 * COL_WAVES);
-#define GSS_COL_LAUNCH(NTV)                                                                                          \
-  hipLaunchKernelGGL((cokrig_local_kernel<DIM, KIND, NTV>), grid, block, 0, a.s, *a.vg, a.sp, a.xg, a.zres, a.cotab, \
-                     a.x0, a.m, a.idx, a.cnt, a.mean, a.var, a.status, a.ldo)
+#define GSS_COL_LAUNCH(NTV)                                                                                            \
+  do {                                                                                                                 \
+    if constexpr (CV)                                                                                                  \
+      hipLaunchKernelGGL((cokrig_cv_kernel<DIM, KIND, NTV>), grid, block, 0, a.s, *a.vg, a.sp, a.xg, a.zres, a.cotab,  \
+                         a.row, a.q0, a.m, a.idx, a.cnt, a.mean, a.var, a.status);                                     \
+    else                                                                                                               \
+      hipLaunchKernelGGL((cokrig_local_kernel<DIM, KIND, NTV>), grid, block, 0, a.s, *a.vg, a.sp, a.xg, a.zres,        \
+                         a.cotab, a.x0, a.m, a.idx, a.cnt, a.mean, a.var, a.status, a.ldo);                            \
+  } while (0)
   if (a.sp.ksum <= 16) GSS_COL_LAUNCH(1);
   else if (a.sp.ksum <= 32) GSS_COL_LAUNCH(2);
   else GSS_COL_LAUNCH(4);
@@ -425,17 +489,44 @@ int32_t cokrig_local_launch(const CoLocalLaunch& a) {
 // the compile-time kinds of 2-D and 3-D have units of their own (cokrig_local_2d.hip, cokrig_local_3d.hip)
 int32_t cokrig_local_launch_2d(int kind, const CoLocalLaunch& a);
 int32_t cokrig_local_launch_3d(int kind, const CoLocalLaunch& a);
+int32_t cokrig_cv_launch_2d(int kind, const CoLocalLaunch& a);
+int32_t cokrig_cv_launch_3d(int kind, const CoLocalLaunch& a);
 
-template <int DIM>
+template <int DIM, bool CV = false>
 int32_t cokrig_local_launch_kinds(int kind, const CoLocalLaunch& a) {
   switch (kind) {
-    case GSS_VG_GAUSSIAN: return cokrig_local_launch<DIM, GSS_VG_GAUSSIAN>(a);
-    case GSS_VG_EXPONENTIAL: return cokrig_local_launch<DIM, GSS_VG_EXPONENTIAL>(a);
-    case GSS_VG_SPHERICAL: return cokrig_local_launch<DIM, GSS_VG_SPHERICAL>(a);
-    case VG_MATERN12: return cokrig_local_launch<DIM, VG_MATERN12>(a);
-    case VG_MATERN32: return cokrig_local_launch<DIM, VG_MATERN32>(a);
-    default: return cokrig_local_launch<DIM, VG_MATERN52>(a);
+    case GSS_VG_GAUSSIAN: return cokrig_local_launch<DIM, GSS_VG_GAUSSIAN, CV>(a);
+    case GSS_VG_EXPONENTIAL: return cokrig_local_launch<DIM, GSS_VG_EXPONENTIAL, CV>(a);
+    case GSS_VG_SPHERICAL: return cokrig_local_launch<DIM, GSS_VG_SPHERICAL, CV>(a);
+    case VG_MATERN12: return cokrig_local_launch<DIM, VG_MATERN12, CV>(a);
+    case VG_MATERN32: return cokrig_local_launch<DIM, VG_MATERN32, CV>(a);
+    default: return cokrig_local_launch<DIM, VG_MATERN52, CV>(a);
   }
 }
+
+// the kernel of one chunk by dimension and model: the fixed kinds of 2-D and 3-D, else the general one (kind = -1 for a
+// nested model); instantiated by the unit of each driver
+template <bool CV>
+int32_t cokrig_local_dispatch(int dim, int kind, const CoLocalLaunch& a) {
+  const bool fixed = kind == GSS_VG_GAUSSIAN || kind == GSS_VG_EXPONENTIAL || kind == GSS_VG_SPHERICAL ||
+                     kind == VG_MATERN12 || kind == VG_MATERN32 || kind == VG_MATERN52;
+  if (dim == 3) {
+    if (!fixed) return cokrig_local_launch<3, -1, CV>(a);
+    return CV ? cokrig_cv_launch_3d(kind, a) : cokrig_local_launch_3d(kind, a);
+  }
+  if (dim == 2) {
+    if (!fixed) return cokrig_local_launch<2, -1, CV>(a);
+    return CV ? cokrig_cv_launch_2d(kind, a) : cokrig_local_launch_2d(kind, a);
+  }
+  return cokrig_local_launch<1, -1, CV>(a);
+}
+
+// the launch parameters of a call from its arguments (cokrig_local.hip); refuses nz > COL_MAXZ and sum k > LMAX_K
+int32_t cokrig_spec(const CoGrouped& g, int variant, const int* k, int minneighbors, CoLocalSpec* out);
+
+// idx_out (m x ksum, the caller's rows, -1 beyond a variable's count) and count_out (m x nz) from the lists of the
+// searches (cokrig_local.hip); qrow: the output row of every point of the chunk (NULL: point p at row p)
+int32_t cokrig_lists_dev(const CoLocalSpec& sp, const int* idx, const int* cnt, const int* row, const int* qrow,
+                         int64_t m, int* idx_out, int* count_out, hipStream_t s);
 
 }  // namespace gss

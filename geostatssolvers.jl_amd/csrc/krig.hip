@@ -1139,7 +1139,8 @@ static int32_t krig_quadform_attrs() {
 // entry points that know one variable only
 static int32_t krig_refuse_cokrig(const gss_krig* h, const char* who) {
   GSS_REQUIRE(h->nz == 0, "%s: the handle is a cokriging system over %d variables; its estimates come from "
-              "gss_cokrig_predict_global (cross-validation: gss_krig_cv_global, gss_krig_cv_global_folds)", who, h->nz);
+              "gss_cokrig_predict_global and gss_cokrig_predict_knn (cross-validation: gss_krig_cv_global, "
+              "gss_krig_cv_global_folds, gss_cokrig_cv_knn)", who, h->nz);
   return GSS_OK;
 }
 
@@ -1402,6 +1403,17 @@ static int64_t cokrig_chunk_points(int64_t N1pad, int nz, int64_t m) {
     if (cap > 0 && cap < mc) mc = cap;
   }
   return mc;
+}
+
+// the handle's samples grouped by variable, as the moving-neighbourhood drivers take them (cokrig.h)
+static void cokrig_grouped(const gss_krig* h, CoGrouped* g) {
+  g->x = h->co_xg.as<double>();
+  g->x_raw = h->co_xg_raw.as<double>();
+  g->zres = h->co_zres.as<double>();
+  g->row = h->co_row.as<int>();
+  g->tab = h->cotab.as<double>();
+  g->nz = h->nz;
+  for (int a = 0; a <= CO_MAXZ; ++a) g->off[a] = h->co_off[a];
 }
 
 // The body of both creators.  factor: fit the global system (gss_cokrig_create) or keep the samples only
@@ -1720,13 +1732,7 @@ int32_t gss_cokrig_predict_knn(gss_krig_t* h, const double* xdom, int64_t m, con
     pipe.frame = &h->fr;
   }
   CoGrouped g;
-  g.x = h->co_xg.as<double>();
-  g.x_raw = h->co_xg_raw.as<double>();
-  g.zres = h->co_zres.as<double>();
-  g.row = h->co_row.as<int>();
-  g.tab = h->cotab.as<double>();
-  g.nz = nz;
-  for (int a = 0; a <= CO_MAXZ; ++a) g.off[a] = h->co_off[a];
+  cokrig_grouped(h, &g);
   for (int a = 0; a < nz; ++a)
     GSS_TRY(sr[a].samples(g.x + g.off[a] * dim, g.x_raw ? g.x_raw + g.off[a] * dim : nullptr, g.off[a + 1] - g.off[a], s));
   const double* x0_raw = sx.as<double>();   // as staged; the covariance-frame copy follows
@@ -2037,6 +2043,80 @@ int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radiu
   GSS_TRY(sstat.back(status, (size_t)n, mem, s));
   GSS_TRY(sidx.back(idx_out, sizeof(int32_t) * (size_t)(n * k), mem, s));
   GSS_TRY(scnt.back(count_out, sizeof(int32_t) * (size_t)n, mem, s));
+  return GSS_OK;
+}
+
+int32_t gss_cokrig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radius, const int32_t* k,
+                          int32_t minneighbors, double radius, const double* inv_radii, int32_t metric,
+                          double metric_param, double* pred, double* var, uint8_t* status, int32_t* idx_out,
+                          int32_t* count_out, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(h->nz > 0, "gss_cokrig_cv_knn: the handle is not a cokriging system (gss_cokrig_create and "
+              "gss_cokrig_create_local make one; one variable: gss_krig_cv_knn)");
+  const int nz = h->nz, dim = h->dim;
+  if (nz > COL_MAXZ) {
+    set_error("gss_cokrig_cv_knn: the handle holds %d variables, the moving neighbourhood takes at most %d", nz,
+              COL_MAXZ);
+    return GSS_ERR_UNSUPPORTED;
+  }
+  if (metric == GSS_METRIC_HAVERSINE) {
+    set_error("gss_cokrig_cv_knn: cross-validation under the haversine distance is not available: the fold search runs "
+              "on the k-d index, which that key has no box bounds for (DESIGN.md section 7)");
+    return GSS_ERR_UNSUPPORTED;
+  }
+  GSS_REQUIRE(k != nullptr, "gss_cokrig_cv_knn: k is NULL (one neighbour count per variable)");
+  int ksum = 0;
+  for (int a = 0; a < nz; ++a) {
+    const int64_t na = h->co_off[a + 1] - h->co_off[a];
+    GSS_REQUIRE(k[a] >= 1 && k[a] <= na, "gss_cokrig_cv_knn: k[%d] = %d outside 1 .. %lld, the sample count of "
+                "variable %d (a front-end clamps it)", a, k[a], (long long)na, a);
+    ksum += k[a];
+  }
+  if (ksum > 64) {
+    set_error("gss_cokrig_cv_knn: %d neighbours in total, the tile kernel holds at most 64", ksum);
+    return GSS_ERR_UNSUPPORTED;
+  }
+  GSS_REQUIRE(!(exclude_radius != exclude_radius), "gss_cokrig_cv_knn: exclude_radius is NaN");
+  GSS_REQUIRE(pred && var, "gss_cokrig_cv_knn: NULL array");
+  Searcher sr[COL_MAXZ];   // one per variable, over that variable's samples; all in the same frame
+  for (int a = 0; a < nz; ++a) GSS_TRY(sr[a].init(metric, metric_param, radius, inv_radii, dim, &h->fr));
+  hipStream_t s = to_stream(stream);
+  const int64_t n = h->n;
+  Staged sf, smean, svar, sstat, sidx, scnt;
+  if (fold) {
+    std::vector<int32_t> fh;
+    const int32_t* fhost = fold;
+    if (mem != GSS_MEM_HOST) {   // the ids are checked before any kernel compares them
+      fh.resize((size_t)n);
+      GSS_HIP(hipMemcpyAsync(fh.data(), fold, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+      GSS_HIP(hipStreamSynchronize(s));
+      fhost = fh.data();
+    }
+    for (int64_t i = 0; i < n; ++i)
+      GSS_REQUIRE(fhost[i] >= 0, "gss_cokrig_cv_knn: fold id %d of sample %lld is negative", fhost[i], (long long)i);
+    GSS_TRY(sf.in(fold, sizeof(int32_t) * (size_t)n, mem, s));
+  }
+  GSS_TRY(smean.out(pred, sizeof(double) * (size_t)n, mem));
+  GSS_TRY(svar.out(var, sizeof(double) * (size_t)n, mem));
+  GSS_TRY(sstat.out(status, (size_t)n, mem));
+  GSS_TRY(sidx.out(idx_out, sizeof(int32_t) * (size_t)(n * ksum), mem));
+  GSS_TRY(scnt.out(count_out, sizeof(int32_t) * (size_t)(n * nz), mem));
+  CoGrouped g;
+  cokrig_grouped(h, &g);
+  for (int a = 0; a < nz; ++a)
+    GSS_TRY(sr[a].samples(g.x + g.off[a] * dim, g.x_raw ? g.x_raw + g.off[a] * dim : nullptr, g.off[a + 1] - g.off[a], s));
+  // the exclusion ball in the search key: squared (and scaled like the ball) for the Euclidean family, else as it is
+  const double ex = exclude_radius < 0.0 ? -1.0 : (sr[0].metric == GSS_METRIC_EUCLIDEAN ? exclude_radius * exclude_radius
+                                                                                        : exclude_radius);
+  GSS_TRY(cokrig_cv_dev(h->vg, h->variant, dim, g, sr, k, minneighbors, fold ? sf.as<int>() : nullptr, ex,
+                        smean.as<double>(), svar.as<double>(), status ? sstat.as<uint8_t>() : nullptr,
+                        idx_out ? sidx.as<int>() : nullptr, count_out ? scnt.as<int>() : nullptr, s));
+  GSS_TRY(smean.back(pred, sizeof(double) * (size_t)n, mem, s));
+  GSS_TRY(svar.back(var, sizeof(double) * (size_t)n, mem, s));
+  GSS_TRY(sstat.back(status, (size_t)n, mem, s));
+  GSS_TRY(sidx.back(idx_out, sizeof(int32_t) * (size_t)(n * ksum), mem, s));
+  GSS_TRY(scnt.back(count_out, sizeof(int32_t) * (size_t)(n * nz), mem, s));
   return GSS_OK;
 }
 

@@ -307,12 +307,12 @@ class CoKrigHandle(KrigHandle):
     """gss_krig_t* of a cokriging system (gss.h, gss_cokrig_create): the stacked samples of nz variables under
     C_ab(h) = B1[a, b] rho(h) (+ B0[a, b] at a zero lag).  `structure` is a single variogram model of which only the
     shape is read (kind, range or ball, order).  `cv_global` and `cv_global_folds` are those of the kriging handle,
-    `predict_knn` is the moving neighbourhood of cokriging; every other method of the kriging handle is refused by the
+    `predict_knn` and `cv_knn` are the moving neighbourhood of cokriging; every other method of the kriging handle is refused by the
     library."""
 
     def __init__(self, structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False, factor=True):
-        """`factor=False`: gss_cokrig_create_local -- no system, no factor; the handle serves `predict_knn` only (at most
-        four variables)."""
+        """`factor=False`: gss_cokrig_create_local -- no system, no factor; the handle serves `predict_knn` and `cv_knn` only
+        (at most four variables)."""
         self._l = _lib.lib()
         x = np.ascontiguousarray(xdata, dtype=np.float64)
         if x.ndim == 1:
@@ -379,6 +379,52 @@ class CoKrigHandle(KrigHandle):
         if return_idx:
             return mean, var, status, idx, cnt
         return mean, var, status
+
+    def cv_knn(self, k, fold=None, exclude_radius=None, minneighbors=1, radius=None, radii=None, return_idx=False,
+               rotation=None, device=False):
+        """Cross-validation under the moving neighbourhood (gss.h, gss_cokrig_cv_knn): every stacked sample predicted as
+        its own variable from the `k[a]` nearest samples of every variable a outside its fold.  `k`: one count per
+        variable, as a sequence (a bare int stays the one-variable call of the kriging handle, gss_krig_cv_knn, which
+        the library refuses for a cokriging system and answers with the name of this one).  `fold`: n ids >= 0 (numpy: host arrays out; CUDA int32 tensor, or
+        `device=True` without folds: everything stays in HBM) or None, every sample its own fold (collocated samples of
+        other variables stay in play; one id per location removes whole locations); `exclude_radius`: leave-ball-out.
+        -> (pred[n], variance[n], status[n][, idx[n, sum k], count[n, nz]])."""
+        if np.ndim(k) == 0:
+            return KrigHandle.cv_knn(self, k, fold, exclude_radius, minneighbors, radius, radii, return_idx,
+                                     rotation=rotation, device=device)
+        device = bool(device) or (is_torch(fold) and fold.is_cuda)
+        if device and fold is not None and not (is_torch(fold) and fold.is_cuda):
+            raise ValueError("device=True needs the fold ids as a CUDA tensor")
+        if fold is not None:
+            if device:
+                import torch
+                fold = fold.to(torch.int32).contiguous()
+            else:
+                fold = np.ascontiguousarray(fold, dtype=np.int32)
+            if fold.shape != (self.n,):
+                raise ValueError(f"fold must hold one id per sample ({self.n}), got shape {tuple(fold.shape)}")
+        kk = np.ascontiguousarray(k, dtype=np.int32)
+        if kk.shape != (self.nz,):
+            raise ValueError(f"k must hold one count per variable ({self.nz}), got shape {kk.shape}")
+        ksum = int(kk.sum())
+        out = self._cv_out(device)
+        if return_idx:
+            if device:
+                import torch
+                out += [torch.empty((self.n, max(ksum, 0)), dtype=torch.int32, device=out[0].device),
+                        torch.empty((self.n, self.nz), dtype=torch.int32, device=out[0].device)]
+            else:
+                out += [np.empty((self.n, max(ksum, 0)), dtype=np.int32), np.empty((self.n, self.nz), dtype=np.int32)]
+        pred, var, status = out[:3]
+        idx, cnt = (out[3], out[4]) if return_idx else (None, None)
+        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
+        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
+        met, ir = _ball_metric(0, ir, radii, rotation)
+        check(self._l.gss_cokrig_cv_knn(self._h, ptr(fold), -1.0 if exclude_radius is None else float(exclude_radius),
+                                        ptr(kk), int(minneighbors), r, ptr(ir), met, 0.0, ptr(pred), ptr(var),
+                                        ptr(status), ptr(idx), ptr(cnt), MEM_DEVICE if device else MEM_HOST,
+                                        current_stream()))
+        return tuple(out)
 
 
 class FFTGSHandle(_NativeState):

@@ -8,7 +8,16 @@ are this library's own and are stated in include/gss.h).
 Host logic only: the folds are built here, every prediction and the error summary come from the engine (the global
 neighbourhood reads leave-one-out, gss_krig_cv_global, and folds, gss_krig_cv_global_folds, off the factor of the fitted
 system; a moving neighbourhood searches each sample's neighbours outside its own fold, gss_krig_cv_knn; gss_cv_summary
-reduces the errors)."""
+reduces the errors).
+
+A CoKrigingSolver is cross-validated by LOCATION: the stacked samples of a joint group that share their coordinates form
+one location, the method partitions the locations, and a sample is predicted from the samples of the other folds -- so a
+collocated secondary value never helps to predict the primary one it sits on.  (Leaving one datum out with its collocated
+partners in play is the handle-level `CoKrigHandle.cv_knn(k, fold=None)`.)  The result is per variable; errors of variables
+on different scales are never pooled.
+
+    res = cross_validate(problem, CoKrigingSolver((("cu", "zn"), dict(model=lmc, maxneighbors=(8, 16)))), KFoldValidation(10))
+    res["cu"].summary.cverror"""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -18,7 +27,7 @@ import numpy as np
 from .engine import EDK
 from .geo import GeoTable, PointSet
 from .problems import EstimationProblem
-from .solvers import KrigingSolver, _ball, _distance, _rot_kw, kriging_ui, searcher_ui
+from .solvers import CoKrigingSolver, KrigingSolver, _ball, _distance, _rot_kw, kriging_ui, searcher_ui
 
 
 class LeaveOneOut:
@@ -101,23 +110,87 @@ def _host(a):
     return a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a)
 
 
+def location_ids(x):
+    """One id per distinct location of the stacked samples `x` (exact coordinate equality), numbered in the order of
+    first appearance -> (ids[n], the coordinates of the locations)."""
+    x = np.asarray(x, dtype=np.float64)
+    _, first, inv = np.unique(x, axis=0, return_index=True, return_inverse=True)
+    rank = np.empty(first.size, dtype=np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(first.size)
+    return np.ascontiguousarray(rank[np.asarray(inv).reshape(-1)], dtype=np.int32), x[np.sort(first)]
+
+
+def _cross_validate_cokriging(data, variables, solver, method, eng):
+    """Per joint group: stack as `preprocess` does, give each location one fold id from the method's partition of the
+    locations, predict every stacked sample (global neighbourhood: cv_global_folds off the fitted factor; moving
+    neighbourhood: gss_cokrig_cv_knn), and summarise per variable."""
+    pre = solver.preprocess(SimpleNamespace(data=data, variables=tuple(variables)))
+    out = {}
+    for grp, q in pre.items():
+        x, z, var = q["x"], np.ascontiguousarray(q["z"], dtype=np.float64), q["var"]
+        if x.shape[0] < 2:
+            raise AssertionError(f"cross-validation of {grp} needs at least two non-missing samples")
+        loc, ucoords = location_ids(x)
+        exact = q["nmax"] is None
+        if exact and method.exclude_radius is not None:
+            raise ValueError(f"{type(method).__name__} under the global neighbourhood (maxneighbors=None) is not "
+                             "available: the factor of the system gives leave-one-out only; set maxneighbors")
+        if not exact and sum(q["nmax"]) > 64:
+            raise ValueError(f"maxneighbors: {sum(q['nmax'])} neighbours in total for {grp}, the moving "
+                             f"neighbourhood of cokriging holds at most 64")
+        lfold, _ = method.folds(ucoords)
+        # LeaveOneOut / LeaveBallOut give no ids: one fold per location
+        fold = loc if lfold is None else np.ascontiguousarray(np.asarray(lfold)[loc], dtype=np.int32)
+        h = eng.cokrig(q["structure"], q["B0"], q["B1"], q["variant"], x, z, var, means=q["means"], factor=exact)
+        try:
+            if exact:
+                pred, var_, st = h.cv_global_folds(fold)
+            else:
+                radius, radii = _ball(q["neighborhood"])
+                pred, var_, st = h.cv_knn(q["nmax"], fold=fold, exclude_radius=method.exclude_radius,
+                                          minneighbors=q["minneighbors"], radius=radius, radii=radii,
+                                          **_rot_kw(q["neighborhood"]))[:3]
+        finally:
+            h.close()
+        pred, var_, st = _host(pred), _host(var_), _host(st)
+        for a, v in enumerate(grp):
+            own = var == a
+            inds = np.flatnonzero(~np.isnan(np.asarray(data[v], dtype=np.float64)))
+            # this variable's samples only, its folds compacted to 0 .. nfolds - 1
+            _, fa = np.unique(fold[own], return_inverse=True)
+            fa = np.ascontiguousarray(np.asarray(fa).reshape(-1), dtype=np.int32)
+            nfa = int(fa.max()) + 1
+            za, pa, va, sa = (np.ascontiguousarray(t[own]) for t in (z, pred, var_, st))
+            fields, fmse = eng.cv_summary(za, pa, va, sa, fa, nfa)
+            summary = SimpleNamespace(**fields, fold_mse=_host(fmse))
+            out[v] = CrossValidationResult(inds, za, pa, va, sa, fa, summary)
+    return {v: out[v] for v in variables if v in out}
+
+
 def cross_validate(problem_or_geotable, solver, method=None, engine=None):
     """{variable: CrossValidationResult}.  Of an EstimationProblem only the data are used.  The dispatch follows the
     KrigingSolver's own parameters: the kriging variant by `kriging_ui`; `maxneighbors`, `minneighbors`, `neighborhood`
     and `distance` by `searcher_ui`.  `maxneighbors=None` is the global neighbourhood: leave-one-out and the methods that
     partition the samples into folds (KFoldValidation, BlockValidation) are read off the factor of the one fitted system;
-    LeaveBallOut, whose sets overlap, needs a moving neighbourhood."""
+    LeaveBallOut, whose sets overlap, needs a moving neighbourhood.  A CoKrigingSolver follows its joint parameters the same
+    way, with the folds made of locations (module docstring)."""
     method = LeaveOneOut() if method is None else method
-    if not isinstance(solver, KrigingSolver):
-        raise TypeError(f"cross-validation is available for KrigingSolver, not {type(solver).__name__}")
+    if not isinstance(solver, (KrigingSolver, CoKrigingSolver)):
+        raise TypeError("cross-validation is available for KrigingSolver and CoKrigingSolver, not "
+                        f"{type(solver).__name__}")
     if isinstance(problem_or_geotable, EstimationProblem):
         data, variables = problem_or_geotable.data, problem_or_geotable.variables
     elif isinstance(problem_or_geotable, GeoTable):
         data = problem_or_geotable
-        variables = tuple(v for v in solver.vparams if v in data.table) or tuple(data.table)
+        if isinstance(solver, CoKrigingSolver):
+            variables = tuple(v for grp in solver._spec for v in grp if v in data.table)
+        else:
+            variables = tuple(v for v in solver.vparams if v in data.table) or tuple(data.table)
     else:
         raise TypeError("cross_validate needs an EstimationProblem or a GeoTable")
     eng = engine or solver.engine
+    if isinstance(solver, CoKrigingSolver):
+        return _cross_validate_cokriging(data, variables, solver, method, eng)
     coords = data.domain.centroids()
     out = {}
     for var in variables:

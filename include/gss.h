@@ -460,7 +460,8 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
  *   the ordinary variant a fold that holds every sample of some variable leaves that variable's constraint without
  *   support: it is caught by the pivot test of the fold only.)  Every other entry point that takes a gss_krig_t
  *   (gss_krig_predict_global, _predict_global_batch, _predict_knn, _cv_knn, _set_block_support) refuses such a handle
- *   with GSS_ERR_INVALID; the moving neighbourhood of cokriging is gss_cokrig_predict_knn below.
+ *   with GSS_ERR_INVALID; the moving neighbourhood of cokriging is gss_cokrig_predict_knn below, its cross-validation
+ *   gss_cokrig_cv_knn.
  *
  * gss_cokrig_predict_global: every target variable at every domain point in one call.  xdom m x dim point-major;
  *   mean and variance: nz columns of m (column t at + t * m); status: nz x m bytes (may be NULL).
@@ -478,9 +479,9 @@ int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, 
 
 /* ---- moving-neighbourhood cokriging: per-variable search, one small system per domain point.
  *
- * gss_cokrig_create_local: a cokriging handle without a system and without a factor, for gss_cokrig_predict_knn only
- *   (a sparse primary variable beside a dense secondary one: sample counts beyond what the O(n^3) fit of
- *   gss_cokrig_create and its n^2 factor allow).  Arguments, checks, frame, coefficient table and row order are those
+ * gss_cokrig_create_local: a cokriging handle without a system and without a factor, for gss_cokrig_predict_knn and
+ *   gss_cokrig_cv_knn (a sparse primary variable beside a dense secondary one: sample counts beyond what the O(n^3)
+ *   fit of gss_cokrig_create and its n^2 factor allow).  Arguments, checks, frame, coefficient table and row order are those
  *   of gss_cokrig_create, with one difference: nz is 1 .. 4 here; 5 .. 8 -> GSS_ERR_UNSUPPORTED (the right-hand sides
  *   of a point -- nz covariance columns, one data column, nz indicator columns -- ride along in one 16-column tile
  *   whose per-wave storage holds twelve).  gss_krig_info (n stacked samples, nc) and gss_krig_destroy apply.  Every
@@ -514,7 +515,8 @@ int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, 
  *              gss_cokrig_create: collocated samples of two variables meet through the cross nugget inside the
  *              neighbourhood, and a domain point on a sample of variable t reproduces that datum.
  *   Not here   block support and the drift variants (refused by the creators and by gss_krig_set_block_support);
- *              gss_krig_predict_knn and gss_krig_cv_knn keep refusing cokriging handles.
+ *              gss_krig_predict_knn and gss_krig_cv_knn keep refusing cokriging handles (cross-validation under the
+ *              moving neighbourhood: gss_cokrig_cv_knn, below).
  *   Chunks     the domain is walked in chunks of 2^20 points (131 072 for host arrays, which travel piece by piece);
  *              GSS_COKRIG_CHUNK_POINTS caps them as it caps gss_cokrig_predict_global's, for tests: the results are the
  *              same.  gss_profile_read names: "knn" (the nz searches), "cokrig_local" (the systems). */
@@ -566,6 +568,40 @@ int32_t gss_cokrig_predict_knn(gss_krig_t* h, const double* xdom, int64_t m, con
  *   gss_krig_predict_knn; GSS_METRIC_HAVERSINE has no indexed search: GSS_ERR_UNSUPPORTED.  Fewer than minneighbors
  *   eligible samples: GSS_PT_MISSING, pred = var = NaN.  External drifts at the queries are the handle's own rows.
  *   Works on GSS_KRIG_NO_FACTOR handles.  pred, var, status, idx_out (n x k) / count_out (may be NULL) live in `mem`.
+ *   A cokriging handle is refused (GSS_ERR_INVALID); its moving-neighbourhood cross-validation is gss_cokrig_cv_knn.
+ *
+ * gss_cokrig_cv_knn: moving-neighbourhood cross-validation of a cokriging handle of either creator (gss_cokrig_create,
+ *   gss_cokrig_create_local; nz <= 4, more -> GSS_ERR_UNSUPPORTED; a handle that is no cokriging system:
+ *   GSS_ERR_INVALID) -- the conventions of gss_krig_cv_knn and gss_cokrig_predict_knn put together, without the O(n^3)
+ *   fit and the n^2 factor the global identities need.
+ *   Per sample  stacked sample p (variable v_p, caller's row p) is predicted as target v_p at its own location from,
+ *              for every variable a, the k[a] nearest samples j of variable a with fold[j] != fold[p] and, when
+ *              exclude_radius >= 0, search distance(p, j) > exclude_radius (a sample exactly on the radius is left
+ *              out).  Each variable is searched separately among its own samples, in ascending (key, caller's row).
+ *   fold       n ids >= 0 in `mem` (a negative id: GSS_ERR_INVALID; ids in device memory are copied to the host for
+ *              that check, which waits for the stream).  NULL: every stacked sample is its own fold, leave one DATUM
+ *              out -- collocated samples of other variables stay in play and a sample never sees itself.  A caller
+ *              removes a whole location by giving its collocated samples one id, the convention of gss_cokrig_create
+ *              for gss_krig_cv_global_folds.  exclude_radius NaN: GSS_ERR_INVALID.
+ *   k          nz counts, 1 <= k[a] <= the sample count of variable a (GSS_ERR_INVALID otherwise), sum k[a] <= 64
+ *              (more -> GSS_ERR_UNSUPPORTED); fewer eligible samples than k[a] give a shorter list.  minneighbors,
+ *              radius, inv_radii, metric, metric_param as gss_cokrig_predict_knn; GSS_METRIC_HAVERSINE has no indexed
+ *              search, which the fold search needs: GSS_ERR_UNSUPPORTED.
+ *   Outcome    with c_a neighbours found of variable a and K = sum c_a: K < max(minneighbors, 1): GSS_PT_MISSING.
+ *              GSS_KRIG_ORDINARY: c_{v_p} = 0 leaves no unbiased estimator, GSS_PT_MISSING; the constraint of any other
+ *              variable with c_a = 0 is dropped.  A non-positive pivot: GSS_PT_SINGULAR.  In all of those
+ *              pred = var = NaN.  The variance formula, its clamp at 0, the zero-key rule and the symmetrised
+ *              coefficient table are those of gss_cokrig_predict_knn: a collocated sample of another variable that is
+ *              still eligible enters the right-hand side through the cross nugget c0[v_j][v_p], and a duplicate
+ *              coordinate of the same variable in another fold reproduces that datum.
+ *   Outputs    pred, var: n doubles; status: n bytes, may be NULL; idx_out: n x sum k laid out as in
+ *              gss_cokrig_predict_knn (caller's rows, -1 beyond the number found); count_out: n x nz; both may be NULL.
+ *              Everything is indexed by the caller's row and lives in `mem`, as for gss_krig_cv_knn.
+ *   The system of a sample carries one target, so its right-hand sides are [c0_{v_p} | z - means | indicators], at most
+ *   nz + 2 columns where gss_cokrig_predict_knn carries 2 nz + 1.  No atomics, every sum in a fixed order: the same
+ *   bits on every run.  GSS_COKRIG_CHUNK_POINTS caps the samples per chunk as it caps the points of
+ *   gss_cokrig_predict_knn, for tests: the results are the same.  gss_profile_read names: "knn" (the nz fold searches
+ *   of every chunk), "cokrig_cv" (the systems).
  *
  * gss_cv_summary: one deterministic reduction (per-workgroup partial sums in a fixed order, then one workgroup; no
  *   floating-point atomics: the same bits on every run) over e_i = z_i - pred_i.
@@ -584,6 +620,10 @@ int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radiu
                         double radius, const double* inv_radii, int32_t metric, double metric_param,
                         double* pred, double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out,
                         int32_t mem, void* stream);
+int32_t gss_cokrig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radius, const int32_t* k,
+                          int32_t minneighbors, double radius, const double* inv_radii, int32_t metric,
+                          double metric_param, double* pred, double* var, uint8_t* status, int32_t* idx_out,
+                          int32_t* count_out, int32_t mem, void* stream);
 typedef struct gss_cv_summary {
   double n_ok, n_missing, n_singular, me, mae, mse, mse_std_n, mean_std, msq_std, cverror;
 } gss_cv_summary_t;

@@ -17,7 +17,14 @@ stdout.  python tools/cokrig_sweep.py [--reps 3] [--points 1000000]
   the per-variable searches ("knn") and the system kernel ("cokrig_local"); beside it, in the same session, the global
   call, and single-variable ordinary gss_krig_predict_knn with k = 32 over the same 5 000 locations and points, split
   into its one search ("knn") and K5 ("krig_local").  The three alternate.  Written to
-  profiles/cokrig_local_sweep.json as well."""
+  profiles/cokrig_local_sweep.json as well.
+
+--cv: cross-validation under the moving neighbourhood on the same samples (no domain), gss_cokrig_cv_knn with 16
+  neighbours per variable on device arrays: leave-one-out (every location is its own fold) and 10 folds of locations,
+  split into the fold searches ("knn") and the one-target kernel ("cokrig_cv").  Beside them, in the same session on the
+  same samples and k, gss_cokrig_predict_knn at the 5 000 sample locations, split into its plain searches ("knn") and
+  "cokrig_local".  The three alternate; the splits are means over `--split-reps` profiled calls.  Per-query kernel times
+  in microseconds.  Written to profiles/cokrig_cv_sweep.json as well."""
 import argparse
 import json
 import os
@@ -49,12 +56,14 @@ def timed(fn, reps, warm=1):
     return statistics.median(ms)
 
 
-def split(fn, names):
+def split(fn, names, reps=1):
     _lib.profile_enable(True)
     _lib.profile_reset()
-    fn()
+    for _ in range(reps):
+        fn()
     torch.cuda.synchronize()
-    out = {k: (round(_lib.profile_read(k)[0], 3), _lib.profile_read(k)[1]) for k in names}
+    out = {k: (round(_lib.profile_read(k)[0] / reps, 4 if reps > 1 else 3), _lib.profile_read(k)[1] // reps)
+           for k in names}
     _lib.profile_enable(False)
     return out
 
@@ -66,7 +75,9 @@ def main():
     ap.add_argument("--primary", type=int, default=1000)
     ap.add_argument("--secondary", type=int, default=4000)
     ap.add_argument("--local", action="store_true", help="the moving neighbourhood beside the global call and K5")
-    ap.add_argument("--neighbors", type=int, default=16, help="--local: neighbours per variable")
+    ap.add_argument("--cv", action="store_true", help="cross-validation beside the moving neighbourhood at the samples")
+    ap.add_argument("--split-reps", type=int, default=20, help="--cv: profiled calls behind every split")
+    ap.add_argument("--neighbors", type=int, default=16, help="--local, --cv: neighbours per variable")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     _lib.lib()
@@ -77,8 +88,10 @@ def main():
     z = rng.normal(size=n)
     B1 = np.array([[0.9, 0.5], [0.5, 0.8]])
     B0 = np.array([[0.1, 0.02], [0.02, 0.2]])
-    xdom = torch.as_tensor(rng.uniform(0.0, 1000.0, (args.points, 3)), device="cuda")
     g = gss.SphericalVariogram(range=120.0)
+    if args.cv:
+        return cv(args, g, B0, B1, x, z, var)
+    xdom = torch.as_tensor(rng.uniform(0.0, 1000.0, (args.points, 3)), device="cuda")
 
     if args.local:
         return local(args, g, B0, B1, x, z, var, xdom)
@@ -144,6 +157,50 @@ def local(args, g, B0, B1, x, z, var, xdom):
     line = json.dumps(res)
     print(line, flush=True)
     with open(os.path.join(ROOT, "profiles", "cokrig_local_sweep.json"), "w") as f:
+        f.write(line + "\n")
+
+
+def cv(args, g, B0, B1, x, z, var):
+    k, n = (args.neighbors, args.neighbors), x.shape[0]
+    h = HipEngine.cokrig(g, B0, B1, OK, x, z, var, factor=False)
+    xs = torch.as_tensor(x, device="cuda")
+    # the samples are scattered: every location holds one of them, so folds of locations are folds of samples
+    assert np.unique(x, axis=0).shape[0] == n
+    fold10 = torch.as_tensor(np.random.default_rng(2).integers(0, 10, n).astype(np.int32), device="cuda")
+
+    def loo():
+        h.cv_knn(k, device=True)
+
+    def folds():
+        h.cv_knn(k, fold=fold10)
+
+    def at_samples():
+        h.predict_knn(xs, k)
+    tl, tf, tp = [], [], []
+    for _ in range(3):                                      # alternating blocks
+        tl.append(timed(loo, args.reps, warm=2))
+        tf.append(timed(folds, args.reps, warm=2))
+        tp.append(timed(at_samples, args.reps, warm=2))
+    ls = split(loo, ("knn", "cokrig_cv"), args.split_reps)
+    fs = split(folds, ("knn", "cokrig_cv"), args.split_reps)
+    ps = split(at_samples, ("knn", "cokrig_local"), args.split_reps)
+    h.close()
+    us = lambda ms: round(1e3 * ms / n, 4)                      # noqa: E731
+    res = {"what": "cokrig_cv_knn", "primary": args.primary, "secondary": args.secondary, "nz": 2, "queries": n,
+           "neighbors_per_variable": args.neighbors, "reps": args.reps, "split_reps": args.split_reps,
+           "loo_ms": round(statistics.median(tl), 3), "folds10_ms": round(statistics.median(tf), 3),
+           "predict_at_samples_ms": round(statistics.median(tp), 3),
+           "loo_search_ms": ls["knn"][0], "loo_kernel_ms": ls["cokrig_cv"][0],
+           "folds10_search_ms": fs["knn"][0], "folds10_kernel_ms": fs["cokrig_cv"][0],
+           "plain_search_ms": ps["knn"][0], "local_kernel_ms": ps["cokrig_local"][0],
+           "cv_kernel_us_per_query": us(ls["cokrig_cv"][0]), "cv_kernel_folds10_us_per_query": us(fs["cokrig_cv"][0]),
+           "local_kernel_us_per_point": us(ps["cokrig_local"][0]),
+           "kernel_cv_over_local": round(ls["cokrig_cv"][0] / ps["cokrig_local"][0], 3),
+           "search_loo_over_plain": round(ls["knn"][0] / ps["knn"][0], 3),
+           "search_folds10_over_plain": round(fs["knn"][0] / ps["knn"][0], 3)}
+    line = json.dumps(res)
+    print(line, flush=True)
+    with open(os.path.join(ROOT, "profiles", "cokrig_cv_sweep.json"), "w") as f:
         f.write(line + "\n")
 
 
