@@ -1,9 +1,11 @@
-// Shared by the cokriging paths (krig.hip: the global neighbourhood; cokrig_local*.hip: the moving neighbourhood;
-// cokrig_cv.hip: its cross-validation): the layout of the coefficient table, the correlation with its zero-key flag, and
-// the interfaces of the moving-neighbourhood drivers.
+// Shared by the cokriging paths (cokrig.hip: the creators, the global neighbourhood and the entry of the moving one;
+// cokrig_local*.hip: the moving neighbourhood; cokrig_cv.hip: its cross-validation, entry in krig_cv.hip): the layout of
+// the coefficient table, the correlation with its zero-key flag, and the interfaces of the moving-neighbourhood drivers.
 #pragma once
 
 #include "gss_internal.h"
+
+#include <cstdlib>
 
 namespace gss {
 
@@ -37,6 +39,23 @@ struct CoGrouped {
   int64_t off[CO_MAXZ + 1] = {};
   int nz = 0;
 };
+
+// GSS_COKRIG_CHUNK_POINTS caps the points per chunk of every cokriging call (tests: a chunk loop that runs more than once
+// at a small size)
+inline int64_t cokrig_chunk_cap(int64_t chunk) {
+  if (const char* e = std::getenv("GSS_COKRIG_CHUNK_POINTS")) {
+    const int64_t cap = std::atoll(e) / 256 * 256;
+    if (cap > 0 && cap < chunk) chunk = cap;
+  }
+  return chunk;
+}
+
+// what a launch of the moving-neighbourhood kernel and of its cross-validation kernel have in common: model, spec,
+// grouped samples and the lists of mv queries; x0, outputs, ldo, row and q0 are left to the driver (cokrig_local.hip)
+struct CoLocalSpec;
+struct CoLocalLaunch;
+CoLocalLaunch cokrig_launch_common(const VgDev& vg, const CoLocalSpec& sp, const CoGrouped& g, const int* idx,
+                                   const int* cnt, int64_t mv, hipStream_t s);
 
 // One search per variable (sr[a] over the samples of variable a, already given to it) and one system per domain point.
 // x0: m centres on the covariance frame, x0_raw: before it (read when the searches run in another frame).  mean, var:

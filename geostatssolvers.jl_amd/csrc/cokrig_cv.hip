@@ -5,8 +5,6 @@
 // instantiations (any model, 1-D); the compile-time kinds of 2-D and 3-D are in cokrig_local_2d.hip / _3d.hip.
 #include "cokrig_local_kernel.h"
 
-#include <cstdlib>
-
 namespace gss {
 
 // fold ids in grouped order: the caller's id of the sample's row, or the row itself (every sample its own fold)
@@ -27,11 +25,7 @@ int32_t cokrig_cv_dev(const VgDev& vg, int variant, int dim, const CoGrouped& g,
   const int64_t n = g.off[nz];
   if (n <= 0) return GSS_OK;
 
-  int64_t chunk = 1 << 20;
-  if (const char* e = std::getenv("GSS_COKRIG_CHUNK_POINTS")) {   // tests: the chunk loop past its first turn
-    const int64_t cap = std::atoll(e) / 256 * 256;
-    if (cap > 0 && cap < chunk) chunk = cap;
-  }
+  const int64_t chunk = cokrig_chunk_cap(1 << 20);
   const int64_t mc = n < chunk ? n : chunk;
   DevBuf idx_s, cnt_s, fold_s;
   GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)(mc * sp.ksum)));
@@ -59,21 +53,10 @@ int32_t cokrig_cv_dev(const VgDev& vg, int variant, int dim, const CoGrouped& g,
     }
     {
       ProfScope pl("cokrig_cv", s);
-      CoLocalLaunch a;
-      a.vg = &vg;
-      a.sp = sp;
-      a.xg = g.x;
-      a.zres = g.zres;
-      a.cotab = g.tab;
-      a.x0 = nullptr;
-      a.m = mv;
-      a.idx = idx;
-      a.cnt = cnt;
+      CoLocalLaunch a = cokrig_launch_common(vg, sp, g, idx, cnt, mv, s);
       a.mean = pred;
       a.var = var;
       a.status = status;
-      a.ldo = 0;
-      a.s = s;
       a.row = g.row;
       a.q0 = off;
       GSS_TRY(cokrig_local_dispatch<true>(dim, kind, a));

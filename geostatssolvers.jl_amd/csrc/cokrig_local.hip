@@ -5,7 +5,6 @@
 // (cokrig_local_2d.hip, cokrig_local_3d.hip).
 #include "cokrig_local_kernel.h"
 
-#include <cstdlib>
 #include <cstring>
 
 namespace gss {
@@ -68,6 +67,11 @@ int32_t cokrig_spec(const CoGrouped& g, int variant, const int* k, int minneighb
   return GSS_OK;
 }
 
+CoLocalLaunch cokrig_launch_common(const VgDev& vg, const CoLocalSpec& sp, const CoGrouped& g, const int* idx,
+                                   const int* cnt, int64_t mv, hipStream_t s) {
+  return CoLocalLaunch{&vg, sp, g.x, g.zres, g.tab, nullptr, mv, idx, cnt, nullptr, nullptr, nullptr, 0, s};
+}
+
 int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped& g, Searcher* sr, const int* k,
                          int minneighbors, const double* x0, const double* x0_raw, int64_t m, double* mean, double* var,
                          uint8_t* status, int64_t ldo, int* idx_out, int* count_out, hipStream_t s, HostPipe* pipe) {
@@ -76,11 +80,7 @@ int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped&
   GSS_TRY(cokrig_spec(g, variant, k, minneighbors, &sp));
 
   const bool piped = pipe && pipe->on;
-  int64_t chunk = piped ? HostPipe::PIECE : (1 << 20);
-  if (const char* e = std::getenv("GSS_COKRIG_CHUNK_POINTS")) {   // tests: the chunk loop past its first turn
-    const int64_t cap = std::atoll(e) / 256 * 256;
-    if (cap > 0 && cap < chunk) chunk = cap;
-  }
+  const int64_t chunk = cokrig_chunk_cap(piped ? HostPipe::PIECE : (1 << 20));
   const int64_t mc = m < chunk ? m : chunk;
   DevBuf idx_s, cnt_s;
   GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)(mc * sp.ksum)));
@@ -99,21 +99,12 @@ int32_t cokrig_local_dev(const VgDev& vg, int variant, int dim, const CoGrouped&
     }
     {
       ProfScope pl("cokrig_local", s);
-      CoLocalLaunch a;
-      a.vg = &vg;
-      a.sp = sp;
-      a.xg = g.x;
-      a.zres = g.zres;
-      a.cotab = g.tab;
+      CoLocalLaunch a = cokrig_launch_common(vg, sp, g, idx, cnt, mv, s);
       a.x0 = x0 + off * dim;
-      a.m = mv;
-      a.idx = idx;
-      a.cnt = cnt;
       a.mean = mean + off;
       a.var = var + off;
       a.status = status ? status + off : nullptr;
       a.ldo = ldo;
-      a.s = s;
       GSS_TRY(cokrig_local_dispatch<false>(dim, kind, a));
     }
     if (idx_out || count_out) {

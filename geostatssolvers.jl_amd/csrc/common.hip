@@ -225,6 +225,7 @@ int32_t Staged::in(const void* src, size_t bytes, int32_t mem, hipStream_t s) {
 }
 
 int32_t Staged::out(void* dst, size_t bytes, int32_t mem) {
+  host_dst = nullptr;
   if (dst == nullptr) {
     p = nullptr;
     return GSS_OK;
@@ -235,12 +236,14 @@ int32_t Staged::out(void* dst, size_t bytes, int32_t mem) {
   }
   GSS_TRY(own.alloc(bytes));
   p = own.p;
+  host_dst = dst;
+  out_bytes = bytes;
   return GSS_OK;
 }
 
-int32_t Staged::back(void* dst, size_t bytes, int32_t mem, hipStream_t s) {
-  if (dst == nullptr || mem == GSS_MEM_DEVICE) return GSS_OK;
-  GSS_HIP(hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, s));
+int32_t Staged::back(hipStream_t s) {
+  if (host_dst == nullptr) return GSS_OK;
+  GSS_HIP(hipMemcpyAsync(host_dst, own.p, out_bytes, hipMemcpyDeviceToHost, s));
   GSS_HIP(hipStreamSynchronize(s));
   return GSS_OK;
 }
@@ -357,6 +360,49 @@ int32_t HostPipe::finish(hipStream_t s) {
   GSS_HIP(hipStreamSynchronize(cout));
   GSS_HIP(hipStreamSynchronize(s));
   on = false;   // (nothing left for the destructor to join)
+  return GSS_OK;
+}
+
+// ---- DomainCall (gss_internal.h) -----------------------------------------------------------------------------
+Staged* DomainCall::in(const void* host, size_t stride) { return out(const_cast<void*>(host), stride, -1); }
+
+Staged* DomainCall::out(void* host, size_t stride, int cols) {   // (cols < 0: an input)
+  Arr& a = cols < 0 ? ins[nin++] : outs[nout++];
+  a.host = host;
+  a.stride = stride;
+  a.cols = cols;
+  return &a.st;
+}
+
+int32_t DomainCall::begin(int32_t mem, int64_t m, hipStream_t s, bool allow_pipe, const Frame* frame) {
+  if (allow_pipe) GSS_TRY(pipe.begin(mem, m, s));
+  piped = pipe.on;
+  for (int i = 0; i < nin; ++i) {
+    Arr& a = ins[i];
+    if (piped) {   // device scratch only: the pipe fills it piece by piece
+      GSS_TRY(a.st.out(a.host, a.stride * (size_t)m, mem));
+      a.st.host_dst = nullptr;
+    } else {
+      GSS_TRY(a.st.in(a.host, a.stride * (size_t)m, mem, s));
+    }
+  }
+  for (int i = 0; i < nout; ++i) GSS_TRY(outs[i].st.out(outs[i].host, outs[i].stride * (size_t)m * outs[i].cols, mem));
+  x_raw = x();
+  if (!piped) return frame ? xfr.of(*frame, &ins[0].st, m, s) : GSS_OK;
+  for (int i = 0; i < nin; ++i) pipe.add_in(ins[i].host, ins[i].st.p, ins[i].stride);
+  for (int i = 0; i < nout; ++i) {
+    const Arr& a = outs[i];
+    for (int t = 0; t < a.cols && a.host; ++t)   // column t of an output is an array of its own to the pipe
+      pipe.add_out(static_cast<char*>(a.host) + a.stride * (size_t)(t * m), a.st.as<char>() + a.stride * (size_t)(t * m),
+                   a.stride);
+  }
+  pipe.frame = frame;   // a rotated model: each piece moves into the frame where it lands
+  return GSS_OK;
+}
+
+int32_t DomainCall::finish(hipStream_t s) {
+  if (piped) return pipe.finish(s);
+  for (int i = 0; i < nout; ++i) GSS_TRY(outs[i].st.back(s));
   return GSS_OK;
 }
 

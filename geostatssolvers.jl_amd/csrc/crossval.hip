@@ -185,6 +185,6 @@ extern "C" int32_t gss_cv_summary(const double* z, const double* pred, const dou
   GSS_HIP(hipMemcpyAsync(host, dout, sizeof(host), hipMemcpyDeviceToHost, s));
   GSS_HIP(hipStreamSynchronize(s));
   std::memcpy(out, host, sizeof(host));
-  if (nf > 0) GSS_TRY(sfm.back(fold_mse, sizeof(double) * (size_t)nf, mem, s));
+  if (nf > 0) GSS_TRY(sfm.back(s));
   return GSS_OK;
 }

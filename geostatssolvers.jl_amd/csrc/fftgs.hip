@@ -1162,7 +1162,7 @@ int32_t gss_fftgs_spectrum(gss_fftgs_t* h, double* f_out, int32_t mem, void* str
   hipLaunchKernelGGL(fftgs_expand_kernel, dim3(grid_blocks(h->N)), dim3(256), 0, s, h->g, h->Fh(), h->scal(),
                      so.as<double>());
   GSS_HIP(hipGetLastError());
-  return so.back(f_out, sizeof(double) * (size_t)h->N, mem, s);
+  return so.back(s);
 }
 
 int32_t gss_fftgs_state_buffer(gss_fftgs_t* h, void** dev_ptr, int64_t* bytes) {

@@ -91,12 +91,14 @@ struct DevBuf {
 struct Staged {
   DevBuf own;
   void* p = nullptr;
+  void* host_dst = nullptr;   // what out() was given to copy back to and how much (NULL: nothing to copy)
+  size_t out_bytes = 0;
   // input array: copy host->device when mem == HOST
   int32_t in(const void* src, size_t bytes, int32_t mem, hipStream_t s);
   // output array: allocate device scratch when mem == HOST
   int32_t out(void* dst, size_t bytes, int32_t mem);
-  // copy back to host destination (no-op for DEVICE)
-  int32_t back(void* dst, size_t bytes, int32_t mem, hipStream_t s);
+  // copy back to the host destination of out() and wait for it (no-op for DEVICE or a NULL destination)
+  int32_t back(hipStream_t s);
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -192,6 +194,34 @@ struct HostPipe {
   void add_out(void* host, void* dev, size_t stride);   // NULL host or dev: skipped
   int32_t fetch(int64_t off, int64_t n, hipStream_t s);
   int32_t deliver(int64_t off, int64_t n, hipStream_t s);
+  int32_t finish(hipStream_t s);
+};
+
+// The per-point arrays of one C-ABI call over m domain points whose host arrays may travel in pieces: the pipe, the
+// frame copy of the coordinates and the staged images.  Usage: in() / out() for every array, the coordinates first
+// (NULL arrays are skipped and stage to NULL); begin(); the work on x() and the as<>() of what in() / out() returned,
+// with pipe.fetch / pipe.deliver around every piece (no-ops when whole); finish().  Piped: the inputs are device scratch
+// that fetch() fills, every array is known to the pipe and the pipe moves each piece of the coordinates into `frame`.
+// Whole: the inputs are copied in at begin(), the coordinates are moved into `frame` there (x_raw keeps them as
+// staged) and finish() copies every output back in the order of registration.
+struct DomainCall {
+  struct Arr {
+    void* host;
+    size_t stride;   // bytes per point
+    int cols;        // columns of m points each, column t at offset t * m (outputs; the pipe sees an array per column)
+    Staged st;
+  };
+  Arr ins[2], outs[6];   // (declared first: the pipe and the frame copy join their streams before the images go)
+  int nin = 0, nout = 0;
+  HostPipe pipe;
+  FrameCopy xfr;
+  bool piped = false;
+  const double* x_raw = nullptr;   // the coordinates before the frame (== x() when piped or without a frame)
+  Staged* in(const void* host, size_t stride);
+  Staged* out(void* host, size_t stride, int cols = 1);
+  int32_t begin(int32_t mem, int64_t m, hipStream_t s, bool allow_pipe, const Frame* frame);
+  const double* x() const { return ins[0].st.as<double>(); }
+  // piped: pipe.finish (a no-op after a local driver that ended with it); whole: every output back
   int32_t finish(hipStream_t s);
 };
 

@@ -855,42 +855,26 @@ static int32_t est_predict(EstSpec sp, const double* xdata, const double* z, int
   GSS_REQUIRE(m >= 0 && (m == 0 || (xdata && z && xdom && mean && aux)), "NULL array");
   if (m == 0) return GSS_OK;
   hipStream_t s = to_stream(stream);
-  Staged sxd, sz, sx, smean, saux, sstat;
-  FrameCopy fx;
+  Staged sxd, sz;
   GSS_TRY(sxd.in(xdata, sizeof(double) * n * dim, mem, s));
   if (sr.frame.on) GSS_TRY(frame_origin(&sr.frame, xdata, mem, s));
   GSS_TRY(sr.samples(sxd.as<double>(), nullptr, n, s));
   GSS_TRY(sz.in(z, sizeof(double) * n * nz, mem, s));
-  HostPipe pipe;   // host arrays of the domain: in and out piece by piece beside the computation (k <= 64, one column)
-  GSS_TRY(pipe.begin(k <= 64 && nz == 1 ? mem : GSS_MEM_DEVICE, m, s));
-  if (pipe.on) GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
-  else GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
-  GSS_TRY(smean.out(mean, sizeof(double) * m * nz, mem));
-  GSS_TRY(saux.out(aux, sizeof(double) * m, mem));
+  DomainCall dc;   // host arrays of the domain: in and out piece by piece beside the computation (k <= 64, one column)
+  dc.in(xdom, sizeof(double) * dim);
+  Staged& smean = *dc.out(mean, sizeof(double), nz);
+  Staged& saux = *dc.out(aux, sizeof(double));
+  Staged& sstat = *dc.out(status, 1);
+  GSS_TRY(dc.begin(mem, m, s, k <= 64 && nz == 1, &sr.frame));
   DevBuf st_own;
-  uint8_t* st = nullptr;
-  if (status) {
-    GSS_TRY(sstat.out(status, (size_t)m, mem));
-    st = sstat.as<uint8_t>();
-  } else {
+  uint8_t* st = sstat.as<uint8_t>();
+  if (!status) {
     GSS_TRY(st_own.alloc((size_t)m));
     st = st_own.as<uint8_t>();
   }
-  if (pipe.on) {
-    pipe.add_in(xdom, sx.p, sizeof(double) * dim);
-    pipe.add_out(mean, smean.p, sizeof(double));
-    pipe.add_out(aux, saux.p, sizeof(double));
-    pipe.add_out(status, status ? sstat.p : nullptr, 1);
-    pipe.frame = &sr.frame;
-  } else {
-    GSS_TRY(fx.of(sr.frame, &sx, m, s));
-  }
-  GSS_TRY(est_local_dev(sp, sr, sz.as<double>(), sx.as<double>(), m, k, minneighbors, smean.as<double>(),
-                        saux.as<double>(), st, s, &pipe));
-  if (pipe.on) return GSS_OK;   // everything is home (est_local_dev ends with pipe.finish and a synchronisation)
-  GSS_TRY(smean.back(mean, sizeof(double) * m * nz, mem, s));
-  GSS_TRY(saux.back(aux, sizeof(double) * m, mem, s));
-  if (status) GSS_TRY(sstat.back(status, (size_t)m, mem, s));
+  GSS_TRY(est_local_dev(sp, sr, sz.as<double>(), dc.x(), m, k, minneighbors, smean.as<double>(), saux.as<double>(), st, s,
+                        &dc.pipe));
+  GSS_TRY(dc.finish(s));   // (piped: est_local_dev ended with pipe.finish and a synchronisation, everything is home)
   if (!status) GSS_HIP(hipStreamSynchronize(s));  // st_own is released on return
   return GSS_OK;
 }
@@ -969,9 +953,9 @@ int32_t gss_lwr_predict_weights(const double* xdata, const double* z, int64_t n,
   }
 #undef GSS_LWRW_ARGS
   GSS_HIP(hipGetLastError());
-  GSS_TRY(smean.back(mean, sizeof(double) * m, mem, s));
-  GSS_TRY(svar.back(var, sizeof(double) * m, mem, s));
-  if (status) GSS_TRY(sstat.back(status, (size_t)m, mem, s));
+  GSS_TRY(smean.back(s));
+  GSS_TRY(svar.back(s));
+  if (status) GSS_TRY(sstat.back(s));
   GSS_HIP(hipStreamSynchronize(s));   // the staged copies are released on return
   return GSS_OK;
 }

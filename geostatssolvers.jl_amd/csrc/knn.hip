@@ -920,7 +920,7 @@ extern "C" int32_t gss_knn_search(const double* xdata, int64_t n, int32_t dim, c
   GSS_TRY(sr.samples(sx.as<double>(), nullptr, n, s));
   GSS_TRY(fc.of(sr.frame, &sc, m, s));
   GSS_TRY(sr.query(sc.as<double>(), nullptr, m, k, si.as<int>(), sn.as<int>(), s));
-  GSS_TRY(si.back(idx, sizeof(int32_t) * (size_t)(m * k), mem, s));
-  GSS_TRY(sn.back(count, sizeof(int32_t) * (size_t)m, mem, s));
+  GSS_TRY(si.back(s));
+  GSS_TRY(sn.back(s));
   return GSS_OK;
 }

@@ -16,18 +16,14 @@
 //                         and accumulates the dual-form mean on the fly
 //   krig_quadform_kernel  K3: FP64 MFMA triangular GEMM W' * R fused with the signed column norms
 //
-// Cokriging (gss.h, gss_cokrig_create): the same system over the stacked samples of nz variables
-// under C_ab(h) = b1[a][b] rho(h) (+ b0[a][b] at a zero key), with the per-variable indicators as constraint columns.
-//   cokrig_system_kernel  the n x n block of the system, replacing the pairwise covariances of the fit
-//   cokrig_rhs_kernel     the right-hand sides of all nz targets from one evaluation of rho per (sample, point)
-// The factorisation, K3 and the cross-validation identities are those of the single-variable handle.
-// The moving neighbourhood of cokriging (gss_cokrig_predict_knn) has its entry point here and its kernel and driver in
-// cokrig_local.hip.
-#include "gss_internal.h"
-#include "cokrig.h"
+// The handle and what this unit shares with the cokriging entries (cokrig.hip) and the cross-validation (krig_cv.hip):
+// krig_handle.h.  A cokriging handle is fitted here as well: the fit asks cokrig.hip for the system block, the indicator
+// columns and the centred data; the factorisation and K3 are those of the single-variable handle.
+#include "krig_handle.h"
+
+#include "mfma_f64.h"
 
 #include <mutex>
-#include "mfma_f64.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -36,18 +32,6 @@
 #include <vector>
 
 namespace gss {
-
-constexpr int MAX_NC = 64;
-constexpr int NSEG = 4;  // row segments of the RHS assembly (mean partials are summed in fixed order)
-
-struct DriftSpec {
-  int variant;
-  int nc;
-  int dim;
-  signed char e[MAX_NC][3];
-  double center[3];
-  double inv_scale[3];
-};
 
 // out[c * ld + p] = f_c(x_p) for c < nc, zero rows up to nrows
 template <int DIM>
@@ -161,138 +145,6 @@ static int32_t launch_krig_rhs(hipStream_t s, const VgDev& vg, const double* xd,
     default: GSS_K1W_LAUNCH(-1); break;
   }
 #undef GSS_K1W_LAUNCH
-  return GSS_OK;
-}
-
-// ---- cokriging -------------------------------------------------------------------------------------------------------
-// (the coefficient table CO_* and co_rho: cokrig.h, shared with the moving neighbourhood)
-
-// M[i * ldw + j] = C_{var_i var_j}(x_i, x_j) for i, j < n (the block is symmetric: the table is, and so is the key).
-// Lane = column sample j, the row sample i is wave-uniform (cov_pairwise_kernel's layout).
-template <int DIM>
-__global__ __launch_bounds__(256) void cokrig_system_kernel(VgDev vg, const double* __restrict__ xd,
-                                                            const int* __restrict__ var,
-                                                            const double* __restrict__ tab, int n,
-                                                            double* __restrict__ M, int64_t ldw) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  const int i0 = blockIdx.y * 64;
-  const int i1 = i0 + 64 < n ? i0 + 64 : n;
-  if (j >= n) return;
-  double c[DIM];
-#pragma unroll
-  for (int k = 0; k < DIM; ++k) c[k] = xd[(int64_t)j * DIM + k];
-  const int vj = var[j];
-  for (int i = i0; i < i1; ++i) {
-    double x[DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) x[k] = xd[(int64_t)i * DIM + k];
-    bool zero;
-    const double rho = co_rho<DIM, -1>(vg, x, c, &zero);
-    const int e = var[i] * CO_MAXZ + vj;
-    M[(int64_t)i * ldw + j] = zero ? tab[CO_C0 + e] : tab[e] * rho;
-  }
-}
-
-// Fd[c * n + i] = [var_i == c]: the unbiasedness columns of ordinary cokriging
-__global__ __launch_bounds__(256) void cokrig_indicator_kernel(const int* __restrict__ var, int n, int nc,
-                                                               double* __restrict__ Fd) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int v = var[i];
-  for (int c = 0; c < nc; ++c) Fd[(int64_t)c * n + i] = v == c ? 1.0 : 0.0;
-}
-
-// z_i -= means[var_i] (simple cokriging kriges the residuals)
-__global__ __launch_bounds__(256) void cokrig_center_kernel(double* __restrict__ z, const int* __restrict__ var,
-                                                            const double* __restrict__ tab, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) z[i] -= tab[CO_MEANS + var[i]];
-}
-
-// Right-hand sides of all targets: block t of R (blk = N1pad * ldr doubles apart) gets, in row j < n,
-// b1[var_j][t] rho(x_j, x0_p), or c0[var_j][t] when the key is zero.  The unit walk, the two adjacent points per thread
-// and the 16-B stores are those of krig_rhs2_kernel; rho is evaluated once per (sample, point) and scaled nz times.  j is
-// wave-uniform, so x_j, var_j and row var_j of the two tables come through the scalar cache and the scale is a scalar
-// operand of the multiply.
-// nz is a run-time loop bound: the loop body keeps two products and two selects live whatever nz is, so the kernel
-// needs no more registers than krig_rhs2_kernel plus the two key flags (DESIGN.md section 4 has the counts), and one
-// instantiation per (DIM, KIND) serves nz = 1 .. 8.  Unrolling over a compile-time nz would only let the compiler
-// hoist the nz scalar loads in front of the shape, which the scalar cache already hides behind the sqrt / exp chain.
-template <int DIM, int KIND>
-__global__ __launch_bounds__(256) void cokrig_rhs_kernel(VgDev vg, const double* __restrict__ xd,
-                                                         const int* __restrict__ var, const double* __restrict__ tab,
-                                                         int nz, int n, const double* __restrict__ x0, int64_t m_valid,
-                                                         double* __restrict__ R, int64_t ldr, int64_t blk, int seg_len,
-                                                         int nblk, int64_t ncols) {
-  for (int unit = blockIdx.x; unit < nblk * NSEG; unit += gridDim.x) {
-    const int seg = unit % NSEG;
-    const int64_t p = (int64_t)(unit / NSEG) * 512 + 2 * threadIdx.x;
-    if (p >= ncols) continue;
-    const int64_t pa = p < m_valid ? p : m_valid - 1, pb = p + 1 < m_valid ? p + 1 : m_valid - 1;
-    double ca[DIM], cb[DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) {
-      ca[k] = x0[pa * DIM + k];
-      cb[k] = x0[pb * DIM + k];
-    }
-    const int j0 = seg * seg_len;
-    const int j1 = j0 + seg_len < n ? j0 + seg_len : n;
-    double2* rp = reinterpret_cast<double2*>(R + (int64_t)j0 * ldr + p);
-    const int64_t ld2 = ldr >> 1, blk2 = blk >> 1;
-#pragma unroll 2
-    for (int j = j0; j < j1; ++j) {
-      double x[DIM];
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) x[k] = xd[j * DIM + k];
-      bool za, zb;
-      const double ra = co_rho<DIM, KIND>(vg, x, ca, &za);
-      const double rb = co_rho<DIM, KIND>(vg, x, cb, &zb);
-      const double* row = tab + var[j] * CO_MAXZ;
-      double2* rt = rp;
-      for (int t = 0; t < nz; ++t) {
-        const double b = row[t], c = row[CO_C0 + t];
-        double2 v;
-        v.x = za ? c : b * ra;
-        v.y = zb ? c : b * rb;
-        *rt = v;
-        rt += blk2;
-      }
-      rp += ld2;
-    }
-  }
-}
-
-// rows n .. n + nrows - 1 of every block: the indicator [c == t] in row n + c (c < nc), zero rows up to N1pad
-__global__ __launch_bounds__(256) void cokrig_tail_rows_kernel(double* __restrict__ R, int64_t ldr, int64_t blk, int n,
-                                                               int nc, int nrows, int nz, int64_t ncols) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= ncols) return;
-  for (int t = 0; t < nz; ++t)
-    for (int r = 0; r < nrows; ++r) R[t * blk + (int64_t)(n + r) * ldr + p] = (r < nc && r == t) ? 1.0 : 0.0;
-}
-
-template <int DIM>
-static int32_t launch_cokrig_rhs(hipStream_t s, const VgDev& vg, const double* xd, const int* var, const double* tab,
-                                 int nz, int n, const double* x0, int64_t m_valid, double* R, int64_t ldr, int64_t blk,
-                                 int seg_len, int nblk) {
-  GSS_REQUIRE((ldr & 1) == 0 && (blk & 1) == 0, "launch_cokrig_rhs: odd leading dimension %lld (16-B stores need an "
-              "even one)", (long long)ldr);
-  const int64_t ncols = (int64_t)nblk * 256;
-  const int nblk2 = (int)((ncols + 511) / 512);
-  const dim3 g2((unsigned)(nblk2 * NSEG));
-#define GSS_CK_LAUNCH(KIND)                                                                                          \
-  hipLaunchKernelGGL((cokrig_rhs_kernel<DIM, KIND>), g2, dim3(256), 0, s, vg, xd, var, tab, nz, n, x0, m_valid, R,   \
-                     ldr, blk, seg_len, nblk2, ncols)
-  switch (vg.kind) {
-    case GSS_VG_GAUSSIAN: GSS_CK_LAUNCH(GSS_VG_GAUSSIAN); break;
-    case GSS_VG_EXPONENTIAL: GSS_CK_LAUNCH(GSS_VG_EXPONENTIAL); break;
-    case GSS_VG_SPHERICAL: GSS_CK_LAUNCH(GSS_VG_SPHERICAL); break;
-    case VG_MATERN12: GSS_CK_LAUNCH(VG_MATERN12); break;
-    case VG_MATERN32: GSS_CK_LAUNCH(VG_MATERN32); break;
-    case VG_MATERN52: GSS_CK_LAUNCH(VG_MATERN52); break;
-    default: GSS_CK_LAUNCH(-1); break;
-  }
-#undef GSS_CK_LAUNCH
   return GSS_OK;
 }
 
@@ -610,102 +462,9 @@ __global__ void sub_scalar_kernel(double* z, int64_t n, double mu) {
   if (i < n) z[i] -= mu;
 }
 
-// Leave-one-out from the factor (gss_krig_cv_global; Dubrule 1983): K^-1 = W'^T D W' with D = +1 on the n data rows and
-// -1 on the nc constraint rows, so B_ii = (K^-1)_ii = sum_{k=i}^{N1-1} D_k W'(k, i)^2 -- W' is lower triangular and its
-// columns are contiguous.  Row N1 of W' holds the dual weights (wd_row_kernel): it is not part of the factor and the
-// sum stops in front of it.  One wave per column; lane l adds rows i + l, i + l + 64, ... in that order, the 64 lane
-// sums meet in a fixed butterfly: the same bits on every run.  pred_i = z_i - wd_i / B_ii (wd was formed from z - mean
-// for simple kriging, so the mean cancels), var_i = max(0, 1 / B_ii) = the Schur complement of the system without i.
-__global__ __launch_bounds__(256) void krig_loo_kernel(const double* __restrict__ Wp, int64_t ldw, int n, int N1,
-                                                       const double* __restrict__ wd, const double* __restrict__ z,
-                                                       double* __restrict__ pred, double* __restrict__ var,
-                                                       uint8_t* __restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;  // whole wave
-  const double* col = Wp + (int64_t)i * ldw;
-  double acc = 0.0;
-  for (int k = i + lane; k < N1; k += 64) {
-    const double w = col[k];
-    acc = k < n ? fma(w, w, acc) : fma(-w, w, acc);
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-  if (lane != 0) return;
-  const double NaN = __longlong_as_double(0x7ff8000000000000LL);
-  const bool ok = acc > 0.0 && acc < __builtin_huge_val();
-  const double v = 1.0 / acc;
-  pred[i] = ok ? z[i] - wd[i] * v : NaN;
-  var[i] = ok ? (v > 0.0 ? v : 0.0) : NaN;
-  if (status) status[i] = ok ? GSS_PT_OK : GSS_PT_SINGULAR;
-}
-
 }  // namespace gss
 
 using namespace gss;
-
-struct gss_krig {
-  VgDev vg;
-  int variant = GSS_KRIG_ORDINARY;
-  double sk_mean = 0.0;
-  int degree = 0;
-  int ndrift = 0;
-  int dim = 0;
-  int64_t n = 0;
-  int nc = 0;
-  int64_t N1 = 0, N1pad = 0, ldw = 0;
-  DriftSpec ds;
-  DevBuf xdata, z, drift_data;
-  // rotated variogram: xdata holds the frame coordinates R^T (x - c) of the samples, xraw the coordinates as given
-  // (for searches in another frame); c = the first sample.  Every predict call moves its domain into the same frame.
-  Frame fr;
-  DevBuf xraw;
-  DevBuf factor;  // W' (ldw x N1pad, column-major) followed by wd (N1pad)
-  // fit in flight: workspace, completion event and status words (joined by krig_fit_wait)
-  DevBuf fit_ws;
-  hipEvent_t fit_done = nullptr;
-  bool fit_pending = false;
-  int* fit_info = nullptr;
-  hipStream_t fit_stream = nullptr;  // stream of the fit in flight (a retry goes back on it)
-  // GSS_KRIG_ASYNC_FIT: the fit runs on the library's fit stream beside whatever the caller queues next (K1 of the
-  // first prediction); its two status words travel to pinned host memory on that stream, in front of fit_done
-  bool fit_async = false;
-  int* fit_info_host = nullptr;
-  ~gss_krig() {
-    if (fit_pending && fit_done) (void)hipEventSynchronize(fit_done);
-    if (fit_done) (void)hipEventDestroy(fit_done);
-    if (fit_info_host) (void)hipHostFree(fit_info_host);
-  }
-  bool factored = false;
-  // block support (gss_krig_set_block_support): right-hand sides regularised over a cell of size `cell` sampled at
-  // the centres of nsub^dim sub-cells; c_vv = mean covariance between two samples of the cell (replaces the sill in
-  // the variance).  nsub = 0: point support.
-  int block_nsub = 0;
-  double block_cell[3] = {0.0, 0.0, 0.0};
-  double block_cvv = 0.0;
-  // cokriging (gss_cokrig_create): nz > 0, the system is over the stacked samples of nz variables.  covar: the
-  // variable id of every stacked sample; cotab: the coefficient table the kernels read (CO_TAB doubles); c00 / means:
-  // host copies of C_tt(0) = b0[t][t] + b1[t][t] and of the known means (zero under the ordinary variant)
-  int nz = 0;
-  DevBuf covar, cotab;
-  double c00[CO_MAXZ] = {}, means[CO_MAXZ] = {};
-  // the same samples grouped by variable for the per-variable searches of gss_cokrig_predict_knn (cokrig.h, CoGrouped):
-  // coordinates on the covariance frame / as given (only with a frame), residuals z - means[var], the caller's row of
-  // every grouped sample, and where each variable starts
-  DevBuf co_xg, co_xg_raw, co_zres, co_row;
-  int64_t co_off[CO_MAXZ + 1] = {};
-  double* Wp() const { return factor.as<double>(); }
-  double* wd() const { return factor.as<double>() + ldw * N1pad; }
-};
-
-namespace gss {
-int32_t krig_local_dev(const VgDev& vg, int variant, int nc, int dim, const signed char* exps, double inv_scale,
-                       double sk_mean, Searcher& sr, const double* xdata, const double* z, const double* drift_data,
-                       const double* x0, const double* x0_raw, const double* drift_dom, int64_t m, int k,
-                       int minneighbors, double* mean, double* var, uint8_t* status, int* idx_out, int* count_out,
-                       hipStream_t s, HostPipe* pipe, int block_nsub, const double* block_cell, double block_cvv,
-                       const KnnMask* mask = nullptr);
-}
 
 
 // Block support (krig.jl:180 passes the cell geometry to predictprob; [RECALL] its covariances are averages over sample
@@ -801,7 +560,7 @@ static void uk_exponents(int dim, int degree, std::vector<signed char>& e) {
 // resident slots (2 per CU), so small chunks lose up to one slot-round to the tail: the budget defaults to
 // min(16 GiB, half of the free HBM) -- 10^6 points at n = 1000 are one launch -- and, when the domain must be
 // split, chunks are multiples of 512 * 128 points.  GSS_KRIG_WS_MB overrides the budget.
-static int64_t krig_chunk_points(int64_t N1pad, int64_t m) {
+int64_t gss::krig_chunk_points(int64_t N1pad, int64_t m) {
   size_t ws = (size_t)16 << 30;
   size_t freeb = 0, totalb = 0;
   if (hipMemGetInfo(&freeb, &totalb) == hipSuccess && freeb / 2 < ws) ws = freeb / 2;
@@ -825,7 +584,7 @@ struct KrigWorkspace {
 };
 static KrigWorkspace g_ws;
 
-static int32_t krig_workspace(int64_t N1pad, int64_t mc, hipStream_t s, double** R, double** mean_part) {
+int32_t gss::krig_workspace(int64_t N1pad, int64_t mc, hipStream_t s, double** R, double** mean_part) {
   const int64_t nI = (N1pad + BM - 1) / BM + 1;
   if (g_ws.doubles < N1pad * mc || g_ws.mc < mc || g_ws.nI < nI) {
     GSS_HIP(hipStreamSynchronize(s));
@@ -946,13 +705,7 @@ static int32_t krig_fit_enqueue(gss_krig* h, const FitPlan& fp, hipStream_t s) {
   GSS_TRY(dev_zero_bytes(h->factor.p, h->factor.bytes, s));
   GSS_TRY(dev_zero_bytes(info2, sizeof(int), s));
   if (h->nz > 0) {
-    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)((n + 63) / 64));
-    switch (h->dim) {
-      case 1: hipLaunchKernelGGL(cokrig_system_kernel<1>, grid, dim3(256), 0, s, h->vg, h->xdata.as<double>(), h->covar.as<int>(), h->cotab.as<double>(), (int)n, M, ldw); break;
-      case 2: hipLaunchKernelGGL(cokrig_system_kernel<2>, grid, dim3(256), 0, s, h->vg, h->xdata.as<double>(), h->covar.as<int>(), h->cotab.as<double>(), (int)n, M, ldw); break;
-      default: hipLaunchKernelGGL(cokrig_system_kernel<3>, grid, dim3(256), 0, s, h->vg, h->xdata.as<double>(), h->covar.as<int>(), h->cotab.as<double>(), (int)n, M, ldw); break;
-    }
-    GSS_HIP(hipGetLastError());
+    GSS_TRY(cokrig_fit_system(h, M, s));
   } else {
     GSS_TRY(cov_pairwise_dev(h->vg, h->xdata.as<double>(), n, h->xdata.as<double>(), n, M, ldw, s));
   }
@@ -964,9 +717,7 @@ static int32_t krig_fit_enqueue(gss_krig* h, const FitPlan& fp, hipStream_t s) {
     GSS_TRY(dev_zero_bytes(S, sizeof(double) * (size_t)szS, s));
     // Fd (n x nc, column-major): drift functions at the data locations
     if (h->nz > 0) {   // cokriging: one indicator column per variable
-      hipLaunchKernelGGL(cokrig_indicator_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                         h->covar.as<int>(), (int)n, nc, Fd);
-      GSS_HIP(hipGetLastError());
+      GSS_TRY(cokrig_fit_indicators(h, Fd, s));
     } else {
       GSS_TRY(launch_drift_rows(h, h->xdata.as<double>(), h->drift_data.as<double>(), n, n, Fd, n, nc, s));
     }
@@ -988,9 +739,7 @@ static int32_t krig_fit_enqueue(gss_krig* h, const FitPlan& fp, hipStream_t s) {
   GSS_TRY(dev_zero_bytes(zz, sizeof(double) * (size_t)(2 * ldw), s));
   GSS_TRY(dev_copy_f64(zz, h->z.as<double>(), n, s));
   if (h->nz > 0) {
-    if (h->variant == GSS_KRIG_SIMPLE)
-      hipLaunchKernelGGL(cokrig_center_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, zz,
-                         h->covar.as<int>(), h->cotab.as<double>(), (int)n);
+    if (h->variant == GSS_KRIG_SIMPLE) cokrig_fit_center(h, zz, s);
   } else if (h->variant == GSS_KRIG_SIMPLE && h->sk_mean != 0.0) {
     hipLaunchKernelGGL(sub_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, zz, n, h->sk_mean);
   }
@@ -1015,7 +764,7 @@ static int32_t krig_factor_alloc(gss_krig* h) {
   return h->factor.alloc(sizeof(double) * (size_t)(h->ldw * h->N1pad + h->N1pad));
 }
 
-static int32_t krig_factorize(gss_krig* h, hipStream_t s, bool async = false) {
+int32_t gss::krig_factorize(gss_krig* h, hipStream_t s, bool async) {
   GSS_TRY(krig_factor_alloc(h));
   hipStream_t fs = s;
   if (async) {
@@ -1047,13 +796,13 @@ static int32_t krig_factorize(gss_krig* h, hipStream_t s, bool async = false) {
 }
 
 // device side of the join: what `s` receives next runs behind the fit
-static int32_t krig_join_device(gss_krig* h, hipStream_t s) {
+int32_t gss::krig_join_device(gss_krig* h, hipStream_t s) {
   if (h->fit_pending && h->fit_done && h->fit_stream != s) GSS_HIP(hipStreamWaitEvent(s, h->fit_done, 0));
   return GSS_OK;
 }
 
 // Joins a pending fit: waits for it, reads the two status words, releases the workspace.
-static int32_t krig_fit_wait(gss_krig* h) {
+int32_t gss::krig_fit_wait(gss_krig* h) {
   if (!h->fit_pending) return GSS_OK;
   h->fit_pending = false;
   GSS_HIP(hipEventSynchronize(h->fit_done));
@@ -1100,7 +849,7 @@ static int32_t krig_fit_wait(gss_krig* h) {
 // mv rounded up to 256 columns assembled).  Whole rounds of 512 resident workgroups (2 per CU) run one workgroup per
 // strip; the remainder strips would occupy a full extra round, so they run as (strip, row block) units, which pack ~3x
 // tighter.
-static void launch_krig_quadform(const gss_krig* h, const double* Rws, int64_t ldr, double c00, double mean0,
+void gss::launch_krig_quadform(const gss_krig* h, const double* Rws, int64_t ldr, double c00, double mean0,
                                  int64_t mv, int64_t cols, double* mean_out, double* var_out, uint8_t* stp,
                                  double* qpart, hipStream_t s) {
   const int nstrips = (int)(cols / BN);
@@ -1125,7 +874,7 @@ static void launch_krig_quadform(const gss_krig* h, const double* Rws, int64_t l
 }
 
 // the quadratic form keeps 4 LDS stages: above the default limit of a launch, raised once per device
-static int32_t krig_quadform_attrs() {
+int32_t gss::krig_quadform_attrs() {
   static uint64_t attr_set = 0;
   if (first_on_this_device(attr_set)) {
     GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(krig_quadform_kernel<false>),
@@ -1136,12 +885,17 @@ static int32_t krig_quadform_attrs() {
   return GSS_OK;
 }
 
-// entry points that know one variable only
-static int32_t krig_refuse_cokrig(const gss_krig* h, const char* who) {
-  GSS_REQUIRE(h->nz == 0, "%s: the handle is a cokriging system over %d variables; its estimates come from "
-              "gss_cokrig_predict_global and gss_cokrig_predict_knn (cross-validation: gss_krig_cv_global, "
-              "gss_krig_cv_global_folds, gss_cokrig_cv_knn)", who, h->nz);
-  return GSS_OK;
+int32_t gss::krig_upload_samples(const Frame& fr, const double* xhost, int64_t n, int dim, DevBuf* x, DevBuf* xraw,
+                                 hipStream_t s) {
+  const size_t bytes = sizeof(double) * (size_t)(n * dim);
+  GSS_TRY(x->alloc(bytes));
+  if (!fr.on) {
+    GSS_HIP(hipMemcpyAsync(x->p, xhost, bytes, hipMemcpyHostToDevice, s));
+    return GSS_OK;
+  }
+  GSS_TRY(xraw->alloc(bytes));
+  GSS_HIP(hipMemcpyAsync(xraw->p, xhost, bytes, hipMemcpyHostToDevice, s));
+  return frame_apply_dev(fr, xraw->as<double>(), n, x->as<double>(), s);
 }
 
 extern "C" {
@@ -1232,15 +986,8 @@ int32_t gss_krig_create(gss_krig_t** out, const gss_variogram_t* vg, int32_t var
   h->ldw = round_up(h->N1 + 1, BM);
 
   hipStream_t s = to_stream(stream);
-  GSS_TRY(h->xdata.alloc(sizeof(double) * (size_t)(n * h->dim)));
   GSS_TRY(h->z.alloc(sizeof(double) * (size_t)n));
-  if (h->fr.on) {
-    GSS_TRY(h->xraw.alloc(sizeof(double) * (size_t)(n * h->dim)));
-    GSS_HIP(hipMemcpyAsync(h->xraw.p, xdata, sizeof(double) * n * h->dim, hipMemcpyHostToDevice, s));
-    GSS_TRY(frame_apply_dev(h->fr, h->xraw.as<double>(), n, h->xdata.as<double>(), s));
-  } else {
-    GSS_HIP(hipMemcpyAsync(h->xdata.p, xdata, sizeof(double) * n * h->dim, hipMemcpyHostToDevice, s));
-  }
+  GSS_TRY(krig_upload_samples(h->fr, xdata, n, h->dim, &h->xdata, &h->xraw, s));
   GSS_HIP(hipMemcpyAsync(h->z.p, z, sizeof(double) * n, hipMemcpyHostToDevice, s));
   if (variant == GSS_KRIG_EXTDRIFT) {
     GSS_TRY(h->drift_data.alloc(sizeof(double) * (size_t)(n * ndrift)));
@@ -1307,44 +1054,24 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
   int64_t mc = krig_chunk_points(h->N1pad, m);
   // host arrays: pieces of the call (two rounds of resident workgroups of the quadratic form each) overlap their
   // transfers with the computation of their neighbours
-  HostPipe pipe;
-  GSS_TRY(pipe.begin(mem, m, s));
-  const bool piped = pipe.on;
-  const int64_t piece = HostPipe::PIECE;
-  if (piped && piece >= 256 && mc > piece) mc = piece;
+  DomainCall dc;
+  Staged& sx = *dc.in(xdom, sizeof(double) * dim);
+  Staged& sd = *dc.in(h->variant == GSS_KRIG_EXTDRIFT ? drift_dom : nullptr, sizeof(double) * h->ndrift);
+  Staged& smean = *dc.out(mean, sizeof(double));
+  Staged& svar = *dc.out(var, sizeof(double));
+  Staged& sstat = *dc.out(status, 1);
+  GSS_TRY(dc.begin(mem, m, s, true, &h->fr));
+  if (dc.piped && mc > HostPipe::PIECE) mc = HostPipe::PIECE;
   double *Rws = nullptr, *mpart = nullptr;
   GSS_TRY(krig_workspace(h->N1pad, mc, s, &Rws, &mpart));
   const int64_t ldr = mc;
   const int seg_len = (int)((h->n + NSEG - 1) / NSEG);
 
-  Staged sx, sd, smean, svar, sstat;
-  if (piped) {
-    GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
-    if (h->variant == GSS_KRIG_EXTDRIFT)
-      GSS_TRY(sd.out(const_cast<double*>(drift_dom), sizeof(double) * m * h->ndrift, mem));
-  } else {
-    GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
-    if (h->variant == GSS_KRIG_EXTDRIFT) GSS_TRY(sd.in(drift_dom, sizeof(double) * m * h->ndrift, mem, s));
-  }
-  GSS_TRY(smean.out(mean, sizeof(double) * m, mem));
-  GSS_TRY(svar.out(var, sizeof(double) * m, mem));
-  GSS_TRY(sstat.out(status, (size_t)m, mem));
-  if (piped) {
-    pipe.add_in(xdom, sx.p, sizeof(double) * dim);
-    if (h->variant == GSS_KRIG_EXTDRIFT) pipe.add_in(drift_dom, sd.p, sizeof(double) * h->ndrift);
-    pipe.add_out(mean, smean.p, sizeof(double));
-    pipe.add_out(var, svar.p, sizeof(double));
-    pipe.add_out(status, sstat.p, 1);
-    pipe.frame = &h->fr;   // rotated variogram: each piece moves into the frame where it lands
-  }
-  FrameCopy xfr;
-  if (!piped) GSS_TRY(xfr.of(h->fr, &sx, m, s));
-
   for (int64_t off = 0; off < m; off += mc) {
     const int64_t mv = (m - off) < mc ? (m - off) : mc;
     const int64_t cols = round_up(mv, 256);  // multiple of BN as well
     const double* x0 = sx.as<double>() + off * dim;
-    GSS_TRY(pipe.fetch(off, mv, s));
+    GSS_TRY(dc.pipe.fetch(off, mv, s));
     const int nblk = (int)(cols / 256);
     const int nrows = (int)(h->N1pad - h->n);
     {
@@ -1380,374 +1107,10 @@ int32_t gss_krig_predict_global(gss_krig_t* h, const double* xdom, const double*
                            mpart, s);
     }
     GSS_HIP(hipGetLastError());
-    GSS_TRY(pipe.deliver(off, mv, s));
+    GSS_TRY(dc.pipe.deliver(off, mv, s));
   }
-  if (piped) {
-    GSS_TRY(pipe.finish(s));
-  } else {
-    GSS_TRY(smean.back(mean, sizeof(double) * m, mem, s));
-    GSS_TRY(svar.back(var, sizeof(double) * m, mem, s));
-    GSS_TRY(sstat.back(status, (size_t)m, mem, s));
-  }
+  GSS_TRY(dc.finish(s));
   return krig_fit_wait(h);   // status of an asynchronous fit (it finished while the assembly ran)
-}
-
-
-// ---- cokriging (gss.h) -----------------------------------------------------------------------------------------------
-// Points per chunk of a cokriging call: the workspace holds nz blocks of N1pad rows.  GSS_COKRIG_CHUNK_POINTS caps it
-// (tests: a chunk loop that runs more than once at a small size).
-static int64_t cokrig_chunk_points(int64_t N1pad, int nz, int64_t m) {
-  int64_t mc = krig_chunk_points(N1pad * nz, m);
-  if (const char* e = std::getenv("GSS_COKRIG_CHUNK_POINTS")) {
-    int64_t cap = std::atoll(e) / 256 * 256;
-    if (cap > 0 && cap < mc) mc = cap;
-  }
-  return mc;
-}
-
-// the handle's samples grouped by variable, as the moving-neighbourhood drivers take them (cokrig.h)
-static void cokrig_grouped(const gss_krig* h, CoGrouped* g) {
-  g->x = h->co_xg.as<double>();
-  g->x_raw = h->co_xg_raw.as<double>();
-  g->zres = h->co_zres.as<double>();
-  g->row = h->co_row.as<int>();
-  g->tab = h->cotab.as<double>();
-  g->nz = h->nz;
-  for (int a = 0; a <= CO_MAXZ; ++a) g->off[a] = h->co_off[a];
-}
-
-// The body of both creators.  factor: fit the global system (gss_cokrig_create) or keep the samples only
-// (gss_cokrig_create_local); who: the entry point the messages name.
-static int32_t cokrig_create_impl(const char* who, bool factor, gss_krig_t** out, const gss_variogram_t* structure,
-                                  int32_t nz, const double* b0, const double* b1, int32_t variant, const double* means,
-                                  const double* xdata, const double* z, const int32_t* var, int64_t n, int32_t flags,
-                                  void* stream) {
-  GSS_REQUIRE(out != nullptr, "%s: out is NULL", who);
-  *out = nullptr;
-  GSS_REQUIRE(structure != nullptr, "%s: structure is NULL", who);
-  GSS_REQUIRE(nz >= 1 && nz <= CO_MAXZ, "%s: nz = %d outside 1 .. %d", who, nz, CO_MAXZ);
-  GSS_REQUIRE(b0 != nullptr && b1 != nullptr, "%s: b0 or b1 is NULL", who);
-  if (structure->kind == GSS_VG_POWER) {
-    set_error("%s: a power structure has no sill, the coregionalisation model needs one", who);
-    return GSS_ERR_UNSUPPORTED;
-  }
-  GSS_REQUIRE(structure->nextra == 0, "%s: one structure plus nugget (nextra = %d)", who, structure->nextra);
-  if (variant == GSS_KRIG_UNIVERSAL || variant == GSS_KRIG_EXTDRIFT) {
-    set_error("%s: cokriging with a drift is not available (simple and ordinary only)", who);
-    return GSS_ERR_UNSUPPORTED;
-  }
-  GSS_REQUIRE(variant == GSS_KRIG_SIMPLE || variant == GSS_KRIG_ORDINARY, "unknown kriging variant %d", variant);
-  GSS_REQUIRE((flags & GSS_KRIG_NO_FACTOR) == 0, "%s: GSS_KRIG_NO_FACTOR is refused: a handle without a factor, for the "
-              "moving neighbourhood only, comes from gss_cokrig_create_local", who);
-  if (!factor && nz > COL_MAXZ) {
-    set_error("%s: nz = %d: the moving neighbourhood takes at most %d variables (2 nz + 1 right-hand-side columns ride "
-              "along in one 16-column tile)", who, nz, COL_MAXZ);
-    return GSS_ERR_UNSUPPORTED;
-  }
-  GSS_REQUIRE(variant != GSS_KRIG_SIMPLE || means != nullptr, "%s: simple cokriging needs means[nz]", who);
-  GSS_REQUIRE(xdata != nullptr && z != nullptr && var != nullptr, "%s: NULL data", who);
-  GSS_REQUIRE(n >= 1, "all samples are missing, aborting...");
-  GSS_REQUIRE(n < (1 << 30), "too many samples");
-
-  // the coefficient table: b1 symmetrised (so that the system block and the right-hand sides read the same numbers
-  // whichever index comes first), c0 = b0 + b1, the means
-  double tab[CO_TAB] = {};
-  double big = 0.0;
-  for (int e = 0; e < nz * nz; ++e) {
-    GSS_REQUIRE(std::isfinite(b0[e]) && std::isfinite(b1[e]), "%s: b0 / b1 entry [%d][%d] is not finite", who,
-                e / nz, e % nz);
-    big = std::fmax(big, std::fmax(std::fabs(b0[e]), std::fabs(b1[e])));
-  }
-  for (int a = 0; a < nz; ++a)
-    for (int b = 0; b < nz; ++b) {
-      GSS_REQUIRE(std::fabs(b0[a * nz + b] - b0[b * nz + a]) <= 1e-12 * big,
-                  "%s: b0 is not symmetric at [%d][%d]", who, a, b);
-      GSS_REQUIRE(std::fabs(b1[a * nz + b] - b1[b * nz + a]) <= 1e-12 * big,
-                  "%s: b1 is not symmetric at [%d][%d]", who, a, b);
-      const double s1 = 0.5 * (b1[a * nz + b] + b1[b * nz + a]), s0 = 0.5 * (b0[a * nz + b] + b0[b * nz + a]);
-      tab[a * CO_MAXZ + b] = s1;
-      tab[CO_C0 + a * CO_MAXZ + b] = s0 + s1;
-    }
-  for (int a = 0; a < nz; ++a)
-    GSS_REQUIRE(tab[CO_C0 + a * CO_MAXZ + a] > 0.0, "%s: variable %d has no positive sill "
-                "b0[%d][%d] + b1[%d][%d]", who, a, a, a, a, a);
-  if (variant == GSS_KRIG_SIMPLE)
-    for (int a = 0; a < nz; ++a) {
-      GSS_REQUIRE(std::isfinite(means[a]), "%s: means[%d] is not finite", who, a);
-      tab[CO_MEANS + a] = means[a];
-    }
-
-  gss_krig* h = new (std::nothrow) gss_krig();
-  if (!h) return GSS_ERR_ALLOC;
-  struct Guard {
-    gss_krig* h;
-    ~Guard() { delete h; }
-  } guard{h};
-  gss_variogram_t unit = *structure, plain;   // rho: sill 1, no nugget
-  unit.sill = 1.0;
-  unit.nugget = 0.0;
-  GSS_TRY(vg_frame_split(&unit, &plain, &h->fr));
-  GSS_TRY(make_vgdev(&plain, &h->vg));
-  const int dim = h->vg.dim;
-  int64_t per[CO_MAXZ] = {};
-  for (int64_t i = 0; i < n; ++i) {
-    GSS_REQUIRE(var[i] >= 0 && var[i] < nz, "%s: variable id %d of sample %lld outside 0 .. %d", who, var[i],
-                (long long)i, nz - 1);
-    GSS_REQUIRE(std::isfinite(z[i]), "%s: value of sample %lld is not finite", who, (long long)i);
-    for (int k = 0; k < dim; ++k)
-      GSS_REQUIRE(std::isfinite(xdata[i * dim + k]), "%s: coordinate %d of sample %lld is not finite", who, k,
-                  (long long)i);
-    ++per[var[i]];
-  }
-  if (variant == GSS_KRIG_ORDINARY)
-    for (int a = 0; a < nz; ++a)
-      GSS_REQUIRE(per[a] >= 1, "%s: variable %d has no sample (ordinary cokriging needs one "
-                  "unbiasedness row per variable)", who, a);
-
-  GSS_TRY(frame_origin(&h->fr, xdata, GSS_MEM_HOST, nullptr));
-  h->variant = variant;
-  h->dim = dim;
-  h->n = n;
-  h->nz = nz;
-  for (int a = 0; a < nz; ++a) {
-    h->c00[a] = tab[CO_C0 + a * CO_MAXZ + a];
-    h->means[a] = tab[CO_MEANS + a];
-  }
-  std::memset(&h->ds, 0, sizeof(h->ds));
-  h->ds.variant = variant;
-  h->ds.dim = dim;
-  for (int k = 0; k < 3; ++k) h->ds.inv_scale[k] = 1.0;
-  h->nc = variant == GSS_KRIG_ORDINARY ? nz : 0;
-  h->ds.nc = h->nc;
-  h->N1 = n + h->nc;
-  h->N1pad = round_up(h->N1 + 1, BK);   // (the spare row of the dual weights: gss_krig_create)
-  h->ldw = round_up(h->N1 + 1, BM);
-
-  hipStream_t s = to_stream(stream);
-  GSS_TRY(h->xdata.alloc(sizeof(double) * (size_t)(n * dim)));
-  GSS_TRY(h->z.alloc(sizeof(double) * (size_t)n));
-  GSS_TRY(h->covar.alloc(sizeof(int32_t) * (size_t)n));
-  GSS_TRY(h->cotab.alloc(sizeof(tab)));
-  if (h->fr.on) {
-    GSS_TRY(h->xraw.alloc(sizeof(double) * (size_t)(n * dim)));
-    GSS_HIP(hipMemcpyAsync(h->xraw.p, xdata, sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
-    GSS_TRY(frame_apply_dev(h->fr, h->xraw.as<double>(), n, h->xdata.as<double>(), s));
-  } else {
-    GSS_HIP(hipMemcpyAsync(h->xdata.p, xdata, sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
-  }
-  GSS_HIP(hipMemcpyAsync(h->z.p, z, sizeof(double) * n, hipMemcpyHostToDevice, s));
-  GSS_HIP(hipMemcpyAsync(h->covar.p, var, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-  GSS_HIP(hipMemcpyAsync(h->cotab.p, tab, sizeof(tab), hipMemcpyHostToDevice, s));
-  // grouped by variable, the caller's order inside a variable: what the per-variable searches index
-  {
-    std::vector<double> xg((size_t)(n * dim)), zr((size_t)n);
-    std::vector<int32_t> row((size_t)n);
-    int64_t at[CO_MAXZ];
-    h->co_off[0] = 0;
-    for (int a = 0; a < CO_MAXZ; ++a) {
-      at[a] = h->co_off[a];
-      h->co_off[a + 1] = h->co_off[a] + per[a];
-    }
-    for (int64_t i = 0; i < n; ++i) {
-      const int64_t j = at[var[i]]++;
-      for (int k = 0; k < dim; ++k) xg[(size_t)(j * dim + k)] = xdata[i * dim + k];
-      zr[(size_t)j] = z[i] - tab[CO_MEANS + var[i]];
-      row[(size_t)j] = (int32_t)i;
-    }
-    GSS_TRY(h->co_xg.alloc(sizeof(double) * (size_t)(n * dim)));
-    GSS_TRY(h->co_zres.alloc(sizeof(double) * (size_t)n));
-    GSS_TRY(h->co_row.alloc(sizeof(int32_t) * (size_t)n));
-    if (h->fr.on) {
-      GSS_TRY(h->co_xg_raw.alloc(sizeof(double) * (size_t)(n * dim)));
-      GSS_HIP(hipMemcpyAsync(h->co_xg_raw.p, xg.data(), sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
-      GSS_TRY(frame_apply_dev(h->fr, h->co_xg_raw.as<double>(), n, h->co_xg.as<double>(), s));
-    } else {
-      GSS_HIP(hipMemcpyAsync(h->co_xg.p, xg.data(), sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
-    }
-    GSS_HIP(hipMemcpyAsync(h->co_zres.p, zr.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
-    GSS_HIP(hipMemcpyAsync(h->co_row.p, row.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    GSS_HIP(hipStreamSynchronize(s));   // tab and the grouped copies live on this frame
-  }
-  if (factor) {
-    const bool async = (flags & GSS_KRIG_ASYNC_FIT) != 0;
-    GSS_TRY(krig_factorize(h, s, async));
-    if (!async) GSS_TRY(krig_fit_wait(h));   // otherwise joined by the first call that needs the factor
-  }
-  guard.h = nullptr;
-  *out = h;
-  return GSS_OK;
-}
-
-int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
-                          const double* b1, int32_t variant, const double* means, const double* xdata,
-                          const double* z, const int32_t* var, int64_t n, int32_t flags, void* stream) {
-  GSS_ENTRY();
-  return cokrig_create_impl("gss_cokrig_create", true, out, structure, nz, b0, b1, variant, means, xdata, z, var, n,
-                            flags, stream);
-}
-
-int32_t gss_cokrig_create_local(gss_krig_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
-                                const double* b1, int32_t variant, const double* means, const double* xdata,
-                                const double* z, const int32_t* var, int64_t n, void* stream) {
-  GSS_ENTRY();
-  return cokrig_create_impl("gss_cokrig_create_local", false, out, structure, nz, b0, b1, variant, means, xdata, z, var,
-                            n, 0, stream);
-}
-
-int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, double* mean, double* variance,
-                                  uint8_t* status, int32_t mem, void* stream) {
-  GSS_ENTRY();
-  GSS_REQUIRE(h != nullptr, "NULL handle");
-  GSS_REQUIRE(h->nz > 0, "gss_cokrig_predict_global: the handle is not a cokriging system (gss_cokrig_create makes one)");
-  GSS_REQUIRE(h->factored, "handle has no factor");
-  GSS_REQUIRE(m >= 0 && (m == 0 || (xdom && mean && variance)), "gss_cokrig_predict_global: NULL array");
-  if (m == 0) return GSS_OK;
-  hipStream_t s = to_stream(stream);
-  const int dim = h->dim, nz = h->nz;
-  GSS_TRY(krig_quadform_attrs());
-
-  int64_t mc = cokrig_chunk_points(h->N1pad, nz, m);
-  HostPipe pipe;   // host arrays: pieces of the call overlap their transfers with the computation of their neighbours
-  GSS_TRY(pipe.begin(mem, m, s));
-  const bool piped = pipe.on;
-  if (piped && mc > HostPipe::PIECE) mc = HostPipe::PIECE;
-  double *Rws = nullptr, *mpart = nullptr;
-  GSS_TRY(krig_workspace(h->N1pad * nz, mc, s, &Rws, &mpart));
-  const int64_t ldr = mc, blk = h->N1pad * ldr;
-  const int seg_len = (int)((h->n + NSEG - 1) / NSEG);
-
-  Staged sx, smean, svar, sstat;
-  if (piped) GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
-  else GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
-  GSS_TRY(smean.out(mean, sizeof(double) * (size_t)(nz * m), mem));
-  GSS_TRY(svar.out(variance, sizeof(double) * (size_t)(nz * m), mem));
-  GSS_TRY(sstat.out(status, (size_t)(nz * m), mem));
-  if (piped) {
-    pipe.add_in(xdom, sx.p, sizeof(double) * dim);
-    for (int t = 0; t < nz; ++t) {   // column t of every output is an array of its own to the pipe
-      pipe.add_out(mean + t * m, smean.as<double>() + t * m, sizeof(double));
-      pipe.add_out(variance + t * m, svar.as<double>() + t * m, sizeof(double));
-      if (status) pipe.add_out(status + t * m, sstat.as<uint8_t>() + t * m, 1);
-    }
-    pipe.frame = &h->fr;   // rotated structure: each piece moves into the frame where it lands
-  }
-  FrameCopy xfr;
-  if (!piped) GSS_TRY(xfr.of(h->fr, &sx, m, s));
-
-  for (int64_t off = 0; off < m; off += mc) {
-    const int64_t mv = (m - off) < mc ? (m - off) : mc;
-    const int64_t cols = round_up(mv, 256);  // multiple of BN as well
-    const double* x0 = sx.as<double>() + off * dim;
-    GSS_TRY(pipe.fetch(off, mv, s));
-    const int nblk = (int)(cols / 256);
-    const int nrows = (int)(h->N1pad - h->n);
-    {
-      ProfScope ps("cokrig_rhs", s);
-      const double* xd = h->xdata.as<double>();
-      const int* cv = h->covar.as<int>();
-      const double* tab = h->cotab.as<double>();
-      switch (dim) {
-        case 1: GSS_TRY(launch_cokrig_rhs<1>(s, h->vg, xd, cv, tab, nz, (int)h->n, x0, mv, Rws, ldr, blk, seg_len, nblk)); break;
-        case 2: GSS_TRY(launch_cokrig_rhs<2>(s, h->vg, xd, cv, tab, nz, (int)h->n, x0, mv, Rws, ldr, blk, seg_len, nblk)); break;
-        default: GSS_TRY(launch_cokrig_rhs<3>(s, h->vg, xd, cv, tab, nz, (int)h->n, x0, mv, Rws, ldr, blk, seg_len, nblk)); break;
-      }
-      hipLaunchKernelGGL(cokrig_tail_rows_kernel, dim3((unsigned)(cols / 256)), dim3(256), 0, s, Rws, ldr, blk,
-                         (int)h->n, h->nc, nrows, nz, cols);
-      GSS_HIP(hipGetLastError());
-    }
-    GSS_TRY(krig_join_device(h, s));   // an asynchronous fit ran beside the assembly; the quadratic form needs it
-    {
-      ProfScope pq("krig_quadform", s);
-      for (int t = 0; t < nz; ++t) {
-        uint8_t* stp = status ? sstat.as<uint8_t>() + t * m + off : nullptr;
-        launch_krig_quadform(h, Rws + t * blk, ldr, h->c00[t], h->means[t], mv, cols,
-                             smean.as<double>() + t * m + off, svar.as<double>() + t * m + off, stp, mpart, s);
-      }
-    }
-    GSS_HIP(hipGetLastError());
-    GSS_TRY(pipe.deliver(off, mv, s));
-  }
-  if (piped) {
-    GSS_TRY(pipe.finish(s));
-  } else {
-    GSS_TRY(smean.back(mean, sizeof(double) * (size_t)(nz * m), mem, s));
-    GSS_TRY(svar.back(variance, sizeof(double) * (size_t)(nz * m), mem, s));
-    GSS_TRY(sstat.back(status, (size_t)(nz * m), mem, s));
-  }
-  return krig_fit_wait(h);   // status of an asynchronous fit (it finished while the assembly ran)
-}
-
-int32_t gss_cokrig_predict_knn(gss_krig_t* h, const double* xdom, int64_t m, const int32_t* k, int32_t minneighbors,
-                               double radius, const double* inv_radii, int32_t metric, double metric_param,
-                               double* mean, double* variance, uint8_t* status, int32_t* idx_out, int32_t* count_out,
-                               int32_t mem, void* stream) {
-  GSS_ENTRY();
-  GSS_REQUIRE(h != nullptr, "NULL handle");
-  GSS_REQUIRE(h->nz > 0, "gss_cokrig_predict_knn: the handle is not a cokriging system (gss_cokrig_create and "
-              "gss_cokrig_create_local make one)");
-  const int nz = h->nz, dim = h->dim;
-  if (nz > COL_MAXZ) {
-    set_error("gss_cokrig_predict_knn: the handle holds %d variables, the moving neighbourhood takes at most %d", nz,
-              COL_MAXZ);
-    return GSS_ERR_UNSUPPORTED;
-  }
-  GSS_REQUIRE(k != nullptr, "gss_cokrig_predict_knn: k is NULL (one neighbour count per variable)");
-  int ksum = 0;
-  for (int a = 0; a < nz; ++a) {
-    const int64_t na = h->co_off[a + 1] - h->co_off[a];
-    GSS_REQUIRE(k[a] >= 1 && k[a] <= na, "gss_cokrig_predict_knn: k[%d] = %d outside 1 .. %lld, the sample count of "
-                "variable %d (a front-end clamps it; gss_cokrig_predict_global uses every sample)", a, k[a],
-                (long long)na, a);
-    ksum += k[a];
-  }
-  if (ksum > 64) {
-    set_error("gss_cokrig_predict_knn: %d neighbours in total, the tile kernel holds at most 64", ksum);
-    return GSS_ERR_UNSUPPORTED;
-  }
-  GSS_REQUIRE(m >= 0 && (m == 0 || (xdom && mean && variance)), "gss_cokrig_predict_knn: NULL array");
-
-  Searcher sr[COL_MAXZ];   // one per variable, over that variable's samples; all in the same frame
-  for (int a = 0; a < nz; ++a) GSS_TRY(sr[a].init(metric, metric_param, radius, inv_radii, dim, &h->fr));
-  if (m == 0) return GSS_OK;
-  hipStream_t s = to_stream(stream);
-  Staged sx, smean, svar, sstat, sidx, scnt;
-  HostPipe pipe;   // host arrays: in and out piece by piece beside the computation (gss_internal.h)
-  if (!sr[0].two_frames) GSS_TRY(pipe.begin(mem, m, s));   // two frames: the domain is needed twice, it comes in whole
-  if (pipe.on) GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
-  else GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
-  GSS_TRY(smean.out(mean, sizeof(double) * (size_t)(nz * m), mem));
-  GSS_TRY(svar.out(variance, sizeof(double) * (size_t)(nz * m), mem));
-  GSS_TRY(sstat.out(status, (size_t)(nz * m), mem));
-  GSS_TRY(sidx.out(idx_out, sizeof(int32_t) * (size_t)(m * ksum), mem));
-  GSS_TRY(scnt.out(count_out, sizeof(int32_t) * (size_t)(m * nz), mem));
-  if (pipe.on) {
-    pipe.add_in(xdom, sx.p, sizeof(double) * dim);
-    for (int t = 0; t < nz; ++t) {   // column t of every output is an array of its own to the pipe
-      pipe.add_out(mean + t * m, smean.as<double>() + t * m, sizeof(double));
-      pipe.add_out(variance + t * m, svar.as<double>() + t * m, sizeof(double));
-      if (status) pipe.add_out(status + t * m, sstat.as<uint8_t>() + t * m, 1);
-    }
-    pipe.add_out(idx_out, sidx.p, sizeof(int32_t) * (size_t)ksum);
-    pipe.add_out(count_out, scnt.p, sizeof(int32_t) * (size_t)nz);
-    pipe.frame = &h->fr;
-  }
-  CoGrouped g;
-  cokrig_grouped(h, &g);
-  for (int a = 0; a < nz; ++a)
-    GSS_TRY(sr[a].samples(g.x + g.off[a] * dim, g.x_raw ? g.x_raw + g.off[a] * dim : nullptr, g.off[a + 1] - g.off[a], s));
-  const double* x0_raw = sx.as<double>();   // as staged; the covariance-frame copy follows
-  FrameCopy xfr;
-  if (!pipe.on) GSS_TRY(xfr.of(h->fr, &sx, m, s));
-  GSS_TRY(cokrig_local_dev(h->vg, h->variant, dim, g, sr, k, minneighbors, sx.as<double>(),
-                           sr[0].two_frames ? x0_raw : nullptr, m, smean.as<double>(), svar.as<double>(),
-                           status ? sstat.as<uint8_t>() : nullptr, m, sidx.as<int>(), scnt.as<int>(), s, &pipe));
-  if (pipe.on) return GSS_OK;   // everything is home (cokrig_local_dev ends with pipe.finish)
-  GSS_TRY(smean.back(mean, sizeof(double) * (size_t)(nz * m), mem, s));
-  GSS_TRY(svar.back(variance, sizeof(double) * (size_t)(nz * m), mem, s));
-  GSS_TRY(sstat.back(status, (size_t)(nz * m), mem, s));
-  GSS_TRY(sidx.back(idx_out, sizeof(int32_t) * (size_t)(m * ksum), mem, s));
-  GSS_TRY(scnt.back(count_out, sizeof(int32_t) * (size_t)(m * nz), mem, s));
-  return GSS_OK;
 }
 
 int32_t gss_krig_set_block_support(gss_krig_t* h, const double* cell, int32_t nsub, void* stream) {
@@ -1804,48 +1167,22 @@ int32_t gss_krig_predict_knn(gss_krig_t* h, const double* xdom, const double* dr
   if (m == 0) return GSS_OK;
   hipStream_t s = to_stream(stream);
   const int dim = h->dim;
-  Staged sx, sd, smean, svar, sstat, sidx, scnt;
-  HostPipe pipe;   // host arrays: in and out piece by piece beside the computation (gss_internal.h)
-  if (!sr.two_frames) GSS_TRY(pipe.begin(mem, m, s));   // two frames: the domain is needed twice, it comes in whole
-  if (pipe.on) {
-    GSS_TRY(sx.out(const_cast<double*>(xdom), sizeof(double) * m * dim, mem));   // device scratch only
-    if (h->variant == GSS_KRIG_EXTDRIFT)
-      GSS_TRY(sd.out(const_cast<double*>(drift_dom), sizeof(double) * m * h->ndrift, mem));
-  } else {
-    GSS_TRY(sx.in(xdom, sizeof(double) * m * dim, mem, s));
-    if (h->variant == GSS_KRIG_EXTDRIFT) GSS_TRY(sd.in(drift_dom, sizeof(double) * m * h->ndrift, mem, s));
-  }
-  GSS_TRY(smean.out(mean, sizeof(double) * m, mem));
-  GSS_TRY(svar.out(var, sizeof(double) * m, mem));
-  GSS_TRY(sstat.out(status, (size_t)m, mem));
-  GSS_TRY(sidx.out(idx_out, sizeof(int32_t) * (size_t)(m * k), mem));
-  GSS_TRY(scnt.out(count_out, sizeof(int32_t) * (size_t)m, mem));
-  if (pipe.on) {
-    pipe.add_in(xdom, sx.p, sizeof(double) * dim);
-    if (h->variant == GSS_KRIG_EXTDRIFT) pipe.add_in(drift_dom, sd.p, sizeof(double) * h->ndrift);
-    pipe.add_out(mean, smean.p, sizeof(double));
-    pipe.add_out(var, svar.p, sizeof(double));
-    pipe.add_out(status, sstat.p, 1);
-    pipe.add_out(idx_out, sidx.p, sizeof(int32_t) * (size_t)k);
-    pipe.add_out(count_out, scnt.p, sizeof(int32_t));
-    pipe.frame = &h->fr;
-  }
   GSS_TRY(sr.samples(h->xdata.as<double>(), h->xraw.as<double>(), h->n, s));
-  const double* x0_raw = sx.as<double>();   // as staged; the covariance-frame copy follows
-  FrameCopy xfr;
-  if (!pipe.on) GSS_TRY(xfr.of(h->fr, &sx, m, s));
+  DomainCall dc;   // host arrays: in and out piece by piece beside the computation (gss_internal.h)
+  dc.in(xdom, sizeof(double) * dim);
+  Staged& sd = *dc.in(h->variant == GSS_KRIG_EXTDRIFT ? drift_dom : nullptr, sizeof(double) * h->ndrift);
+  Staged& smean = *dc.out(mean, sizeof(double));
+  Staged& svar = *dc.out(var, sizeof(double));
+  Staged& sstat = *dc.out(status, 1);
+  Staged& sidx = *dc.out(idx_out, sizeof(int32_t) * (size_t)k);
+  Staged& scnt = *dc.out(count_out, sizeof(int32_t));
+  GSS_TRY(dc.begin(mem, m, s, !sr.two_frames, &h->fr));   // two frames: the domain is needed twice, it comes in whole
   GSS_TRY(krig_local_dev(h->vg, h->variant, h->nc, dim, &h->ds.e[0][0], h->ds.inv_scale[0], h->sk_mean, sr,
-                         h->xdata.as<double>(), h->z.as<double>(), h->drift_data.as<double>(), sx.as<double>(),
-                         sr.two_frames ? x0_raw : nullptr, sd.as<double>(), m, k, minneighbors, smean.as<double>(),
-                         svar.as<double>(), sstat.as<uint8_t>(), sidx.as<int>(), scnt.as<int>(), s, &pipe,
+                         h->xdata.as<double>(), h->z.as<double>(), h->drift_data.as<double>(), dc.x(),
+                         sr.two_frames ? dc.x_raw : nullptr, sd.as<double>(), m, k, minneighbors, smean.as<double>(),
+                         svar.as<double>(), sstat.as<uint8_t>(), sidx.as<int>(), scnt.as<int>(), s, &dc.pipe,
                          h->block_nsub, h->block_cell, h->block_cvv));
-  if (pipe.on) return GSS_OK;   // everything is home (krig_local_dev ends with pipe.finish)
-  GSS_TRY(smean.back(mean, sizeof(double) * m, mem, s));
-  GSS_TRY(svar.back(var, sizeof(double) * m, mem, s));
-  GSS_TRY(sstat.back(status, (size_t)m, mem, s));
-  GSS_TRY(sidx.back(idx_out, sizeof(int32_t) * (size_t)(m * k), mem, s));
-  GSS_TRY(scnt.back(count_out, sizeof(int32_t) * (size_t)m, mem, s));
-  return GSS_OK;
+  return dc.finish(s);   // (piped: krig_local_dev ended with pipe.finish, everything is home)
 }
 
 
@@ -1914,209 +1251,8 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
     GSS_HIP(hipGetLastError());
   }
   GSS_HIP(hipGetLastError());
-  GSS_TRY(so.back(mean_out, sizeof(double) * (size_t)(nbatch * m), mem, s));
+  GSS_TRY(so.back(s));
   GSS_HIP(hipStreamSynchronize(s));  // Zm / U / WD are freed on return
-  return GSS_OK;
-}
-
-// ---- cross-validation (gss.h): every sample predicted from samples outside its own fold ------------------------------
-int32_t gss_krig_cv_global(gss_krig_t* h, double* pred, double* var, uint8_t* status, int32_t mem, void* stream) {
-  GSS_ENTRY();
-  GSS_REQUIRE(h != nullptr, "NULL handle");
-  GSS_REQUIRE(h->factored, "gss_krig_cv_global: the handle has no factor (created with GSS_KRIG_NO_FACTOR and never "
-                           "adopted one); gss_krig_cv_knn works without");
-  GSS_REQUIRE(h->block_nsub == 0, "cross-validation is at point support: the handle has block support set");
-  GSS_REQUIRE(pred && var, "gss_krig_cv_global: NULL array");
-  hipStream_t s = to_stream(stream);
-  GSS_TRY(krig_join_device(h, s));
-  GSS_TRY(krig_fit_wait(h));   // an asynchronous fit: its status (GSS_ERR_NOT_POSDEF) is reported here
-  const int64_t n = h->n;
-  Staged sp, sv, sst;
-  GSS_TRY(sp.out(pred, sizeof(double) * (size_t)n, mem));
-  GSS_TRY(sv.out(var, sizeof(double) * (size_t)n, mem));
-  GSS_TRY(sst.out(status, (size_t)n, mem));
-  {
-    ProfScope ps("krig_loo", s);
-    hipLaunchKernelGGL(krig_loo_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, h->Wp(), h->ldw, (int)n,
-                       (int)h->N1, h->wd(), h->z.as<double>(), sp.as<double>(), sv.as<double>(), sst.as<uint8_t>());
-    GSS_HIP(hipGetLastError());
-  }
-  GSS_TRY(sp.back(pred, sizeof(double) * (size_t)n, mem, s));
-  GSS_TRY(sv.back(var, sizeof(double) * (size_t)n, mem, s));
-  GSS_TRY(sst.back(status, (size_t)n, mem, s));
-  return GSS_OK;
-}
-
-// Folds under the global neighbourhood: the block form of the identity above, e_F = (B_FF)^-1 wd_F (crossval_folds.hip)
-int32_t gss_krig_cv_global_folds(gss_krig_t* h, const int32_t* fold, double* pred, double* var, uint8_t* status,
-                                 int32_t mem, void* stream) {
-  GSS_ENTRY();
-  if (fold == nullptr) return gss_krig_cv_global(h, pred, var, status, mem, stream);
-  GSS_REQUIRE(h != nullptr, "NULL handle");
-  GSS_REQUIRE(h->factored, "gss_krig_cv_global_folds: the handle has no factor (created with GSS_KRIG_NO_FACTOR and "
-                           "never adopted one); gss_krig_cv_knn works without");
-  GSS_REQUIRE(h->block_nsub == 0, "cross-validation is at point support: the handle has block support set");
-  GSS_REQUIRE(pred && var, "gss_krig_cv_global_folds: NULL array");
-  hipStream_t s = to_stream(stream);
-  GSS_TRY(krig_join_device(h, s));
-  GSS_TRY(krig_fit_wait(h));   // an asynchronous fit: its status (GSS_ERR_NOT_POSDEF) is reported here
-  const int64_t n = h->n;
-  std::vector<int32_t> fh;
-  const int32_t* fhost = fold;
-  if (mem != GSS_MEM_HOST) {   // the samples are grouped by fold on the host
-    fh.resize((size_t)n);
-    GSS_HIP(hipMemcpyAsync(fh.data(), fold, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-    GSS_HIP(hipStreamSynchronize(s));
-    fhost = fh.data();
-  }
-  for (int64_t i = 0; i < n; ++i)
-    GSS_REQUIRE(fhost[i] >= 0, "gss_krig_cv_global_folds: fold id %d of sample %lld is negative", fhost[i], (long long)i);
-  Staged sp, sv, sst;
-  GSS_TRY(sp.out(pred, sizeof(double) * (size_t)n, mem));
-  GSS_TRY(sv.out(var, sizeof(double) * (size_t)n, mem));
-  GSS_TRY(sst.out(status, (size_t)n, mem));
-  GSS_TRY(cv_global_folds_dev(h->Wp(), h->ldw, n, h->N1, h->nc, h->variant == GSS_KRIG_SIMPLE, h->wd(),
-                              h->z.as<double>(), fhost, sp.as<double>(), sv.as<double>(), sst.as<uint8_t>(), s));
-  GSS_TRY(sp.back(pred, sizeof(double) * (size_t)n, mem, s));
-  GSS_TRY(sv.back(var, sizeof(double) * (size_t)n, mem, s));
-  GSS_TRY(sst.back(status, (size_t)n, mem, s));
-  return GSS_OK;
-}
-
-int32_t gss_krig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radius, int32_t k, int32_t minneighbors,
-                        double radius, const double* inv_radii, int32_t metric, double metric_param, double* pred,
-                        double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out, int32_t mem,
-                        void* stream) {
-  GSS_ENTRY();
-  GSS_REQUIRE(h != nullptr, "NULL handle");
-  GSS_TRY(krig_refuse_cokrig(h, "gss_krig_cv_knn"));
-  if (metric == GSS_METRIC_HAVERSINE) {
-    set_error("cross-validation under the haversine distance is not available: the fold search runs on the k-d index, "
-              "which that key has no box bounds for (DESIGN.md section 7)");
-    return GSS_ERR_UNSUPPORTED;
-  }
-  Searcher sr;
-  GSS_TRY(sr.init(metric, metric_param, radius, inv_radii, h->dim, &h->fr));
-  GSS_REQUIRE(h->block_nsub == 0, "cross-validation is at point support: the handle has block support set");
-  GSS_REQUIRE(pred && var, "gss_krig_cv_knn: NULL array");
-  const int64_t n = h->n;
-  GSS_REQUIRE(k >= 1 && k <= n - 1, "gss_krig_cv_knn: maxneighbors %d outside 1..n-1 = %lld (a sample is never its own "
-                                    "neighbour)", k, (long long)(n - 1));
-  GSS_REQUIRE(!(exclude_radius != exclude_radius), "gss_krig_cv_knn: exclude_radius is NaN");
-  hipStream_t s = to_stream(stream);
-  const int dim = h->dim;
-  Staged sf, smean, svar, sstat, sidx, scnt;
-  if (fold) {
-    std::vector<int32_t> fh;
-    const int32_t* fhost = fold;
-    if (mem != GSS_MEM_HOST) {   // the ids are checked before any kernel indexes by them
-      fh.resize((size_t)n);
-      GSS_HIP(hipMemcpyAsync(fh.data(), fold, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-      GSS_HIP(hipStreamSynchronize(s));
-      fhost = fh.data();
-    }
-    for (int64_t i = 0; i < n; ++i)
-      GSS_REQUIRE(fhost[i] >= 0, "gss_krig_cv_knn: fold id %d of sample %lld is negative", fhost[i], (long long)i);
-    GSS_TRY(sf.in(fold, sizeof(int32_t) * (size_t)n, mem, s));
-  }
-  GSS_TRY(smean.out(pred, sizeof(double) * (size_t)n, mem));
-  GSS_TRY(svar.out(var, sizeof(double) * (size_t)n, mem));
-  GSS_TRY(sstat.out(status, (size_t)n, mem));
-  GSS_TRY(sidx.out(idx_out, sizeof(int32_t) * (size_t)(n * k), mem));
-  GSS_TRY(scnt.out(count_out, sizeof(int32_t) * (size_t)n, mem));
-  GSS_TRY(sr.samples(h->xdata.as<double>(), h->xraw.as<double>(), n, s));
-  // the exclusion ball in the search key: squared (and scaled like the ball) for the Euclidean family, else as it is
-  const double ex = exclude_radius < 0.0 ? -1.0 : (sr.metric == GSS_METRIC_EUCLIDEAN ? exclude_radius * exclude_radius
-                                                                                     : exclude_radius);
-  const int* fold_dev = fold ? sf.as<int>() : nullptr;   // the samples are the queries: one array serves both
-  const KnnMask mask(KnnMask::Fold{fold_dev, fold_dev, 0, ex});
-  // the queries are the samples themselves: covariance frame, raw frame for a search in a second one, own drift rows
-  // (xraw only exists beside a rotated variogram; without one xdata holds the coordinates as given)
-  const double* xq_raw = h->fr.on ? h->xraw.as<double>() : h->xdata.as<double>();
-  GSS_TRY(krig_local_dev(h->vg, h->variant, h->nc, dim, &h->ds.e[0][0], h->ds.inv_scale[0], h->sk_mean, sr,
-                         h->xdata.as<double>(), h->z.as<double>(), h->drift_data.as<double>(), h->xdata.as<double>(),
-                         sr.two_frames ? xq_raw : nullptr, h->drift_data.as<double>(), n, k, minneighbors,
-                         smean.as<double>(), svar.as<double>(), sstat.as<uint8_t>(), sidx.as<int>(), scnt.as<int>(), s,
-                         nullptr, 0, nullptr, 0.0, &mask));
-  GSS_TRY(smean.back(pred, sizeof(double) * (size_t)n, mem, s));
-  GSS_TRY(svar.back(var, sizeof(double) * (size_t)n, mem, s));
-  GSS_TRY(sstat.back(status, (size_t)n, mem, s));
-  GSS_TRY(sidx.back(idx_out, sizeof(int32_t) * (size_t)(n * k), mem, s));
-  GSS_TRY(scnt.back(count_out, sizeof(int32_t) * (size_t)n, mem, s));
-  return GSS_OK;
-}
-
-int32_t gss_cokrig_cv_knn(gss_krig_t* h, const int32_t* fold, double exclude_radius, const int32_t* k,
-                          int32_t minneighbors, double radius, const double* inv_radii, int32_t metric,
-                          double metric_param, double* pred, double* var, uint8_t* status, int32_t* idx_out,
-                          int32_t* count_out, int32_t mem, void* stream) {
-  GSS_ENTRY();
-  GSS_REQUIRE(h != nullptr, "NULL handle");
-  GSS_REQUIRE(h->nz > 0, "gss_cokrig_cv_knn: the handle is not a cokriging system (gss_cokrig_create and "
-              "gss_cokrig_create_local make one; one variable: gss_krig_cv_knn)");
-  const int nz = h->nz, dim = h->dim;
-  if (nz > COL_MAXZ) {
-    set_error("gss_cokrig_cv_knn: the handle holds %d variables, the moving neighbourhood takes at most %d", nz,
-              COL_MAXZ);
-    return GSS_ERR_UNSUPPORTED;
-  }
-  if (metric == GSS_METRIC_HAVERSINE) {
-    set_error("gss_cokrig_cv_knn: cross-validation under the haversine distance is not available: the fold search runs "
-              "on the k-d index, which that key has no box bounds for (DESIGN.md section 7)");
-    return GSS_ERR_UNSUPPORTED;
-  }
-  GSS_REQUIRE(k != nullptr, "gss_cokrig_cv_knn: k is NULL (one neighbour count per variable)");
-  int ksum = 0;
-  for (int a = 0; a < nz; ++a) {
-    const int64_t na = h->co_off[a + 1] - h->co_off[a];
-    GSS_REQUIRE(k[a] >= 1 && k[a] <= na, "gss_cokrig_cv_knn: k[%d] = %d outside 1 .. %lld, the sample count of "
-                "variable %d (a front-end clamps it)", a, k[a], (long long)na, a);
-    ksum += k[a];
-  }
-  if (ksum > 64) {
-    set_error("gss_cokrig_cv_knn: %d neighbours in total, the tile kernel holds at most 64", ksum);
-    return GSS_ERR_UNSUPPORTED;
-  }
-  GSS_REQUIRE(!(exclude_radius != exclude_radius), "gss_cokrig_cv_knn: exclude_radius is NaN");
-  GSS_REQUIRE(pred && var, "gss_cokrig_cv_knn: NULL array");
-  Searcher sr[COL_MAXZ];   // one per variable, over that variable's samples; all in the same frame
-  for (int a = 0; a < nz; ++a) GSS_TRY(sr[a].init(metric, metric_param, radius, inv_radii, dim, &h->fr));
-  hipStream_t s = to_stream(stream);
-  const int64_t n = h->n;
-  Staged sf, smean, svar, sstat, sidx, scnt;
-  if (fold) {
-    std::vector<int32_t> fh;
-    const int32_t* fhost = fold;
-    if (mem != GSS_MEM_HOST) {   // the ids are checked before any kernel compares them
-      fh.resize((size_t)n);
-      GSS_HIP(hipMemcpyAsync(fh.data(), fold, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-      GSS_HIP(hipStreamSynchronize(s));
-      fhost = fh.data();
-    }
-    for (int64_t i = 0; i < n; ++i)
-      GSS_REQUIRE(fhost[i] >= 0, "gss_cokrig_cv_knn: fold id %d of sample %lld is negative", fhost[i], (long long)i);
-    GSS_TRY(sf.in(fold, sizeof(int32_t) * (size_t)n, mem, s));
-  }
-  GSS_TRY(smean.out(pred, sizeof(double) * (size_t)n, mem));
-  GSS_TRY(svar.out(var, sizeof(double) * (size_t)n, mem));
-  GSS_TRY(sstat.out(status, (size_t)n, mem));
-  GSS_TRY(sidx.out(idx_out, sizeof(int32_t) * (size_t)(n * ksum), mem));
-  GSS_TRY(scnt.out(count_out, sizeof(int32_t) * (size_t)(n * nz), mem));
-  CoGrouped g;
-  cokrig_grouped(h, &g);
-  for (int a = 0; a < nz; ++a)
-    GSS_TRY(sr[a].samples(g.x + g.off[a] * dim, g.x_raw ? g.x_raw + g.off[a] * dim : nullptr, g.off[a + 1] - g.off[a], s));
-  // the exclusion ball in the search key: squared (and scaled like the ball) for the Euclidean family, else as it is
-  const double ex = exclude_radius < 0.0 ? -1.0 : (sr[0].metric == GSS_METRIC_EUCLIDEAN ? exclude_radius * exclude_radius
-                                                                                        : exclude_radius);
-  GSS_TRY(cokrig_cv_dev(h->vg, h->variant, dim, g, sr, k, minneighbors, fold ? sf.as<int>() : nullptr, ex,
-                        smean.as<double>(), svar.as<double>(), status ? sstat.as<uint8_t>() : nullptr,
-                        idx_out ? sidx.as<int>() : nullptr, count_out ? scnt.as<int>() : nullptr, s));
-  GSS_TRY(smean.back(pred, sizeof(double) * (size_t)n, mem, s));
-  GSS_TRY(svar.back(var, sizeof(double) * (size_t)n, mem, s));
-  GSS_TRY(sstat.back(status, (size_t)n, mem, s));
-  GSS_TRY(sidx.back(idx_out, sizeof(int32_t) * (size_t)(n * ksum), mem, s));
-  GSS_TRY(scnt.back(count_out, sizeof(int32_t) * (size_t)(n * nz), mem, s));
   return GSS_OK;
 }
 

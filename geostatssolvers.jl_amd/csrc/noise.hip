@@ -59,7 +59,7 @@ int32_t gss_philox_uniform(uint64_t seed, int64_t real, int64_t n, double* out, 
   Staged so;
   GSS_TRY(so.out(out, sizeof(double) * n, mem));
   GSS_TRY(philox_uniform_dev(seed, real, n, so.as<double>(), n, n, s));
-  return so.back(out, sizeof(double) * n, mem, s);
+  return so.back(s);
 }
 
 int32_t gss_philox_normal(uint64_t seed, int64_t real, int64_t n, double* out, int32_t mem, void* stream) {
@@ -69,7 +69,7 @@ int32_t gss_philox_normal(uint64_t seed, int64_t real, int64_t n, double* out, i
   Staged so;
   GSS_TRY(so.out(out, sizeof(double) * n, mem));
   GSS_TRY(philox_normal_dev(seed, real, n, so.as<double>(), s));
-  return so.back(out, sizeof(double) * n, mem, s);
+  return so.back(s);
 }
 
 }  // extern "C"

@@ -239,6 +239,39 @@ def test_host_and_device_arrays_give_identical_bits():
         assert np.array_equal(a.cpu().numpy(), b, equal_nan=True)
 
 
+@pytest.mark.parametrize("name", ["tiles_8_8", "rotated"])
+def test_host_arrays_past_one_piece(name):
+    """Host arrays longer than one piece of the host pipeline (131072 points; the last piece holds 300): the domain comes
+    in and all five outputs leave piece by piece, and with the rotated structure every fetched piece is moved into the
+    frame where it lands.  Model of the named small case over 300 + 1000 samples, k = (3, 4).  Equal bit for bit to the
+    same call on device tensors (whole arrays; test_chunks: the answers do not depend on the chunking), and 64 of the
+    points, the last one among them, agree with the reference."""
+    import torch
+    small = LC.CASES[name]()
+    rng = np.random.default_rng(3100)
+    loc = CC.lattice((37, 36), 10.0, 3101)
+    loc = loc[rng.permutation(loc.shape[0])[:1300]]
+    var = rng.permutation(np.repeat([0, 1], [300, 1000]))
+    m = 131072 + 300
+    xdom = rng.uniform(15.0, 335.0, (m, 2))
+    c = LC._case(small["structure"], small["B0"], small["B1"], loc, var, xdom, (3, 4), 3102)
+    h = handle_of(c)
+    got = run(h, c)
+    dev = run(h, c, torch.as_tensor(c["xdom"], device="cuda"))
+    torch.cuda.synchronize()
+    h.close()
+    assert all(isinstance(a, np.ndarray) for a in got)
+    assert got[0].shape == got[1].shape == got[2].shape == (2, m) and got[3].shape == (m, 7) and got[4].shape == (m, 2)
+    for a, b in zip(got, dev):
+        assert np.array_equal(a, b.cpu().numpy(), equal_nan=True)
+    sel = np.concatenate([np.sort(rng.permutation(m - 1)[:63]), [m - 1]])
+    rmu, rvar, rst, ridx, rcnt = LR.predict(LR.Model(c["structure"], c["B0"], c["B1"]), c["x"], c["z"], c["var"],
+                                            c["xdom"][sel], c["k"], c["variant"], c["means"], **c["search"])
+    assert (sel > 131072).any() and (sel < 131072).any()
+    assert np.array_equal(got[3][sel], ridx) and np.array_equal(got[4][sel], rcnt) and np.array_equal(got[2][:, sel], rst)
+    assert close(got[0][:, sel], rmu) and close(got[1][:, sel], rvar)
+
+
 def test_chunks():
     """m = 600 under a cap of 256 points: three chunks, equal to the one-chunk answer bit for bit."""
     assert agrees("chunks")

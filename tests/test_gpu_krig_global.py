@@ -307,8 +307,8 @@ def test_asynchronous_fit_same_results_and_status_at_the_first_prediction():
 
 def test_host_arrays_in_pieces_equal_device_arrays():
     """Host arrays beyond 131 072 points are handed over in pieces whose transfers overlap the computation of their
-    neighbours (krig.hip, HOST_PIPE_POINTS): same results as one call on device arrays, also with a last piece that is
-    not full, external drifts riding along, and with the switch off."""
+    neighbours (common.hip: DomainCall, HostPipe::PIECE): same results as one call on device arrays, also with a last
+    piece that is not full, external drifts riding along, and with the switch off."""
     import os
     import subprocess
     import sys

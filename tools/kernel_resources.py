@@ -20,15 +20,15 @@ for co in code_objects(path):
     cur = {}
     rows = []
     for line in out.splitlines():
-        m = re.search(r"\.(name|vgpr_count|sgpr_count|group_segment_fixed_size|vgpr_spill_count|private_segment_fixed_size|"
-                      r"max_flat_workgroup_size):\s+(\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "name":
+        # an entry of amdhsa.kernels opens with "  - .<first key>:" and lists its keys in alphabetical order, so the
+        # LDS size comes in front of the name: a record runs from one opening line to the next, not from name to name
+        if re.match(r"  - \.", line):
             if cur.get("name") and "vgpr_count" in cur:
                 rows.append(cur)
-            cur = {"name": m.group(2)} if not m.group(2).endswith(".kd") else cur
-        else:
+            cur = {}
+        m = re.match(r"    \.(name|vgpr_count|sgpr_count|group_segment_fixed_size|vgpr_spill_count|"
+                     r"private_segment_fixed_size|max_flat_workgroup_size):\s+(\S+)", line)
+        if m:
             cur[m.group(1)] = m.group(2)
     if cur.get("name") and "vgpr_count" in cur:
         rows.append(cur)
