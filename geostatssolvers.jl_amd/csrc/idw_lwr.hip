@@ -7,13 +7,19 @@
 //   * k <= 64     : K4 (k-d ordered exact k-NN) then one wave per estimation point, lane = neighbour;
 //   * k == n > 64 : "all samples" (maxneighbors = nothing): no search at all, one thread per estimation
 //                   point sweeping the samples staged through LDS (broadcast reads).
+// Cross-validation (gss_idw_cv / gss_lwr_cv, gss.h): the same two paths with the samples as estimation points -- the
+// fold-aware search in front of the list kernels, and for k == n a self-join with an eligibility test per pair
+// (est_cv_all_kernel, idw_cv_all_fast_kernel).
 // LWR solves its (d+1) x (d+1) normal equations about the estimation point (same predictor, better conditioned
 // than the raw coordinates the reference uses) with an unpivoted Cholesky; a non-positive pivot is reported as
 // GSS_PT_SINGULAR where the reference's `\` would throw.
+#include "cv_fold.h"
 #include "gss_internal.h"
 
 #include <climits>
+#include <cstdlib>
 #include <cstring>
+#include <vector>
 
 namespace gss {
 
@@ -576,6 +582,284 @@ __global__ __launch_bounds__(256) void lwr_all_fast_kernel(double wa, const doub
 }
 
 // ---------------------------------------------------------------------------------------------
+// cross-validation, k == n: the self-join of the samples (gss.h, gss_idw_cv / gss_lwr_cv).  Query p of a launch is
+// sample qoff + p; sample j is eligible for it iff fold[j] != fold[qoff + p], key(p, j) > ex (ex = -1: no exclusion
+// ball; every key is >= 0) and, with a neighbourhood ball, key(p, j) <= r2.  `fold` is never NULL here: for
+// leave-one-out the driver passes the samples' indices (est_cv_iota_kernel).  Outputs are the launch's own slices
+// (column c of the estimates at mean_out + c * sp.ldm).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void est_cv_iota_kernel(int* __restrict__ out, int n) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j < n) out[j] = j;
+}
+
+// The reference's default IDW cross-validated: Euclidean, no ball, no exclusion radius, exponent 1 or 2, one column.
+// Written like idw_all_fast_kernel: the sample index is wave-uniform, so coordinates, value and fold id arrive
+// through the scalar cache as scalar operands.  The weight of an ineligible sample is selected to zero, never multiplied
+// by it -- the query's own sample has d^2 = 0 and the NaN of the Newton step would pass through a product -- and its
+// d^2 is kept out of the running minimum.  A NaN or infinite sum therefore means a coincident ELIGIBLE sample, and the
+// rescan for the first one applies the same test.
+template <int DIM, bool E1>
+__global__ __launch_bounds__(256) void idw_cv_all_fast_kernel(const double* __restrict__ xdata,
+                                                              const double* __restrict__ z,
+                                                              const int* __restrict__ fold, int n, int64_t qoff,
+                                                              int64_t m, int minneighbors,
+                                                              double* __restrict__ mean_out,
+                                                              double* __restrict__ aux_out,
+                                                              uint8_t* __restrict__ status_out) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = p < m;
+  const int64_t g = live ? qoff + p : qoff;   // (qoff < n: a launch has at least one query)
+  double qc[DIM];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) qc[a] = xdata[g * DIM + a];
+  const int myfold = fold[g];
+  double sw = 0.0, swz = 0.0, dmin2 = __builtin_huge_val();
+  int cnt = 0;
+#pragma unroll 8
+  for (int j = 0; j < n; ++j) {
+    double d2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+      const double t = xdata[(int64_t)j * DIM + a] - qc[a];
+      d2 = fma(t, t, d2);
+    }
+    const bool in = fold[j] != myfold;
+    cnt += in ? 1 : 0;
+    dmin2 = fmin(dmin2, in ? d2 : __builtin_huge_val());
+    double y;
+    if (E1) {
+      y = __builtin_amdgcn_rsq(d2);
+      const double hh = 0.5 * d2;
+      y = fma(y, fma(-hh * y, y, 0.5), y);
+      y = fma(y, fma(-hh * y, y, 0.5), y);
+    } else {
+      y = __builtin_amdgcn_rcp(d2);
+      y = fma(y, fma(-d2, y, 1.0), y);
+      y = fma(y, fma(-d2, y, 1.0), y);
+    }
+    const double w = in ? y : 0.0;
+    sw += w;
+    swz = fma(w, z[j], swz);
+  }
+  if (!live) return;
+  const double NaN = __builtin_nan("");
+  double mu = swz / sw, dist = gss_sqrt(dmin2);
+  if (!(sw < __builtin_huge_val())) {  // NaN (coincident eligible sample) or overflow: the first coincident value
+    for (int j = 0; j < n; ++j) {
+      double d2 = 0.0;
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        const double t = xdata[(int64_t)j * DIM + a] - qc[a];
+        d2 = fma(t, t, d2);
+      }
+      if (fold[j] != myfold && d2 == 0.0) {
+        mu = z[j];
+        dist = 0.0;
+        break;
+      }
+    }
+  }
+  const bool enough = cnt >= minneighbors && cnt >= 1;
+  mean_out[p] = enough ? mu : NaN;
+  aux_out[p] = enough ? dist : NaN;
+  status_out[p] = enough ? GSS_PT_OK : GSS_PT_MISSING;
+}
+
+// The general self-join: est_all_kernel with the eligibility test.  The samples are staged through LDS in EST_TILE
+// pieces with their fold ids beside them; the mask is one predicate per pair, the same in every sweep.
+template <int DIM, int ZC>
+__global__ __launch_bounds__(256) void est_cv_all_kernel(EstSpec sp, const double* __restrict__ xdata,
+                                                         const double* __restrict__ z,
+                                                         const int* __restrict__ fold, int n, int64_t qoff, int64_t m,
+                                                         int minneighbors, double ex, double r2, int use_ball,
+                                                         int aniso, double ir0, double ir1, double ir2,
+                                                         double* __restrict__ mean_out, double* __restrict__ aux_out,
+                                                         uint8_t* __restrict__ status_out) {
+  __shared__ double sx[EST_TILE * DIM];
+  __shared__ double sz[ZC][EST_TILE];
+  __shared__ int sf[EST_TILE];
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = p < m;
+  const int64_t g = live ? qoff + p : qoff;
+  const double ir[3] = {ir0, ir1, ir2};
+  const double NaN = __builtin_nan("");
+  double qc[DIM];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) qc[a] = xdata[g * DIM + a];
+  const int myfold = fold[g];
+  constexpr int NP = DIM + 1, NT = NP * (NP + 1) / 2;
+  const bool euclid = sp.metric == GSS_METRIC_EUCLIDEAN;
+
+  for (int c0 = 0; c0 < sp.nz; c0 += ZC) {
+  const int ncz = (sp.nz - c0) < ZC ? (sp.nz - c0) : ZC;
+  const double* zc = z + (int64_t)c0 * sp.ldz;
+  double* mo = mean_out + (int64_t)c0 * sp.ldm;
+  int cnt = 0;
+  double dmax2 = 0.0, dmin2 = __builtin_huge_val();
+  double sw = 0.0, swz[ZC], zzero[ZC];
+#pragma unroll
+  for (int c = 0; c < ZC; ++c) swz[c] = zzero[c] = 0.0;
+  bool haszero = false;
+  // sweep 1: IDW sums (complete) / LWR farthest eligible sample
+  for (int t0 = 0; t0 < n; t0 += EST_TILE) {
+    const int tn = (n - t0) < EST_TILE ? (n - t0) : EST_TILE;
+    __syncthreads();
+    for (int e = threadIdx.x; e < tn * DIM; e += 256) sx[e] = xdata[(int64_t)t0 * DIM + e];
+    for (int e = threadIdx.x; e < tn; e += 256) sf[e] = fold[t0 + e];
+#pragma unroll
+    for (int c = 0; c < ZC; ++c)
+      if (c < ncz)
+        for (int e = threadIdx.x; e < tn; e += 256) sz[c][e] = zc[(int64_t)c * sp.ldz + t0 + e];
+    __syncthreads();
+    if (sp.method == 0 && euclid && (sp.exponent == 1.0 || sp.exponent == 2.0)) {
+      // exponent 1 and 2: branch-free, 1 / d from v_rsq_f64 and 1 / d^2 from v_rcp_f64 (two Newton steps each)
+      const bool e1 = sp.exponent == 1.0;
+#pragma unroll 4
+      for (int j = 0; j < tn; ++j) {
+        const double d2 = sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0);
+        const bool in = sf[j] != myfold && d2 > ex && (!use_ball || d2 <= r2);
+        const bool zero = in && d2 == 0.0;
+        cnt += in ? 1 : 0;
+        dmin2 = (in && d2 < dmin2) ? d2 : dmin2;
+#pragma unroll
+        for (int c = 0; c < ZC; ++c) zzero[c] = (zero && !haszero && c < ncz) ? sz[c][j] : zzero[c];
+        haszero = haszero || zero;
+        double y;
+        if (e1) {
+          y = __builtin_amdgcn_rsq(d2);
+          const double hh = 0.5 * d2;
+          y = fma(y, fma(-hh * y, y, 0.5), y);
+          y = fma(y, fma(-hh * y, y, 0.5), y);
+        } else {
+          y = __builtin_amdgcn_rcp(d2);
+          y = fma(y, fma(-d2, y, 1.0), y);
+          y = fma(y, fma(-d2, y, 1.0), y);
+        }
+        const double w = (in && !zero) ? y : 0.0;
+        sw += w;
+#pragma unroll
+        for (int c = 0; c < ZC; ++c)
+          if (c < ncz) swz[c] = fma(w, sz[c][j], swz[c]);
+      }
+      continue;
+    }
+    if (sp.method == 1 && euclid) {  // LWR, first sweep: farthest eligible sample and count
+#pragma unroll 4
+      for (int j = 0; j < tn; ++j) {
+        const double d2 = sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0);
+        const bool in = sf[j] != myfold && d2 > ex && (!use_ball || d2 <= r2);
+        cnt += in ? 1 : 0;
+        dmax2 = (in && d2 > dmax2) ? d2 : dmax2;
+      }
+      continue;
+    }
+    for (int j = 0; j < tn; ++j) {
+      const double d2 = est_key<DIM>(sp.metric, &sx[j * DIM], qc, ir, aniso != 0);
+      if (!(sf[j] != myfold && d2 > ex && (!use_ball || d2 <= r2))) continue;
+      ++cnt;
+      dmax2 = d2 > dmax2 ? d2 : dmax2;
+      dmin2 = d2 < dmin2 ? d2 : dmin2;
+      if (sp.method == 0) {
+        if (d2 == 0.0) {
+          if (!haszero) {
+#pragma unroll
+            for (int c = 0; c < ZC; ++c)
+              if (c < ncz) zzero[c] = sz[c][j];
+          }
+          haszero = true;
+        } else {
+          const double dd = metric_dist(sp.metric, d2, sp.mparam);
+          const double w = idw_weight(dd, euclid ? d2 : dd * dd, sp.exponent);
+          sw += w;
+#pragma unroll
+          for (int c = 0; c < ZC; ++c)
+            if (c < ncz) swz[c] += w * sz[c][j];
+        }
+      }
+    }
+  }
+  const bool enough = cnt >= minneighbors && cnt >= 1;
+  if (sp.method == 0) {
+    if (live) {
+#pragma unroll
+      for (int c = 0; c < ZC; ++c)
+        if (c < ncz) mo[(int64_t)c * sp.ldm + p] = !enough ? NaN : (haszero ? zzero[c] : swz[c] / sw);
+      if (c0 == 0) {
+        aux_out[p] = !enough ? NaN : (haszero ? 0.0 : metric_dist(sp.metric, dmin2, sp.mparam));
+        status_out[p] = enough ? GSS_PT_OK : GSS_PT_MISSING;
+      }
+    }
+    continue;
+  }
+  // sweep 2 (LWR): moments with delta = d / dmax over the same eligible samples
+  const double dmax = metric_dist(sp.metric, dmax2, sp.mparam);
+  double S1[NT], S2[NT], b[ZC][NP];
+#pragma unroll
+  for (int e = 0; e < NT; ++e) S1[e] = S2[e] = 0.0;
+#pragma unroll
+  for (int c = 0; c < ZC; ++c)
+#pragma unroll
+    for (int e = 0; e < NP; ++e) b[c][e] = 0.0;
+  for (int t0 = 0; t0 < n; t0 += EST_TILE) {
+    const int tn = (n - t0) < EST_TILE ? (n - t0) : EST_TILE;
+    __syncthreads();
+    for (int e = threadIdx.x; e < tn * DIM; e += 256) sx[e] = xdata[(int64_t)t0 * DIM + e];
+    for (int e = threadIdx.x; e < tn; e += 256) sf[e] = fold[t0 + e];
+#pragma unroll
+    for (int c = 0; c < ZC; ++c)
+      if (c < ncz)
+        for (int e = threadIdx.x; e < tn; e += 256) sz[c][e] = zc[(int64_t)c * sp.ldz + t0 + e];
+    __syncthreads();
+    const bool gauss_w = sp.wkind == GSS_WEIGHT_EXP && sp.wp == 2.0;  // exp(-a delta^2): no square root needed
+    const double inv_dmax2 = 1.0 / dmax2;
+    for (int j = 0; j < tn; ++j) {
+      const double d2 = euclid ? sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0)
+                               : est_key<DIM>(sp.metric, &sx[j * DIM], qc, ir, aniso != 0);
+      if (!(sf[j] != myfold && d2 > ex && (!use_ball || d2 <= r2))) continue;
+      double w;
+      if (euclid && gauss_w) w = gss_exp(-sp.wa * (d2 * inv_dmax2));
+      else if (euclid) w = lwr_weight(sp.wkind, sp.wa, sp.wp, gss_sqrt(d2 * inv_dmax2));
+      else w = lwr_weight(sp.wkind, sp.wa, sp.wp, metric_dist(sp.metric, d2, sp.mparam) / dmax);
+      double u[NP];
+      u[0] = 1.0;
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) u[a + 1] = sx[j * DIM + a] - qc[a];
+#pragma unroll
+      for (int r = 0; r < NP; ++r) {
+        const double wu = w * u[r];
+#pragma unroll
+        for (int c = 0; c < ZC; ++c)
+          if (c < ncz) b[c][r] += wu * sz[c][j];
+#pragma unroll
+        for (int q = 0; q <= r; ++q) {
+          const double t = wu * u[q];
+          S1[r * (r + 1) / 2 + q] += t;
+          S2[r * (r + 1) / 2 + q] += w * t;
+        }
+      }
+    }
+  }
+  if (live) {
+    bool ok = enough && dmax > 0.0;
+    double var = 0.0;
+#pragma unroll
+    for (int c = 0; c < ZC; ++c) {
+      if (c < ncz) {
+        double mu = 0.0;
+        ok = ok && lwr_solve<NP>(S1, S2, b[c], &mu, &var);
+        mo[(int64_t)c * sp.ldm + p] = ok ? mu : NaN;
+      }
+    }
+    if (c0 == 0) {
+      aux_out[p] = ok ? var : NaN;
+      status_out[p] = !enough ? GSS_PT_MISSING : (ok ? GSS_PT_OK : GSS_PT_SINGULAR);
+    }
+  }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // 64 < k < n: one thread per estimation point walks its neighbour list (m x k, ascending key, written by the
 // passes of the search).  Same sums, in the same (ascending-distance) order, as est_knn_kernel.
 // ---------------------------------------------------------------------------------------------
@@ -704,33 +988,56 @@ __global__ __launch_bounds__(256) void est_list_kernel(EstSpec sp, const double*
   }
 }
 
+// Cross-validation on the list estimators (gss_idw_cv / gss_lwr_cv, k < n): the centres are the samples themselves
+// (x0 = sr.xs, m = n) and the search of every chunk takes the fold mask of its queries.
+struct EstCv {
+  KnnMask mask;                // KnnMask::Fold over the samples
+  int *idx_out, *count_out;    // the lists of the call (n x k, n) where the caller asked for them, else NULL
+};
+
+// GSS_EST_CV_CHUNK caps the samples per chunk of a cross-validation call (tests: a chunk loop that runs more than once
+// at a small size)
+static int64_t est_cv_chunk_cap(int64_t chunk) {
+  if (const char* e = std::getenv("GSS_EST_CV_CHUNK")) {
+    const int64_t cap = std::atoll(e);
+    if (cap > 0 && cap < chunk) chunk = cap;
+  }
+  return chunk;
+}
+
 // xdata / x0: samples and domain on the Searcher's frame, which the weights are evaluated on as well
 static int32_t est_local_dev(const EstSpec& sp, Searcher& sr, const double* z, const double* x0, int64_t m, int k,
                              int minneighbors, double* mean, double* aux, uint8_t* status, hipStream_t s,
-                             HostPipe* pipe = nullptr /* k <= 64 only */) {
+                             HostPipe* pipe = nullptr /* k <= 64 only */, const EstCv* cv = nullptr /* k < n only */) {
   const double* xdata = sr.xs;
   const int64_t n = sr.n;
   const int dim = sr.dim, use_ball = sr.use_ball, aniso = sr.aniso;
   const double r2 = sr.r2;
   const double* ir = sr.ir;
-  const char* pname = sp.method == 0 ? "idw" : "lwr";
+  const char* pname = sp.method == 0 ? (cv ? "idw_cv" : "idw") : (cv ? "lwr_cv" : "lwr");
+  int* const idx_out = cv ? cv->idx_out : nullptr;
+  int* const count_out = cv ? cv->count_out : nullptr;
 
   if (k > 64 && (int64_t)k < n) {
     // 65 .. n - 1 neighbours (ui.jl:16-23 accepts any count): the search runs in passes of 64, the estimator walks
     // the lists with one thread per point
-    const int64_t chunk = k > 512 ? (1 << 16) : (1 << 19);
+    int64_t chunk = k > 512 ? (1 << 16) : (1 << 19);
+    if (cv) chunk = est_cv_chunk_cap(chunk);
     DevBuf idx_s, cnt_s;
-    GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
-    GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(m < chunk ? m : chunk)));
+    if (!idx_out) GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
+    if (!count_out) GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(m < chunk ? m : chunk)));
     for (int64_t off = 0; off < m; off += chunk) {
       const int64_t mv = (m - off) < chunk ? (m - off) : chunk;
+      int* idx = idx_out ? idx_out + off * k : idx_s.as<int>();
+      int* cnt = count_out ? count_out + off : cnt_s.as<int>();
       {
         ProfScope ps("knn", s);
-        GSS_TRY(sr.query(x0 + off * dim, nullptr, mv, k, idx_s.as<int>(), cnt_s.as<int>(), s));
+        const KnnMask mk = cv ? cv->mask.from(off) : KnnMask();   // cross-validation: the query folds of this chunk
+        GSS_TRY(sr.query(x0 + off * dim, nullptr, mv, k, idx, cnt, s, cv ? &mk : nullptr));
       }
       ProfScope pl(pname, s);
       const dim3 grid((unsigned)((mv + 255) / 256));
-#define GSS_EST_LIST_ARGS sp, xdata, z, x0 + off * dim, mv, k, minneighbors, idx_s.as<int>(), cnt_s.as<int>(), aniso, \
+#define GSS_EST_LIST_ARGS sp, xdata, z, x0 + off * dim, mv, k, minneighbors, idx, cnt, aniso, \
                           ir[0], ir[1], ir[2], mean + off, aux + off, status + off, 0
 #define GSS_EST_LIST(D)                                                                                      \
   if (sp.nz > 1) hipLaunchKernelGGL((est_list_kernel<D, 4>), grid, dim3(256), 0, s, GSS_EST_LIST_ARGS);      \
@@ -796,19 +1103,23 @@ static int32_t est_local_dev(const EstSpec& sp, Searcher& sr, const double* z, c
   }
 
   const bool piped = pipe && pipe->on;   // host arrays of the domain arrive and leave piece by piece (gss_internal.h)
-  const int64_t chunk = piped ? HostPipe::PIECE : (1 << 20);
+  int64_t chunk = piped ? HostPipe::PIECE : (1 << 20);
+  if (cv) chunk = est_cv_chunk_cap(chunk);
   DevBuf idx_s, cnt_s;
-  GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
-  GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(m < chunk ? m : chunk)));
+  if (!idx_out) GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
+  if (!count_out) GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(m < chunk ? m : chunk)));
   for (int64_t off = 0; off < m; off += chunk) {
     const int64_t mv = (m - off) < chunk ? (m - off) : chunk;
+    int* idx = idx_out ? idx_out + off * k : idx_s.as<int>();
+    int* cnt = count_out ? count_out + off : cnt_s.as<int>();
     if (piped) GSS_TRY(pipe->fetch(off, mv, s));
     {
       ProfScope ps("knn", s);
-      GSS_TRY(sr.query(x0 + off * dim, nullptr, mv, k, idx_s.as<int>(), cnt_s.as<int>(), s));
+      const KnnMask mk = cv ? cv->mask.from(off) : KnnMask();   // cross-validation: the query folds of this chunk
+      GSS_TRY(sr.query(x0 + off * dim, nullptr, mv, k, idx, cnt, s, cv ? &mk : nullptr));
     }
     ProfScope pl(pname, s);
-#define GSS_EST_KNN_ARGS sp, xdata, z, x0 + off * dim, mv, k, minneighbors, idx_s.as<int>(), cnt_s.as<int>(), aniso, \
+#define GSS_EST_KNN_ARGS sp, xdata, z, x0 + off * dim, mv, k, minneighbors, idx, cnt, aniso, \
                          ir[0], ir[1], ir[2], mean + off, aux + off, status + off
     if (k <= 16) {  // sixteen lanes per point, sixteen points per workgroup
       dim3 grid((unsigned)((mv + 15) / 16));
@@ -876,6 +1187,126 @@ static int32_t est_predict(EstSpec sp, const double* xdata, const double* z, int
                         &dc.pipe));
   GSS_TRY(dc.finish(s));   // (piped: est_local_dev ended with pipe.finish and a synchronisation, everything is home)
   if (!status) GSS_HIP(hipStreamSynchronize(s));  // st_own is released on return
+  return GSS_OK;
+}
+
+// Cross-validation with every eligible sample (k == n): the self-join kernels over the samples on the Searcher's frame.
+// fold: the caller's ids on the device, or NULL for leave-one-out (the indices are written out once).
+static int32_t est_cv_all_dev(const EstSpec& sp, const Searcher& sr, const double* z, const int* fold, double ex,
+                              int minneighbors, double* mean, double* aux, uint8_t* status, hipStream_t s) {
+  const double* xdata = sr.xs;
+  const int64_t n = sr.n;
+  const int dim = sr.dim, use_ball = sr.use_ball, aniso = sr.aniso;
+  const double r2 = sr.r2;
+  const double* ir = sr.ir;
+  DevBuf own;
+  if (!fold) {
+    GSS_TRY(own.alloc(sizeof(int) * (size_t)n));
+    hipLaunchKernelGGL(est_cv_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, own.as<int>(), (int)n);
+    GSS_HIP(hipGetLastError());
+    fold = own.as<int>();
+  }
+  ProfScope ps(sp.method == 0 ? "idw_cv" : "lwr_cv", s);   // the self-join alone, not the indices above
+  const bool fast = sp.nz == 1 && sp.method == 0 && sp.metric == GSS_METRIC_EUCLIDEAN && !use_ball && ex < 0.0 &&
+                    (sp.exponent == 1.0 || sp.exponent == 2.0);
+  const int64_t chunk = est_cv_chunk_cap(n);
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t mv = (n - off) < chunk ? (n - off) : chunk;
+    const dim3 grid((unsigned)((mv + 255) / 256));
+    if (fast) {
+#define GSS_IDW_CV_FAST(D)                                                                                         \
+  if (sp.exponent == 1.0)                                                                                          \
+    hipLaunchKernelGGL((idw_cv_all_fast_kernel<D, true>), grid, dim3(256), 0, s, xdata, z, fold, (int)n, off, mv,  \
+                       minneighbors, mean + off, aux + off, status + off);                                         \
+  else                                                                                                             \
+    hipLaunchKernelGGL((idw_cv_all_fast_kernel<D, false>), grid, dim3(256), 0, s, xdata, z, fold, (int)n, off, mv, \
+                       minneighbors, mean + off, aux + off, status + off)
+      switch (dim) {
+        case 1: GSS_IDW_CV_FAST(1); break;
+        case 2: GSS_IDW_CV_FAST(2); break;
+        default: GSS_IDW_CV_FAST(3); break;
+      }
+#undef GSS_IDW_CV_FAST
+    } else {
+#define GSS_EST_CV_ALL_ARGS sp, xdata, z, fold, (int)n, off, mv, minneighbors, ex, r2, use_ball, aniso, ir[0], ir[1], \
+                            ir[2], mean + off, aux + off, status + off
+#define GSS_EST_CV_ALL(D)                                                                                        \
+  if (sp.nz > 1) hipLaunchKernelGGL((est_cv_all_kernel<D, 4>), grid, dim3(256), 0, s, GSS_EST_CV_ALL_ARGS);      \
+  else hipLaunchKernelGGL((est_cv_all_kernel<D, 1>), grid, dim3(256), 0, s, GSS_EST_CV_ALL_ARGS)
+      switch (dim) {
+        case 1: GSS_EST_CV_ALL(1); break;
+        case 2: GSS_EST_CV_ALL(2); break;
+        default: GSS_EST_CV_ALL(3); break;
+      }
+#undef GSS_EST_CV_ALL
+#undef GSS_EST_CV_ALL_ARGS
+    }
+    GSS_HIP(hipGetLastError());
+  }
+  if (own.p) GSS_HIP(hipStreamSynchronize(s));   // the indices are released on return
+  return GSS_OK;
+}
+
+// gss_idw_cv / gss_lwr_cv (gss.h): every check that needs no device comes first
+static int32_t est_cv(EstSpec sp, const char* who, const double* xdata, const double* z, int64_t n, int32_t dim,
+                      int32_t nz, const int32_t* fold, double exclude_radius, int32_t k, int32_t minneighbors,
+                      double radius, const double* inv_radii, double* pred, double* aux, uint8_t* status,
+                      int32_t* idx_out, int32_t* count_out, int32_t mem, void* stream) {
+  GSS_REQUIRE(nz >= 1 && nz <= 4096, "%s: %d value columns: 1 .. 4096", who, nz);
+  sp.nz = nz;
+  sp.ldz = n;
+  sp.ldm = n;
+  GSS_REQUIRE(n >= 2 && n < INT_MAX, "%s: cross-validation needs at least two samples", who);
+  GSS_REQUIRE(dim >= 1 && dim <= 3, "%s: dim = %d outside 1..3", who, dim);
+  GSS_REQUIRE(k >= 1 && k <= n, "%s: maxneighbors %d outside 1..n = %lld (n: every eligible sample; a sample is never "
+                                "its own neighbour)", who, k, (long long)n);
+  GSS_REQUIRE(minneighbors <= k, "%s: invalid min/max number of neighbors", who);  // idw.jl:97, lwr.jl:99
+  GSS_REQUIRE(!(exclude_radius != exclude_radius), "%s: exclude_radius is NaN", who);
+  const bool all = (int64_t)k == n;
+  GSS_REQUIRE(!all || (!idx_out && !count_out), "%s: maxneighbors = n runs no search: idx_out / count_out must be NULL",
+              who);
+  if (!all && sp.metric == GSS_METRIC_HAVERSINE) {
+    set_error("cross-validation under the haversine distance is not available: the fold search runs on the k-d index, "
+              "which that key has no box bounds for (DESIGN.md section 7)");
+    return GSS_ERR_UNSUPPORTED;
+  }
+  Searcher sr;
+  GSS_TRY(sr.init(sp.metric, sp.mparam, radius, inv_radii, dim));
+  sp.metric = sr.metric;
+  GSS_REQUIRE(xdata && z && pred && aux, "%s: NULL array", who);
+  std::vector<int32_t> fh;
+  if (fold && mem == GSS_MEM_HOST) GSS_TRY(fold_ids_host(who, fold, n, mem, nullptr, &fh));
+  hipStream_t s = to_stream(stream);
+  if (fold && mem != GSS_MEM_HOST) GSS_TRY(fold_ids_host(who, fold, n, mem, s, &fh));
+  Staged sxd, sz, sf;
+  GSS_TRY(sxd.in(xdata, sizeof(double) * n * dim, mem, s));
+  if (sr.frame.on) GSS_TRY(frame_origin(&sr.frame, xdata, mem, s));   // a rotated ball: origin xdata[0]
+  GSS_TRY(sr.samples(sxd.as<double>(), nullptr, n, s));
+  GSS_TRY(sz.in(z, sizeof(double) * n * nz, mem, s));
+  if (fold) GSS_TRY(sf.in(fold, sizeof(int32_t) * (size_t)n, mem, s));
+  DomainCall dc;   // the outputs over the n samples (whole: nothing is piped)
+  Staged& smean = *dc.out(pred, sizeof(double), nz);
+  Staged &saux = *dc.out(aux, sizeof(double)), &sstat = *dc.out(status, 1);
+  Staged &sidx = *dc.out(idx_out, sizeof(int32_t) * (size_t)k), &scnt = *dc.out(count_out, sizeof(int32_t));
+  GSS_TRY(dc.begin(mem, n, s, false, nullptr));
+  DevBuf st_own;
+  uint8_t* st = sstat.as<uint8_t>();
+  if (!status) {
+    GSS_TRY(st_own.alloc((size_t)n));
+    st = st_own.as<uint8_t>();
+  }
+  const double ex = exclusion_key(exclude_radius, sr.metric);
+  const int* fold_dev = fold ? sf.as<int>() : nullptr;   // the samples are the queries: one array serves both
+  if (all) {
+    GSS_TRY(est_cv_all_dev(sp, sr, sz.as<double>(), fold_dev, ex, minneighbors, smean.as<double>(), saux.as<double>(),
+                           st, s));
+  } else {
+    const EstCv cv{KnnMask(KnnMask::Fold{fold_dev, fold_dev, 0, ex}), sidx.as<int>(), scnt.as<int>()};
+    GSS_TRY(est_local_dev(sp, sr, sz.as<double>(), sr.xs, n, k, minneighbors, smean.as<double>(), saux.as<double>(), st,
+                          s, nullptr, &cv));
+  }
+  GSS_TRY(dc.finish(s));
+  GSS_HIP(hipStreamSynchronize(s));  // the staged samples and st_own are released on return
   return GSS_OK;
 }
 
@@ -987,6 +1418,44 @@ int32_t gss_lwr_predict_cols(const double* xdata, const double* z, int64_t n, in
   sp.mparam = metric_param;
   return est_predict(sp, xdata, z, n, dim, nz, xdom, m, k, minneighbors, radius, inv_radii, mean, var, status, mem,
                      stream);
+}
+
+// ---- cross-validation (gss.h): every sample predicted from samples outside its own fold ------------------------------
+int32_t gss_idw_cv(const double* xdata, const double* z, int64_t n, int32_t dim, int32_t nz, const int32_t* fold,
+                   double exclude_radius, int32_t k, int32_t minneighbors, double radius, const double* inv_radii,
+                   int32_t metric, double metric_param, double exponent, double* pred, double* dist, uint8_t* status,
+                   int32_t* idx_out, int32_t* count_out, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(exponent > 0.0, "exponent must be positive");  // idw.jl:96
+  EstSpec sp;
+  std::memset(&sp, 0, sizeof(sp));
+  sp.method = 0;
+  sp.exponent = exponent;
+  sp.metric = metric;
+  sp.mparam = metric_param;
+  return est_cv(sp, "gss_idw_cv", xdata, z, n, dim, nz, fold, exclude_radius, k, minneighbors, radius, inv_radii, pred,
+                dist, status, idx_out, count_out, mem, stream);
+}
+
+int32_t gss_lwr_cv(const double* xdata, const double* z, int64_t n, int32_t dim, int32_t nz, const int32_t* fold,
+                   double exclude_radius, int32_t k, int32_t minneighbors, double radius, const double* inv_radii,
+                   int32_t metric, double metric_param, int32_t weight_kind, double weight_a, double weight_p,
+                   double* pred, double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out, int32_t mem,
+                   void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(weight_kind == GSS_WEIGHT_EXP || weight_kind == GSS_WEIGHT_TRICUBE, "unknown weight function %d",
+              weight_kind);
+  GSS_REQUIRE(weight_kind != GSS_WEIGHT_EXP || weight_p > 0.0, "weight exponent must be positive");
+  EstSpec sp;
+  std::memset(&sp, 0, sizeof(sp));
+  sp.method = 1;
+  sp.wkind = weight_kind;
+  sp.wa = weight_a;
+  sp.wp = weight_p;
+  sp.metric = metric;
+  sp.mparam = metric_param;
+  return est_cv(sp, "gss_lwr_cv", xdata, z, n, dim, nz, fold, exclude_radius, k, minneighbors, radius, inv_radii, pred,
+                var, status, idx_out, count_out, mem, stream);
 }
 
 }  // extern "C"

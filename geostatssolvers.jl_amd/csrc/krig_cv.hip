@@ -1,6 +1,7 @@
 // Cross-validation of a kriging or cokriging handle (gss.h): every sample predicted from samples outside its own fold.
 // Global neighbourhood: leave-one-out off the factor (krig_loo_kernel) and folds off the factor (crossval_folds.hip);
 // moving neighbourhood: the fold-aware search with the drivers of krig_local.hip and cokrig_cv.hip.
+#include "cv_fold.h"
 #include "krig_handle.h"
 
 #include <vector>
@@ -35,27 +36,6 @@ __global__ __launch_bounds__(256) void krig_loo_kernel(const double* __restrict_
   pred[i] = ok ? z[i] - wd[i] * v : NaN;
   var[i] = ok ? (v > 0.0 ? v : 0.0) : NaN;
   if (status) status[i] = ok ? GSS_PT_OK : GSS_PT_SINGULAR;
-}
-
-// The fold ids of n samples where the host can read them (own->data() after a copy of device memory, else `fold`
-// itself), none of them negative: they are checked before any kernel indexes or compares by them.
-static int32_t fold_ids_host(const char* who, const int32_t* fold, int64_t n, int32_t mem, hipStream_t s,
-                             std::vector<int32_t>* own) {
-  if (mem != GSS_MEM_HOST) {
-    own->resize((size_t)n);
-    GSS_HIP(hipMemcpyAsync(own->data(), fold, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-    GSS_HIP(hipStreamSynchronize(s));
-    fold = own->data();
-  }
-  for (int64_t i = 0; i < n; ++i)
-    GSS_REQUIRE(fold[i] >= 0, "%s: fold id %d of sample %lld is negative", who, fold[i], (long long)i);
-  return GSS_OK;
-}
-
-// the exclusion ball in the search key: squared (and scaled like the ball) for the Euclidean family, else as it is
-static double exclusion_key(double exclude_radius, int metric) {
-  if (exclude_radius < 0.0) return -1.0;
-  return metric == GSS_METRIC_EUCLIDEAN ? exclude_radius * exclude_radius : exclude_radius;
 }
 
 }  // namespace gss

@@ -747,6 +747,71 @@ class HipEngine:
         return HipEngine._estimate("gss_lwr_predict", (int(kind), float(a), float(p)), xdata, z, xdom, k,
                                    minneighbors, radius, radii, distance, rotation)
 
+    @staticmethod
+    def _estimate_cv(fn_name, extra, xdata, z, k, fold, exclude_radius, minneighbors, radius, radii, return_idx,
+                     distance, rotation, device):
+        """gss_idw_cv / gss_lwr_cv (gss.h): every sample predicted from samples outside its own fold.  Host arrays in ->
+        host arrays out; CUDA tensors for `xdata` / `z` / `fold` (all of them) with `device=True`, or a CUDA `fold`,
+        keep everything in HBM.  `z` of shape (n,) is one value column, (nz, n) nz columns on one search and one weight
+        vector per sample (`pred` comes back in the shape of `z`).  `k == n`: every eligible sample, no search (no
+        lists: `return_idx` is refused).  -> (pred, aux, status[, idx, count])."""
+        l = _lib.lib()
+        device = bool(device) or (is_torch(fold) and fold.is_cuda)
+        if device:
+            import torch
+            if fold is not None and not (is_torch(fold) and fold.is_cuda):
+                raise ValueError("device=True needs the fold ids as a CUDA tensor")
+            x = xdata if is_torch(xdata) else torch.as_tensor(np.asarray(xdata, dtype=np.float64), device="cuda")
+            x = _prep_in(x.reshape(x.shape[0], -1))
+            zz = _prep_in(z if is_torch(z) else torch.as_tensor(np.asarray(z, dtype=np.float64), device="cuda"))
+            if fold is not None:
+                fold = fold.to(torch.int32).contiguous()
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=x.device)   # noqa: E731
+            f64, u8, i32 = torch.float64, torch.uint8, torch.int32
+        else:
+            x = np.ascontiguousarray(xdata, dtype=np.float64)
+            if x.ndim == 1:
+                x = x[:, None]
+            zz = np.ascontiguousarray(z, dtype=np.float64)
+            if fold is not None:
+                fold = np.ascontiguousarray(fold, dtype=np.int32)
+            mk = lambda shape, dt: np.empty(shape, dtype=dt)   # noqa: E731
+            f64, u8, i32 = np.float64, np.uint8, np.int32
+        n = x.shape[0]
+        if zz.ndim not in (1, 2) or zz.shape[-1] != n:
+            raise ValueError("z must have shape (n,) or (nz, n)")
+        if fold is not None and tuple(fold.shape) != (n,):
+            raise ValueError(f"fold must hold one id per sample ({n}), got shape {tuple(fold.shape)}")
+        if return_idx and int(k) >= n:
+            raise ValueError("maxneighbors = n takes every eligible sample and runs no search: there are no lists")
+        pred, aux, st = mk(tuple(zz.shape), f64), mk((n,), f64), mk((n,), u8)
+        idx, cnt = (mk((n, int(k)), i32), mk((n,), i32)) if return_idx else (None, None)
+        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
+        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
+        met, mpar = _lib.metric_spec(distance)
+        met, ir = _ball_metric(met, ir, radii, rotation)
+        check(getattr(l, fn_name)(ptr(x), ptr(zz), n, x.shape[1], 1 if zz.ndim == 1 else int(zz.shape[0]), ptr(fold),
+                                  -1.0 if exclude_radius is None else float(exclude_radius), int(k), int(minneighbors),
+                                  r, ptr(ir), met, mpar, *extra, ptr(pred), ptr(aux), ptr(st), ptr(idx), ptr(cnt),
+                                  MEM_DEVICE if device else MEM_HOST, current_stream()))
+        return (pred, aux, st, idx, cnt) if return_idx else (pred, aux, st)
+
+    @staticmethod
+    def idw_cv(xdata, z, k, fold=None, exclude_radius=None, minneighbors=1, exponent=1.0, radius=None, radii=None,
+               return_idx=False, distance=None, rotation=None, device=False):
+        """Cross-validation of inverse distance weighting (gss.h, gss_idw_cv) -> (pred, distance to the nearest eligible
+        sample, status[, idx, count]); the arguments of `_estimate_cv`."""
+        return HipEngine._estimate_cv("gss_idw_cv", (float(exponent),), xdata, z, k, fold, exclude_radius, minneighbors,
+                                      radius, radii, return_idx, distance, rotation, device)
+
+    @staticmethod
+    def lwr_cv(xdata, z, k, fold=None, exclude_radius=None, minneighbors=1, weight=(0, 3.0, 2.0), radius=None,
+               radii=None, return_idx=False, distance=None, rotation=None, device=False):
+        """Cross-validation of locally weighted regression (gss.h, gss_lwr_cv); weight = (kind, a, p) -> (pred, norm(r),
+        status[, idx, count]); the arguments of `_estimate_cv`."""
+        kind, a, p = weight
+        return HipEngine._estimate_cv("gss_lwr_cv", (int(kind), float(a), float(p)), xdata, z, k, fold, exclude_radius,
+                                      minneighbors, radius, radii, return_idx, distance, rotation, device)
 
     @staticmethod
     def lwr_callable(xdata, z, xdom, k, minneighbors, weightfun, radius=None, radii=None, distance=None, rotation=None):

@@ -17,7 +17,15 @@ partners in play is the handle-level `CoKrigHandle.cv_knn(k, fold=None)`.)  The 
 on different scales are never pooled.
 
     res = cross_validate(problem, CoKrigingSolver((("cu", "zn"), dict(model=lmc, maxneighbors=(8, 16)))), KFoldValidation(10))
-    res["cu"].summary.cverror"""
+    res["cu"].summary.cverror
+
+IDWSolver and LWRSolver are cross-validated on the same samples and folds, so that the estimators can be compared
+(gss_idw_cv / gss_lwr_cv); the solver names the variables it estimates (`IDWSolver(z={})` for the defaults).
+`maxneighbors=None` takes every eligible sample, with every method, LeaveBallOut included.
+Neither estimator has a prediction variance: `variance` is None, the summary's `mse_std_n` is 0 and its standardised
+means are NaN; `aux` holds what the solver returns beside the estimate (`<var>_distance`, `<var>_variance`).
+
+    cverror(IDWSolver(z=dict(exponent=2, maxneighbors=16)), problem, KFoldValidation(10))["z"]"""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -27,7 +35,8 @@ import numpy as np
 from .engine import EDK
 from .geo import GeoTable, PointSet
 from .problems import EstimationProblem
-from .solvers import CoKrigingSolver, KrigingSolver, _ball, _distance, _rot_kw, kriging_ui, searcher_ui
+from .solvers import (CoKrigingSolver, ExpWeight, IDWSolver, KrigingSolver, LWRSolver, _ball, _distance, _rot_kw,
+                      kriging_ui, searcher_ui)
 
 
 class LeaveOneOut:
@@ -94,12 +103,14 @@ class BlockValidation:
 class CrossValidationResult:
     """Per variable: `pred`, `variance`, `residual` (z - pred), `status` (0 ok, 1 missing, 2 singular) and `fold` (ids;
     None for leave-one-out) of the non-missing samples `indices`, and `summary` (the fields of gss_cv_summary_t plus
-    `fold_mse`)."""
+    `fold_mse`).  IDWSolver / LWRSolver: `variance` is None and `aux` = {"<var>_distance" or "<var>_variance":
+    column}."""
 
-    def __init__(self, indices, z, pred, variance, status, fold, summary):
+    def __init__(self, indices, z, pred, variance, status, fold, summary, aux=None):
         self.indices, self.z, self.pred, self.variance, self.status, self.fold = indices, z, pred, variance, status, fold
         self.residual = z - pred
         self.summary = summary
+        self.aux = aux
 
     def __repr__(self):
         s = self.summary
@@ -167,17 +178,87 @@ def _cross_validate_cokriging(data, variables, solver, method, eng):
     return {v: out[v] for v in variables if v in out}
 
 
+def _cross_validate_estimator(data, variables, solver, method, eng):
+    """IDWSolver / LWRSolver: per variable the non-missing samples, the solver's own `maxneighbors`, `minneighbors`,
+    `neighborhood` and `distance` (as `_NeighborEstimator.solve` reads them), one engine call (gss_idw_cv / gss_lwr_cv)
+    per group of scalar variables with the same parameters and the same valid samples, one summary per variable."""
+    idw = isinstance(solver, IDWSolver)
+    call = "idw_cv" if idw else "lwr_cv"
+    if not hasattr(eng, call):
+        raise TypeError(f"cross-validation of {type(solver).__name__} needs an engine with `{call}`; "
+                        f"{getattr(eng, '__name__', type(eng).__name__)} has none")
+    coords = data.domain.centroids()
+    for v in variables:
+        if getattr(data[v], "dtype", None) == object:
+            raise TypeError(f"cross-validation of compositional (object) columns is not available: variable {v!r}")
+
+    def _key(v):
+        valid = np.flatnonzero(~np.isnan(np.asarray(data[v], dtype=np.float64)))
+        ident = lambda o: o if isinstance(o, (int, float, str, type(None))) else id(o)   # noqa: E731
+        return tuple(sorted((k, ident(x)) for k, x in solver.params(v).items())) + (valid.tobytes(),)
+    keys = {v: _key(v) for v in variables}
+    out, batched = {}, {}
+    for var in variables:
+        if var not in batched:
+            p = solver.params(var)
+            group = [v for v in variables if keys[v] == keys[var]]
+            inds = np.flatnonzero(~np.isnan(np.asarray(data[var], dtype=np.float64)))      # idw.jl:77, lwr.jl:80
+            n = inds.size
+            if n < 2:
+                raise AssertionError(f"cross-validation of {var} needs at least two non-missing samples")
+            dist = _distance(p)
+            solver._check(p)
+            extra = {}
+            if idw:
+                extra["exponent"] = float(p["exponent"])
+            else:
+                wf = p["weightfun"] or ExpWeight()
+                if not hasattr(wf, "spec"):
+                    raise NotImplementedError("cross-validation with a callable weightfun is not available: weightfun "
+                                              "must be ExpWeight(a, p) or TricubeWeight()")
+                extra["weight"] = wf.spec()
+            x = np.ascontiguousarray(coords[inds])
+            _, nmax = searcher_ui(PointSet(x), p["maxneighbors"], p["distance"], p["neighborhood"])
+            # every sample (maxneighbors=None or >= n): every ELIGIBLE sample; else a sample is never its own neighbour
+            k = n if p["maxneighbors"] is None or nmax >= n else min(nmax, n - 1)
+            assert p["minneighbors"] <= k, "invalid min/max number of neighbors"             # idw.jl:97
+            fold, nfolds = method.folds(x)
+            radius, radii = _ball(p["neighborhood"])
+            zs = np.stack([np.asarray(data[v], dtype=np.float64)[inds] for v in group])
+            pred, aux, st = getattr(eng, call)(x, zs if len(group) > 1 else zs[0], k, fold=fold,
+                                               exclude_radius=method.exclude_radius, minneighbors=p["minneighbors"],
+                                               radius=radius, radii=radii, distance=dist,
+                                               **extra, **_rot_kw(p["neighborhood"]))[:3]
+            pred, aux, st = _host(pred).reshape(len(group), n), _host(aux), _host(st)
+            for j, v in enumerate(group):
+                batched[v] = (inds, zs[j], np.ascontiguousarray(pred[j]), aux, st, fold, nfolds)
+        inds, zv, pv, aux, st, fold, nfolds = batched.pop(var)
+        fields, fmse = eng.cv_summary(zv, pv, np.zeros_like(zv), st, fold, nfolds)   # no prediction variance
+        summary = SimpleNamespace(**fields, fold_mse=None if fmse is None else _host(fmse))
+        out[var] = CrossValidationResult(inds, zv, pv, None, st, fold, summary, aux={f"{var}_{solver.AUX}": aux})
+    return out
+
+
 def cross_validate(problem_or_geotable, solver, method=None, engine=None):
     """{variable: CrossValidationResult}.  Of an EstimationProblem only the data are used.  The dispatch follows the
     KrigingSolver's own parameters: the kriging variant by `kriging_ui`; `maxneighbors`, `minneighbors`, `neighborhood`
     and `distance` by `searcher_ui`.  `maxneighbors=None` is the global neighbourhood: leave-one-out and the methods that
     partition the samples into folds (KFoldValidation, BlockValidation) are read off the factor of the one fitted system;
     LeaveBallOut, whose sets overlap, needs a moving neighbourhood.  A CoKrigingSolver follows its joint parameters the same
-    way, with the folds made of locations (module docstring)."""
+    way, with the folds made of locations (module docstring).  IDWSolver / LWRSolver: the solver has to name at least
+    one variable (`IDWSolver(z={})` takes the defaults; a solver without any is a `TypeError`, as every estimator was
+    before these two could be scored); every method works with and without `maxneighbors`; `variance` is None and
+    the summary is formed with a zero variance column, so `mse_std_n` is 0 and `mean_std` / `msq_std` are NaN --
+    neither estimator has a prediction variance."""
     method = LeaveOneOut() if method is None else method
-    if not isinstance(solver, (KrigingSolver, CoKrigingSolver)):
-        raise TypeError("cross-validation is available for KrigingSolver and CoKrigingSolver, not "
-                        f"{type(solver).__name__}")
+    if not isinstance(solver, (KrigingSolver, CoKrigingSolver, IDWSolver, LWRSolver)):
+        raise TypeError("cross-validation is available for KrigingSolver and CoKrigingSolver, IDWSolver and LWRSolver, "
+                        f"not {type(solver).__name__}")
+    if isinstance(solver, (IDWSolver, LWRSolver)) and not solver.vparams:
+        name = type(solver).__name__
+        raise TypeError("cross-validation is available for KrigingSolver and CoKrigingSolver, and for an IDWSolver or "
+                        f"LWRSolver that names the variables it estimates: {name}() names none (write "
+                        f"{name}(z=dict(...)); z={{}} takes the defaults)")
     if isinstance(problem_or_geotable, EstimationProblem):
         data, variables = problem_or_geotable.data, problem_or_geotable.variables
     elif isinstance(problem_or_geotable, GeoTable):
@@ -191,6 +272,8 @@ def cross_validate(problem_or_geotable, solver, method=None, engine=None):
     eng = engine or solver.engine
     if isinstance(solver, CoKrigingSolver):
         return _cross_validate_cokriging(data, variables, solver, method, eng)
+    if isinstance(solver, (IDWSolver, LWRSolver)):
+        return _cross_validate_estimator(data, variables, solver, method, eng)
     coords = data.domain.centroids()
     out = {}
     for var in variables:

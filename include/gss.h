@@ -681,6 +681,58 @@ int32_t gss_lwr_predict_weights(const double* xdata, const double* z, int64_t n,
                                 const double* weights, double* mean, double* var, uint8_t* status, int32_t mem,
                                 void* stream);
 
+/* ---- cross-validation of IDWSolver / LWRSolver: every sample predicted at its own location from samples outside its
+ *      own fold, by the estimators above.  No model is fitted, so there is no handle: the samples are the call's.
+ *   Eligibility  sample p is predicted from the samples j with fold[j] != fold[p] and, when exclude_radius >= 0, search
+ *              distance(p, j) > exclude_radius (leave-ball-out: a sample exactly on the radius is left out; the radius
+ *              is compared in the search key, as in gss_krig_cv_knn).  fold: n ids >= 0 in `mem`, arbitrary and not
+ *              necessarily compact (a negative id: GSS_ERR_INVALID; ids in device memory are copied to the host for
+ *              that check, which waits for the stream); NULL: leave-one-out, a sample's fold is its own index.
+ *              exclude_radius NaN: GSS_ERR_INVALID.  n >= 2.
+ *   Columns    z: nz columns of n values (column c at z + c * n), pred: nz columns of n (column c at pred + c * n); one
+ *              search and one weight vector per sample, dist / var / status one per sample, as in the _cols calls.
+ *   Zero distances  a coordinate duplicated in another fold is an ordinary zero-distance neighbour: IDW copies the first
+ *              such sample and reports dist = 0 (idw.jl:131-134).  A duplicate inside the sample's own fold is invisible
+ *              and does not trigger that rule.
+ *   Outcome    fewer eligible neighbours than max(minneighbors, 1): GSS_PT_MISSING, pred = dist / var = NaN -- a fold that
+ *              holds every sample makes all of them missing.  LWR normal equations that are not positive definite:
+ *              GSS_PT_SINGULAR, as in gss_lwr_predict.
+ *   1 <= k <= n - 1  the search path: the k nearest eligible samples by the fold-aware search of gss_krig_cv_knn (order
+ *              by (key, index); beyond 64 in passes of 64), then the list estimators of gss_idw_predict /
+ *              gss_lwr_predict with the samples as estimation points -- the same kernels, lists and order of summation
+ *              as a prediction from the eligible samples alone.  GSS_METRIC_HAVERSINE has no indexed search, which the
+ *              fold search needs: GSS_ERR_UNSUPPORTED.  idx_out (n x k, -1 beyond the count) and count_out (n) may be
+ *              NULL.
+ *   k == n     every eligible sample (inside the neighbourhood ball, if one is given): no search, a self-join of the
+ *              samples.  Thread = sample p; the samples pass by in pieces of 1 024 staged through LDS with their fold
+ *              ids beside them, and a sample contributes only if it is eligible by fold, exclusion key and ball.  IDW
+ *              completes in one sweep (sums, nearest eligible distance, first eligible zero distance); LWR takes two
+ *              (farthest eligible sample, then the moments X'WX, X'W^2X, X'Wz), the mask applied identically in both.
+ *              All four metrics, haversine included, with or without a ball.  The reference's default IDW (Euclidean, no
+ *              ball, no exclusion radius, exponent 1 or 2, one column) runs on a dedicated kernel: the sample index is
+ *              wave-uniform, so coordinates, value and fold id arrive through the scalar cache as scalar operands; the
+ *              weight of an ineligible sample is selected to zero (never multiplied: the sample itself has d^2 = 0) and
+ *              its d^2 is kept out of the running minimum; a coincident eligible sample is found by a rescan under the
+ *              same test.  With an exclusion radius the general kernel runs, whose key is the search's own (no FMA).
+ *              idx_out / count_out must be NULL (GSS_ERR_INVALID otherwise).  k outside 1 .. n: GSS_ERR_INVALID.
+ *   minneighbors, radius, inv_radii, metric, metric_param, exponent, weight_* as gss_idw_predict / gss_lwr_predict.
+ *   No floating-point atomics and every sum in a fixed order: the same bits on every run.  The samples are served in
+ *   chunks (2^20 per chunk on the search path up to 64 neighbours, as in the prediction calls); the environment
+ *   variable GSS_EST_CV_CHUNK caps the samples per chunk on every path, for tests, like GSS_COKRIG_CHUNK_POINTS: the
+ *   results are the same.  pred, dist / var, status (may be NULL), idx_out, count_out live in `mem`; the call returns
+ *   when they are complete.  gss_profile_read names: "knn" (the fold searches), "idw_cv" / "lwr_cv" (the estimator,
+ *   on either path).  The errors are summarised by gss_cv_summary with a zero variance column: neither estimator has a
+ *   prediction variance (dist is a distance, var the norm of lwr.jl:145). */
+int32_t gss_idw_cv(const double* xdata, const double* z, int64_t n, int32_t dim, int32_t nz, const int32_t* fold,
+                   double exclude_radius, int32_t k, int32_t minneighbors, double radius, const double* inv_radii,
+                   int32_t metric, double metric_param, double exponent, double* pred, double* dist, uint8_t* status,
+                   int32_t* idx_out, int32_t* count_out, int32_t mem, void* stream);
+int32_t gss_lwr_cv(const double* xdata, const double* z, int64_t n, int32_t dim, int32_t nz, const int32_t* fold,
+                   double exclude_radius, int32_t k, int32_t minneighbors, double radius, const double* inv_radii,
+                   int32_t metric, double metric_param, int32_t weight_kind, double weight_a, double weight_p,
+                   double* pred, double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out, int32_t mem,
+                   void* stream);
+
 /* ---- FFTGS ------------------------------------------------------------------------------
  * gss_fftgs_create replaces preprocess fft.jl:62-103 (unconditional part): covariance to the
  * centre cell, F = sqrt(|fft(fftshift(C))|), F[1] = 0.  dims[0] is the fastest axis (Julia

@@ -11,6 +11,13 @@
     gss_krig_predict_global at the fold's samples.  The two alternate; the Gram kernel's share and its fraction of the
     FP64 matrix peak (--fp64-peak-tflops, 78.6 for the MI355X) come from gss_profile_read ("cv_fold_gram").
 
+  * --estimators: gss_idw_cv / gss_lwr_cv at 5 000 and 100 000 uniform 3-D samples -- k = 16 with leave-one-out and ten
+    folds, and k = n (every eligible sample) for IDW with exponent 2 under leave-one-out -- each beside the plain
+    gss_idw_predict / gss_lwr_predict with xdom = xdata and the same k in the same session, alternating; the "knn" /
+    estimator split of each comes from gss_profile_read ("idw_cv" / "lwr_cv" beside "idw" / "lwr"), and the k = n rows
+    report the pair rate of the masked self-join beside the unmasked all-sample kernel, the latter also at a domain of
+    other points (at xdom = xdata each of its points hits its own sample and rescans).
+
 Method: warm-up, then `--reps` timed runs bracketed by events on the stream; the median is reported.  One JSON line per
 row on stdout.  python tools/cv_sweep.py [--reps 5] [--max-n 1000000]"""
 import argparse
@@ -181,15 +188,75 @@ def fold_rows(lib, reps, peak_tflops):
                           "gram_fraction_of_fp64_matrix_peak": round(gram_tflops / peak_tflops, 4)}), flush=True)
 
 
+def estimator_rows(reps, max_n):
+    from gss.engine import HipEngine
+    rng = np.random.default_rng(4)
+
+    def parts(fn, names):
+        _lib.profile_enable(True)
+        _lib.profile_reset()
+        fn()
+        torch.cuda.synchronize()
+        out = [round(_lib.profile_read(nm)[0], 4) for nm in names]
+        _lib.profile_enable(False)
+        return out
+
+    for n in (5_000, 100_000):
+        if n > max_n:
+            continue
+        x = torch.as_tensor(rng.uniform(0.0, 1000.0, (n, 3)), device="cuda")
+        z = torch.as_tensor(rng.normal(size=n), device="cuda")
+        xo = x + 0.25 * 1000.0 / n ** (1.0 / 3.0)          # the same cloud a quarter of a spacing away: no sample is hit
+        folds = {"loo": None, "10 folds": torch.as_tensor(gss.KFoldValidation(10, rng=1).folds(np.empty((n, 3)))[0],
+                                                          device="cuda")}
+        rows = [("idw", 16, name, dict(exponent=2.0)) for name in folds] + \
+               [("lwr", 16, name, dict(weight=(0, 3.0, 2.0))) for name in folds] + [("idw", n, "loo", dict(exponent=2.0))]
+        for est, k, name, kw in rows:
+            cvf = HipEngine.idw_cv if est == "idw" else HipEngine.lwr_cv
+            prf = HipEngine.idw if est == "idw" else HipEngine.lwr
+
+            def cv():
+                cvf(x, z, k, fold=folds[name], device=True, **kw)
+
+            def predict():
+                prf(x, z, x, k, **kw)
+            tc, tp = [], []
+            for _ in range(3):                          # alternating blocks
+                tc.append(timed(cv, reps))
+                tp.append(timed(predict, reps))
+            c, p = statistics.median(tc), statistics.median(tp)
+            cs, ps = parts(cv, ("knn", est + "_cv")), parts(predict, ("knn", est))
+            row = {"what": est + "_cv", "n": n, "k": "n" if k == n else k, "folds": name, "cv_ms": round(c, 4),
+                   "predict_ms": round(p, 4), "cv_over_predict": round(c / p, 3), "cv_search_ms": cs[0],
+                   "cv_estimator_ms": cs[1], "predict_search_ms": ps[0], "predict_estimator_ms": ps[1]}
+            if cs[0] > 0 and ps[0] > 0:
+                row["search_ratio"] = round(cs[0] / ps[0], 3)
+            if k == n:
+                # with xdom = xdata every point of the unmasked kernel meets its own sample, its sum turns NaN and it
+                # rescans the samples up to its own index one by one: the fair baseline predicts at other points
+                prf(x, z, xo, k, **kw)
+                po = parts(lambda: prf(x, z, xo, k, **kw), ("knn", est))
+                row["predict_other_points_estimator_ms"] = po[1]
+                row["predict_other_points_pairs_per_s"] = float("%.4g" % (n * float(n) / (po[1] * 1e-3)))
+                row["kernel_ratio_other_points"] = round(cs[1] / po[1], 3)
+                row["cv_pairs_per_s"] = float("%.4g" % (n * float(n) / (cs[1] * 1e-3)))
+                row["predict_pairs_per_s"] = float("%.4g" % (n * float(n) / (ps[1] * 1e-3)))
+                row["kernel_ratio"] = round(cs[1] / ps[1], 3)
+            print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fp64-peak-tflops", type=float, default=78.6)
     ap.add_argument("--only-folds", action="store_true", help="the gss_krig_cv_global_folds rows only")
     ap.add_argument("--max-n", type=int, default=1_000_000)
+    ap.add_argument("--estimators", action="store_true", help="the gss_idw_cv / gss_lwr_cv rows only")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     lib = _lib.lib()
+    if args.estimators:
+        return estimator_rows(args.reps, args.max_n)
     fold_rows(lib, args.reps, args.fp64_peak_tflops)
     if args.only_folds:
         return
