@@ -18,6 +18,7 @@
 #include "gss_internal.h"
 #include "fftgs_fused.h"
 #include "fftgs_generic.h"
+#include "fftgs_lmc.h"
 
 #include <sys/stat.h>
 #include <cerrno>
@@ -251,6 +252,9 @@ struct gss_fftgs {
   // of the process, slab_stream()); the events that fence them belong to the handle
   static constexpr int SLAB_MAX_STREAMS = 4;
   hipEvent_t slab_e0 = nullptr, slab_e[SLAB_MAX_STREAMS] = {nullptr, nullptr, nullptr, nullptr};
+  // co-simulation (gss_fftgs_create_lmc): the spectrum is rho's with unit sill and mean 0, the factors mix its fields
+  int lmc_nz = 0;   // 0: a plain handle
+  LmcCoef lmc;
   double* Fh() const { return state.as<double>(); }
   double* scal() const { return state.as<double>() + NH; }
   ~gss_fftgs() {
@@ -719,31 +723,42 @@ static int32_t fftgs_setup_generic(gss_fftgs* h, hipStream_t s) {
   return GSS_OK;
 }
 
+// How the members of a batch of realisations (grid y) are spaced: realisation numbers `real` apart, noise arrays and
+// outputs `noise` / `out` doubles apart (0: the N of the grid).  The default is the consecutive batch of
+// gss_fftgs_realize; the unit fields of a co-simulation (fftgs_lmc.h) step over the columns of other fields.
+struct BatchStep {
+  uint32_t real = 1;
+  int64_t noise = 0, out = 0;
+};
+
 // (nb: realisations in this launch, grid y)
 template <int SRC>
-static void gen_launch_p1(gss_fftgs* h, uint64_t seed, uint32_t real, const double* noise, hipStream_t s, int nb = 1) {
+static void gen_launch_p1(gss_fftgs* h, uint64_t seed, uint32_t real, const double* noise, hipStream_t s, int nb = 1,
+                          const BatchStep& bs = BatchStep()) {
   const GenGrid& g = h->gg;
+  const int64_t nbs = bs.noise > 0 ? bs.noise : h->N;
   const int64_t nrows = (int64_t)g.n2 * g.n3;
   const unsigned gx = (unsigned)((nrows + h->g_rows - 1) / h->g_rows);
   if (h->g_tg)
     hipLaunchKernelGGL((gen_x_fwd_kernel<SRC, true>), dim3(gx, nb), dim3(GEN_XNT), gen_x_lds(h->gp[0], h->g_rows, true), s, g, h->gp[0],
                        h->g_rows, h->tw1.as<double2>(), h->gtab[0].as<double2>(), seed, real, noise, h->X.as<double2>(), h->vg,
-                       h->g_xbs);
+                       h->g_xbs, bs.real, nbs);
   else
     hipLaunchKernelGGL((gen_x_fwd_kernel<SRC, false>), dim3(gx, nb), dim3(GEN_XNT), gen_x_lds(h->gp[0], h->g_rows, false), s, g, h->gp[0],
                        h->g_rows, h->tw1.as<double2>(), h->gtab[0].as<double2>(), seed, real, noise, h->X.as<double2>(), h->vg,
-                       h->g_xbs);
+                       h->g_xbs, bs.real, nbs);
 }
-static void gen_launch_p5(gss_fftgs* h, double* z, hipStream_t s, int nb = 1) {
+static void gen_launch_p5(gss_fftgs* h, double* z, hipStream_t s, int nb = 1, int64_t obs = 0) {
   const GenGrid& g = h->gg;
+  if (obs <= 0) obs = h->N;
   const int64_t nrows = (int64_t)g.n2 * g.n3;
   const unsigned gx = (unsigned)((nrows + h->g_rows - 1) / h->g_rows);
   if (h->g_tg)
     hipLaunchKernelGGL(gen_x_inv_kernel<true>, dim3(gx, nb), dim3(GEN_XNT), gen_x_lds(h->gp[0], h->g_rows, true), s, g, h->gp[0], h->g_rows,
-                       h->tw1.as<double2>(), h->gtab[0].as<double2>(), h->X.as<double2>(), z, h->g_xbs, h->N);
+                       h->tw1.as<double2>(), h->gtab[0].as<double2>(), h->X.as<double2>(), z, h->g_xbs, obs);
   else
     hipLaunchKernelGGL(gen_x_inv_kernel<false>, dim3(gx, nb), dim3(GEN_XNT), gen_x_lds(h->gp[0], h->g_rows, false), s, g, h->gp[0], h->g_rows,
-                       h->tw1.as<double2>(), h->gtab[0].as<double2>(), h->X.as<double2>(), z, h->g_xbs, h->N);
+                       h->tw1.as<double2>(), h->gtab[0].as<double2>(), h->X.as<double2>(), z, h->g_xbs, obs);
 }
 // strided pass `MODE` along y (axis 1) or z (axis 2)
 template <int MODE>
@@ -798,10 +813,10 @@ static int32_t fftgs_spectrum_generic(gss_fftgs* h, double* partial, hipStream_t
 // one realisation (fft.jl:163-170): five passes on 3-D grids, three on 2-D grids
 // nb > 1: realisations real .. real + nb - 1 in the same launches (noise arrays and outputs N doubles apart)
 static int32_t fftgs_generic_realize(gss_fftgs* h, uint64_t seed, int64_t real, const double* noise, double* z, hipStream_t s,
-                                     int nb = 1) {
+                                     int nb = 1, const BatchStep& bs = BatchStep()) {
   ProfScope ps("fftgs_generic", s);
-  if (noise) gen_launch_p1<FF_SRC_ARRAY>(h, seed, (uint32_t)real, noise, s, nb);
-  else gen_launch_p1<FF_SRC_PHILOX>(h, seed, (uint32_t)real, nullptr, s, nb);
+  if (noise) gen_launch_p1<FF_SRC_ARRAY>(h, seed, (uint32_t)real, noise, s, nb, bs);
+  else gen_launch_p1<FF_SRC_PHILOX>(h, seed, (uint32_t)real, nullptr, s, nb, bs);
   if (h->ndim == 3) {
     // The slab order of the power-of-two pipeline (fftgs_fused_rest: the three strided passes slab by slab over the x
     // tiles, slabs alternating over the caller's and the helper streams) is available here as an A/B switch only:
@@ -856,7 +871,7 @@ static int32_t fftgs_generic_realize(gss_fftgs* h, uint64_t seed, int64_t real, 
   } else {
     gen_launch_axis<2>(h, 1, s, 0, 0, nb);
   }
-  gen_launch_p5(h, z, s, nb);
+  gen_launch_p5(h, z, s, nb, bs.out);
   GSS_HIP(hipGetLastError());
   return GSS_OK;
 }
@@ -1183,6 +1198,8 @@ int32_t gss_fftgs_realize(gss_fftgs_t* h, uint64_t seed, int64_t first_real, int
                           const int64_t* inds, int64_t ninds, double* out, int32_t mem, void* stream) {
   GSS_ENTRY();
   GSS_REQUIRE(h != nullptr && out != nullptr && nreals >= 0 && first_real >= 0, "gss_fftgs_realize: bad arguments");
+  GSS_REQUIRE(h->lmc_nz == 0, "gss_fftgs_realize: the handle co-simulates %d variables (gss_fftgs_create_lmc): "
+              "gss_fftgs_realize_lmc realises it", h->lmc_nz);
   GSS_REQUIRE(h->ready, "handle has no spectrum");
   if (nreals == 0) return GSS_OK;
   hipStream_t s = to_stream(stream);
@@ -1300,6 +1317,193 @@ int32_t gss_fftgs_realize(gss_fftgs_t* h, uint64_t seed, int64_t first_real, int
     }
     GSS_TRY(os.done(r + nb - 1, s));
     r += nb - 1;
+  }
+  return os.finish(s);
+}
+
+// n fields of the handle's spectrum into device memory: field i is realisation id0 + i * bs.real of `seed`, read from
+// noise + i * bs.noise when the caller supplied uniforms (device memory), written to z + i * bs.out.  The pipelines
+// and their batches are those of gss_fftgs_realize, so a field has the bits that call gives for its realisation
+// number; the generic passes take any spacing in one launch, the batched rocFFT plans only the consecutive one.
+static int32_t fftgs_fields_dev(gss_fftgs* h, uint64_t seed, int64_t id0, int64_t n, const BatchStep& bs,
+                                const double* noise, double* z, hipStream_t s) {
+  const int64_t N = h->N;
+  const int64_t nstep = bs.noise > 0 ? bs.noise : N, zstep = bs.out > 0 ? bs.out : N;
+  const bool packed = bs.real == 1 && nstep == N && zstep == N;
+  int rbatch = 0;
+  if (!h->fused && !h->generic) {
+    GSS_TRY(ensure_rocfft(h));
+    if (packed) GSS_TRY(ensure_rocfft_batch(h, n, &rbatch));
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t real = id0 + i * (int64_t)bs.real;
+    const double* nzp = noise ? noise + i * nstep : nullptr;
+    double* zi = z + i * zstep;
+    if (h->fused) {
+      h->Xcur = h->X.as<double2>();
+      GSS_TRY(fftgs_fused_p1(h, seed, real, nzp, s));
+      GSS_TRY(fftgs_fused_rest(h, zi, s));
+      continue;
+    }
+    if (h->generic) {
+      const int64_t nb = h->g_batch < n - i ? h->g_batch : n - i;
+      GSS_TRY(fftgs_generic_realize(h, seed, real, nzp, zi, s, (int)nb, bs));
+      i += nb - 1;
+      continue;
+    }
+    const int64_t nb = rbatch > 1 && n - i >= rbatch ? rbatch : 1;
+    double* u = h->U.as<double>();
+    if (noise) {
+      u = const_cast<double*>(nzp);  // the forward transform does not overwrite its input
+    } else {
+      ProfScope ps("fftgs_noise", s);
+      GSS_TRY(philox_uniform_dev(seed, real, N, u, N, N, s, (int)nb, N));
+    }
+    {
+      ProfScope ps("fftgs_fwd", s);
+      GSS_TRY(fft_exec(h, nb > 1 ? h->plans->fwdB : h->fwd, u, h->Xn.p, s));
+    }
+    {
+      ProfScope ps("fftgs_phase", s);
+      hipLaunchKernelGGL(fftgs_phase_kernel, dim3(grid_blocks(h->NH), (unsigned)nb), dim3(256), 0, s, h->Xn.as<double2>(),
+                         h->Fh(), h->NH, h->mean);
+      GSS_HIP(hipGetLastError());
+    }
+    {
+      ProfScope ps("fftgs_inv", s);
+      GSS_TRY(fft_exec(h, nb > 1 ? h->plans->invB : h->inv, h->Xn.p, zi, s));
+    }
+    i += nb - 1;
+  }
+  return GSS_OK;
+}
+
+// the unit fields of realisations real0 .. real0 + nb - 1 of a co-simulation into their slots of Z (nb x nz x N): every
+// field of the chunk in one batch when all columns of L1 are live, else one batch per live column
+static int32_t lmc_fields(gss_fftgs* h, uint64_t seed, int64_t real0, int64_t nb, const double* noise, double* Z,
+                          hipStream_t s) {
+  const int nz = h->lmc_nz;
+  const int64_t N = h->N;
+  if (h->lmc.live1 == (1u << nz) - 1u) return fftgs_fields_dev(h, seed, real0 * nz, nb * nz, BatchStep(), noise, Z, s);
+  BatchStep bs;
+  bs.real = (uint32_t)nz;
+  bs.noise = bs.out = (int64_t)nz * N;
+  for (int j = 0; j < nz; ++j)
+    if ((h->lmc.live1 >> j) & 1u)
+      GSS_TRY(fftgs_fields_dev(h, seed, real0 * nz + j, nb, bs, noise ? noise + j * N : nullptr, Z + j * N, s));
+  return GSS_OK;
+}
+
+int32_t gss_fftgs_create_lmc(gss_fftgs_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
+                             const double* b1, const double* means, int32_t ndim, const int64_t* dims,
+                             const double* spacing, int32_t flags, void* stream) {
+  GSS_ENTRY();
+  const char* who = "gss_fftgs_create_lmc";
+  GSS_REQUIRE(out != nullptr, "%s: out is NULL", who);
+  *out = nullptr;
+  GSS_REQUIRE(structure != nullptr, "%s: structure is NULL", who);
+  GSS_REQUIRE(nz >= 1 && nz <= LMC_MAXZ, "%s: nz = %d outside 1 .. %d", who, nz, LMC_MAXZ);
+  GSS_REQUIRE(b0 != nullptr && b1 != nullptr, "%s: b0 or b1 is NULL", who);
+  GSS_REQUIRE(means != nullptr, "%s: means is NULL", who);
+  GSS_REQUIRE(dims != nullptr, "%s: dims is NULL", who);
+  if (structure->kind == GSS_VG_POWER) {
+    set_error("%s: a power structure has no sill, the coregionalisation model needs one", who);
+    return GSS_ERR_UNSUPPORTED;
+  }
+  GSS_REQUIRE(structure->nextra == 0, "%s: one structure plus nugget (nextra = %d)", who, structure->nextra);
+  // the checks of gss_cokrig_create, then the factors
+  LmcCoef c = {};
+  double B0[LMC_MAXZ * LMC_MAXZ] = {}, B1[LMC_MAXZ * LMC_MAXZ] = {};
+  double big = 0.0;
+  for (int e = 0; e < nz * nz; ++e) {
+    GSS_REQUIRE(std::isfinite(b0[e]) && std::isfinite(b1[e]), "%s: b0 / b1 entry [%d][%d] is not finite", who, e / nz,
+                e % nz);
+    big = std::fmax(big, std::fmax(std::fabs(b0[e]), std::fabs(b1[e])));
+  }
+  for (int a = 0; a < nz; ++a)
+    for (int b = 0; b < nz; ++b) {
+      GSS_REQUIRE(std::fabs(b0[a * nz + b] - b0[b * nz + a]) <= 1e-12 * big, "%s: b0 is not symmetric at [%d][%d]", who,
+                  a, b);
+      GSS_REQUIRE(std::fabs(b1[a * nz + b] - b1[b * nz + a]) <= 1e-12 * big, "%s: b1 is not symmetric at [%d][%d]", who,
+                  a, b);
+      B0[a * LMC_MAXZ + b] = 0.5 * (b0[a * nz + b] + b0[b * nz + a]);
+      B1[a * LMC_MAXZ + b] = 0.5 * (b1[a * nz + b] + b1[b * nz + a]);
+    }
+  for (int a = 0; a < nz; ++a) {
+    GSS_REQUIRE(B0[a * LMC_MAXZ + a] + B1[a * LMC_MAXZ + a] > 0.0, "%s: variable %d has no positive sill "
+                "b0[%d][%d] + b1[%d][%d]", who, a, a, a, a, a);
+    GSS_REQUIRE(std::isfinite(means[a]), "%s: means[%d] is not finite", who, a);
+    c.means[a] = means[a];
+  }
+  GSS_TRY(lmc_factor(who, "b0", B0, nz, c.L0, &c.live0));
+  GSS_TRY(lmc_factor(who, "b1", B1, nz, c.L1, &c.live1));
+  gss_variogram_t unit = *structure;   // rho: sill 1, no nugget
+  unit.sill = 1.0;
+  unit.nugget = 0.0;
+  GSS_TRY(gss_fftgs_create(out, &unit, ndim, dims, spacing, 0.0, flags, stream));
+  (*out)->lmc_nz = nz;
+  (*out)->lmc = c;
+  return GSS_OK;
+}
+
+int32_t gss_fftgs_realize_lmc(gss_fftgs_t* h, uint64_t seed, int64_t first_real, int64_t nreals, const double* noise,
+                              const double* nugget_noise, const int64_t* inds, int64_t ninds, double* out, int32_t mem,
+                              void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr && out != nullptr && nreals >= 0 && first_real >= 0, "gss_fftgs_realize_lmc: bad arguments");
+  GSS_REQUIRE(h->lmc_nz > 0, "gss_fftgs_realize_lmc: the handle is a plain one (gss_fftgs_create): gss_fftgs_realize "
+              "realises it, gss_fftgs_create_lmc makes a handle for this call");
+  GSS_REQUIRE(h->ready, "handle has no spectrum");
+  GSS_REQUIRE(inds == nullptr || ninds >= 0, "gss_fftgs_realize_lmc: ninds = %lld", (long long)ninds);
+  if (nreals == 0) return GSS_OK;
+  hipStream_t s = to_stream(stream);
+  const int nz = h->lmc_nz;
+  const int64_t N = h->N, npts = inds ? ninds : N;
+  const bool host = mem == GSS_MEM_HOST;
+  const size_t joint = sizeof(double) * (size_t)nz * (size_t)N;   // the fields of one realisation
+  // Realisations per chunk: what the ring takes at a time for a host destination, what a workspace of the ring's
+  // chunk size holds when the fields cannot be realised where the results go (a grid view, staged noise); a device
+  // destination without a view is mixed in place, chunked only by the launch grid.
+  const bool in_place = !host && !inds;
+  int64_t chunk = in_place ? nreals : OutStream::default_chunk(joint, nreals);
+  if (chunk > 65535 / nz) chunk = 65535 / nz;   // (grid y of the mix and of the gather)
+  if (const char* e = std::getenv("GSS_FFTGS_LMC_CHUNK_REALS")) {   // tests: a chunk loop that runs more than once
+    const long long v = std::atoll(e);
+    if (v > 0 && v < chunk) chunk = v;
+  }
+  Staged si;
+  OutStream os;
+  GSS_TRY(si.in(inds, sizeof(int64_t) * (size_t)(inds ? ninds : 0), mem, s));
+  GSS_TRY(os.begin(out, sizeof(double) * (size_t)nz * (size_t)npts, nreals, mem, s, chunk));
+  DevBuf ws, un, en;   // fields of a chunk (view), staged uniforms, staged normals
+  if (inds) GSS_TRY(ws.alloc(joint * (size_t)chunk));
+  if (host && noise) GSS_TRY(un.alloc(joint * (size_t)chunk));
+  if (host && nugget_noise) GSS_TRY(en.alloc(joint * (size_t)chunk));
+  const uint64_t nseed = seed ^ GSS_FFTGS_LMC_NUGGET_SALT;
+
+  for (int64_t r = 0; r < nreals; r += chunk) {
+    const int64_t nb = chunk < nreals - r ? chunk : nreals - r;
+    double* dst = nullptr;   // the chunk's place: the caller's HBM or a chunk of the ring (chunks start at multiples)
+    GSS_TRY(os.slot(r, s, &dst));
+    const double* u = noise ? noise + r * nz * N : nullptr;
+    const double* e = nugget_noise ? nugget_noise + r * nz * N : nullptr;
+    if (host && u) {
+      GSS_HIP(hipMemcpyAsync(un.p, u, joint * (size_t)nb, hipMemcpyHostToDevice, s));
+      u = un.as<double>();
+    }
+    if (host && e) {
+      GSS_HIP(hipMemcpyAsync(en.p, e, joint * (size_t)nb, hipMemcpyHostToDevice, s));
+      e = en.as<double>();
+    }
+    double* Z = inds ? ws.as<double>() : dst;
+    GSS_TRY(lmc_fields(h, seed, first_real + r, nb, u, Z, s));
+    GSS_TRY(lmc_mix_launch(nz, h->lmc, Z, N, nb, nseed, first_real + r, e, s));
+    if (inds && ninds > 0) {
+      hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((ninds + 255) / 256), (unsigned)(nb * nz)), dim3(256), 0, s, Z,
+                         si.as<int64_t>(), ninds, dst, N);
+      GSS_HIP(hipGetLastError());
+    }
+    GSS_TRY(os.done(r + nb - 1, s));
   }
   return os.finish(s);
 }

@@ -211,7 +211,7 @@ template <int SRC, bool TG>
 __global__ __launch_bounds__(GEN_XNT) void gen_x_fwd_kernel(GenGrid g, GenPlan pl, int rows, const double2* __restrict__ tw1,
                                                             const double2* __restrict__ xtw, uint64_t seed, uint32_t real,
                                                             const double* __restrict__ noise, double2* __restrict__ X,
-                                                            VgDev vg, int64_t xbs) {
+                                                            VgDev vg, int64_t xbs, uint32_t rstep, int64_t nbs) {
   extern __shared__ __attribute__((aligned(16))) double2 gsm[];
   const int M = pl.L;
   const float inv_m = 1.0f / (float)M;   // (rows * M <= 2 048: g_div is exact)
@@ -221,10 +221,11 @@ __global__ __launch_bounds__(GEN_XNT) void gen_x_fwd_kernel(GenGrid g, GenPlan p
   const int tid = threadIdx.x;
   const int64_t nrows = (int64_t)g.n2 * g.n3;
   const int64_t row0 = (int64_t)blockIdx.x * rows;
-  // blockIdx.y: member of a batch of realisations (consecutive realisation numbers, noise arrays and X buffers xbs apart)
-  real += blockIdx.y;
+  // blockIdx.y: member of a batch of realisations (realisation numbers rstep apart -- 1 but for the fields of a
+  // co-simulation, fftgs_lmc.h --, noise arrays nbs doubles and X buffers xbs apart)
+  real += blockIdx.y * rstep;
   X += (int64_t)blockIdx.y * xbs;
-  if (SRC == FF_SRC_ARRAY) noise += (int64_t)blockIdx.y * (2 * nrows * M);
+  if (SRC == FF_SRC_ARRAY) noise += (int64_t)blockIdx.y * nbs;
   if (!TG) {
     for (int k = tid; k < M; k += GEN_XNT) gsm[k] = tw1[k];
     for (int k = tid; k < pl.tlen; k += GEN_XNT) gsm[M + k] = xtw[k];

@@ -25,6 +25,7 @@ OK, ERR_INVALID, ERR_HIP, ERR_NOT_POSDEF, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_AL
 KRIG_NO_FACTOR = 1
 KRIG_ASYNC_FIT = 2
 FFTGS_NO_SPECTRUM = 1
+FFTGS_LMC_NUGGET_SALT = 0x6e75676765744c4d      # gss.h, GSS_FFTGS_LMC_NUGGET_SALT
 LUGS_NO_FACTOR = 1
 LUGS_FACT_LU = 2
 SGS_MASK_AFTER_SEARCH = 1
@@ -128,6 +129,8 @@ SIGNATURES = {
     "gss_fftgs_state_buffer": [_p, C.POINTER(_p), C.POINTER(_i64)],
     "gss_fftgs_adopt_state": [_p, _p],
     "gss_fftgs_realize": [_p, _u64, _i64, _i64, _p, _p, _i64, _p, _i32, _p],
+    "gss_fftgs_create_lmc": [C.POINTER(_p), _VG, _i32, _p, _p, _p, _i32, _p, _p, _i32, _p],
+    "gss_fftgs_realize_lmc": [_p, _u64, _i64, _i64, _p, _p, _p, _i64, _p, _i32, _p],
     "gss_lugs_create": [C.POINTER(_p), _VG, _p, _i64, _p, _p, _i64, _f64, _i32, _p],
     "gss_lugs_destroy": [_p],
     "gss_lugs_info": [_p, C.POINTER(_i64), C.POINTER(_i64)],

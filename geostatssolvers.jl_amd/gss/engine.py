@@ -446,6 +446,36 @@ class FFTGSHandle(_NativeState):
         self._h = h
         self.N = int(np.prod(self.dims))
 
+    @classmethod
+    def lmc(cls, structure, B0, B1, means, dims, spacing=None, spectrum=True):
+        """The handle of a co-simulation under a linear model of coregionalisation (gss.h, gss_fftgs_create_lmc):
+        C_ab(h) = B1[a, b] rho(h) (+ B0[a, b] at a zero lag), rho the shape of `structure` (kind, range or ball, order)
+        with unit sill.  Its spectrum is rho's, so `spectrum`, `state_tensor` and `adopt_state` are those of a plain
+        handle; `realize_lmc` realises it."""
+        self = cls.__new__(cls)
+        self._l = _lib.lib()
+        self.dims = tuple(int(d) for d in dims)
+        nd = len(self.dims)
+        b0 = np.ascontiguousarray(np.atleast_2d(np.asarray(B0, dtype=np.float64)))
+        b1 = np.ascontiguousarray(np.atleast_2d(np.asarray(B1, dtype=np.float64)))
+        self.nz = b1.shape[0]
+        if b0.shape != (self.nz, self.nz) or b1.shape != (self.nz, self.nz):
+            raise ValueError(f"B0 and B1 must be square matrices of one size (got {b0.shape}, {b1.shape})")
+        mm = np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if means is None else means, dtype=np.float64),
+                                                  (self.nz,)))
+        if getattr(structure, "kind", None) in ("power", "nested"):
+            raise ValueError("a co-simulation takes one stationary structure (the LMC has one structure plus nugget)")
+        d = (C.c_int64 * 3)(*(list(self.dims) + [1] * (3 - nd)))
+        sp = (C.c_double * 3)(*([float(s) for s in (spacing if spacing is not None else [1.0] * nd)] + [1.0] * (3 - nd)))
+        v = make_variogram(structure.kind, nd, 1.0, 0.0, structure.range, structure.nu, structure.radii,
+                           rotation=getattr(structure, "rotation", None))
+        h = C.c_void_p()
+        check(self._l.gss_fftgs_create_lmc(C.byref(h), C.byref(v), self.nz, ptr(b0), ptr(b1), ptr(mm), nd, d, sp,
+                                           0 if spectrum else _lib.FFTGS_NO_SPECTRUM, current_stream()))
+        self._h = h
+        self.N = int(np.prod(self.dims))
+        return self
+
     def state_tensor(self):
         """CUDA tensor aliasing the spectral state (fft.jl:62-103 runs on one rank, the peers receive this)."""
         p, nb = C.c_void_p(), C.c_int64()
@@ -497,6 +527,37 @@ class FFTGSHandle(_NativeState):
         check(self._l.gss_fftgs_realize(self._h, int(seed), int(first_real), int(nreals), ptr(noise), ptr(ii),
                                         0 if inds is None else npts, ptr(out), mem, current_stream()))
         return out.numpy() if pinned and is_torch(out) and not out.is_cuda else out
+
+    def realize_lmc(self, seed, first_real, nreals, noise=None, nugget_noise=None, inds=None, out=None, device=False):
+        """nreals x nz x npts joint realisations of a handle made by `lmc` (gss.h, gss_fftgs_realize_lmc).  `noise`:
+        (nreals, nz, N) uniforms for the unit fields, `nugget_noise`: (nreals, nz, N) normals for the nugget, each
+        optional (parity checks); `device=True` (or a CUDA `out` / noise array) keeps everything in HBM, where the
+        fields are mixed in place in `out`."""
+        noise, nugget_noise = _prep_in(noise), _prep_in(nugget_noise)
+        npts = self.N if inds is None else len(inds)
+        given = [a for a in (noise, nugget_noise) if a is not None]
+        if out is None:
+            if device or any(is_torch(a) and a.is_cuda for a in given):
+                import torch
+                out = torch.empty((nreals, self.nz, npts), dtype=torch.float64, device="cuda")
+            else:
+                out = np.empty((nreals, self.nz, npts))
+        mem = _space(out)
+        if any(_space(a) != mem for a in given):
+            raise ValueError("noise, nugget_noise and out must live in the same memory space")
+        if any(tuple(a.shape) != (nreals, self.nz, self.N) for a in given):
+            raise ValueError(f"noise and nugget_noise have the shape (nreals, nz, N) = {(nreals, self.nz, self.N)}")
+        ii = None
+        if inds is not None:
+            if mem == MEM_DEVICE:
+                import torch
+                ii = torch.as_tensor(np.asarray(inds, dtype=np.int64), device=out.device)
+            else:
+                ii = np.ascontiguousarray(inds, dtype=np.int64)
+        check(self._l.gss_fftgs_realize_lmc(self._h, int(seed), int(first_real), int(nreals), ptr(noise),
+                                            ptr(nugget_noise), ptr(ii), 0 if inds is None else npts, ptr(out), mem,
+                                            current_stream()))
+        return out
 
 
 class LUGSHandle(_NativeState):
@@ -637,6 +698,7 @@ class HipEngine:
     Krig = KrigHandle
     CoKrig = CoKrigHandle
     FFTGS = FFTGSHandle
+    FFTGS_LMC = FFTGSHandle.lmc
     LUGS = LUGSHandle
     SGS = SGSHandle
 

@@ -762,18 +762,90 @@ class LWRSolver(_NeighborEstimator):
 # FFTGS
 # ------------------------------------------------------------------------------------------
 class FFTGS(_Solver):
+    """fft.jl:51-198, one variable at a time, and -- not in the reference -- the joint simulation of several variables
+    under a fitted linear model of coregionalisation: `FFTGS((("cu", "zn"), dict(model=lmc)))` co-simulates the named
+    variables (gss.h, gss_fftgs_create_lmc).  `model`: an LMCModel, or anything with `names`, `kind`, `range`, `order`,
+    `B0` and `B1`; its names are matched to the group by name, so a permuted or sub-selected group takes the matching
+    sub-matrices.  Each variable's `mean` comes from its own parameters; the structure is the model's, so a variable of
+    a joint group takes no `variogram`.  A Gaussian structure gets the `nugget + 1e-6` rule of the package on the
+    diagonal of B0.  Unconditional only."""
     PARAMS = dict(variogram=GaussianVariogram(), mean=0.0, minneighbors=1, maxneighbors=None, neighborhood=None,
                   distance="euclidean")                                                        # fft.jl:51-60
+    JPARAMS = dict(model=None)
     GLOBALS = dict(threads=None, rng=None)
 
+    def __init__(self, *pairs, **kw):
+        super().__init__(*pairs, **kw)
+        self._joint = {}
+        for key, p in self.jparams.items():
+            names = self._jorder[key]
+            model = p["model"]
+            if model is None or not all(hasattr(model, a) for a in ("names", "kind", "range", "order", "B0", "B1")):
+                raise ValueError(f"variables {names}: `model` must be an LMCModel (fit_lmc)")
+            mnames = list(model.names)
+            missing = [v for v in names if v not in mnames]
+            if missing:
+                raise ValueError(f"variables {missing} are not in the coregionalisation model (it has {tuple(mnames)})")
+            if len(set(names)) != len(names) or not 1 <= len(names) <= 8:
+                raise ValueError("between 1 and 8 distinct variables per co-simulation (gss.h, gss_fftgs_create_lmc)")
+            own = [v for v in names if v in self.vparams and self.vparams[v]["variogram"] is not self.PARAMS["variogram"]]
+            if own:
+                raise ValueError(f"variables {own} are simulated under the joint model of {names}: they take no "
+                                 f"`variogram` of their own")
+            idx = [mnames.index(v) for v in names]
+            B0 = np.array(np.asarray(model.B0, dtype=np.float64)[np.ix_(idx, idx)])
+            B1 = np.array(np.asarray(model.B1, dtype=np.float64)[np.ix_(idx, idx)])
+            for name, B in (("B0", B0), ("B1", B1)):
+                if not np.all(np.isfinite(B)):
+                    raise ValueError(f"{name} has a non-finite entry")
+                if np.max(np.abs(B - B.T)) > 1e-12 * max(np.max(np.abs(B)), 1e-300):
+                    raise ValueError(f"{name} is not symmetric")
+                ev = np.linalg.eigvalsh(0.5 * (B + B.T))
+                if ev[0] < -1e-12 * max(np.trace(B), 0.0):
+                    raise ValueError(f"{name} is not positive semidefinite for {names} (smallest eigenvalue {ev[0]:.3g}): "
+                                     f"not an admissible coregionalisation model")
+            if np.any(np.diag(B0) + np.diag(B1) <= 0.0):
+                raise ValueError("every variable needs a positive sill B0_aa + B1_aa")
+            if model.kind == "gaussian":
+                B0 = B0 + 1e-6 * np.eye(len(names))
+            structure = VariogramModel(model.kind, 1.0, 0.0, float(model.range), float(model.order),
+                                       getattr(model, "radii", None), False, getattr(model, "rotation", None))
+            self._joint[names] = dict(structure=structure, B0=B0, B1=B1)
+
+    def _preprocess_joint(self, problem, grp, pgrid):
+        """The handle of one joint group (gss_fftgs_create_lmc): rank 0 computes the spectrum of the shared structure,
+        the peers receive it as for a single variable; the factors of B0 and B1 are recomputed on every rank."""
+        pdata = problem.data
+        have = [v for v in grp if pdata is not None and v in pdata.table]
+        if have:
+            raise NotImplementedError(
+                f"variables {have} of the joint group {grp} have data: conditional co-simulation needs a cokriging "
+                f"predict with batched value columns (every realisation's data kriged against one factor), which the "
+                f"library does not have; co-simulation is unconditional")
+        q = self._joint[grp]
+        means = np.array([float(self.params(v)["mean"]) for v in grp])
+        h = parallel.replicate_state(
+            lambda compute: self.engine.FFTGS_LMC(q["structure"], q["B0"], q["B1"], means, pgrid.dims, pgrid.spacing,
+                                                  **({} if compute else {"spectrum": False})),
+            self._share("broadcast"))
+        return dict(handle=h, means=means, **q)
+
     def preprocess(self, problem: SimulationProblem):
-        """fft.jl:62-143."""
+        """fft.jl:62-143; a joint group is keyed by its tuple of names."""
         pdom = problem.domain
         pgrid = parent(pdom)
         if not hasattr(pgrid, "dims"):
             raise ValueError("FFTGS is limited to simulations on Cartesian grids")
         pre = {}
-        for (var,) in [g for g in self.covariables(problem)]:
+        for key, p in self.jparams.items():
+            if len(key) > 1 and 0 < sum(v in problem.variables for v in key) < len(key):
+                raise ValueError(f"the joint group {self._jorder[key]} is only partly among the problem's variables "
+                                 f"{tuple(problem.variables)}")
+        for grp in self.covariables(problem):
+            if len(grp) > 1:
+                pre[grp] = self._preprocess_joint(problem, grp, pgrid)
+                continue
+            var, = grp
             p = self.params(var)
             vg = p["variogram"]
             if not vg.isstationary():
@@ -851,9 +923,21 @@ class FFTGS(_Solver):
             out[r] = q["zbar"] + (zu[r] - zbar_u)
         return out
 
+    def _block_joint(self, problem, pre, grp, lo, count):
+        """Joint realisations lo .. lo+count-1 of the group on the problem domain, shape (count, len(grp), npts).  The
+        group's streams are those of its first variable."""
+        pdom = problem.domain
+        seed = pre["_run"]["seed"] + pre["_run"]["vindex"][grp[0]]
+        if count <= 0:
+            return np.empty((0, len(grp), pdom.nelements()))
+        return pre[grp]["handle"].realize_lmc(seed, lo, count, inds=parentindices(pdom))
+
     def solvesingle(self, problem: SimulationProblem, covars, preproc):
         """fft.jl:145-198 with the reference's signature: one realisation per call, no index (see _run_state)."""
         r = _next_real(preproc, covars)
+        if len(covars) > 1:
+            z = self._block_joint(problem, preproc, tuple(covars), r, 1)[0]
+            return {var: z[a] for a, var in enumerate(covars)}
         return {var: self._block(problem, preproc, var, r, 1)[0] for var in covars}
 
     def solve(self, problem: SimulationProblem, gather: bool = True):
@@ -865,13 +949,23 @@ class FFTGS(_Solver):
         rank, ws = parallel.world()
         lo, hi = parallel.shard_range(problem.nreals, rank, ws)
         reals = {}
-        for var in problem.variables:
+        for grp in self.covariables(problem):
+            if len(grp) > 1:
+                zj = self._block_joint(problem, pre, grp, lo, hi - lo)
+                pre[grp]["handle"].close()
+                for a, var in enumerate(grp):
+                    zu = np.ascontiguousarray(zj[:, a])
+                    if gather and ws > 1:
+                        zu = parallel.all_gather_concat(zu, problem.nreals)
+                    reals[var] = [zu[r] for r in range(zu.shape[0])]
+                continue
+            var, = grp
             zu = self._block(problem, pre, var, lo, hi - lo)
             pre[var]["handle"].close()
             if gather and ws > 1:
                 zu = parallel.all_gather_concat(zu, problem.nreals)
             reals[var] = [zu[r] for r in range(zu.shape[0])]
-        return Ensemble(problem.domain, reals)
+        return Ensemble(problem.domain, {var: reals[var] for var in problem.variables})
 
 
 def _domain_points(engine, pdom, lo, hi, need_host=False):

@@ -758,6 +758,45 @@ int32_t gss_fftgs_realize(gss_fftgs_t* h, uint64_t seed, int64_t first_real, int
                           const double* noise, const int64_t* inds, int64_t ninds, double* out,
                           int32_t mem, void* stream);
 
+/* ---- FFTGS co-simulation under a linear model of coregionalisation ------------------------
+ * nz variables (1 .. 8) with the conventions of gss_cokrig_create: C_ab(h) = b1[a][b] rho(h) for h != 0 and
+ * C_ab(0) = b0[a][b] + b1[a][b], rho = `structure` with sill 1 and nugget 0 (only kind, dim, range, nu, aniso,
+ * inv_radii and rotation are read; nextra must be 0, GSS_VG_POWER gives GSS_ERR_UNSUPPORTED, Gaussian is the bare
+ * formula: a front end adds its 1e-6 to the diagonal of b0).  b0, b1: nz x nz row-major, symmetric to 1e-12 of the
+ * largest absolute entry, finite, b0[a][a] + b1[a][a] > 0; means: nz doubles.  A realisation is
+ *     Z_a = means[a] + sum_j L1[a][j] Y_j + sum_j L0[a][j] E_j ,   a = 0 .. nz-1,
+ * with Y_j independent unconditional FFTGS fields of rho (what a gss_fftgs_create handle with sill 1, nugget 0 and
+ * mean 0 realises), E_j independent standard-normal white noise, and L0 / L1 the lower factors of (b0 + b0^T) / 2 and
+ * (b1 + b1^T) / 2.  The nugget is explicit Gaussian white noise here, not a floor in the spectrum: the marginal of
+ * the nugget part is exactly normal and independent from cell to cell, where a plain handle with a nugget shapes one
+ * uniform-phase field by spectrum + nugget.
+ *   Factors: left-looking Cholesky without pivoting, on the host, the same on every rank.  With d the largest
+ * diagonal entry, a pivot <= 1e-12 d makes its column a zero column (what remains of the column must then be
+ * <= 1e-12 d in magnitude too); otherwise, and for a pivot below -1e-12 d, the matrix is not positive semidefinite:
+ * GSS_ERR_INVALID, the message names the matrix and the entry.  A zero column costs nothing afterwards -- no
+ * transform, no noise stream --, so a rank-1 b1 (intrinsic correlation) costs one field per realisation whatever nz.
+ *   The handle is a gss_fftgs_t whose spectrum is that of rho with unit sill: gss_fftgs_destroy, _spectrum,
+ * _state_buffer and _adopt_state apply unchanged, GSS_FFTGS_NO_SPECTRUM is accepted (the factors are recomputed from
+ * the arguments on every rank).  gss_fftgs_realize refuses such a handle, gss_fftgs_realize_lmc a plain one.
+ *   Stream numbering: Y_j of realisation r is what gss_fftgs_realize(plain unit handle, seed, first_real = r nz + j,
+ * nreals = 1) returns; E_j of realisation r is gss_philox_normal(seed ^ GSS_FFTGS_LMC_NUGGET_SALT, r nz + j, N).
+ * Numbers depend on (seed, r, j) only: sharding the realisations over ranks or splitting a call changes nothing.
+ *   out: nreals x nz x (ninds or N); variable a of realisation r (counted from first_real) at ((r nz) + a) npts.
+ * inds gathers a grid view as in gss_fftgs_realize.  noise (may be NULL): nreals x nz x N uniforms, slot j feeds Y_j
+ * (parity mode of gss_fftgs_realize); nugget_noise (may be NULL, independently): nreals x nz x N normals, slot j is
+ * E_j.  Slots of zero columns are not read.  `mem` says where noise, nugget_noise, inds and out live.  A device `out`
+ * without inds receives the fields in the slots of their realisation and is mixed in place (8 N (live fields + nz)
+ * bytes of traffic per realisation, no workspace); a grid view goes through a workspace and a host `out` through the
+ * ring of gss_fftgs_realize, chunk by chunk -- the environment variable GSS_FFTGS_LMC_CHUNK_REALS caps the
+ * realisations per chunk, for tests, like GSS_COKRIG_CHUNK_POINTS: the results are the same bits. */
+#define GSS_FFTGS_LMC_NUGGET_SALT 0x6e75676765744c4dULL /* "nuggetLM" */
+int32_t gss_fftgs_create_lmc(gss_fftgs_t** out, const gss_variogram_t* structure, int32_t nz, const double* b0,
+                             const double* b1, const double* means, int32_t ndim, const int64_t* dims,
+                             const double* spacing, int32_t flags, void* stream);
+int32_t gss_fftgs_realize_lmc(gss_fftgs_t* h, uint64_t seed, int64_t first_real, int64_t nreals, const double* noise,
+                              const double* nugget_noise, const int64_t* inds, int64_t ninds, double* out, int32_t mem,
+                              void* stream);
+
 /* ---- LUGS -------------------------------------------------------------------------------
  * gss_lugs_create replaces preprocess lu.jl:105-147 for one variable: covariance blocks,
  * L11, B12 = L11 \ C12, d2, L22 = chol(C22 - B12'B12).  centroids N x d point-major;
