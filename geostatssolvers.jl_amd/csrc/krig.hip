@@ -898,6 +898,39 @@ int32_t gss::krig_upload_samples(const Frame& fr, const double* xhost, int64_t n
   return frame_apply_dev(fr, xraw->as<double>(), n, x->as<double>(), s);
 }
 
+// WD = K^-1 [Z - mean; 0] for nbatch data vectors against the factor of the handle: Zm = [Z - mean; 0], U = W' Zm, the
+// constraint rows of U change sign, WD = W'^T U.  A cokriging handle has the same factor layout; only the centring of a
+// simple system differs (one mean per variable: cokrig_batch_center).
+int32_t gss::krig_batch_dual(const gss_krig* h, const double* zdev, int64_t nbatch, BatchDual* d, hipStream_t s) {
+  const int64_t n = h->n, N1 = h->N1, ldw = h->ldw;
+  DevBuf &Zm = d->Zm, &U = d->U, &WD = d->WD;
+  GSS_TRY(Zm.alloc(sizeof(double) * (size_t)(ldw * nbatch)));
+  GSS_TRY(U.alloc(sizeof(double) * (size_t)(ldw * nbatch)));
+  GSS_TRY(WD.alloc(sizeof(double) * (size_t)(ldw * nbatch)));
+  GSS_HIP(hipMemsetAsync(Zm.p, 0, Zm.bytes, s));
+  GSS_HIP(hipMemsetAsync(WD.p, 0, WD.bytes, s));
+  GSS_HIP(hipMemcpy2DAsync(Zm.p, sizeof(double) * ldw, zdev, sizeof(double) * n, sizeof(double) * n, nbatch,
+                           hipMemcpyDeviceToDevice, s));
+  if (h->nz > 0) {
+    if (h->variant == GSS_KRIG_SIMPLE) cokrig_batch_center(h, Zm.as<double>(), nbatch, s);
+  } else if (h->variant == GSS_KRIG_SIMPLE && h->sk_mean != 0.0) {
+    // only the first n rows of each column hold data; the padding rows are multiplied by zero columns of W'
+    hipLaunchKernelGGL(add_scalar_kernel, dim3((unsigned)((ldw * nbatch + 255) / 256)), dim3(256), 0, s,
+                       Zm.as<double>(), ldw * nbatch, -h->sk_mean);
+  }
+  // U = W' Zm ; flip constraint rows ; WD = W'' U
+  GSS_TRY(gemm_f64(N1, nbatch, n, 1.0, h->Wp(), 1, ldw, Zm.as<double>(), 1, ldw, 0.0, U.as<double>(), 1, ldw,
+                   false, s));
+  if (h->nc > 0) {
+    hipLaunchKernelGGL(flip_rows_kernel, dim3(1, (unsigned)nbatch), dim3(256), 0, s, U.as<double>(), ldw, n, N1,
+                       nbatch);
+  }
+  GSS_TRY(gemm_f64(N1, nbatch, N1, 1.0, h->Wp(), ldw, 1, U.as<double>(), 1, ldw, 0.0, WD.as<double>(), 1, ldw,
+                   false, s));
+  GSS_HIP(hipGetLastError());
+  return GSS_OK;
+}
+
 extern "C" {
 
 int32_t gss_krig_create(gss_krig_t** out, const gss_variogram_t* vg, int32_t variant, double sk_mean,
@@ -1211,29 +1244,9 @@ int32_t gss_krig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t
   GSS_TRY(xfr.of(h->fr, &sx, m, s));
   GSS_TRY(so.out(mean_out, sizeof(double) * (size_t)(nbatch * m), mem));
 
-  DevBuf Zm, U, WD;
-  GSS_TRY(Zm.alloc(sizeof(double) * (size_t)(ldw * nbatch)));
-  GSS_TRY(U.alloc(sizeof(double) * (size_t)(ldw * nbatch)));
-  GSS_TRY(WD.alloc(sizeof(double) * (size_t)(ldw * nbatch)));
-  GSS_HIP(hipMemsetAsync(Zm.p, 0, Zm.bytes, s));
-  GSS_HIP(hipMemsetAsync(WD.p, 0, WD.bytes, s));
-  GSS_HIP(hipMemcpy2DAsync(Zm.p, sizeof(double) * ldw, sz.p, sizeof(double) * n, sizeof(double) * n, nbatch,
-                           hipMemcpyDeviceToDevice, s));
-  if (h->variant == GSS_KRIG_SIMPLE && h->sk_mean != 0.0) {
-    // only the first n rows of each column hold data; the padding rows are multiplied by zero columns of W'
-    hipLaunchKernelGGL(add_scalar_kernel, dim3((unsigned)((ldw * nbatch + 255) / 256)), dim3(256), 0, s,
-                       Zm.as<double>(), ldw * nbatch, -h->sk_mean);
-  }
-  // U = W' Zm ; flip constraint rows ; WD = W'' U
-  GSS_TRY(gemm_f64(N1, nbatch, n, 1.0, h->Wp(), 1, ldw, Zm.as<double>(), 1, ldw, 0.0, U.as<double>(), 1, ldw,
-                   false, s));
-  if (h->nc > 0) {
-    hipLaunchKernelGGL(flip_rows_kernel, dim3(1, (unsigned)nbatch), dim3(256), 0, s, U.as<double>(), ldw, n, N1,
-                       nbatch);
-  }
-  GSS_TRY(gemm_f64(N1, nbatch, N1, 1.0, h->Wp(), ldw, 1, U.as<double>(), 1, ldw, 0.0, WD.as<double>(), 1, ldw,
-                   false, s));
-  GSS_HIP(hipGetLastError());
+  BatchDual bd;   // Zm / U / WD
+  GSS_TRY(krig_batch_dual(h, sz.as<double>(), nbatch, &bd, s));
+  DevBuf& WD = bd.WD;
 
   // out(b, p) = sum_k WD(k, b) R(k, p), sixteen data vectors per pass, R never materialised
   const double add = (h->variant == GSS_KRIG_SIMPLE) ? h->sk_mean : 0.0;

@@ -100,6 +100,13 @@ void launch_krig_quadform(const gss_krig* h, const double* Rws, int64_t ldr, dou
 int32_t krig_quadform_attrs();
 // entry points that know one variable only
 int32_t krig_refuse_cokrig(const gss_krig* h, const char* who);
+// Dual weights of nbatch data vectors (zdev: nbatch x n, device) against the factor of a kriging or cokriging handle,
+// shared by gss_krig_predict_global_batch and gss_cokrig_predict_global_batch: WD is N1 x nbatch, column-major with
+// leading dimension h->ldw.  Everything is queued on s; the buffers must outlive it.
+struct BatchDual {
+  DevBuf Zm, U, WD;
+};
+int32_t krig_batch_dual(const gss_krig* h, const double* zdev, int64_t nbatch, BatchDual* d, hipStream_t s);
 
 // ---- cokrig.hip: what the fit and the cross-validation need of a cokriging handle -------------------------------------
 // the n x n block of the system, the indicator columns Fd and the centring of the data vector (simple cokriging)
@@ -114,5 +121,9 @@ int32_t cokrig_knn_counts(const gss_krig* h, const char* who, const char* clamp_
 // one searcher per variable (sr[COL_MAXZ]) over that variable's grouped samples, all in the same frame
 int32_t cokrig_searchers(const gss_krig* h, const CoGrouped& g, Searcher* sr, int32_t metric, double metric_param,
                          double radius, const double* inv_radii, hipStream_t s);
+
+// ---- cokrig_batch.hip ---------------------------------------------------------------------------------------------------
+// Zm(i, b) -= means[var_i] for i < n in each of nbatch columns of leading dimension h->ldw (simple cokriging)
+void cokrig_batch_center(const gss_krig* h, double* Zm, int64_t nbatch, hipStream_t s);
 
 }  // namespace gss

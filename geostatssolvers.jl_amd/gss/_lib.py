@@ -100,6 +100,7 @@ SIGNATURES = {
     "gss_krig_predict_global_batch": [_p, _p, _i64, _p, _i64, _p, _i32, _p],
     "gss_cokrig_create": [C.POINTER(_p), _VG, _i32, _p, _p, _i32, _p, _p, _p, _p, _i64, _i32, _p],
     "gss_cokrig_predict_global": [_p, _p, _i64, _p, _p, _p, _i32, _p],
+    "gss_cokrig_predict_global_batch": [_p, _p, _i64, _p, _i64, _p, _i32, _p],
     "gss_cokrig_create_local": [C.POINTER(_p), _VG, _i32, _p, _p, _i32, _p, _p, _p, _p, _i64, _p],
     "gss_cokrig_predict_knn": [_p, _p, _i64, _p, _i32, _f64, _p, _i32, _f64, _p, _p, _p, _p, _p, _i32, _p],
     "gss_cokrig_cv_knn": [_p, _p, _f64, _p, _i32, _f64, _p, _i32, _f64, _p, _p, _p, _p, _p, _i32, _p],

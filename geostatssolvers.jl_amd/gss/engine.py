@@ -357,6 +357,26 @@ class CoKrigHandle(KrigHandle):
                                                 current_stream()))
         return mean, var, status
 
+    def predict_batch(self, xdom, zbatch):
+        """Means of every target for many value vectors at the handle's stacked samples (gss.h,
+        gss_cokrig_predict_global_batch).  `zbatch`: (nbatch, n) in the row order the handle was created with (one
+        vector: (n,)); numpy in, numpy out; CUDA tensors stay in HBM.  -> mean[nbatch, nz, m].  (The inherited
+        `predict_global_batch` is the single-variable call, which the library refuses for a cokriging system.)"""
+        xdom = _prep_in(xdom)
+        zb = _prep_in(zbatch)
+        if zb.ndim == 1:
+            zb = zb[None, :]
+        if _space(zb) != _space(xdom):
+            raise ValueError("xdom and zbatch must live in the same memory space")
+        if zb.ndim != 2 or zb.shape[1] != self.n:
+            raise ValueError(f"zbatch must hold one value per stacked sample ({self.n}) in every row, got shape "
+                             f"{tuple(zb.shape)}")
+        nb, m = zb.shape[0], xdom.shape[0]
+        out = _empty_like_space(xdom, (nb, self.nz, m), np.float64)
+        check(self._l.gss_cokrig_predict_global_batch(self._h, ptr(xdom), m, ptr(zb), nb, ptr(out), _space(xdom),
+                                                      current_stream()))
+        return out
+
     def predict_knn(self, xdom, k, minneighbors=1, radius=None, radii=None, return_idx=False, rotation=None):
         """Moving neighbourhood (gss.h, gss_cokrig_predict_knn): the `k[a]` nearest samples of every variable a, each
         variable searched on its own.  `k`: one count per variable, or an int for all of them.
@@ -705,7 +725,7 @@ class HipEngine:
     @staticmethod
     def cokrig(structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False, factor=True):
         """A cokriging handle (CoKrigHandle).  `factor=True`: the fitted global system -- `predict_global(xdom)`,
-        `cv_global()`, `cv_global_folds(fold)`, `predict_knn(xdom, k)`; `factor=False`: the samples only, for
+        `predict_batch(xdom, zbatch)`, `cv_global()`, `cv_global_folds(fold)`, `predict_knn(xdom, k)`; `factor=False`: the samples only, for
         `predict_knn` (moving neighbourhood)."""
         return CoKrigHandle(structure, B0, B1, variant, xdata, z, var, means=means, async_fit=async_fit, factor=factor)
 

@@ -768,7 +768,10 @@ class FFTGS(_Solver):
     `B0` and `B1`; its names are matched to the group by name, so a permuted or sub-selected group takes the matching
     sub-matrices.  Each variable's `mean` comes from its own parameters; the structure is the model's, so a variable of
     a joint group takes no `variogram`.  A Gaussian structure gets the `nugget + 1e-6` rule of the package on the
-    diagonal of B0.  Unconditional only."""
+    diagonal of B0.  Variables of the group that have a column in the problem's data are honoured: the stacked data of
+    the group (heterotopic sampling included) and every unconditional realisation at the data cells are kriged by simple
+    cokriging under the same model (gss.h, gss_cokrig_predict_global_batch) -- global neighbourhood only, so such a
+    variable takes no `maxneighbors` or `neighborhood`."""
     PARAMS = dict(variogram=GaussianVariogram(), mean=0.0, minneighbors=1, maxneighbors=None, neighborhood=None,
                   distance="euclidean")                                                        # fft.jl:51-60
     JPARAMS = dict(model=None)
@@ -817,18 +820,63 @@ class FFTGS(_Solver):
         the peers receive it as for a single variable; the factors of B0 and B1 are recomputed on every rank."""
         pdata = problem.data
         have = [v for v in grp if pdata is not None and v in pdata.table]
-        if have:
+        if have and not hasattr(self.engine, "cokrig"):
             raise NotImplementedError(
                 f"variables {have} of the joint group {grp} have data: conditional co-simulation needs a cokriging "
                 f"predict with batched value columns (every realisation's data kriged against one factor), which the "
                 f"library does not have; co-simulation is unconditional")
         q = self._joint[grp]
         means = np.array([float(self.params(v)["mean"]) for v in grp])
+        cond = self._condition_joint(problem, grp, have, q, means) if have else None
         h = parallel.replicate_state(
             lambda compute: self.engine.FFTGS_LMC(q["structure"], q["B0"], q["B1"], means, pgrid.dims, pgrid.spacing,
                                                   **({} if compute else {"spectrum": False})),
             self._share("broadcast"))
-        return dict(handle=h, means=means, **q)
+        return dict(handle=h, means=means, cond=cond, **q)
+
+    def _condition_joint(self, problem, grp, have, q, means):
+        """fft.jl:105-135 for a joint group: the data of all its variables, stacked, are kriged together -- simple
+        cokriging under the group's model about the variables' `mean` parameters, global neighbourhood, on every rank --
+        and each variable's data cells are looked up on their own.  Sampling may be heterotopic: a variable's rows are
+        those where its column is not NaN, and a variable without a column has none.
+        -> dict(cent, zbar[nz, npts], dinds: one array of unique cells per variable)."""
+        for v in grp:
+            for name in ("maxneighbors", "neighborhood"):
+                if self.params(v)[name] is not None:
+                    raise NotImplementedError(
+                        f"variable {v} of the joint group {grp} sets `{name}`: conditional co-simulation kriges under "
+                        f"the global neighbourhood only (gss.h, gss_cokrig_predict_global_batch works on the fitted "
+                        f"factor)")
+        pdom, pdata = problem.domain, problem.data
+        device = getattr(self.engine, "device_resident", False)
+        cent = _centroids_device(pdom) if device else pdom.centroids()
+        xd = pdata.domain.centroids()
+        xs, zs, vs = [], [], []
+        for a, v in enumerate(grp):
+            zd = np.asarray(pdata[v], dtype=np.float64) if v in have else np.full(xd.shape[0], np.nan)
+            keep = ~np.isnan(zd)                                                      # krig.jl:97
+            xs.append(xd[keep])
+            zs.append(zd[keep])
+            vs.append(np.full(int(keep.sum()), a, dtype=np.int32))
+        x, z, var = np.concatenate(xs), np.concatenate(zs), np.concatenate(vs)
+        if z.size == 0:
+            raise AssertionError(f"all samples of {tuple(have)} are missing, aborting...")
+        dinds = []
+        for xa in xs:                                                                 # fft.jl:129-132, per variable
+            found = (_nearest_cells(self.engine, pdom, (lambda: cent) if device else cent, xa) if xa.shape[0]
+                     else np.empty(0, dtype=np.int64))
+            _, first = np.unique(found, return_index=True)
+            dinds.append(np.asarray(found[np.sort(first)], dtype=np.int64))
+        kh = self.engine.cokrig(q["structure"], q["B0"], q["B1"], SK, x, z, var, means=means)
+        try:
+            zin = z[None, :]
+            if device:
+                import torch
+                zin = torch.as_tensor(zin, device="cuda")
+            zbar = kh.predict_batch(cent, zin)[0]                                     # only the means are used: fft.jl:126
+        finally:
+            kh.close()
+        return dict(cent=cent, zbar=zbar, dinds=dinds)
 
     def preprocess(self, problem: SimulationProblem):
         """fft.jl:62-143; a joint group is keyed by its tuple of names."""
@@ -930,7 +978,36 @@ class FFTGS(_Solver):
         seed = pre["_run"]["seed"] + pre["_run"]["vindex"][grp[0]]
         if count <= 0:
             return np.empty((0, len(grp), pdom.nelements()))
-        return pre[grp]["handle"].realize_lmc(seed, lo, count, inds=parentindices(pdom))
+        q = pre[grp]
+        if q.get("cond") is None:
+            return q["handle"].realize_lmc(seed, lo, count, inds=parentindices(pdom))
+        # fft.jl:176-192 jointly: the unconditional block at the data cells of every variable is kriged back from ONE
+        # simple cokriging system at those cells (the same locations for every realisation: one factor, the values as
+        # batched columns) and the residual field is added to the kriged data
+        cd = q["cond"]
+        cent, dinds = cd["cent"], cd["dinds"]
+        var = np.concatenate([np.full(d.size, a, dtype=np.int32) for a, d in enumerate(dinds)])
+        if getattr(self.engine, "device_resident", False):
+            import torch
+            zu = q["handle"].realize_lmc(seed, lo, count, inds=parentindices(pdom), device=True)
+            ddev = [torch.as_tensor(d, device=zu.device) for d in dinds]
+            zdat = torch.cat([zu[:, a].index_select(1, d) for a, d in enumerate(ddev)], dim=1).contiguous()
+            xdat = cent.index_select(0, torch.cat(ddev)).cpu().numpy()
+        else:
+            zu = q["handle"].realize_lmc(seed, lo, count, inds=parentindices(pdom))
+            zdat = np.ascontiguousarray(np.concatenate([zu[:, a][:, d] for a, d in enumerate(dinds)], axis=1))
+            xdat = cent[np.concatenate(dinds)]
+        h = self.engine.cokrig(q["structure"], q["B0"], q["B1"], SK, xdat, np.zeros(var.size), var, means=q["means"])
+        try:
+            zbar_u = h.predict_batch(cent, zdat)
+        finally:
+            h.close()
+        zu -= zbar_u
+        zu += cd["zbar"][None]                                                        # fft.jl:191
+        if hasattr(zu, "is_cuda"):
+            from .engine import to_host
+            return to_host(zu)
+        return zu
 
     def solvesingle(self, problem: SimulationProblem, covars, preproc):
         """fft.jl:145-198 with the reference's signature: one realisation per call, no index (see _run_state)."""

@@ -477,6 +477,31 @@ int32_t gss_cokrig_create(gss_krig_t** out, const gss_variogram_t* structure, in
 int32_t gss_cokrig_predict_global(gss_krig_t* h, const double* xdom, int64_t m, double* mean, double* variance,
                                   uint8_t* status, int32_t mem, void* stream);
 
+/* gss_cokrig_predict_global_batch: the fitted system of gss_cokrig_create with new value vectors at the same stacked
+ *   samples -- the counterpart of gss_krig_predict_global_batch, and the conditioning step of co-simulation
+ *   (gss_fftgs_realize_lmc), where the data and every unconditional realisation are kriged from one set of locations.
+ *   Means only: no variances, no status.
+ *   zbatch     nbatch x n, one value per stacked sample in the caller's row order (the order of gss_cokrig_create's
+ *              arrays); it replaces the handle's own values.  nbatch <= 65535.
+ *   mean_out   nbatch x nz x m: batch r, target t at (r * nz + t) * m -- the layout of gss_fftgs_realize_lmc's `out`,
+ *              so that the two arrays combine elementwise.
+ *   xdom, mem, stream   as gss_cokrig_predict_global (a rotated ball: the domain is moved into the frame of the
+ *              samples); host arrays are staged whole.  xdom, zbatch and mean_out live in `mem`.
+ *   Variants   GSS_KRIG_SIMPLE: the residuals z - means[var] are kriged and means[t] is added back.
+ *              GSS_KRIG_ORDINARY: the constraint part of the dual weights supplies the e_t row of target t.
+ *   Arithmetic WD = K^-1 [Z - means; 0] by two products with the factor (the block gss_krig_predict_global_batch runs),
+ *              then mean(r, t, p) = sum_j C_{var_j t}(x_j, p) WD(j, r) + WD(n + t, r) | means[t] in ascending j, with rho
+ *              evaluated once per (sample, point) for all value vectors and targets of a pass.  The zero-key rule is that
+ *              of gss_cokrig_create: a domain point on a sample of variable t takes c0 = b0 + b1 there, and so reproduces
+ *              the value given for that sample.  The result of a point does not depend on the chunk it falls into
+ *              (GSS_COKRIG_CHUNK_POINTS applies) nor on the memory space of the arrays.
+ *   Refusals   GSS_ERR_INVALID, the message names the entry: a single-variable handle (gss_krig_create), a handle of
+ *              gss_cokrig_create_local (no factor), negative sizes, a NULL array with non-zero sizes.  m == 0 or
+ *              nbatch == 0: GSS_OK, nothing is read or written.  gss_krig_predict_global_batch keeps refusing cokriging
+ *              handles.  gss_profile_read name: "cokrig_batch" (the mean kernel). */
+int32_t gss_cokrig_predict_global_batch(gss_krig_t* h, const double* xdom, int64_t m, const double* zbatch,
+                                        int64_t nbatch, double* mean_out, int32_t mem, void* stream);
+
 /* ---- moving-neighbourhood cokriging: per-variable search, one small system per domain point.
  *
  * gss_cokrig_create_local: a cokriging handle without a system and without a factor, for gss_cokrig_predict_knn and
