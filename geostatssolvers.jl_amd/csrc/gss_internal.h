@@ -819,8 +819,8 @@ __device__ __forceinline__ double vg_shape_kpos(double d2, double inv_range, dou
   return vg_shape(KIND, d2, inv_range, mscale, pw);
 }
 
-// a * b rounded once and never fused into a following addition or subtraction (variography.hip: bin edges and squared
-// increments that must be the same doubles wherever they are formed)
+// a * b rounded once and never fused into a following addition or subtraction (the pair kernels of variography.hip: bin
+// edges, squared increments and products of increments that must be the same doubles wherever they are formed)
 __device__ __forceinline__ double mul_rounded(double a, double b) {
 #pragma clang fp contract(off)
   const double r = a * b;
@@ -1080,7 +1080,7 @@ struct Searcher {
 int32_t knn_index_build_device(const double* xdev, int64_t n, int dim, KnnIndex* ix, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
-// variography (variography.hip)
+// variography (variography.hip; the model fits are host code of their own in variography_fit.hip)
 // ---------------------------------------------------------------------------------------------
 // gss_stat counters "vario_tiles_total" / "vario_tiles_opened" of the last gss_variogram_empirical; -1: not one of them
 int32_t vario_stat(const char* name, int64_t* value);

@@ -1,6 +1,13 @@
-// K7: empirical variograms on the device (gss_variogram_empirical) and the model fit (gss_variogram_fit, host code).
-// Replaces [DEP] Variography's EmpiricalVariogram / DirectionalVariogram / fit -- the step that produces the
-// `variogram=` parameter every solver takes.  The conventions are the library's own (include/gss.h).
+// K7: empirical variograms on the device (gss_variogram_empirical, gss_variogram_plane, gss_variogram_cross).  The model
+// fits to them (gss_variogram_fit and its kin) are host code in variography_fit.hip.  Replaces [DEP] Variography's
+// EmpiricalVariogram / DirectionalVariogram -- the step that produces the `variogram=` parameter every solver takes.
+// The conventions are the library's own (include/gss.h).
+//
+// Three kernels -- vario_window_kernel (lag bins), vario_plane_kernel (sector and lag), vario_cross_kernel (products of
+// differences) -- each hold their own accumulation and nothing of the others'.  What they share is written once, as
+// __forceinline__ pieces: the LDS set-up (vario_lds_init), the unit draw with the triangle skip (vario_next_unit), the
+// box cull (vario_cull), the load of batch J (vario_load_j), the pair key and pair test (vario_pair) and the copy-out
+// (vario_copy_out).  One loop around an accumulator object was tried and cost registers ("Cross-variograms").
 //
 // Layout.  The samples are put in a space-filling order -- the Searcher's k-d order (knn_build.hip) from 32 768 samples,
 // one sort by Morton key below that, where the level-by-level build would cost as much as the pair pass: batches of 64
@@ -14,30 +21,31 @@
 // the squared distance, accumulated with the rounded operations of the pair key itself, so it never exceeds a real
 // pair's key; a tile whose bound lies beyond the last bin edge is never opened, and the results cannot depend on that.
 //
-// Accumulation.  Pairs of one tile fall into few neighbouring bins, all of them at or above the bin of the tile's lower
-// bound.  Every lane therefore keeps a window of VW consecutive bins, starting at that bin, in registers (count, sum of
+// Accumulation (vario_window_kernel).  Pairs of one tile fall into few neighbouring bins, all of them at or above the
+// bin of the tile's lower bound.  Every lane therefore keeps a window of VW consecutive bins, starting at that bin, in registers (count, sum of
 // h, sums per value column: selected with an exact 0 / 1 factor); the rare pair beyond the window goes to the
 // workgroup's histogram in LDS with one LDS atomic per quantity.  After the tile the window is flushed to the same
 // histogram.  At the end each workgroup writes its histogram to its own slice of a scratch array and a second kernel adds
 // the slices in workgroup order: no global atomic per pair, 64-bit integer counts that do not depend on the schedule.
 //
-// Varioplane (gss_variogram_plane).  The PLANE instantiations of the same kernel bin every kept pair by (direction
-// sector, lag): the sector is found by bisection over the sector boundaries held in LDS (the truth pattern of the
-// header's rule is a prefix, so the bisection returns its count).  The wave-uniform window of lag bins does not carry
+// Varioplane (gss_variogram_plane).  vario_plane_kernel bins every kept pair by (direction sector, lag), without the
+// direction test of the other two: the sector is found by bisection over the sector boundaries held in LDS (the truth
+// pattern of the header's rule is a prefix, so the bisection returns its count).  The wave-uniform window of lag bins does not carry
 // over -- a near tile scatters over every sector -- but a far tile subtends few sectors and few lags, so consecutive
 // pairs of a lane often share a bin: every lane keeps its current run (bin, count, sums) in registers and sends it to
 // the workgroup's nangles x nlags histogram in LDS, one atomic per quantity, when the bin changes and after the tile.
-// Plain LDS atomics for every pair lost to this by up to 3 x ("Varioplane").  Ordering, check, gather,
-// batches, unit drawing, culling and the reduction are the code of the omnidirectional pass.
+// Plain LDS atomics for every pair lost to this by up to 3 x ("Varioplane").
 //
 // Cross-variograms (gss_variogram_cross).  vario_cross_kernel bins every kept pair once and adds the NZ (NZ + 1) / 2
 // products dz_a dz_b of its value differences.  A window of VW bins times 36 products does not fit the register file
 // (288 VGPRs at VW = 4), so the kernel takes the run form of the plane path for every NZ: a lane keeps one current bin
 // (count, sum of h, NP products: NP + 2 accumulators) and sends it to the workgroup's histogram in LDS when the bin
 // changes.  The bin is a lag, the same for a lane's whole life, so a run is carried across tiles and units and flushed
-// last at the end of the kernel.  Everything else -- ordering, check, gather, batches, unit drawing, culling, reduction
-// -- is the code of the omnidirectional pass; the histogram is (2 + NP) nlags + 2 words (78 KiB at NZ = 8, 256 lags:
-// room for two workgroups per compute unit; the registers of that instantiation admit one).  Registers and times: DESIGN.md, "Cross-variograms".
+// last at the end of the kernel.  The histogram is (2 + NP) nlags + 2 words (78 KiB at NZ = 8, 256 lags: room for two
+// workgroups per compute unit; the registers of that instantiation admit one).  Registers and times: DESIGN.md,
+// "Cross-variograms".
+//
+// Ordering, check, gather, batches, grid sizing and the reduction are one host path for the three calls (vario_run).
 #include "gss_internal.h"
 
 #include <hipcub/hipcub.hpp>
@@ -45,7 +53,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <vector>
 
 namespace gss {
 
@@ -66,13 +73,12 @@ struct VarioArgs {
   int nchunks;          // ceil(nb / jw)
   int grab;             // units a wave draws per atomic (large sets: the counter must not become the bottleneck)
   int nlags;
-  int estimator;
   int directional;
   int nocull;
   double delta, inv_delta;
   double u[3];
   double dtol2, cos2;
-  // varioplane (PLANE instantiations only)
+  // varioplane (vario_plane_kernel only)
   int nangles;          // sectors
   int nsteps;           // ceil(log2(nangles)): bisection steps
   double e[9];          // 3-D: in-plane axes e1, e2 and the normal
@@ -153,75 +159,158 @@ __device__ __forceinline__ int vario_sector(const double* dir, int nangles, int 
   return p == q ? 0 : lo;
 }
 
-template <int DIM, int NZ, bool CRESSIE, bool PLANE>
-__global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
-    const double* __restrict__ xs,      // n x DIM, k-d order
-    const double* __restrict__ zs,      // NZ columns of n, k-d order
-    const double* __restrict__ blo,     // nb x DIM batch boxes
-    const double* __restrict__ bhi,
-    VarioArgs A, unsigned long long* __restrict__ unit_counter,
-    unsigned long long* __restrict__ partial,     // per workgroup: cnt[nbins], ndup, opened, hsum[nbins], zsum[NZ nbins]
-    const double* __restrict__ dirs) {            // PLANE: (c_s, s_s), 2 nangles doubles
-  constexpr int VW = NZ <= 2 ? 6 : 4;   // bins of the register window
-  extern __shared__ double smem[];
-  const int nlags = A.nlags;
-  const int nbins = PLANE ? A.nangles * nlags : nlags;                    // bins of the histogram: (sector, lag) or lag
-  double* s_edge = smem;                                                  // nlags + 1
-  unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + nlags + 1);   // nbins + 2 (ndup, opened)
-  double* s_h = smem + nlags + 1 + nbins + 2;                             // nbins
-  double* s_z = s_h + nbins;                                              // NZ * nbins
-  const int nwords = (nbins + 2) + nbins + NZ * nbins;                    // what is flushed: s_cnt onwards
-  double* s_dir = smem + nlags + 1 + nwords;                              // PLANE: 2 nangles
-  if (PLANE) {
-    for (int t = threadIdx.x; t < 2 * A.nangles; t += VARIO_THREADS) s_dir[t] = dirs[t];
-  }
-  // squared bin edges edge2[k] = fl(fl(k delta)^2): two rounded products of exactly represented operands, the same
-  // doubles on every workgroup and on the host
+// ---- the pieces of the pair pass that the three kernels below share ------------------------------------------------
+// Every kernel takes the same arguments and lays out its dynamic LDS the same way: nlags + 1 squared bin edges, then
+// what is flushed -- cnt[nbins], ndup, opened, hsum[nbins], sums[rows nbins] -- then whatever else the kernel wants.
+
+// squared bin edges edge2[k] = fl(fl(k delta)^2): two rounded products of exactly represented operands, the same
+// doubles on every workgroup and on the host; the histogram is cleared; ends with the barrier
+__device__ __forceinline__ void vario_lds_init(double* s_edge, unsigned long long* s_cnt, int nlags, int nwords,
+                                               double delta) {
   for (int t = threadIdx.x; t <= nlags; t += VARIO_THREADS) {
-    const double e = mul_rounded((double)t, A.delta);
+    const double e = mul_rounded((double)t, delta);
     s_edge[t] = mul_rounded(e, e);
   }
   for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) s_cnt[t] = 0ull;   // +0.0 is all-zero bits
   __syncthreads();
+}
 
-  const int lane = threadIdx.x & 63;
-  const double emax2 = s_edge[nlags];
-  const int64_t n = A.n;
+// The next work unit (batch I, tiles J0 .. J0 + jw - 1) of this wave: drawn from the global counter, A.grab units per
+// atomic; units in the empty half of the triangle are passed over.  false: the counter is exhausted.
+__device__ __forceinline__ bool vario_next_unit(const VarioArgs& A, unsigned long long* unit_counter, int lane,
+                                                unsigned long long& unext, unsigned long long& uend, int& I, int& J0) {
   const unsigned long long nunits = (unsigned long long)A.nb * (unsigned long long)A.nchunks;
-  unsigned long long ndup = 0ull, opened = 0ull;
-
-  unsigned long long unext = 0ull, uend = 0ull;
   while (true) {
     if (unext == uend) {
       unsigned long long u0 = 0ull;
       if (lane == 0) u0 = atomicAdd(unit_counter, (unsigned long long)A.grab);
       unext = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u0 >> 32)) << 32) |
               (unsigned)__builtin_amdgcn_readfirstlane((int)u0);
-      if (unext >= nunits) break;
+      if (unext >= nunits) return false;
       uend = unext + (unsigned long long)A.grab < nunits ? unext + (unsigned long long)A.grab : nunits;
     }
     const unsigned long long u = unext++;
-    const int I = (int)(u / (unsigned)A.nchunks);
-    const int J0 = (int)(u % (unsigned)A.nchunks) * A.jw;
-    if (J0 + A.jw - 1 < I) continue;   // the empty half of the triangle
+    I = (int)(u / (unsigned)A.nchunks);
+    J0 = (int)(u % (unsigned)A.nchunks) * A.jw;
+    if (J0 + A.jw - 1 >= I) return true;   // else: the empty half of the triangle
+  }
+}
 
-    // lanes 0..15: bound of tile (I, J0 + lane)
-    const int Jl = J0 + lane;
-    bool cand = lane < A.jw && Jl >= I && Jl < A.nb;
-    double lb = 0.0;
-    if (cand) {
-      double loa[DIM], hia[DIM], lob[DIM], hib[DIM];
+// lanes 0..15: bound of tile (I, J0 + lane), kept in lb; -> the mask of the tiles to open
+template <int DIM>
+__device__ __forceinline__ unsigned long long vario_cull(const double* __restrict__ blo, const double* __restrict__ bhi,
+                                                         const VarioArgs& A, int I, int J0, int lane, double emax2,
+                                                         double& lb) {
+  const int Jl = J0 + lane;
+  bool cand = lane < A.jw && Jl >= I && Jl < A.nb;
+  lb = 0.0;
+  if (cand) {
+    double loa[DIM], hia[DIM], lob[DIM], hib[DIM];
 #pragma unroll
-      for (int a = 0; a < DIM; ++a) {
-        loa[a] = blo[(int64_t)I * DIM + a];
-        hia[a] = bhi[(int64_t)I * DIM + a];
-        lob[a] = blo[(int64_t)Jl * DIM + a];
-        hib[a] = bhi[(int64_t)Jl * DIM + a];
-      }
-      lb = vario_box_d2<DIM>(loa, hia, lob, hib);
-      cand = A.nocull || lb <= emax2;
+    for (int a = 0; a < DIM; ++a) {
+      loa[a] = blo[(int64_t)I * DIM + a];
+      hia[a] = bhi[(int64_t)I * DIM + a];
+      lob[a] = blo[(int64_t)Jl * DIM + a];
+      hib[a] = bhi[(int64_t)Jl * DIM + a];
     }
-    unsigned long long open = __ballot(cand);
+    lb = vario_box_d2<DIM>(loa, hia, lob, hib);
+    cand = A.nocull || lb <= emax2;
+  }
+  return __ballot(cand);
+}
+
+// batch J into registers: lane = point (a lane past the end holds a copy of the last point and vj = false)
+template <int DIM, int NZ>
+__device__ __forceinline__ bool vario_load_j(const double* __restrict__ xs, const double* __restrict__ zs, int64_t n,
+                                             int J, int lane, double* xj, double* zj) {
+  const int64_t j = (int64_t)J * 64 + lane;
+  const bool vj = j < n;
+  const int64_t jc = vj ? j : n - 1;
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) xj[a] = xs[jc * DIM + a];
+#pragma unroll
+  for (int c = 0; c < NZ; ++c) zj[c] = zs[(int64_t)c * n + jc];
+  return vj;
+}
+
+// The pair (sample i of batch I: wave uniform, scalar loads; the lane's point): key d2, delta vector dl, duplicates
+// counted apart, -> keep.  DIRECTIONAL: with the direction test of gss_variogram_empirical (when A.directional).
+template <int DIM, bool DIRECTIONAL>
+__device__ __forceinline__ bool vario_pair(const double* __restrict__ xs, int64_t i, const double* xj, bool pairok,
+                                           const VarioArgs& A, double emax2, double& d2, double* dl,
+                                           unsigned long long& ndup) {
+  double xi[DIM];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) xi[a] = xs[i * DIM + a];
+  d2 = vario_d2<DIM>(xi, xj, dl);
+  ndup += (pairok && d2 == 0.0) ? 1ull : 0ull;
+  bool keep = pairok && d2 > 0.0 && d2 <= emax2;
+  if (DIRECTIONAL && A.directional) {
+#pragma clang fp contract(off)
+    double t = dl[0] * A.u[0];
+    if (DIM > 1) t = t + dl[1] * A.u[1];
+    if (DIM > 2) t = t + dl[2] * A.u[2];
+    const double tt = t * t;
+    const double p2 = d2 - tt;
+    const double cd = A.cos2 * d2;
+    keep = keep && p2 <= A.dtol2 && tt >= cd;
+  }
+  return keep;
+}
+
+// the wave's counters into the histogram, the histogram into the workgroup's slice
+__device__ __forceinline__ void vario_copy_out(unsigned long long* s_cnt, int nbins, int nwords, unsigned long long ndup,
+                                               unsigned long long opened, int lane,
+                                               unsigned long long* __restrict__ partial) {
+  if (ndup) atomicAdd(&s_cnt[nbins], ndup);
+  if (lane == 0 && opened) atomicAdd(&s_cnt[nbins + 1], opened);
+  __syncthreads();
+  unsigned long long* out = partial + (size_t)blockIdx.x * nwords;
+  for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) out[t] = s_cnt[t];
+}
+
+// the increments of a pair that the direct estimators sum: dz^2 (Matheron), sqrt|dz| (Cressie-Hawkins)
+template <int NZ, bool CRESSIE>
+__device__ __forceinline__ void vario_increments(const double* __restrict__ zs, int64_t n, int64_t i, const double* zj,
+                                                 double* val) {
+#pragma unroll
+  for (int c = 0; c < NZ; ++c) {
+    const double dz = zs[(int64_t)c * n + i] - zj[c];
+    val[c] = CRESSIE ? gss_sqrt(fabs(dz)) : mul_rounded(dz, dz);
+  }
+}
+
+#define VARIO_KERNEL_ARGS                                                                                             \
+  const double* __restrict__ xs,  /* n x DIM, k-d order */                                                            \
+      const double* __restrict__ zs,  /* NZ columns of n, k-d order */                                                \
+      const double* __restrict__ blo, /* nb x DIM batch boxes */                                                      \
+      const double* __restrict__ bhi, VarioArgs A, unsigned long long* __restrict__ unit_counter,                     \
+      unsigned long long* __restrict__ partial, /* per workgroup: what is flushed (above) */                          \
+      const double* __restrict__ dirs           /* plane: (c_s, s_s), 2 nangles doubles; else unused */
+
+// Lag bins: a register window of VW bins from the bin of the tile's lower bound, LDS atomics beyond it.
+template <int DIM, int NZ, bool CRESSIE>
+__global__ __launch_bounds__(VARIO_THREADS) void vario_window_kernel(VARIO_KERNEL_ARGS) {
+  constexpr int VW = NZ <= 2 ? 6 : 4;   // bins of the register window
+  extern __shared__ double smem[];
+  const int nlags = A.nlags;
+  double* s_edge = smem;                                                  // nlags + 1
+  unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + nlags + 1);   // nlags + 2 (ndup, opened)
+  double* s_h = smem + nlags + 1 + nlags + 2;                             // nlags
+  double* s_z = s_h + nlags;                                              // NZ * nlags
+  const int nwords = (nlags + 2) + nlags + NZ * nlags;
+  vario_lds_init(s_edge, s_cnt, nlags, nwords, A.delta);
+
+  const int lane = threadIdx.x & 63;
+  const double emax2 = s_edge[nlags];
+  const int64_t n = A.n;
+  unsigned long long ndup = 0ull, opened = 0ull;
+
+  unsigned long long unext = 0ull, uend = 0ull;
+  int I, J0;
+  while (vario_next_unit(A, unit_counter, lane, unext, uend, I, J0)) {
+    double lb;
+    unsigned long long open = vario_cull<DIM>(blo, bhi, A, I, J0, lane, emax2, lb);
     opened += (unsigned long long)__popcll(open);
 
     const int ni = (int64_t)I * 64 + 64 <= n ? 64 : (int)(n - (int64_t)I * 64);
@@ -233,20 +322,11 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
                                           __builtin_amdgcn_readlane(__double2loint(lb), pick));
       // first bin any pair of this tile can fall into (wave uniform)
       int kb = 0;
-      if (!PLANE) {
-        if (lbJ > 0.0 && lbJ <= emax2) kb = vario_bin(s_edge, nlags, lbJ, gss_sqrt(lbJ), A.inv_delta);
-        kb = __builtin_amdgcn_readfirstlane(kb);
-      }
+      if (lbJ > 0.0 && lbJ <= emax2) kb = vario_bin(s_edge, nlags, lbJ, gss_sqrt(lbJ), A.inv_delta);
+      kb = __builtin_amdgcn_readfirstlane(kb);
       const bool diag = I == J;
-
-      const int64_t j = (int64_t)J * 64 + lane;
-      const bool vj = j < n;
-      const int64_t jc = vj ? j : n - 1;
       double xj[DIM], zj[NZ];
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) xj[a] = xs[jc * DIM + a];
-#pragma unroll
-      for (int c = 0; c < NZ; ++c) zj[c] = zs[(int64_t)c * n + jc];
+      const bool vj = vario_load_j<DIM, NZ>(xs, zs, n, J, lane, xj, zj);
 
       unsigned int wc[VW];
       double wh[VW], wz[NZ][VW];
@@ -257,73 +337,16 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
 #pragma unroll
         for (int c = 0; c < NZ; ++c) wz[c][w] = 0.0;
       }
-
-      int rb = -1;   // PLANE: the lane's current run -- its bin, its pairs, its sums
-      unsigned int rc = 0u;
-      double rh = 0.0, rz[NZ];
-#pragma unroll
-      for (int c = 0; c < NZ; ++c) rz[c] = 0.0;
 #pragma unroll 2
       for (int ii = 0; ii < ni; ++ii) {
-        const int64_t i = (int64_t)I * 64 + ii;   // wave uniform: scalar loads
-        double xi[DIM], dl[DIM];
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) xi[a] = xs[i * DIM + a];
-        const double d2 = vario_d2<DIM>(xi, xj, dl);
-        const bool pairok = vj && (!diag || ii < lane);
-        ndup += (pairok && d2 == 0.0) ? 1ull : 0ull;
-        bool keep = pairok && d2 > 0.0 && d2 <= emax2;
-        if (!PLANE && A.directional) {
-#pragma clang fp contract(off)
-          double t = dl[0] * A.u[0];
-          if (DIM > 1) t = t + dl[1] * A.u[1];
-          if (DIM > 2) t = t + dl[2] * A.u[2];
-          const double tt = t * t;
-          const double p2 = d2 - tt;
-          const double cd = A.cos2 * d2;
-          keep = keep && p2 <= A.dtol2 && tt >= cd;
-        }
+        const int64_t i = (int64_t)I * 64 + ii;
+        double d2, dl[DIM];
+        const bool keep = vario_pair<DIM, true>(xs, i, xj, vj && (!diag || ii < lane), A, emax2, d2, dl, ndup);
         const double h = gss_sqrt(d2);
         const int k = vario_bin(s_edge, nlags, d2, h, A.inv_delta);
         const int w = keep ? k - kb : -1;
         double val[NZ];
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) {
-          const double dz = zs[(int64_t)c * n + i] - zj[c];
-          val[c] = CRESSIE ? gss_sqrt(fabs(dz)) : mul_rounded(dz, dz);
-        }
-        if constexpr (PLANE) {
-          double a1 = dl[0], a2 = dl[DIM > 1 ? 1 : 0];
-          if (DIM == 3) {
-            a1 = vario_project(dl, A.e);
-            a2 = vario_project(dl, A.e + 3);
-            const double wn = vario_project(dl, A.e + 6);
-            keep = keep && mul_rounded(wn, wn) <= A.ptol2;
-          }
-          const int b = vario_sector(s_dir, A.nangles, A.nsteps, a1, a2) * nlags + k;   // < nbins for every pair
-          // every lane keeps the run of consecutive kept pairs that fall into one bin in registers and sends it to the
-          // histogram when the bin changes
-          if (keep && b != rb) {
-            if (rc != 0u) {
-              atomicAdd(&s_cnt[rb], (unsigned long long)rc);
-              lds_add_f64(&s_h[rb], rh);
-#pragma unroll
-              for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nbins + rb], rz[c]);
-            }
-            rb = b;
-            rc = 0u;
-            rh = 0.0;
-#pragma unroll
-            for (int c = 0; c < NZ; ++c) rz[c] = 0.0;
-          }
-          if (keep) {
-            rc += 1u;
-            rh += h;
-#pragma unroll
-            for (int c = 0; c < NZ; ++c) rz[c] += val[c];
-          }
-          continue;
-        }
+        vario_increments<NZ, CRESSIE>(zs, n, i, zj, val);
 #pragma unroll
         for (int s = 0; s < VW; ++s) {
           const bool m = w == s;
@@ -340,12 +363,6 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
           for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nlags + k], val[c]);
         }
       }
-      if (PLANE && rc != 0u) {   // the last run of the tile
-        atomicAdd(&s_cnt[rb], (unsigned long long)rc);
-        lds_add_f64(&s_h[rb], rh);
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nbins + rb], rz[c]);
-      }
       // flush the window (bins kb .. kb + VW - 1, those that exist)
 #pragma unroll
       for (int s = 0; s < VW; ++s) {
@@ -359,23 +376,104 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_pairs_kernel(
       }
     }
   }
-  if (ndup) atomicAdd(&s_cnt[nbins], ndup);
-  if (lane == 0 && opened) atomicAdd(&s_cnt[nbins + 1], opened);
-  __syncthreads();
-  unsigned long long* out = partial + (size_t)blockIdx.x * nwords;
-  for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) out[t] = s_cnt[t];
+  vario_copy_out(s_cnt, nlags, nwords, ndup, opened, lane, partial);
 }
 
-// Cross-variograms: bins by lag like the omnidirectional instantiations above, sums mul_rounded(dz_a, dz_b) for every
-// a <= b (row a NZ - a (a - 1) / 2 + (b - a)).  Run form: see the head of this file.
+// Varioplane: bins by (sector, lag).  Every lane keeps the run of consecutive kept pairs that fall into one bin in
+// registers and sends it to the histogram when the bin changes and after the tile.  No direction test.
+template <int DIM, int NZ, bool CRESSIE>
+__global__ __launch_bounds__(VARIO_THREADS) void vario_plane_kernel(VARIO_KERNEL_ARGS) {
+  extern __shared__ double smem[];
+  const int nlags = A.nlags;
+  const int nbins = A.nangles * nlags;                                    // bins of the histogram: (sector, lag)
+  double* s_edge = smem;                                                  // nlags + 1
+  unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + nlags + 1);   // nbins + 2 (ndup, opened)
+  double* s_h = smem + nlags + 1 + nbins + 2;                             // nbins
+  double* s_z = s_h + nbins;                                              // NZ * nbins
+  const int nwords = (nbins + 2) + nbins + NZ * nbins;
+  double* s_dir = smem + nlags + 1 + nwords;                              // 2 nangles
+  for (int t = threadIdx.x; t < 2 * A.nangles; t += VARIO_THREADS) s_dir[t] = dirs[t];
+  vario_lds_init(s_edge, s_cnt, nlags, nwords, A.delta);
+
+  const int lane = threadIdx.x & 63;
+  const double emax2 = s_edge[nlags];
+  const int64_t n = A.n;
+  unsigned long long ndup = 0ull, opened = 0ull;
+
+  unsigned long long unext = 0ull, uend = 0ull;
+  int I, J0;
+  while (vario_next_unit(A, unit_counter, lane, unext, uend, I, J0)) {
+    double lb;
+    unsigned long long open = vario_cull<DIM>(blo, bhi, A, I, J0, lane, emax2, lb);
+    opened += (unsigned long long)__popcll(open);
+
+    const int ni = (int64_t)I * 64 + 64 <= n ? 64 : (int)(n - (int64_t)I * 64);
+    while (open) {
+      const int pick = __builtin_ctzll(open);
+      open &= open - 1;
+      const int J = J0 + pick;
+      const bool diag = I == J;
+      double xj[DIM], zj[NZ];
+      const bool vj = vario_load_j<DIM, NZ>(xs, zs, n, J, lane, xj, zj);
+
+      int rb = -1;   // the lane's current run -- its bin, its pairs, its sums
+      unsigned int rc = 0u;
+      double rh = 0.0, rz[NZ];
+#pragma unroll
+      for (int c = 0; c < NZ; ++c) rz[c] = 0.0;
+#pragma unroll 2
+      for (int ii = 0; ii < ni; ++ii) {
+        const int64_t i = (int64_t)I * 64 + ii;
+        double d2, dl[DIM];
+        bool keep = vario_pair<DIM, false>(xs, i, xj, vj && (!diag || ii < lane), A, emax2, d2, dl, ndup);
+        const double h = gss_sqrt(d2);
+        const int k = vario_bin(s_edge, nlags, d2, h, A.inv_delta);
+        double val[NZ];
+        vario_increments<NZ, CRESSIE>(zs, n, i, zj, val);
+        double a1 = dl[0], a2 = dl[DIM > 1 ? 1 : 0];
+        if (DIM == 3) {
+          a1 = vario_project(dl, A.e);
+          a2 = vario_project(dl, A.e + 3);
+          const double wn = vario_project(dl, A.e + 6);
+          keep = keep && mul_rounded(wn, wn) <= A.ptol2;
+        }
+        const int b = vario_sector(s_dir, A.nangles, A.nsteps, a1, a2) * nlags + k;   // < nbins for every pair
+        if (keep && b != rb) {   // the bin changes: the run goes to the histogram
+          if (rc != 0u) {
+            atomicAdd(&s_cnt[rb], (unsigned long long)rc);
+            lds_add_f64(&s_h[rb], rh);
+#pragma unroll
+            for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nbins + rb], rz[c]);
+          }
+          rb = b;
+          rc = 0u;
+          rh = 0.0;
+#pragma unroll
+          for (int c = 0; c < NZ; ++c) rz[c] = 0.0;
+        }
+        if (keep) {
+          rc += 1u;
+          rh += h;
+#pragma unroll
+          for (int c = 0; c < NZ; ++c) rz[c] += val[c];
+        }
+      }
+      if (rc != 0u) {   // the last run of the tile
+        atomicAdd(&s_cnt[rb], (unsigned long long)rc);
+        lds_add_f64(&s_h[rb], rh);
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) lds_add_f64(&s_z[c * nbins + rb], rz[c]);
+      }
+    }
+  }
+  vario_copy_out(s_cnt, nbins, nwords, ndup, opened, lane, partial);
+}
+
+// Cross-variograms: bins by lag, sums mul_rounded(dz_a, dz_b) for every a <= b (row a NZ - a (a - 1) / 2 + (b - a)).
+// Run form like the plane's; the bin is a lag, the same for a lane's whole life, so the run is carried across tiles and
+// units and flushed last at the end of the kernel.
 template <int DIM, int NZ>
-__global__ __launch_bounds__(VARIO_THREADS) void vario_cross_kernel(
-    const double* __restrict__ xs,      // n x DIM, k-d order
-    const double* __restrict__ zs,      // NZ columns of n, k-d order
-    const double* __restrict__ blo,     // nb x DIM batch boxes
-    const double* __restrict__ bhi,
-    VarioArgs A, unsigned long long* __restrict__ unit_counter,
-    unsigned long long* __restrict__ partial) {   // per workgroup: cnt[nlags], ndup, opened, hsum[nlags], csum[NP nlags]
+__global__ __launch_bounds__(VARIO_THREADS) void vario_cross_kernel(VARIO_KERNEL_ARGS) {
   constexpr int NP = NZ * (NZ + 1) / 2;
   extern __shared__ double smem[];
   const int nlags = A.nlags;
@@ -383,18 +481,12 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_cross_kernel(
   unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + nlags + 1);   // nlags + 2 (ndup, opened)
   double* s_h = smem + nlags + 1 + nlags + 2;                             // nlags
   double* s_z = s_h + nlags;                                              // NP * nlags
-  const int nwords = (nlags + 2) + nlags + NP * nlags;                    // what is flushed: s_cnt onwards
-  for (int t = threadIdx.x; t <= nlags; t += VARIO_THREADS) {
-    const double e = mul_rounded((double)t, A.delta);
-    s_edge[t] = mul_rounded(e, e);
-  }
-  for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) s_cnt[t] = 0ull;   // +0.0 is all-zero bits
-  __syncthreads();
+  const int nwords = (nlags + 2) + nlags + NP * nlags;
+  vario_lds_init(s_edge, s_cnt, nlags, nwords, A.delta);
 
   const int lane = threadIdx.x & 63;
   const double emax2 = s_edge[nlags];
   const int64_t n = A.n;
-  const unsigned long long nunits = (unsigned long long)A.nb * (unsigned long long)A.nchunks;
   unsigned long long ndup = 0ull, opened = 0ull;
 
   int rb = 0;   // the lane's current run: its bin (valid while rc > 0), its pairs, its sums
@@ -404,35 +496,10 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_cross_kernel(
   for (int p = 0; p < NP; ++p) rz[p] = 0.0;
 
   unsigned long long unext = 0ull, uend = 0ull;
-  while (true) {
-    if (unext == uend) {
-      unsigned long long u0 = 0ull;
-      if (lane == 0) u0 = atomicAdd(unit_counter, (unsigned long long)A.grab);
-      unext = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u0 >> 32)) << 32) |
-              (unsigned)__builtin_amdgcn_readfirstlane((int)u0);
-      if (unext >= nunits) break;
-      uend = unext + (unsigned long long)A.grab < nunits ? unext + (unsigned long long)A.grab : nunits;
-    }
-    const unsigned long long u = unext++;
-    const int I = (int)(u / (unsigned)A.nchunks);
-    const int J0 = (int)(u % (unsigned)A.nchunks) * A.jw;
-    if (J0 + A.jw - 1 < I) continue;   // the empty half of the triangle
-
-    // lanes 0..15: bound of tile (I, J0 + lane)
-    const int Jl = J0 + lane;
-    bool cand = lane < A.jw && Jl >= I && Jl < A.nb;
-    if (cand) {
-      double loa[DIM], hia[DIM], lob[DIM], hib[DIM];
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) {
-        loa[a] = blo[(int64_t)I * DIM + a];
-        hia[a] = bhi[(int64_t)I * DIM + a];
-        lob[a] = blo[(int64_t)Jl * DIM + a];
-        hib[a] = bhi[(int64_t)Jl * DIM + a];
-      }
-      cand = A.nocull || vario_box_d2<DIM>(loa, hia, lob, hib) <= emax2;
-    }
-    unsigned long long open = __ballot(cand);
+  int I, J0;
+  while (vario_next_unit(A, unit_counter, lane, unext, uend, I, J0)) {
+    double lb;
+    unsigned long long open = vario_cull<DIM>(blo, bhi, A, I, J0, lane, emax2, lb);
     opened += (unsigned long long)__popcll(open);
 
     const int ni = (int64_t)I * 64 + 64 <= n ? 64 : (int)(n - (int64_t)I * 64);
@@ -441,36 +508,14 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_cross_kernel(
       open &= open - 1;
       const int J = J0 + pick;
       const bool diag = I == J;
-
-      const int64_t j = (int64_t)J * 64 + lane;
-      const bool vj = j < n;
-      const int64_t jc = vj ? j : n - 1;
       double xj[DIM], zj[NZ];
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) xj[a] = xs[jc * DIM + a];
-#pragma unroll
-      for (int c = 0; c < NZ; ++c) zj[c] = zs[(int64_t)c * n + jc];
+      const bool vj = vario_load_j<DIM, NZ>(xs, zs, n, J, lane, xj, zj);
 
 #pragma unroll 2
       for (int ii = 0; ii < ni; ++ii) {
-        const int64_t i = (int64_t)I * 64 + ii;   // wave uniform: scalar loads
-        double xi[DIM], dl[DIM];
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) xi[a] = xs[i * DIM + a];
-        const double d2 = vario_d2<DIM>(xi, xj, dl);
-        const bool pairok = vj && (!diag || ii < lane);
-        ndup += (pairok && d2 == 0.0) ? 1ull : 0ull;
-        bool keep = pairok && d2 > 0.0 && d2 <= emax2;
-        if (A.directional) {
-#pragma clang fp contract(off)
-          double t = dl[0] * A.u[0];
-          if (DIM > 1) t = t + dl[1] * A.u[1];
-          if (DIM > 2) t = t + dl[2] * A.u[2];
-          const double tt = t * t;
-          const double p2 = d2 - tt;
-          const double cd = A.cos2 * d2;
-          keep = keep && p2 <= A.dtol2 && tt >= cd;
-        }
+        const int64_t i = (int64_t)I * 64 + ii;
+        double d2, dl[DIM];
+        const bool keep = vario_pair<DIM, true>(xs, i, xj, vj && (!diag || ii < lane), A, emax2, d2, dl, ndup);
         const double h = gss_sqrt(d2);
         const int k = vario_bin(s_edge, nlags, d2, h, A.inv_delta);   // in 0 .. nlags - 1 for every pair
         // The run is updated without a branch that writes registers (such a branch makes the compiler keep copies of
@@ -511,12 +556,10 @@ __global__ __launch_bounds__(VARIO_THREADS) void vario_cross_kernel(
 #pragma unroll
     for (int p = 0; p < NP; ++p) lds_add_f64(&s_z[p * nlags + rb], rz[p]);
   }
-  if (ndup) atomicAdd(&s_cnt[nlags], ndup);
-  if (lane == 0 && opened) atomicAdd(&s_cnt[nlags + 1], opened);
-  __syncthreads();
-  unsigned long long* out = partial + (size_t)blockIdx.x * nwords;
-  for (int t = threadIdx.x; t < nwords; t += VARIO_THREADS) out[t] = s_cnt[t];
+  vario_copy_out(s_cnt, nlags, nwords, ndup, opened, lane, partial);
 }
+
+#undef VARIO_KERNEL_ARGS
 
 // Sum of the workgroup slices, one workgroup per output word: thread j adds the slices j, j + 256, ... in ascending
 // order, then the 256 partial sums are folded pairwise in a fixed pattern -- the integer totals are exact and the
@@ -714,12 +757,61 @@ struct VarioPtrs {
   const double* dirs;   // varioplane: sector boundaries (device)
 };
 
-// nwg == 0: *resident = workgroups of this instantiation that fit one CU at a time (nothing is launched)
-template <int DIM, int NZ, bool CRESSIE, bool PLANE>
-int32_t vario_launch_one(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds, hipStream_t s, int* resident) {
-  auto kernel = vario_pairs_kernel<DIM, NZ, CRESSIE, PLANE>;
+// What an entry point asks of the pass: which kernel family, the bins of the histogram (nlags, or nangles nlags), the
+// rows of value sums per bin (nz, or nz (nz + 1) / 2 products) and the plane's sector boundaries (a host array), else NULL.
+enum { VARIO_LAGS, VARIO_PLANE, VARIO_CROSS };
+struct VarioForm {
+  int form;
+  int64_t nbins;
+  int32_t nsum;
+  const double* dirs;
+};
+
+using VarioKernel = void (*)(const double*, const double*, const double*, const double*, VarioArgs, unsigned long long*,
+                             unsigned long long*, const double*);
+
+// (form, dim, nz, estimator) -> the kernel.  Every instantiation: lag bins (dim 1 .. 3, nz 1 .. 8, both estimators),
+// plane (dim 2, 3, nz 1 .. 4, both estimators), cross (dim 1 .. 3, nz 1 .. 8); the entry points have checked the ranges.
+template <int DIM, int NZ>
+VarioKernel vario_kernel_of(int form, bool cressie) {
+  if (form == VARIO_CROSS) return vario_cross_kernel<DIM, NZ>;
+  if constexpr (DIM >= 2 && NZ <= VARIO_PLANE_MAX_NZ) {
+    if (form == VARIO_PLANE)
+      return cressie ? vario_plane_kernel<DIM, NZ, true> : vario_plane_kernel<DIM, NZ, false>;
+  }
+  return cressie ? vario_window_kernel<DIM, NZ, true> : vario_window_kernel<DIM, NZ, false>;
+}
+
+template <int DIM>
+VarioKernel vario_kernel_nz(int form, int nz, bool cressie) {
+  switch (nz) {
+    case 1: return vario_kernel_of<DIM, 1>(form, cressie);
+    case 2: return vario_kernel_of<DIM, 2>(form, cressie);
+    case 3: return vario_kernel_of<DIM, 3>(form, cressie);
+    case 4: return vario_kernel_of<DIM, 4>(form, cressie);
+    case 5: return vario_kernel_of<DIM, 5>(form, cressie);
+    case 6: return vario_kernel_of<DIM, 6>(form, cressie);
+    case 7: return vario_kernel_of<DIM, 7>(form, cressie);
+    default: return vario_kernel_of<DIM, 8>(form, cressie);
+  }
+}
+
+VarioKernel vario_kernel(int form, int dim, int nz, int estimator) {
+  const bool cressie = estimator == GSS_VARIO_CRESSIE;
+  switch (dim) {
+    case 1: return vario_kernel_nz<1>(form, nz, cressie);
+    case 2: return vario_kernel_nz<2>(form, nz, cressie);
+    default: return vario_kernel_nz<3>(form, nz, cressie);
+  }
+}
+
+// nwg == 0: *resident = workgroups of this kernel that fit one CU at a time (nothing is launched).  big: the histogram
+// may pass the 64 KiB a kernel gets without asking (plane: up to VARIO_PLANE_MAX_WORDS; cross: from NP nlags > ~7 900;
+// lag bins alone never: 22 KiB at most).
+int32_t vario_launch(VarioKernel kernel, bool big, const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds,
+                     hipStream_t s, int* resident) {
   if (nwg == 0) {
-    if (PLANE)   // a plane's histogram may pass the 64 KiB a kernel gets without asking
+    if (big)
       GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds));
     GSS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, kernel, VARIO_THREADS, lds));
@@ -729,92 +821,6 @@ int32_t vario_launch_one(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t
                      P.unit_counter, P.partial, P.dirs);
   GSS_HIP(hipGetLastError());
   return GSS_OK;
-}
-
-template <int DIM, int NZ, bool PLANE>
-int32_t vario_launch_nz(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds, hipStream_t s, int* resident) {
-  if (A.estimator == GSS_VARIO_CRESSIE) return vario_launch_one<DIM, NZ, true, PLANE>(P, A, nwg, lds, s, resident);
-  return vario_launch_one<DIM, NZ, false, PLANE>(P, A, nwg, lds, s, resident);
-}
-
-template <int DIM>
-int32_t vario_launch(const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
-                     int* resident) {
-  switch (nz) {
-    case 1: return vario_launch_nz<DIM, 1, false>(P, A, nwg, lds, s, resident);
-    case 2: return vario_launch_nz<DIM, 2, false>(P, A, nwg, lds, s, resident);
-    case 3: return vario_launch_nz<DIM, 3, false>(P, A, nwg, lds, s, resident);
-    case 4: return vario_launch_nz<DIM, 4, false>(P, A, nwg, lds, s, resident);
-    case 5: return vario_launch_nz<DIM, 5, false>(P, A, nwg, lds, s, resident);
-    case 6: return vario_launch_nz<DIM, 6, false>(P, A, nwg, lds, s, resident);
-    case 7: return vario_launch_nz<DIM, 7, false>(P, A, nwg, lds, s, resident);
-    default: return vario_launch_nz<DIM, 8, false>(P, A, nwg, lds, s, resident);
-  }
-}
-
-template <int DIM>
-int32_t vario_launch_plane(const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
-                           int* resident) {
-  switch (nz) {
-    case 1: return vario_launch_nz<DIM, 1, true>(P, A, nwg, lds, s, resident);
-    case 2: return vario_launch_nz<DIM, 2, true>(P, A, nwg, lds, s, resident);
-    case 3: return vario_launch_nz<DIM, 3, true>(P, A, nwg, lds, s, resident);
-    default: return vario_launch_nz<DIM, 4, true>(P, A, nwg, lds, s, resident);
-  }
-}
-
-// every instantiation behind one call: plane (dim 2, 3) or lag bins only (dim 1 .. 3)
-int32_t vario_launch_any(bool plane, int dim, const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds,
-                         hipStream_t s, int* resident) {
-  if (plane)
-    return dim == 2 ? vario_launch_plane<2>(P, A, nz, nwg, lds, s, resident)
-                    : vario_launch_plane<3>(P, A, nz, nwg, lds, s, resident);
-  switch (dim) {
-    case 1: return vario_launch<1>(P, A, nz, nwg, lds, s, resident);
-    case 2: return vario_launch<2>(P, A, nz, nwg, lds, s, resident);
-    default: return vario_launch<3>(P, A, nz, nwg, lds, s, resident);
-  }
-}
-
-// the cross kernel: same protocol (nwg == 0: residency only).  Its histogram passes 64 KiB from NP nlags > ~7 900.
-template <int DIM, int NZ>
-int32_t vario_launch_cross_one(const VarioPtrs& P, const VarioArgs& A, int nwg, size_t lds, hipStream_t s,
-                               int* resident) {
-  auto kernel = vario_cross_kernel<DIM, NZ>;
-  if (nwg == 0) {
-    GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
-    GSS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, kernel, VARIO_THREADS, lds));
-    return GSS_OK;
-  }
-  hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(VARIO_THREADS), lds, s, P.xs, P.zs, P.lo, P.hi, A,
-                     P.unit_counter, P.partial);
-  GSS_HIP(hipGetLastError());
-  return GSS_OK;
-}
-
-template <int DIM>
-int32_t vario_launch_cross_nz(const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
-                              int* resident) {
-  switch (nz) {
-    case 1: return vario_launch_cross_one<DIM, 1>(P, A, nwg, lds, s, resident);
-    case 2: return vario_launch_cross_one<DIM, 2>(P, A, nwg, lds, s, resident);
-    case 3: return vario_launch_cross_one<DIM, 3>(P, A, nwg, lds, s, resident);
-    case 4: return vario_launch_cross_one<DIM, 4>(P, A, nwg, lds, s, resident);
-    case 5: return vario_launch_cross_one<DIM, 5>(P, A, nwg, lds, s, resident);
-    case 6: return vario_launch_cross_one<DIM, 6>(P, A, nwg, lds, s, resident);
-    case 7: return vario_launch_cross_one<DIM, 7>(P, A, nwg, lds, s, resident);
-    default: return vario_launch_cross_one<DIM, 8>(P, A, nwg, lds, s, resident);
-  }
-}
-
-int32_t vario_launch_cross(int dim, const VarioPtrs& P, const VarioArgs& A, int nz, int nwg, size_t lds, hipStream_t s,
-                           int* resident) {
-  switch (dim) {
-    case 1: return vario_launch_cross_nz<1>(P, A, nz, nwg, lds, s, resident);
-    case 2: return vario_launch_cross_nz<2>(P, A, nz, nwg, lds, s, resident);
-    default: return vario_launch_cross_nz<3>(P, A, nz, nwg, lds, s, resident);
-  }
 }
 
 // tile counters of the last call: written by the reduction into page-locked memory, read after the event
@@ -841,542 +847,20 @@ int32_t vario_stat(const char* name, int64_t* value) {
   return -1;
 }
 
-// ---------------------------------------------------------------------------------------------
-// model fit (host)
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-// f(x), x = h / range: the shapes of vg_shape (gss_internal.h), gamma = nugget + (sill - nugget) f
-double fit_shape(int kind, double x, double nu) {
-  const double pi = 3.14159265358979323846;
-  switch (kind) {
-    case GSS_VG_GAUSSIAN: return -std::expm1(-3.0 * x * x);
-    case GSS_VG_EXPONENTIAL: return -std::expm1(-3.0 * x);
-    case GSS_VG_SPHERICAL: return x < 1.0 ? 1.5 * x - 0.5 * x * x * x : 1.0;
-    case GSS_VG_CUBIC: {
-      const double x2 = x * x, x3 = x2 * x;
-      return x < 1.0 ? 7.0 * x2 - 8.75 * x3 + 3.5 * x3 * x2 - 0.75 * x3 * x3 * x : 1.0;
-    }
-    case GSS_VG_PENTASPHERICAL: {
-      const double x2 = x * x, x3 = x2 * x;
-      return x < 1.0 ? 1.875 * x - 1.25 * x3 + 0.375 * x3 * x2 : 1.0;
-    }
-    case GSS_VG_SINEHOLE: {
-      const double t = pi * x;
-      return t > 0.0 ? 1.0 - std::sin(t) / t : 0.0;
-    }
-    default: {  // GSS_VG_MATERN
-      const double d = std::sqrt(2.0 * nu) * 3.0 * x;
-      if (!(d > 0.0)) return 0.0;
-      if (d > 700.0) return 1.0;
-      if (nu == 0.5) return -std::expm1(-d);
-      if (nu == 1.5) return 1.0 - (1.0 + d) * std::exp(-d);
-      if (nu == 2.5) return 1.0 - (1.0 + d + d * d / 3.0) * std::exp(-d);
-      if (nu * std::log(2.0 / d) > 690.0) return 0.0;
-      const double c = std::exp((1.0 - nu) * 0.6931471805599453 - std::lgamma(nu) + nu * std::log(d));
-      return 1.0 - c * std::cyl_bessel_k(nu, d);
-    }
-  }
-}
-
-struct FitData {
-  std::vector<double> h, g, w;
-  double frac;   // nugget <= frac * sill
-};
-
-double fit_residual(const FitData& D, const std::vector<double>& f, double a, double b) {
-  double s = 0.0;
-  for (size_t k = 0; k < f.size(); ++k) {
-    const double r = a + b * f[k] - D.g[k];
-    s += D.w[k] * r * r;
-  }
-  return s;
-}
-
-// For a fixed range the objective is a quadratic in (a, b) = (nugget, sill - nugget) over the cone a >= 0, b >= 0,
-// (1 - frac) a <= frac b.  Its minimum is the unconstrained one if feasible, else it lies on one of the three edges
-// (each a one-variable least squares) or at their common vertex, the origin.  Returns the objective.
-double fit_inner_f(const FitData& D, const std::vector<double>& f, double* a_out, double* b_out);
-
-double fit_inner(const FitData& D, int kind, double nu, double range, double* a_out, double* b_out) {
-  const size_t m = D.h.size();
-  std::vector<double> f(m);
-  for (size_t k = 0; k < m; ++k) f[k] = fit_shape(kind, D.h[k] / range, nu);
-  return fit_inner_f(D, f, a_out, b_out);
-}
-
-// the cone solve for given shape values f_k (isotropic: f(h_k / range); anisotropic: f of the scaled lag)
-double fit_inner_f(const FitData& D, const std::vector<double>& f, double* a_out, double* b_out) {
-  const size_t m = D.h.size();
-  double sw = 0.0, swf = 0.0, swg = 0.0;
-  for (size_t k = 0; k < m; ++k) {
-    sw += D.w[k];
-    swf += D.w[k] * f[k];
-    swg += D.w[k] * D.g[k];
-  }
-  const double fb = swf / sw, gb = swg / sw;
-  double sff = 0.0, sfg = 0.0, swff = 0.0, swfg = 0.0;
-  for (size_t k = 0; k < m; ++k) {
-    sff += D.w[k] * (f[k] - fb) * (f[k] - fb);
-    sfg += D.w[k] * (f[k] - fb) * (D.g[k] - gb);
-    swff += D.w[k] * f[k] * f[k];
-    swfg += D.w[k] * f[k] * D.g[k];
-  }
-  const double frac = D.frac;
-  double best = fit_residual(D, f, 0.0, 0.0), ba = 0.0, bb = 0.0;   // the vertex
-  auto feasible = [&](double a, double b) { return a >= 0.0 && b >= 0.0 && (1.0 - frac) * a <= frac * b; };
-  auto offer = [&](double a, double b) {
-    if (!(std::isfinite(a) && std::isfinite(b)) || !feasible(a, b)) return;
-    const double o = fit_residual(D, f, a, b);
-    if (o < best) {
-      best = o;
-      ba = a;
-      bb = b;
-    }
-  };
-  if (sff > 0.0) {
-    const double b = sfg / sff;
-    offer(gb - b * fb, b);                   // unconstrained
-  }
-  if (swff > 0.0) offer(0.0, swfg / swff);   // nugget = 0
-  offer(gb, 0.0);                            // sill = nugget (feasible only when frac = 1)
-  if (frac < 1.0) {                          // nugget = frac * sill: a = c b, gamma = b (c + f)
-    const double c = frac / (1.0 - frac);
-    double num = 0.0, den = 0.0;
-    for (size_t k = 0; k < m; ++k) {
-      num += D.w[k] * (c + f[k]) * D.g[k];
-      den += D.w[k] * (c + f[k]) * (c + f[k]);
-    }
-    if (den > 0.0) offer(c * (num / den), num / den);
-  }
-  *a_out = ba;
-  *b_out = bb;
-  return best;
-}
-
-constexpr int FIT_GRID = 256;
-
-// range: log-spaced grid over [hmin / 4, 4 hmax], then golden section on the best bracket to 1e-8 relative width
-double fit_kind(const FitData& D, int kind, double nu, double* nugget, double* sill, double* range) {
-  double hmin = D.h[0], hmax = D.h[0];
-  for (double v : D.h) {
-    hmin = v < hmin ? v : hmin;
-    hmax = v > hmax ? v : hmax;
-  }
-  const double r0 = 0.25 * hmin, r1 = 4.0 * hmax;
-  std::vector<double> rg(FIT_GRID), og(FIT_GRID);
-  int ib = 0;
-  double a, b;
-  for (int i = 0; i < FIT_GRID; ++i) {
-    rg[i] = r0 * std::pow(r1 / r0, (double)i / (double)(FIT_GRID - 1));
-    og[i] = fit_inner(D, kind, nu, rg[i], &a, &b);
-    if (og[i] < og[ib]) ib = i;
-  }
-  double lo = rg[ib > 0 ? ib - 1 : 0], hi = rg[ib < FIT_GRID - 1 ? ib + 1 : FIT_GRID - 1];
-  double rbest = rg[ib], obest = og[ib];
-  const double gr = 0.6180339887498949;
-  double x1 = hi - gr * (hi - lo), x2 = lo + gr * (hi - lo);
-  double o1 = fit_inner(D, kind, nu, x1, &a, &b), o2 = fit_inner(D, kind, nu, x2, &a, &b);
-  for (int it = 0; it < 200 && (hi - lo) > 1e-8 * 0.5 * (hi + lo); ++it) {
-    if (o1 < obest) { obest = o1; rbest = x1; }
-    if (o2 < obest) { obest = o2; rbest = x2; }
-    if (o1 <= o2) {
-      hi = x2;
-      x2 = x1;
-      o2 = o1;
-      x1 = hi - gr * (hi - lo);
-      o1 = fit_inner(D, kind, nu, x1, &a, &b);
-    } else {
-      lo = x1;
-      x1 = x2;
-      o1 = o2;
-      x2 = lo + gr * (hi - lo);
-      o2 = fit_inner(D, kind, nu, x2, &a, &b);
-    }
-  }
-  if (o1 < obest) { obest = o1; rbest = x1; }
-  if (o2 < obest) { obest = o2; rbest = x2; }
-  obest = fit_inner(D, kind, nu, rbest, &a, &b);
-  *nugget = a;
-  *sill = a + b;
-  *range = rbest;
-  return obest;
-}
-
-// ---- linear model of coregionalisation (gss_variogram_fit_lmc) -------------------------------------------------------
-// Gamma_k (nz x nz, symmetric) ~ B0 + B1 f_k with B0, B1 positive semidefinite.  Matrices are row-major nz x nz.
-constexpr int LMC_MAX_NZ = 8;
-
-// P+: the nearest positive semidefinite matrix in the Frobenius norm.  Cyclic Jacobi, rotations in the fixed order
-// (0,1), (0,2), .., (nz-2,nz-1), until the off-diagonal part is below 1e-34 of the whole or 64 sweeps; negative
-// eigenvalues are set to 0.  A matrix without a negative eigenvalue is returned as it came (no rounding added).
-void lmc_project(int nz, double* M) {
-  double A[LMC_MAX_NZ * LMC_MAX_NZ], V[LMC_MAX_NZ * LMC_MAX_NZ];
-  for (int i = 0; i < nz; ++i) {
-    for (int j = 0; j < nz; ++j) {
-      A[i * nz + j] = 0.5 * (M[i * nz + j] + M[j * nz + i]);
-      V[i * nz + j] = i == j ? 1.0 : 0.0;
-    }
-  }
-  for (int sweep = 0; sweep < 64; ++sweep) {
-    double off = 0.0, all = 0.0;
-    for (int i = 0; i < nz; ++i) {
-      for (int j = 0; j < nz; ++j) {
-        all += A[i * nz + j] * A[i * nz + j];
-        if (i != j) off += A[i * nz + j] * A[i * nz + j];
-      }
-    }
-    if (off <= 1e-34 * all) break;
-    for (int p = 0; p < nz - 1; ++p) {
-      for (int q = p + 1; q < nz; ++q) {
-        const double apq = A[p * nz + q];
-        if (apq == 0.0) continue;
-        const double theta = (A[q * nz + q] - A[p * nz + p]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-        for (int k = 0; k < nz; ++k) {   // columns p, q
-          const double akp = A[k * nz + p], akq = A[k * nz + q];
-          A[k * nz + p] = c * akp - sn * akq;
-          A[k * nz + q] = sn * akp + c * akq;
-        }
-        for (int k = 0; k < nz; ++k) {   // rows p, q
-          const double apk = A[p * nz + k], aqk = A[q * nz + k];
-          A[p * nz + k] = c * apk - sn * aqk;
-          A[q * nz + k] = sn * apk + c * aqk;
-        }
-        A[p * nz + q] = A[q * nz + p] = 0.0;
-        for (int k = 0; k < nz; ++k) {
-          const double vkp = V[k * nz + p], vkq = V[k * nz + q];
-          V[k * nz + p] = c * vkp - sn * vkq;
-          V[k * nz + q] = sn * vkp + c * vkq;
-        }
-      }
-    }
-  }
-  bool negative = false;
-  for (int i = 0; i < nz; ++i) negative = negative || A[i * nz + i] < 0.0;
-  if (!negative) return;
-  for (int i = 0; i < nz; ++i) {
-    for (int j = i; j < nz; ++j) {
-      double v = 0.0;
-      for (int k = 0; k < nz; ++k) {
-        const double ev = A[k * nz + k];
-        if (ev > 0.0) v += V[i * nz + k] * ev * V[j * nz + k];
-      }
-      M[i * nz + j] = M[j * nz + i] = v;
-    }
-  }
-}
-
-struct LmcData {
-  int nz;
-  std::vector<double> h, w;
-  std::vector<double> G;   // per usable bin: the full nz x nz matrix
-};
-
-double lmc_objective(const LmcData& D, const std::vector<double>& f, const double* B0, const double* B1) {
-  const int nn = D.nz * D.nz;
-  double s = 0.0;
-  for (size_t k = 0; k < f.size(); ++k) {
-    double r2 = 0.0;
-    for (int e = 0; e < nn; ++e) {
-      const double r = D.G[k * nn + e] - B0[e] - B1[e] * f[k];
-      r2 += r * r;
-    }
-    s += D.w[k] * r2;
-  }
-  return s;
-}
-
-// Goulard-Voltz sweeps for given shape values f_k, from the unconstrained least-squares solution of every entry.
-double lmc_inner(const LmcData& D, const std::vector<double>& f, double* B0, double* B1) {
-  const int nz = D.nz, nn = nz * nz;
-  const size_t m = f.size();
-  double sw = 0.0, swf = 0.0, swff = 0.0;
-  for (size_t k = 0; k < m; ++k) {
-    sw += D.w[k];
-    swf += D.w[k] * f[k];
-    swff += D.w[k] * f[k] * f[k];
-  }
-  const double fb = swf / sw;
-  double sff = 0.0;
-  for (size_t k = 0; k < m; ++k) sff += D.w[k] * (f[k] - fb) * (f[k] - fb);
-  double SG[LMC_MAX_NZ * LMC_MAX_NZ], SFG[LMC_MAX_NZ * LMC_MAX_NZ];
-  for (int e = 0; e < nn; ++e) {
-    double sg = 0.0, sfg = 0.0;
-    for (size_t k = 0; k < m; ++k) {
-      sg += D.w[k] * D.G[k * nn + e];
-      sfg += D.w[k] * f[k] * D.G[k * nn + e];
-    }
-    SG[e] = sg;
-    SFG[e] = sfg;
-    const double gb = sg / sw;
-    double c = 0.0;
-    for (size_t k = 0; k < m; ++k) c += D.w[k] * (f[k] - fb) * (D.G[k * nn + e] - gb);
-    B1[e] = sff > 0.0 ? c / sff : 0.0;
-    B0[e] = gb - B1[e] * fb;
-  }
-  for (int sweep = 0; sweep < 1000; ++sweep) {
-    double N0[LMC_MAX_NZ * LMC_MAX_NZ], N1[LMC_MAX_NZ * LMC_MAX_NZ];
-    for (int e = 0; e < nn; ++e) N0[e] = (SG[e] - B1[e] * swf) / sw;
-    lmc_project(nz, N0);
-    for (int e = 0; e < nn; ++e) N1[e] = swff > 0.0 ? (SFG[e] - N0[e] * swf) / swff : 0.0;
-    lmc_project(nz, N1);
-    double d0 = 0.0, d1 = 0.0, n0 = 0.0, n1 = 0.0;
-    for (int e = 0; e < nn; ++e) {
-      d0 += (N0[e] - B0[e]) * (N0[e] - B0[e]);
-      d1 += (N1[e] - B1[e]) * (N1[e] - B1[e]);
-      n0 += N0[e] * N0[e];
-      n1 += N1[e] * N1[e];
-      B0[e] = N0[e];
-      B1[e] = N1[e];
-    }
-    const double tol = 1e-12 * (std::sqrt(n0) + std::sqrt(n1));
-    if (std::sqrt(d0) <= tol && std::sqrt(d1) <= tol) break;
-  }
-  return lmc_objective(D, f, B0, B1);
-}
-
-double lmc_at(const LmcData& D, int kind, double nu, double range, double* B0, double* B1) {
-  std::vector<double> f(D.h.size());
-  for (size_t k = 0; k < f.size(); ++k) f[k] = fit_shape(kind, D.h[k] / range, nu);
-  return lmc_inner(D, f, B0, B1);
-}
-
-// the range search of fit_kind with the sweeps as the inner solve
-double lmc_kind(const LmcData& D, int kind, double nu, double* range, double* B0, double* B1) {
-  double hmin = D.h[0], hmax = D.h[0];
-  for (double v : D.h) {
-    hmin = v < hmin ? v : hmin;
-    hmax = v > hmax ? v : hmax;
-  }
-  const double r0 = 0.25 * hmin, r1 = 4.0 * hmax;
-  std::vector<double> rg(FIT_GRID), og(FIT_GRID);
-  int ib = 0;
-  for (int i = 0; i < FIT_GRID; ++i) {
-    rg[i] = r0 * std::pow(r1 / r0, (double)i / (double)(FIT_GRID - 1));
-    og[i] = lmc_at(D, kind, nu, rg[i], B0, B1);
-    if (og[i] < og[ib]) ib = i;
-  }
-  double lo = rg[ib > 0 ? ib - 1 : 0], hi = rg[ib < FIT_GRID - 1 ? ib + 1 : FIT_GRID - 1];
-  double rbest = rg[ib], obest = og[ib];
-  const double gr = 0.6180339887498949;
-  double x1 = hi - gr * (hi - lo), x2 = lo + gr * (hi - lo);
-  double o1 = lmc_at(D, kind, nu, x1, B0, B1), o2 = lmc_at(D, kind, nu, x2, B0, B1);
-  for (int it = 0; it < 200 && (hi - lo) > 1e-8 * 0.5 * (hi + lo); ++it) {
-    if (o1 < obest) { obest = o1; rbest = x1; }
-    if (o2 < obest) { obest = o2; rbest = x2; }
-    if (o1 <= o2) {
-      hi = x2;
-      x2 = x1;
-      o2 = o1;
-      x1 = hi - gr * (hi - lo);
-      o1 = lmc_at(D, kind, nu, x1, B0, B1);
-    } else {
-      lo = x1;
-      x1 = x2;
-      o1 = o2;
-      x2 = lo + gr * (hi - lo);
-      o2 = lmc_at(D, kind, nu, x2, B0, B1);
-    }
-  }
-  if (o1 < obest) { obest = o1; rbest = x1; }
-  if (o2 < obest) { obest = o2; rbest = x2; }
-  *range = rbest;
-  return lmc_at(D, kind, nu, rbest, B0, B1);
-}
-
-// ---- geometric anisotropy in the plane (gss_variogram_fit_aniso) -----------------------------------------------------
-// Outer parameters u = (log r1, log(r2 / r1) <= 0, theta); for fixed u the scaled lag of bin k is
-// h_k sqrt(cos^2(phi_k - theta) / r1^2 + sin^2(phi_k - theta) / r2^2) and the rest is the cone solve above.
-struct AnisoFit {
-  const FitData& D;
-  const std::vector<double>& phi;
-  int kind;
-  double nu;
-  double ulo, uhi;   // bounds of log r1
-  mutable std::vector<double> f;
-
-  double eval(const double* u, double* a, double* b) const {
-    const double r1 = std::exp(u[0]), r2 = r1 * std::exp(u[1]);
-    const size_t m = D.h.size();
-    f.resize(m);
-    for (size_t k = 0; k < m; ++k) {
-      const double c = std::cos(phi[k] - u[2]) / r1, sn = std::sin(phi[k] - u[2]) / r2;
-      f[k] = fit_shape(kind, D.h[k] * std::sqrt(c * c + sn * sn), nu);
-    }
-    return fit_inner_f(D, f, a, b);
-  }
-  double eval(const double* u) const {
-    double a, b;
-    return eval(u, &a, &b);
-  }
-
-  // golden section along u + t dir over t in [lo, hi] to a width of 1e-8 in the parameter that moves most (u holds
-  // logarithms and an angle: a relative width for the radii); both ends are offered as well, so that a minimum on a
-  // bound (ratio 1) is returned as the bound.  u and *o (the objective at u) are updated when something better is found.
-  void line(double* u, const double* dir, double lo, double hi, double* o) const {
-    const double gr = 0.6180339887498949;
-    const double u0[3] = {u[0], u[1], u[2]};
-    double scale = 0.0;
-    for (int c = 0; c < 3; ++c) scale = std::fabs(dir[c]) > scale ? std::fabs(dir[c]) : scale;
-    double best = *o, tbest = 0.0;
-    auto at = [&](double t) {
-      for (int c = 0; c < 3; ++c) u[c] = u0[c] + t * dir[c];
-      if (u[1] > 0.0) u[1] = 0.0;   // (rounding at the bound)
-      const double val = eval(u);
-      if (val < best) {
-        best = val;
-        tbest = t;
-      }
-      return val;
-    };
-    at(lo);
-    at(hi);
-    double x1 = hi - gr * (hi - lo), x2 = lo + gr * (hi - lo);
-    double o1 = at(x1), o2 = at(x2);
-    for (int it = 0; it < 200 && (hi - lo) * scale > 1e-8; ++it) {
-      if (o1 <= o2) {
-        hi = x2;
-        x2 = x1;
-        o2 = o1;
-        x1 = hi - gr * (hi - lo);
-        o1 = at(x1);
-      } else {
-        lo = x1;
-        x1 = x2;
-        o1 = o2;
-        x2 = lo + gr * (hi - lo);
-        o2 = at(x2);
-      }
-    }
-    for (int c = 0; c < 3; ++c) u[c] = u0[c] + tbest * dir[c];
-    if (u[1] > 0.0) u[1] = 0.0;
-    *o = best;
-  }
-
-  // the part [lo, hi] of t for which u + t dir stays inside the bounds of log r1 and of the log ratio
-  void clip(const double* u, const double* dir, double* lo, double* hi) const {
-    const double blo[2] = {ulo, -2.772588722239781}, bhi[2] = {uhi, 0.0};   // ratio in [1/16, 1]
-    for (int c = 0; c < 2; ++c) {
-      if (dir[c] == 0.0) continue;
-      double t0 = (blo[c] - u[c]) / dir[c], t1 = (bhi[c] - u[c]) / dir[c];
-      if (t0 > t1) {
-        const double t = t0;
-        t0 = t1;
-        t1 = t;
-      }
-      *lo = *lo < t0 ? t0 : *lo;
-      *hi = *hi > t1 ? t1 : *hi;
-    }
-  }
-
-  // Cyclic line searches from u with brackets w that follow the steps taken (twice the last move, at least a quarter
-  // of the last bracket), and after every cycle one search along the cycle's net move, which is what carries the point
-  // along a valley that no axis follows; until a whole cycle moves nothing by more than 1e-10.
-  double refine(double* u, const double* w0) const {
-    double w[3] = {w0[0], w0[1], w0[2]};
-    double o = eval(u);
-    for (int cycle = 0; cycle < 400; ++cycle) {
-      const double start[3] = {u[0], u[1], u[2]};
-      for (int i = 0; i < 3; ++i) {
-        double dir[3] = {0.0, 0.0, 0.0};
-        dir[i] = 1.0;
-        double lo = -w[i], hi = w[i];
-        clip(u, dir, &lo, &hi);
-        const double before = u[i];
-        if (hi > lo) line(u, dir, lo, hi, &o);
-        const double step = std::fabs(u[i] - before);
-        const double shrunk = 0.25 * w[i], grown = 2.0 * step;
-        w[i] = grown > shrunk ? grown : shrunk;
-        if (w[i] < 1e-7) w[i] = 1e-7;
-      }
-      double net[3], moved = 0.0;
-      for (int c = 0; c < 3; ++c) {
-        net[c] = u[c] - start[c];
-        moved = std::fabs(net[c]) > moved ? std::fabs(net[c]) : moved;
-      }
-      if (moved <= 1e-10) break;
-      double lo = -1.0, hi = 8.0;
-      clip(u, net, &lo, &hi);
-      if (hi > lo) line(u, net, lo, hi, &o);
-    }
-    return o;
-  }
-};
-
-constexpr int ANISO_NTHETA = 36, ANISO_NR1 = 32, ANISO_NRATIO = 16, ANISO_STARTS = 4;
-
-// -> objective; u = (log r1, log ratio, theta in [0, pi))
-double fit_kind_aniso(const FitData& D, const std::vector<double>& phi, int kind, double nu, double* nugget,
-                      double* sill, double* u_out) {
-  const double pi = 3.14159265358979323846;
-  double hmin = D.h[0], hmax = D.h[0];
-  for (double v : D.h) {
-    hmin = v < hmin ? v : hmin;
-    hmax = v > hmax ? v : hmax;
-  }
-  AnisoFit F{D, phi, kind, nu, std::log(0.25 * hmin), std::log(4.0 * hmax), {}};
-  const double w0[3] = {(F.uhi - F.ulo) / (ANISO_NR1 - 1), 2.772588722239781 / (ANISO_NRATIO - 1), pi / ANISO_NTHETA};
-  // the grid; the ANISO_STARTS best points (ties: the first met) start a refinement each
-  double so[ANISO_STARTS], su[ANISO_STARTS][3];
-  int ns = 0;
-  for (int it = 0; it < ANISO_NTHETA; ++it) {
-    for (int ir = 0; ir < ANISO_NR1; ++ir) {
-      for (int iq = 0; iq < ANISO_NRATIO; ++iq) {
-        if (iq == ANISO_NRATIO - 1 && it > 0) continue;   // ratio 1: every angle is the same model
-        const double u[3] = {F.ulo + w0[0] * ir, iq == ANISO_NRATIO - 1 ? 0.0 : -2.772588722239781 + w0[1] * iq,
-                             w0[2] * it};
-        const double o = F.eval(u);
-        int pos = ns;
-        while (pos > 0 && o < so[pos - 1]) --pos;
-        if (pos >= ANISO_STARTS) continue;
-        const int last = ns < ANISO_STARTS ? ns : ANISO_STARTS - 1;
-        for (int q = last; q > pos; --q) {
-          so[q] = so[q - 1];
-          for (int c = 0; c < 3; ++c) su[q][c] = su[q - 1][c];
-        }
-        so[pos] = o;
-        for (int c = 0; c < 3; ++c) su[pos][c] = u[c];
-        if (ns < ANISO_STARTS) ++ns;
-      }
-    }
-  }
-  double obest = 0.0;
-  for (int q = 0; q < ns; ++q) {
-    const double o = F.refine(su[q], w0);
-    if (q == 0 || o < obest) {
-      obest = o;
-      for (int c = 0; c < 3; ++c) u_out[c] = su[q][c];
-    }
-  }
-  u_out[2] = u_out[2] - pi * std::floor(u_out[2] / pi);
-  if (!(u_out[2] < pi)) u_out[2] = 0.0;
-  double a, b;
-  obest = F.eval(u_out, &a, &b);
-  *nugget = a;
-  *sill = a + b;
-  return obest;
-}
-
-}  // namespace
-
 }  // namespace gss
 
 using namespace gss;
 
 namespace {
 
-// The pass over the pairs that gss_variogram_empirical and gss_variogram_plane share: checks of the common arguments,
-// staging, the finite-input check, the ordering, the gather, the grid, the pair kernel, the reduction and the way home.
-// A: what the caller has filled in of the kernel's arguments (direction or sectors); nbins: bins of the histogram
-// (nlags, or nangles nlags); dirs: the plane's sector boundaries (host), else NULL.  nsum: rows of value sums per bin
-// (nz, or nz (nz + 1) / 2 products when `cross`: gss_variogram_cross).
-int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, const double* z, int32_t nz, int32_t nlags, double maxlag, int32_t estimator, VarioArgs& A, int64_t nbins, const double* dirs,
-                  int64_t* count, double* lagsum, double* zsum, int64_t* nduplicates, int32_t mem, void* stream,
-                  bool cross = false, int32_t nsum = 0) {
-  const bool plane = dirs != nullptr;
-  if (!cross) nsum = nz;
+// The pass over the pairs that gss_variogram_empirical, gss_variogram_plane and gss_variogram_cross share: checks of
+// the common arguments, staging, the finite-input check, the ordering, the gather, the grid, the pair kernel, the
+// reduction and the way home.  A: what the caller has filled in of the kernel's arguments (direction or sectors).
+int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
+                  int32_t nlags, double maxlag, int32_t estimator, VarioArgs& A, const VarioForm& F, int64_t* count,
+                  double* lagsum, double* zsum, int64_t* nduplicates, int32_t mem, void* stream) {
+  const int64_t nbins = F.nbins;
+  const int32_t nsum = F.nsum;
   // squared bin edges edge2[k] = fl(fl(k delta)^2): the kernel forms the same doubles; only the ends are checked here
   const double delta = maxlag / (double)nlags;
   {
@@ -1424,8 +908,8 @@ int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, cons
   P.lo = ix.lo.as<double>();
   P.hi = ix.hi.as<double>();
   P.dirs = nullptr;
-  if (plane) {   // the sector boundaries: a host array in both memory modes
-    GSS_TRY(sdirs.in(dirs, sizeof(double) * 2 * (size_t)A.nangles, GSS_MEM_HOST, s));
+  if (F.dirs) {   // the sector boundaries: a host array in both memory modes
+    GSS_TRY(sdirs.in(F.dirs, sizeof(double) * 2 * (size_t)A.nangles, GSS_MEM_HOST, s));
     P.dirs = sdirs.as<double>();
   }
   A.n = n;
@@ -1433,7 +917,6 @@ int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, cons
   A.jw = ix.nb < 512 ? 4 : VARIO_JW_MAX;   // below ~32 000 samples 16-tile units are too few to fill the device
   A.nchunks = (ix.nb + A.jw - 1) / A.jw;
   A.nlags = nlags;
-  A.estimator = estimator;
   {
     const char* e = std::getenv("GSS_VARIO_CULL");   // "0": open every tile (tests: results do not depend on it)
     A.nocull = e && e[0] == '0';
@@ -1442,13 +925,13 @@ int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, cons
   A.inv_delta = 1.0 / delta;
   P.unit_counter = d_flags;
   const size_t nwords = (size_t)(nbins + 2) + nbins + (size_t)nsum * nbins;
-  const size_t lds = sizeof(double) * ((size_t)nlags + 1 + nwords + (plane ? 2 * (size_t)A.nangles : 0));
+  const size_t lds = sizeof(double) * ((size_t)nlags + 1 + nwords + (F.dirs ? 2 * (size_t)A.nangles : 0));
+  const VarioKernel kernel = vario_kernel(F.form, dim, nz, estimator);
   // the grid: as many workgroups as are resident at a time for this instantiation (registers and LDS decide: 6 per CU
   // for one value column, 2 for eight), fewer when there are not two units per wave; a workgroup beyond that would only
   // start once the others have emptied the counter
   int resident = 0;
-  if (cross) GSS_TRY(vario_launch_cross(dim, P, A, nz, 0, lds, s, &resident));
-  else GSS_TRY(vario_launch_any(plane, dim, P, A, nz, 0, lds, s, &resident));
+  GSS_TRY(vario_launch(kernel, F.form != VARIO_LAGS, P, A, 0, lds, s, &resident));
   if (resident < 1) resident = 1;
   const int64_t nunits = (int64_t)A.nb * A.nchunks;
   const int64_t want = (nunits + 7) / 8, cap = (int64_t)ncu * resident;
@@ -1470,9 +953,9 @@ int32_t vario_run(const char* who, const double* x, int64_t n, int32_t dim, cons
     GSS_HIP(hipEventCreateWithFlags(&g_vario_event, hipEventDisableTiming));
   }
   {
-    ProfScope prof(cross ? "vario_cross" : (plane ? "vario_plane" : "vario_pairs"), s);
-    if (cross) GSS_TRY(vario_launch_cross(dim, P, A, nz, nwg, lds, s, nullptr));
-    else GSS_TRY(vario_launch_any(plane, dim, P, A, nz, nwg, lds, s, nullptr));
+    static const char* const scope[] = {"vario_pairs", "vario_plane", "vario_cross"};   // by form
+    ProfScope prof(scope[F.form], s);
+    GSS_TRY(vario_launch(kernel, false, P, A, nwg, lds, s, nullptr));
   }
   // (a histogram of nbins bins is reduced as one of nbins lags: sector s of the plane at s * nlags)
   hipLaunchKernelGGL(vario_reduce_kernel, dim3((unsigned)nwords), dim3(256), 0, s, P.partial, nwg,
@@ -1549,8 +1032,8 @@ extern "C" int32_t gss_variogram_empirical(const double* x, int64_t n, int32_t d
                            lagsum, zsum, nduplicates, mem));
   VarioArgs A;
   GSS_TRY(vario_direction("gss_variogram_empirical", dim, direction, dtol, cos_atol, A));
-  return vario_run("gss_variogram_empirical", x, n, dim, z, nz, nlags, maxlag, estimator, A, nlags, nullptr,
-                   count, lagsum, zsum, nduplicates, mem, stream);
+  return vario_run("gss_variogram_empirical", x, n, dim, z, nz, nlags, maxlag, estimator, A,
+                   VarioForm{VARIO_LAGS, nlags, nz, nullptr}, count, lagsum, zsum, nduplicates, mem, stream);
 }
 
 extern "C" int32_t gss_variogram_cross(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
@@ -1562,8 +1045,9 @@ extern "C" int32_t gss_variogram_cross(const double* x, int64_t n, int32_t dim, 
                            count, lagsum, csum, nduplicates, mem));
   VarioArgs A;
   GSS_TRY(vario_direction("gss_variogram_cross", dim, direction, dtol, cos_atol, A));
-  return vario_run("gss_variogram_cross", x, n, dim, z, nz, nlags, maxlag, GSS_VARIO_MATHERON, A, nlags, nullptr, count,
-                   lagsum, csum, nduplicates, mem, stream, true, nz * (nz + 1) / 2);
+  return vario_run("gss_variogram_cross", x, n, dim, z, nz, nlags, maxlag, GSS_VARIO_MATHERON, A,
+                   VarioForm{VARIO_CROSS, nlags, nz * (nz + 1) / 2, nullptr}, count, lagsum, csum, nduplicates, mem,
+                   stream);
 }
 
 extern "C" int32_t gss_variogram_plane(const double* x, int64_t n, int32_t dim, const double* z, int32_t nz,
@@ -1621,8 +1105,9 @@ extern "C" int32_t gss_variogram_plane(const double* x, int64_t n, int32_t dim, 
     volatile double p2 = ptol * ptol;
     A.ptol2 = p2;
   }
-  return vario_run(who, x, n, dim, z, nz, nlags, maxlag, estimator, A, (int64_t)nangles * nlags, dirs,
-                   count, lagsum, zsum, nduplicates, mem, stream);
+  return vario_run(who, x, n, dim, z, nz, nlags, maxlag, estimator, A,
+                   VarioForm{VARIO_PLANE, (int64_t)nangles * nlags, nz, dirs}, count, lagsum, zsum, nduplicates, mem,
+                   stream);
 }
 
 // gss_shutdown: the page-locked tile counter and its event
@@ -1632,238 +1117,4 @@ void gss::vario_release() {
   g_vario_event = nullptr;
   g_vario_stats = nullptr;
   g_vario_pending = false;
-}
-
-extern "C" int32_t gss_variogram_fit(const double* h, const double* gamma, const int64_t* count, int32_t nlags,
-                                     const int32_t* kinds, int32_t nkinds, double nu, int32_t weighting,
-                                     double max_nugget_frac, gss_variogram_t* best, double* objective) {
-  GSS_ENTRY();
-  GSS_REQUIRE(h != nullptr && gamma != nullptr && count != nullptr && kinds != nullptr && best != nullptr &&
-                  objective != nullptr, "gss_variogram_fit: NULL argument");
-  GSS_REQUIRE(nlags >= 1 && nlags <= 65536, "gss_variogram_fit: nlags %d outside 1..65536", nlags);
-  GSS_REQUIRE(nkinds >= 1 && nkinds <= 64, "gss_variogram_fit: nkinds %d outside 1..64", nkinds);
-  GSS_REQUIRE(weighting >= GSS_FIT_W_COUNT && weighting <= GSS_FIT_W_UNIFORM, "gss_variogram_fit: unknown weighting %d",
-              weighting);
-  GSS_REQUIRE(max_nugget_frac >= 0.0 && max_nugget_frac <= 1.0, "gss_variogram_fit: max_nugget_frac outside [0, 1]");
-  bool matern = false;
-  for (int i = 0; i < nkinds; ++i) {
-    if (kinds[i] == GSS_VG_POWER) {
-      set_error("gss_variogram_fit: the power model has no sill and no range to search; only the stationary kinds are "
-                "fitted");
-      return GSS_ERR_UNSUPPORTED;
-    }
-    GSS_REQUIRE(kinds[i] >= GSS_VG_GAUSSIAN && kinds[i] <= GSS_VG_SINEHOLE, "gss_variogram_fit: unknown kind %d",
-                kinds[i]);
-    matern = matern || kinds[i] == GSS_VG_MATERN;
-  }
-  if (matern) GSS_REQUIRE(nu > 0.0 && nu <= 50.0, "gss_variogram_fit: Matern order must lie in (0, 50]");
-  FitData D;
-  D.frac = max_nugget_frac;
-  for (int k = 0; k < nlags; ++k) {
-    if (count[k] <= 0) continue;
-    GSS_REQUIRE(std::isfinite(h[k]) && h[k] > 0.0 && std::isfinite(gamma[k]), "gss_variogram_fit: bin %d has pairs but "
-                "no finite positive lag / finite ordinate", k);
-    const double c = (double)count[k];
-    D.h.push_back(h[k]);
-    D.g.push_back(gamma[k]);
-    D.w.push_back(weighting == GSS_FIT_W_COUNT ? c : (weighting == GSS_FIT_W_COUNT_OVER_H2 ? c / (h[k] * h[k]) : 1.0));
-  }
-  GSS_REQUIRE(D.h.size() >= 2, "gss_variogram_fit: fewer than two bins hold pairs");
-  int ibest = -1;
-  double nbest = 0.0, sbest = 0.0, rbest = 0.0;
-  for (int i = 0; i < nkinds; ++i) {
-    double ng, sl, rg;
-    objective[i] = fit_kind(D, kinds[i], nu, &ng, &sl, &rg);
-    if (!(sl > 0.0)) {   // the ordinates admit no model of this kind with a positive sill
-      objective[i] = std::nan("");
-      continue;
-    }
-    if (ibest < 0 || objective[i] < objective[ibest]) {
-      ibest = i;
-      nbest = ng;
-      sbest = sl;
-      rbest = rg;
-    }
-  }
-  GSS_REQUIRE(ibest >= 0, "gss_variogram_fit: no kind fits these ordinates with a positive sill");
-  std::memset(best, 0, sizeof(*best));
-  best->kind = kinds[ibest];
-  best->dim = 0;   // left to the caller
-  best->sill = sbest;
-  best->nugget = nbest;
-  best->range = rbest;
-  best->nu = kinds[ibest] == GSS_VG_MATERN ? nu : 1.0;
-  for (int a = 0; a < 3; ++a) {
-    best->inv_radii[a] = 1.0;
-    best->rotation[4 * a] = 1.0;
-  }
-  return GSS_OK;
-}
-
-extern "C" int32_t gss_variogram_fit_aniso(const double* h, const double* phi, const double* gamma, const int64_t* count,
-                                           int32_t nbins, const int32_t* kinds, int32_t nkinds, double nu,
-                                           int32_t weighting, double max_nugget_frac, gss_variogram_t* best,
-                                           double* objective) {
-  GSS_ENTRY();
-  GSS_REQUIRE(h != nullptr && phi != nullptr && gamma != nullptr && count != nullptr && kinds != nullptr &&
-                  best != nullptr && objective != nullptr, "gss_variogram_fit_aniso: NULL argument");
-  GSS_REQUIRE(nbins >= 1 && nbins <= 65536, "gss_variogram_fit_aniso: nbins %d outside 1..65536", nbins);
-  GSS_REQUIRE(nkinds >= 1 && nkinds <= 64, "gss_variogram_fit_aniso: nkinds %d outside 1..64", nkinds);
-  GSS_REQUIRE(weighting >= GSS_FIT_W_COUNT && weighting <= GSS_FIT_W_UNIFORM,
-              "gss_variogram_fit_aniso: unknown weighting %d", weighting);
-  GSS_REQUIRE(max_nugget_frac >= 0.0 && max_nugget_frac <= 1.0,
-              "gss_variogram_fit_aniso: max_nugget_frac outside [0, 1]");
-  bool matern = false;
-  for (int i = 0; i < nkinds; ++i) {
-    if (kinds[i] == GSS_VG_POWER) {
-      set_error("gss_variogram_fit_aniso: the power model has no sill and no range to search; only the stationary "
-                "kinds are fitted");
-      return GSS_ERR_UNSUPPORTED;
-    }
-    GSS_REQUIRE(kinds[i] >= GSS_VG_GAUSSIAN && kinds[i] <= GSS_VG_SINEHOLE, "gss_variogram_fit_aniso: unknown kind %d",
-                kinds[i]);
-    matern = matern || kinds[i] == GSS_VG_MATERN;
-  }
-  if (matern) GSS_REQUIRE(nu > 0.0 && nu <= 50.0, "gss_variogram_fit_aniso: Matern order must lie in (0, 50]");
-  FitData D;
-  std::vector<double> ph;
-  D.frac = max_nugget_frac;
-  for (int k = 0; k < nbins; ++k) {
-    if (count[k] <= 0) continue;
-    GSS_REQUIRE(std::isfinite(h[k]) && h[k] > 0.0 && std::isfinite(gamma[k]) && std::isfinite(phi[k]),
-                "gss_variogram_fit_aniso: bin %d has pairs but no finite positive lag / finite ordinate / finite angle",
-                k);
-    const double c = (double)count[k];
-    D.h.push_back(h[k]);
-    D.g.push_back(gamma[k]);
-    ph.push_back(phi[k]);
-    D.w.push_back(weighting == GSS_FIT_W_COUNT ? c : (weighting == GSS_FIT_W_COUNT_OVER_H2 ? c / (h[k] * h[k]) : 1.0));
-  }
-  GSS_REQUIRE(D.h.size() >= 4, "gss_variogram_fit_aniso: fewer than four bins hold pairs");
-  int ibest = -1;
-  double nbest = 0.0, sbest = 0.0, ubest[3] = {0.0, 0.0, 0.0};
-  for (int i = 0; i < nkinds; ++i) {
-    double ng, sl, u[3];
-    objective[i] = fit_kind_aniso(D, ph, kinds[i], nu, &ng, &sl, u);
-    if (!(sl > 0.0)) {   // the ordinates admit no model of this kind with a positive sill
-      objective[i] = std::nan("");
-      continue;
-    }
-    if (ibest < 0 || objective[i] < objective[ibest]) {
-      ibest = i;
-      nbest = ng;
-      sbest = sl;
-      for (int c = 0; c < 3; ++c) ubest[c] = u[c];
-    }
-  }
-  GSS_REQUIRE(ibest >= 0, "gss_variogram_fit_aniso: no kind fits these ordinates with a positive sill");
-  std::memset(best, 0, sizeof(*best));
-  best->kind = kinds[ibest];
-  best->dim = 0;   // left to the caller
-  best->sill = sbest;
-  best->nugget = nbest;
-  best->nu = kinds[ibest] == GSS_VG_MATERN ? nu : 1.0;
-  for (int a = 0; a < 3; ++a) {
-    best->inv_radii[a] = 1.0;
-    best->rotation[4 * a] = 1.0;
-  }
-  const double r1 = std::exp(ubest[0]);
-  if (ubest[1] == 0.0) {   // ratio 1: the isotropic form
-    best->range = r1;
-    return GSS_OK;
-  }
-  const double r2 = r1 * std::exp(ubest[1]), c = std::cos(ubest[2]), sn = std::sin(ubest[2]);
-  best->aniso = 2;
-  best->range = 1.0;
-  best->inv_radii[0] = 1.0 / r1;
-  best->inv_radii[1] = 1.0 / r2;
-  best->rotation[0] = c;
-  best->rotation[1] = -sn;
-  best->rotation[3] = sn;
-  best->rotation[4] = c;
-  return GSS_OK;
-}
-
-extern "C" int32_t gss_variogram_fit_lmc(const double* h, const double* gamma, const int64_t* count, int32_t nlags,
-                                         int32_t nz, const int32_t* kinds, int32_t nkinds, double nu,
-                                         int32_t weighting, int32_t* kind, double* range, double* b0, double* b1,
-                                         double* objective) {
-  GSS_ENTRY();
-  GSS_REQUIRE(h != nullptr && gamma != nullptr && count != nullptr && kinds != nullptr && kind != nullptr &&
-                  range != nullptr && b0 != nullptr && b1 != nullptr && objective != nullptr,
-              "gss_variogram_fit_lmc: NULL argument");
-  GSS_REQUIRE(nz >= 1 && nz <= LMC_MAX_NZ, "gss_variogram_fit_lmc: nz %d outside 1..%d", nz, LMC_MAX_NZ);
-  GSS_REQUIRE(nlags >= 1 && nlags <= 65536, "gss_variogram_fit_lmc: nlags %d outside 1..65536", nlags);
-  GSS_REQUIRE(nkinds >= 1 && nkinds <= 64, "gss_variogram_fit_lmc: nkinds %d outside 1..64", nkinds);
-  GSS_REQUIRE(weighting >= GSS_FIT_W_COUNT && weighting <= GSS_FIT_W_UNIFORM,
-              "gss_variogram_fit_lmc: unknown weighting %d", weighting);
-  bool matern = false;
-  for (int i = 0; i < nkinds; ++i) {
-    if (kinds[i] == GSS_VG_POWER) {
-      set_error("gss_variogram_fit_lmc: the power model has no sill and no range to search; only the stationary kinds "
-                "are fitted");
-      return GSS_ERR_UNSUPPORTED;
-    }
-    GSS_REQUIRE(kinds[i] >= GSS_VG_GAUSSIAN && kinds[i] <= GSS_VG_SINEHOLE, "gss_variogram_fit_lmc: unknown kind %d",
-                kinds[i]);
-    matern = matern || kinds[i] == GSS_VG_MATERN;
-  }
-  if (matern) GSS_REQUIRE(nu > 0.0 && nu <= 50.0, "gss_variogram_fit_lmc: Matern order must lie in (0, 50]");
-  const int nn = nz * nz;
-  LmcData D;
-  D.nz = nz;
-  for (int k = 0; k < nlags; ++k) {
-    if (count[k] <= 0) continue;
-    GSS_REQUIRE(std::isfinite(h[k]) && h[k] > 0.0, "gss_variogram_fit_lmc: bin %d has pairs but no finite positive lag",
-                k);
-    const double c = (double)count[k];
-    D.h.push_back(h[k]);
-    D.w.push_back(weighting == GSS_FIT_W_COUNT ? c : (weighting == GSS_FIT_W_COUNT_OVER_H2 ? c / (h[k] * h[k]) : 1.0));
-    const size_t at = D.G.size();
-    D.G.resize(at + nn);
-    for (int a = 0; a < nz; ++a) {
-      for (int b = a; b < nz; ++b) {
-        const double g = gamma[(size_t)(a * nz - a * (a - 1) / 2 + (b - a)) * nlags + k];
-        GSS_REQUIRE(std::isfinite(g), "gss_variogram_fit_lmc: bin %d has pairs but no finite ordinate (%d, %d)", k, a, b);
-        D.G[at + a * nz + b] = D.G[at + b * nz + a] = g;
-      }
-    }
-  }
-  GSS_REQUIRE(D.h.size() >= 2, "gss_variogram_fit_lmc: fewer than two bins hold pairs");
-  int ibest = -1;
-  double B0[LMC_MAX_NZ * LMC_MAX_NZ], B1[LMC_MAX_NZ * LMC_MAX_NZ];
-  for (int i = 0; i < nkinds; ++i) {
-    double rg = 0.0;
-    bool positive = true;
-    if (nz == 1) {   // one variable: the positive semidefinite cone is nugget >= 0, sill - nugget >= 0 -- the
-      FitData F;     // closed form of gss_variogram_fit with max_nugget_frac = 1, and its very numbers
-      F.h = D.h;
-      F.g = D.G;
-      F.w = D.w;
-      F.frac = 1.0;
-      double ng, sl;
-      objective[i] = fit_kind(F, kinds[i], nu, &ng, &sl, &rg);
-      B0[0] = ng;
-      B1[0] = sl - ng;
-      positive = sl > 0.0;
-    } else {
-      objective[i] = lmc_kind(D, kinds[i], nu, &rg, B0, B1);
-      for (int a = 0; a < nz; ++a) positive = positive && B0[a * nz + a] + B1[a * nz + a] > 0.0;
-    }
-    if (!positive) {   // a variable without a positive sill: no model of this kind
-      objective[i] = std::nan("");
-      continue;
-    }
-    if (ibest < 0 || objective[i] < objective[ibest]) {
-      ibest = i;
-      *range = rg;
-      for (int e = 0; e < nn; ++e) {
-        b0[e] = B0[e];
-        b1[e] = B1[e];
-      }
-    }
-  }
-  GSS_REQUIRE(ibest >= 0, "gss_variogram_fit_lmc: no kind fits these ordinates with a positive sill for every variable");
-  *kind = kinds[ibest];
-  return GSS_OK;
 }
