@@ -8,8 +8,13 @@
 //   * k == n > 64 : "all samples" (maxneighbors = nothing): no search at all, one thread per estimation
 //                   point sweeping the samples staged through LDS (broadcast reads).
 // Cross-validation (gss_idw_cv / gss_lwr_cv, gss.h): the same two paths with the samples as estimation points -- the
-// fold-aware search in front of the list kernels, and for k == n a self-join with an eligibility test per pair
-// (est_cv_all_kernel, idw_cv_all_fast_kernel).
+// fold-aware search in front of the list kernels, and for k == n a self-join with an eligibility test per pair.
+// The masked and the unmasked all-sample kernels are one body each with the test as a compile-time choice:
+// est_all_body<DIM, ZC, CV> behind est_all_kernel / est_cv_all_kernel, idw_all_fast_body<DIM, E1, CV> behind
+// idw_all_fast_kernel / idw_cv_all_fast_kernel; the __global__ wrappers only load the query (and its fold).  Shared
+// pieces: idw_recip (the rsq / rcp Newton steps), lwr_moments (the S1 / S2 / b update, est_list_kernel too),
+// est_stage_tile (the LDS tile of the general sweep), sqdist_fma.  Host side: with_dim turns dim into a template
+// argument for every launch; idw_spec / lwr_spec build the EstSpec of the predict and the cv entry points.
 // LWR solves its (d+1) x (d+1) normal equations about the estimation point (same predictor, better conditioned
 // than the raw coordinates the reference uses) with an unpivoted Cholesky; a non-positive pivot is reported as
 // GSS_PT_SINGULAR where the reference's `\` would throw.
@@ -136,6 +141,56 @@ __device__ __forceinline__ bool lwr_solve(const double* S1, const double* S2, co
     }
   *var = sqrt(q > 0.0 ? q : 0.0);
   return true;
+}
+
+// One sample's term of the LWR moments: S1 += w u u', S2 += w^2 u u', b_c += w u z_c for the ncz live columns
+// (zval(c): the sample's value in column c).  Shared by the all-sample sweep and est_list_kernel.
+template <int NP, int ZC, class Z>
+__device__ __forceinline__ void lwr_moments(double w, const double* u, int ncz, Z&& zval, double* S1, double* S2,
+                                            double (*b)[NP]) {
+#pragma unroll
+  for (int r = 0; r < NP; ++r) {
+    const double wu = w * u[r];
+#pragma unroll
+    for (int c = 0; c < ZC; ++c)
+      if (c < ncz) b[c][r] += wu * zval(c);
+#pragma unroll
+    for (int q = 0; q <= r; ++q) {
+      const double t = wu * u[q];
+      S1[r * (r + 1) / 2 + q] += t;
+      S2[r * (r + 1) / 2 + q] += w * t;
+    }
+  }
+}
+
+// 1 / d (E1) from v_rsq_f64 or 1 / d^2 from v_rcp_f64 of a squared distance, two Newton steps each.  d2 == 0 gives
+// NaN (0 * inf inside the step): the callers select or detect it, they never multiply it away.
+template <bool E1>
+__device__ __forceinline__ double idw_recip(double d2) {
+  double y;
+  if (E1) {
+    y = __builtin_amdgcn_rsq(d2);
+    const double hh = 0.5 * d2;
+    y = fma(y, fma(-hh * y, y, 0.5), y);
+    y = fma(y, fma(-hh * y, y, 0.5), y);
+  } else {
+    y = __builtin_amdgcn_rcp(d2);
+    y = fma(y, fma(-d2, y, 1.0), y);
+    y = fma(y, fma(-d2, y, 1.0), y);
+  }
+  return y;
+}
+
+// squared Euclidean distance of the scalar-operand kernels: one fma per axis, in axis order
+template <int DIM>
+__device__ __forceinline__ double sqdist_fma(const double* xj, const double* qc) {
+  double d2 = 0.0;
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) {
+    const double t = xj[a] - qc[a];
+    d2 = fma(t, t, d2);
+  }
+  return d2;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -269,6 +324,50 @@ constexpr int EST_TILE = 1024;
 // its running minimum (idw.jl:137 returns the nearest distance), 1 / d from v_rsq_f64 (1 / d^2 from v_rcp_f64) with two
 // Newton steps, and the two sums.  A coincident sample turns the weight into NaN (0 * inf inside the Newton step): that
 // is detected once at the end, and only such points rescan the samples for the first zero distance (idw.jl:131-134).
+//
+// CV (the self-join of cross-validation, below): sample j counts iff fold[j] != myfold; the fold id arrives as a scalar
+// operand like the rest.  The weight of an ineligible sample is selected to zero, never multiplied by it -- the query's
+// own sample has d^2 = 0 and the NaN of the Newton step would pass through a product -- and its d^2 is kept out of the
+// running minimum.  A NaN or infinite sum therefore means a coincident ELIGIBLE sample, and the rescan applies the
+// same test.  Without CV there is no fold load, no count and no select.
+template <int DIM, bool E1, bool CV>
+__device__ __forceinline__ void idw_all_fast_body(const double* __restrict__ xdata, const double* __restrict__ z,
+                                                  const int* __restrict__ fold, int n, const double* qc, int myfold,
+                                                  bool live, int64_t p, int minneighbors,
+                                                  double* __restrict__ mean_out, double* __restrict__ aux_out,
+                                                  uint8_t* __restrict__ status_out) {
+  double sw = 0.0, swz = 0.0, dmin2 = __builtin_huge_val();
+  int cnt = 0;
+#pragma unroll 8
+  for (int j = 0; j < n; ++j) {
+    const double d2 = sqdist_fma<DIM>(xdata + (int64_t)j * DIM, qc);
+    const bool in = !CV || fold[j] != myfold;   // (without CV: true at compile time, the selects below fold away)
+    cnt += in ? 1 : 0;
+    dmin2 = fmin(dmin2, in ? d2 : __builtin_huge_val());
+    const double y = idw_recip<E1>(d2);
+    const double w = in ? y : 0.0;
+    sw += w;
+    swz = fma(w, z[j], swz);
+  }
+  if (!live) return;
+  double mu = swz / sw, dist = gss_sqrt(dmin2);
+  if (!(sw < __builtin_huge_val())) {  // NaN (coincident sample) or overflow: the estimate is the first coincident value
+    for (int j = 0; j < n; ++j) {
+      const double d2 = sqdist_fma<DIM>(xdata + (int64_t)j * DIM, qc);
+      if ((!CV || fold[j] != myfold) && d2 == 0.0) {
+        mu = z[j];
+        dist = 0.0;
+        break;
+      }
+    }
+  }
+  const bool enough = !CV || (cnt >= minneighbors && cnt >= 1);
+  const double NaN = __builtin_nan("");
+  mean_out[p] = enough ? mu : NaN;
+  aux_out[p] = enough ? dist : NaN;
+  status_out[p] = enough ? GSS_PT_OK : GSS_PT_MISSING;
+}
+
 template <int DIM, bool E1>
 __global__ __launch_bounds__(256) void idw_all_fast_kernel(const double* __restrict__ xdata,
                                                            const double* __restrict__ z, int n,
@@ -281,71 +380,75 @@ __global__ __launch_bounds__(256) void idw_all_fast_kernel(const double* __restr
   double qc[DIM];
 #pragma unroll
   for (int a = 0; a < DIM; ++a) qc[a] = live ? x0[p * DIM + a] : 0.0;
-  double sw = 0.0, swz = 0.0, dmin2 = __builtin_huge_val();
-#pragma unroll 8
-  for (int j = 0; j < n; ++j) {
-    double d2 = 0.0;
+  idw_all_fast_body<DIM, E1, false>(xdata, z, nullptr, n, qc, 0, live, p, 0, mean_out, aux_out, status_out);
+}
+
+// The same for cross-validation (one column, no exclusion radius): query p of a launch is sample qoff + p.
+template <int DIM, bool E1>
+__global__ __launch_bounds__(256) void idw_cv_all_fast_kernel(const double* __restrict__ xdata,
+                                                              const double* __restrict__ z,
+                                                              const int* __restrict__ fold, int n, int64_t qoff,
+                                                              int64_t m, int minneighbors,
+                                                              double* __restrict__ mean_out,
+                                                              double* __restrict__ aux_out,
+                                                              uint8_t* __restrict__ status_out) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = p < m;
+  const int64_t g = live ? qoff + p : qoff;   // (qoff < n: a launch has at least one query)
+  double qc[DIM];
 #pragma unroll
-    for (int a = 0; a < DIM; ++a) {
-      const double t = xdata[(int64_t)j * DIM + a] - qc[a];
-      d2 = fma(t, t, d2);
-    }
-    dmin2 = fmin(dmin2, d2);
-    double y;
-    if (E1) {
-      y = __builtin_amdgcn_rsq(d2);
-      const double hh = 0.5 * d2;
-      y = fma(y, fma(-hh * y, y, 0.5), y);
-      y = fma(y, fma(-hh * y, y, 0.5), y);
-    } else {
-      y = __builtin_amdgcn_rcp(d2);
-      y = fma(y, fma(-d2, y, 1.0), y);
-      y = fma(y, fma(-d2, y, 1.0), y);
-    }
-    sw += y;
-    swz = fma(y, z[j], swz);
-  }
-  if (!live) return;
-  double mu = swz / sw, dist = gss_sqrt(dmin2);
-  if (!(sw < __builtin_huge_val())) {  // NaN (coincident sample) or overflow: the estimate is the first coincident value
-    for (int j = 0; j < n; ++j) {
-      double d2 = 0.0;
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) {
-        const double t = xdata[(int64_t)j * DIM + a] - qc[a];
-        d2 = fma(t, t, d2);
-      }
-      if (d2 == 0.0) {
-        mu = z[j];
-        dist = 0.0;
-        break;
-      }
-    }
-  }
-  mean_out[p] = mu;
-  aux_out[p] = dist;
-  status_out[p] = GSS_PT_OK;
+  for (int a = 0; a < DIM; ++a) qc[a] = xdata[g * DIM + a];
+  idw_all_fast_body<DIM, E1, true>(xdata, z, fold, n, qc, fold[g], live, p, minneighbors, mean_out, aux_out,
+                                   status_out);
 }
 
 // ZC = value columns carried through one sweep (1, or up to 4 of a multi-column call: sp.nz columns are served in
-// chunks of ZC, each chunk sweeping the samples again -- the weights of a sweep are shared by its columns)
+// chunks of ZC, each chunk sweeping the samples again -- the weights of a sweep are shared by its columns).
+// The samples pass through LDS in pieces of EST_TILE; the self-join of cross-validation (CV) keeps their fold ids
+// beside them, the plain kernel has no such array.
+template <int DIM, int ZC, bool CV>
+struct EstTile {
+  double x[EST_TILE * DIM];
+  double z[ZC][EST_TILE];
+};
 template <int DIM, int ZC>
-__global__ __launch_bounds__(256) void est_all_kernel(EstSpec sp, const double* __restrict__ xdata,
-                                                      const double* __restrict__ z, int n,
-                                                      const double* __restrict__ x0, int64_t m, int minneighbors,
-                                                      double r2, int use_ball, int aniso, double ir0, double ir1,
-                                                      double ir2, double* __restrict__ mean_out,
-                                                      double* __restrict__ aux_out, uint8_t* __restrict__ status_out) {
-  __shared__ double sx[EST_TILE * DIM];
-  __shared__ double sz[ZC][EST_TILE];
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = p < m;
-  const double ir[3] = {ir0, ir1, ir2};
-  const double NaN = __builtin_nan("");
-  double qc[DIM];
+struct EstTile<DIM, ZC, true> : EstTile<DIM, ZC, false> {
+  int f[EST_TILE];
+};
+
+// samples t0 .. t0 + tn of the ncz live columns into the tile (a barrier on either side)
+template <int DIM, int ZC, bool CV>
+__device__ __forceinline__ void est_stage_tile(EstTile<DIM, ZC, CV>& tile, const double* __restrict__ xdata,
+                                               const double* __restrict__ zc, int64_t ldz,
+                                               const int* __restrict__ fold, int t0, int tn, int ncz) {
+  __syncthreads();
+  for (int e = threadIdx.x; e < tn * DIM; e += 256) tile.x[e] = xdata[(int64_t)t0 * DIM + e];
+  if constexpr (CV)
+    for (int e = threadIdx.x; e < tn; e += 256) tile.f[e] = fold[t0 + e];
 #pragma unroll
-  for (int a = 0; a < DIM; ++a) qc[a] = live ? x0[p * DIM + a] : 0.0;
+  for (int c = 0; c < ZC; ++c)
+    if (c < ncz)
+      for (int e = threadIdx.x; e < tn; e += 256) tile.z[c][e] = zc[(int64_t)c * ldz + t0 + e];
+  __syncthreads();
+}
+
+// The general all-sample sweep of one estimation point qc (thread p of the launch).  Sample j is a neighbour iff it
+// lies inside the ball, if any (key <= r2), and, for CV, fold[j] != myfold and key > ex (ex = -1: no exclusion ball;
+// every key is >= 0): one predicate per pair, the same in every sweep.
+template <int DIM, int ZC, bool CV>
+__device__ __forceinline__ void est_all_body(EstTile<DIM, ZC, CV>& tile, const EstSpec& sp,
+                                             const double* __restrict__ xdata, const double* __restrict__ z,
+                                             const int* __restrict__ fold, int n, const double* qc, int myfold,
+                                             bool live, int64_t p, int minneighbors, double ex, double r2, int use_ball,
+                                             int aniso, const double* ir, double* __restrict__ mean_out,
+                                             double* __restrict__ aux_out, uint8_t* __restrict__ status_out) {
+  const double NaN = __builtin_nan("");
   constexpr int NP = DIM + 1, NT = NP * (NP + 1) / 2;
+  const bool euclid = sp.metric == GSS_METRIC_EUCLIDEAN;
+  auto neighbour = [&](int j, double d2) __attribute__((always_inline)) {
+    if constexpr (CV) return tile.f[j] != myfold && d2 > ex && (!use_ball || d2 <= r2);
+    else return !use_ball || d2 <= r2;
+  };
 
   for (int c0 = 0; c0 < sp.nz; c0 += ZC) {
   const int ncz = (sp.nz - c0) < ZC ? (sp.nz - c0) : ZC;
@@ -360,59 +463,42 @@ __global__ __launch_bounds__(256) void est_all_kernel(EstSpec sp, const double* 
   // sweep 1: IDW sums (complete) / LWR farthest neighbour
   for (int t0 = 0; t0 < n; t0 += EST_TILE) {
     const int tn = (n - t0) < EST_TILE ? (n - t0) : EST_TILE;
-    __syncthreads();
-    for (int e = threadIdx.x; e < tn * DIM; e += 256) sx[e] = xdata[(int64_t)t0 * DIM + e];
-#pragma unroll
-    for (int c = 0; c < ZC; ++c)
-      if (c < ncz)
-        for (int e = threadIdx.x; e < tn; e += 256) sz[c][e] = zc[(int64_t)c * sp.ldz + t0 + e];
-    __syncthreads();
-    if (sp.method == 0 && sp.metric == GSS_METRIC_EUCLIDEAN && (sp.exponent == 1.0 || sp.exponent == 2.0)) {
-      // the reference's default (all samples, exponent 1) and its square: branch-free, 1 / d from v_rsq_f64 and
-      // 1 / d^2 from v_rcp_f64 (two Newton steps each), four samples in flight
+    est_stage_tile(tile, xdata, zc, sp.ldz, fold, t0, tn, ncz);
+    if (sp.method == 0 && euclid && (sp.exponent == 1.0 || sp.exponent == 2.0)) {
+      // the reference's default (all samples, exponent 1) and its square: branch-free, four samples in flight
       const bool e1 = sp.exponent == 1.0;
 #pragma unroll 4
       for (int j = 0; j < tn; ++j) {
-        const double d2 = sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0);
-        const bool in = !use_ball || d2 <= r2;
+        const double d2 = sqdist_nofma<DIM>(&tile.x[j * DIM], qc, ir, aniso != 0);
+        const bool in = neighbour(j, d2);
         const bool zero = in && d2 == 0.0;
         cnt += in ? 1 : 0;
         dmin2 = (in && d2 < dmin2) ? d2 : dmin2;
 #pragma unroll
-        for (int c = 0; c < ZC; ++c) zzero[c] = (zero && !haszero && c < ncz) ? sz[c][j] : zzero[c];
+        for (int c = 0; c < ZC; ++c) zzero[c] = (zero && !haszero && c < ncz) ? tile.z[c][j] : zzero[c];
         haszero = haszero || zero;
-        double y;
-        if (e1) {
-          y = __builtin_amdgcn_rsq(d2);
-          const double hh = 0.5 * d2;
-          y = fma(y, fma(-hh * y, y, 0.5), y);
-          y = fma(y, fma(-hh * y, y, 0.5), y);
-        } else {
-          y = __builtin_amdgcn_rcp(d2);
-          y = fma(y, fma(-d2, y, 1.0), y);
-          y = fma(y, fma(-d2, y, 1.0), y);
-        }
+        const double y = e1 ? idw_recip<true>(d2) : idw_recip<false>(d2);
         const double w = (in && !zero) ? y : 0.0;
         sw += w;
 #pragma unroll
         for (int c = 0; c < ZC; ++c)
-          if (c < ncz) swz[c] = fma(w, sz[c][j], swz[c]);
+          if (c < ncz) swz[c] = fma(w, tile.z[c][j], swz[c]);
       }
       continue;
     }
-    if (sp.method == 1 && sp.metric == GSS_METRIC_EUCLIDEAN) {  // LWR, first sweep: farthest neighbour and count
+    if (sp.method == 1 && euclid) {  // LWR, first sweep: farthest neighbour and count
 #pragma unroll 4
       for (int j = 0; j < tn; ++j) {
-        const double d2 = sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0);
-        const bool in = !use_ball || d2 <= r2;
+        const double d2 = sqdist_nofma<DIM>(&tile.x[j * DIM], qc, ir, aniso != 0);
+        const bool in = neighbour(j, d2);
         cnt += in ? 1 : 0;
         dmax2 = (in && d2 > dmax2) ? d2 : dmax2;
       }
       continue;
     }
     for (int j = 0; j < tn; ++j) {
-      const double d2 = est_key<DIM>(sp.metric, &sx[j * DIM], qc, ir, aniso != 0);
-      if (use_ball && !(d2 <= r2)) continue;
+      const double d2 = est_key<DIM>(sp.metric, &tile.x[j * DIM], qc, ir, aniso != 0);
+      if (!neighbour(j, d2)) continue;
       ++cnt;
       dmax2 = d2 > dmax2 ? d2 : dmax2;
       dmin2 = d2 < dmin2 ? d2 : dmin2;
@@ -421,16 +507,16 @@ __global__ __launch_bounds__(256) void est_all_kernel(EstSpec sp, const double* 
           if (!haszero) {
 #pragma unroll
             for (int c = 0; c < ZC; ++c)
-              if (c < ncz) zzero[c] = sz[c][j];
+              if (c < ncz) zzero[c] = tile.z[c][j];
           }
           haszero = true;
         } else {
           const double dd = metric_dist(sp.metric, d2, sp.mparam);
-          const double w = idw_weight(dd, sp.metric == GSS_METRIC_EUCLIDEAN ? d2 : dd * dd, sp.exponent);
+          const double w = idw_weight(dd, euclid ? d2 : dd * dd, sp.exponent);
           sw += w;
 #pragma unroll
           for (int c = 0; c < ZC; ++c)
-            if (c < ncz) swz[c] += w * sz[c][j];
+            if (c < ncz) swz[c] += w * tile.z[c][j];
         }
       }
     }
@@ -448,31 +534,18 @@ __global__ __launch_bounds__(256) void est_all_kernel(EstSpec sp, const double* 
     }
     continue;
   }
-  // sweep 2 (LWR): moments with delta = d / dmax
+  // sweep 2 (LWR): moments with delta = d / dmax over the same neighbours
   const double dmax = metric_dist(sp.metric, dmax2, sp.mparam);
-  double S1[NT], S2[NT], b[ZC][NP];
-#pragma unroll
-  for (int e = 0; e < NT; ++e) S1[e] = S2[e] = 0.0;
-#pragma unroll
-  for (int c = 0; c < ZC; ++c)
-#pragma unroll
-    for (int e = 0; e < NP; ++e) b[c][e] = 0.0;
+  double S1[NT] = {}, S2[NT] = {}, b[ZC][NP] = {};
   for (int t0 = 0; t0 < n; t0 += EST_TILE) {
     const int tn = (n - t0) < EST_TILE ? (n - t0) : EST_TILE;
-    __syncthreads();
-    for (int e = threadIdx.x; e < tn * DIM; e += 256) sx[e] = xdata[(int64_t)t0 * DIM + e];
-#pragma unroll
-    for (int c = 0; c < ZC; ++c)
-      if (c < ncz)
-        for (int e = threadIdx.x; e < tn; e += 256) sz[c][e] = zc[(int64_t)c * sp.ldz + t0 + e];
-    __syncthreads();
-    const bool euclid = sp.metric == GSS_METRIC_EUCLIDEAN;
+    est_stage_tile(tile, xdata, zc, sp.ldz, fold, t0, tn, ncz);
     const bool gauss_w = sp.wkind == GSS_WEIGHT_EXP && sp.wp == 2.0;  // exp(-a delta^2): no square root needed
     const double inv_dmax2 = 1.0 / dmax2;
     for (int j = 0; j < tn; ++j) {
-      const double d2 = euclid ? sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0)
-                               : est_key<DIM>(sp.metric, &sx[j * DIM], qc, ir, aniso != 0);
-      if (use_ball && !(d2 <= r2)) continue;
+      const double d2 = euclid ? sqdist_nofma<DIM>(&tile.x[j * DIM], qc, ir, aniso != 0)
+                               : est_key<DIM>(sp.metric, &tile.x[j * DIM], qc, ir, aniso != 0);
+      if (!neighbour(j, d2)) continue;
       double w;
       if (euclid && gauss_w) w = gss_exp(-sp.wa * (d2 * inv_dmax2));
       else if (euclid) w = lwr_weight(sp.wkind, sp.wa, sp.wp, gss_sqrt(d2 * inv_dmax2));
@@ -480,24 +553,12 @@ __global__ __launch_bounds__(256) void est_all_kernel(EstSpec sp, const double* 
       double u[NP];
       u[0] = 1.0;
 #pragma unroll
-      for (int a = 0; a < DIM; ++a) u[a + 1] = sx[j * DIM + a] - qc[a];
-#pragma unroll
-      for (int r = 0; r < NP; ++r) {
-        const double wu = w * u[r];
-#pragma unroll
-        for (int c = 0; c < ZC; ++c)
-          if (c < ncz) b[c][r] += wu * sz[c][j];
-#pragma unroll
-        for (int q = 0; q <= r; ++q) {
-          const double t = wu * u[q];
-          S1[r * (r + 1) / 2 + q] += t;
-          S2[r * (r + 1) / 2 + q] += w * t;
-        }
-      }
+      for (int a = 0; a < DIM; ++a) u[a + 1] = tile.x[j * DIM + a] - qc[a];
+      lwr_moments<NP, ZC>(w, u, ncz, [&](int c) { return tile.z[c][j]; }, S1, S2, b);
     }
   }
   if (live) {
-    bool ok = enough && (sp.wsup != nullptr || dmax > 0.0);
+    bool ok = enough && ((!CV && sp.wsup != nullptr) || dmax > 0.0);   // (no supplied weights in cross-validation)
     double var = 0.0;
 #pragma unroll
     for (int c = 0; c < ZC; ++c) {
@@ -513,6 +574,47 @@ __global__ __launch_bounds__(256) void est_all_kernel(EstSpec sp, const double* 
     }
   }
   }
+}
+
+template <int DIM, int ZC>
+__global__ __launch_bounds__(256) void est_all_kernel(EstSpec sp, const double* __restrict__ xdata,
+                                                      const double* __restrict__ z, int n,
+                                                      const double* __restrict__ x0, int64_t m, int minneighbors,
+                                                      double r2, int use_ball, int aniso, double ir0, double ir1,
+                                                      double ir2, double* __restrict__ mean_out,
+                                                      double* __restrict__ aux_out, uint8_t* __restrict__ status_out) {
+  __shared__ EstTile<DIM, ZC, false> tile;
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = p < m;
+  const double ir[3] = {ir0, ir1, ir2};
+  double qc[DIM];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) qc[a] = live ? x0[p * DIM + a] : 0.0;
+  est_all_body<DIM, ZC, false>(tile, sp, xdata, z, nullptr, n, qc, 0, live, p, minneighbors, -1.0, r2, use_ball, aniso,
+                               ir, mean_out, aux_out, status_out);
+}
+
+// The self-join of cross-validation (gss.h, gss_idw_cv / gss_lwr_cv): query p of a launch is sample qoff + p.  `fold`
+// is never NULL here: for leave-one-out the driver passes the samples' indices (est_cv_iota_kernel).  Outputs are the
+// launch's own slices (column c of the estimates at mean_out + c * sp.ldm).
+template <int DIM, int ZC>
+__global__ __launch_bounds__(256) void est_cv_all_kernel(EstSpec sp, const double* __restrict__ xdata,
+                                                         const double* __restrict__ z,
+                                                         const int* __restrict__ fold, int n, int64_t qoff, int64_t m,
+                                                         int minneighbors, double ex, double r2, int use_ball,
+                                                         int aniso, double ir0, double ir1, double ir2,
+                                                         double* __restrict__ mean_out, double* __restrict__ aux_out,
+                                                         uint8_t* __restrict__ status_out) {
+  __shared__ EstTile<DIM, ZC, true> tile;
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = p < m;
+  const int64_t g = live ? qoff + p : qoff;   // (qoff < n: a launch has at least one query)
+  const double ir[3] = {ir0, ir1, ir2};
+  double qc[DIM];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) qc[a] = xdata[g * DIM + a];
+  est_all_body<DIM, ZC, true>(tile, sp, xdata, z, fold, n, qc, fold[g], live, p, minneighbors, ex, r2, use_ball, aniso,
+                              ir, mean_out, aux_out, status_out);
 }
 
 // The reference's default LWR -- every sample a neighbour (lwr.jl:96), Euclidean distance, no ball, weight
@@ -534,21 +636,9 @@ __global__ __launch_bounds__(256) void lwr_all_fast_kernel(double wa, const doub
   for (int a = 0; a < DIM; ++a) qc[a] = live ? x0[p * DIM + a] : 0.0;
   double dmax2 = 0.0;
 #pragma unroll 8
-  for (int j = 0; j < n; ++j) {
-    double d2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) {
-      const double t = xdata[(int64_t)j * DIM + a] - qc[a];
-      d2 = fma(t, t, d2);
-    }
-    dmax2 = fmax(dmax2, d2);
-  }
+  for (int j = 0; j < n; ++j) dmax2 = fmax(dmax2, sqdist_fma<DIM>(xdata + (int64_t)j * DIM, qc));
   const double scale = -wa / dmax2;
-  double S1[NT], S2[NT], b[NP];
-#pragma unroll
-  for (int e = 0; e < NT; ++e) S1[e] = S2[e] = 0.0;
-#pragma unroll
-  for (int e = 0; e < NP; ++e) b[e] = 0.0;
+  double S1[NT] = {}, S2[NT] = {}, b[NP] = {};
 #pragma unroll 2
   for (int j = 0; j < n; ++j) {
     double u[NP];
@@ -581,282 +671,10 @@ __global__ __launch_bounds__(256) void lwr_all_fast_kernel(double wa, const doub
   status_out[p] = ok ? GSS_PT_OK : GSS_PT_SINGULAR;
 }
 
-// ---------------------------------------------------------------------------------------------
-// cross-validation, k == n: the self-join of the samples (gss.h, gss_idw_cv / gss_lwr_cv).  Query p of a launch is
-// sample qoff + p; sample j is eligible for it iff fold[j] != fold[qoff + p], key(p, j) > ex (ex = -1: no exclusion
-// ball; every key is >= 0) and, with a neighbourhood ball, key(p, j) <= r2.  `fold` is never NULL here: for
-// leave-one-out the driver passes the samples' indices (est_cv_iota_kernel).  Outputs are the launch's own slices
-// (column c of the estimates at mean_out + c * sp.ldm).
-// ---------------------------------------------------------------------------------------------
+// leave-one-out through the self-join kernels: every sample its own fold
 __global__ __launch_bounds__(256) void est_cv_iota_kernel(int* __restrict__ out, int n) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j < n) out[j] = j;
-}
-
-// The reference's default IDW cross-validated: Euclidean, no ball, no exclusion radius, exponent 1 or 2, one column.
-// Written like idw_all_fast_kernel: the sample index is wave-uniform, so coordinates, value and fold id arrive
-// through the scalar cache as scalar operands.  The weight of an ineligible sample is selected to zero, never multiplied
-// by it -- the query's own sample has d^2 = 0 and the NaN of the Newton step would pass through a product -- and its
-// d^2 is kept out of the running minimum.  A NaN or infinite sum therefore means a coincident ELIGIBLE sample, and the
-// rescan for the first one applies the same test.
-template <int DIM, bool E1>
-__global__ __launch_bounds__(256) void idw_cv_all_fast_kernel(const double* __restrict__ xdata,
-                                                              const double* __restrict__ z,
-                                                              const int* __restrict__ fold, int n, int64_t qoff,
-                                                              int64_t m, int minneighbors,
-                                                              double* __restrict__ mean_out,
-                                                              double* __restrict__ aux_out,
-                                                              uint8_t* __restrict__ status_out) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = p < m;
-  const int64_t g = live ? qoff + p : qoff;   // (qoff < n: a launch has at least one query)
-  double qc[DIM];
-#pragma unroll
-  for (int a = 0; a < DIM; ++a) qc[a] = xdata[g * DIM + a];
-  const int myfold = fold[g];
-  double sw = 0.0, swz = 0.0, dmin2 = __builtin_huge_val();
-  int cnt = 0;
-#pragma unroll 8
-  for (int j = 0; j < n; ++j) {
-    double d2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) {
-      const double t = xdata[(int64_t)j * DIM + a] - qc[a];
-      d2 = fma(t, t, d2);
-    }
-    const bool in = fold[j] != myfold;
-    cnt += in ? 1 : 0;
-    dmin2 = fmin(dmin2, in ? d2 : __builtin_huge_val());
-    double y;
-    if (E1) {
-      y = __builtin_amdgcn_rsq(d2);
-      const double hh = 0.5 * d2;
-      y = fma(y, fma(-hh * y, y, 0.5), y);
-      y = fma(y, fma(-hh * y, y, 0.5), y);
-    } else {
-      y = __builtin_amdgcn_rcp(d2);
-      y = fma(y, fma(-d2, y, 1.0), y);
-      y = fma(y, fma(-d2, y, 1.0), y);
-    }
-    const double w = in ? y : 0.0;
-    sw += w;
-    swz = fma(w, z[j], swz);
-  }
-  if (!live) return;
-  const double NaN = __builtin_nan("");
-  double mu = swz / sw, dist = gss_sqrt(dmin2);
-  if (!(sw < __builtin_huge_val())) {  // NaN (coincident eligible sample) or overflow: the first coincident value
-    for (int j = 0; j < n; ++j) {
-      double d2 = 0.0;
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) {
-        const double t = xdata[(int64_t)j * DIM + a] - qc[a];
-        d2 = fma(t, t, d2);
-      }
-      if (fold[j] != myfold && d2 == 0.0) {
-        mu = z[j];
-        dist = 0.0;
-        break;
-      }
-    }
-  }
-  const bool enough = cnt >= minneighbors && cnt >= 1;
-  mean_out[p] = enough ? mu : NaN;
-  aux_out[p] = enough ? dist : NaN;
-  status_out[p] = enough ? GSS_PT_OK : GSS_PT_MISSING;
-}
-
-// The general self-join: est_all_kernel with the eligibility test.  The samples are staged through LDS in EST_TILE
-// pieces with their fold ids beside them; the mask is one predicate per pair, the same in every sweep.
-template <int DIM, int ZC>
-__global__ __launch_bounds__(256) void est_cv_all_kernel(EstSpec sp, const double* __restrict__ xdata,
-                                                         const double* __restrict__ z,
-                                                         const int* __restrict__ fold, int n, int64_t qoff, int64_t m,
-                                                         int minneighbors, double ex, double r2, int use_ball,
-                                                         int aniso, double ir0, double ir1, double ir2,
-                                                         double* __restrict__ mean_out, double* __restrict__ aux_out,
-                                                         uint8_t* __restrict__ status_out) {
-  __shared__ double sx[EST_TILE * DIM];
-  __shared__ double sz[ZC][EST_TILE];
-  __shared__ int sf[EST_TILE];
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = p < m;
-  const int64_t g = live ? qoff + p : qoff;
-  const double ir[3] = {ir0, ir1, ir2};
-  const double NaN = __builtin_nan("");
-  double qc[DIM];
-#pragma unroll
-  for (int a = 0; a < DIM; ++a) qc[a] = xdata[g * DIM + a];
-  const int myfold = fold[g];
-  constexpr int NP = DIM + 1, NT = NP * (NP + 1) / 2;
-  const bool euclid = sp.metric == GSS_METRIC_EUCLIDEAN;
-
-  for (int c0 = 0; c0 < sp.nz; c0 += ZC) {
-  const int ncz = (sp.nz - c0) < ZC ? (sp.nz - c0) : ZC;
-  const double* zc = z + (int64_t)c0 * sp.ldz;
-  double* mo = mean_out + (int64_t)c0 * sp.ldm;
-  int cnt = 0;
-  double dmax2 = 0.0, dmin2 = __builtin_huge_val();
-  double sw = 0.0, swz[ZC], zzero[ZC];
-#pragma unroll
-  for (int c = 0; c < ZC; ++c) swz[c] = zzero[c] = 0.0;
-  bool haszero = false;
-  // sweep 1: IDW sums (complete) / LWR farthest eligible sample
-  for (int t0 = 0; t0 < n; t0 += EST_TILE) {
-    const int tn = (n - t0) < EST_TILE ? (n - t0) : EST_TILE;
-    __syncthreads();
-    for (int e = threadIdx.x; e < tn * DIM; e += 256) sx[e] = xdata[(int64_t)t0 * DIM + e];
-    for (int e = threadIdx.x; e < tn; e += 256) sf[e] = fold[t0 + e];
-#pragma unroll
-    for (int c = 0; c < ZC; ++c)
-      if (c < ncz)
-        for (int e = threadIdx.x; e < tn; e += 256) sz[c][e] = zc[(int64_t)c * sp.ldz + t0 + e];
-    __syncthreads();
-    if (sp.method == 0 && euclid && (sp.exponent == 1.0 || sp.exponent == 2.0)) {
-      // exponent 1 and 2: branch-free, 1 / d from v_rsq_f64 and 1 / d^2 from v_rcp_f64 (two Newton steps each)
-      const bool e1 = sp.exponent == 1.0;
-#pragma unroll 4
-      for (int j = 0; j < tn; ++j) {
-        const double d2 = sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0);
-        const bool in = sf[j] != myfold && d2 > ex && (!use_ball || d2 <= r2);
-        const bool zero = in && d2 == 0.0;
-        cnt += in ? 1 : 0;
-        dmin2 = (in && d2 < dmin2) ? d2 : dmin2;
-#pragma unroll
-        for (int c = 0; c < ZC; ++c) zzero[c] = (zero && !haszero && c < ncz) ? sz[c][j] : zzero[c];
-        haszero = haszero || zero;
-        double y;
-        if (e1) {
-          y = __builtin_amdgcn_rsq(d2);
-          const double hh = 0.5 * d2;
-          y = fma(y, fma(-hh * y, y, 0.5), y);
-          y = fma(y, fma(-hh * y, y, 0.5), y);
-        } else {
-          y = __builtin_amdgcn_rcp(d2);
-          y = fma(y, fma(-d2, y, 1.0), y);
-          y = fma(y, fma(-d2, y, 1.0), y);
-        }
-        const double w = (in && !zero) ? y : 0.0;
-        sw += w;
-#pragma unroll
-        for (int c = 0; c < ZC; ++c)
-          if (c < ncz) swz[c] = fma(w, sz[c][j], swz[c]);
-      }
-      continue;
-    }
-    if (sp.method == 1 && euclid) {  // LWR, first sweep: farthest eligible sample and count
-#pragma unroll 4
-      for (int j = 0; j < tn; ++j) {
-        const double d2 = sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0);
-        const bool in = sf[j] != myfold && d2 > ex && (!use_ball || d2 <= r2);
-        cnt += in ? 1 : 0;
-        dmax2 = (in && d2 > dmax2) ? d2 : dmax2;
-      }
-      continue;
-    }
-    for (int j = 0; j < tn; ++j) {
-      const double d2 = est_key<DIM>(sp.metric, &sx[j * DIM], qc, ir, aniso != 0);
-      if (!(sf[j] != myfold && d2 > ex && (!use_ball || d2 <= r2))) continue;
-      ++cnt;
-      dmax2 = d2 > dmax2 ? d2 : dmax2;
-      dmin2 = d2 < dmin2 ? d2 : dmin2;
-      if (sp.method == 0) {
-        if (d2 == 0.0) {
-          if (!haszero) {
-#pragma unroll
-            for (int c = 0; c < ZC; ++c)
-              if (c < ncz) zzero[c] = sz[c][j];
-          }
-          haszero = true;
-        } else {
-          const double dd = metric_dist(sp.metric, d2, sp.mparam);
-          const double w = idw_weight(dd, euclid ? d2 : dd * dd, sp.exponent);
-          sw += w;
-#pragma unroll
-          for (int c = 0; c < ZC; ++c)
-            if (c < ncz) swz[c] += w * sz[c][j];
-        }
-      }
-    }
-  }
-  const bool enough = cnt >= minneighbors && cnt >= 1;
-  if (sp.method == 0) {
-    if (live) {
-#pragma unroll
-      for (int c = 0; c < ZC; ++c)
-        if (c < ncz) mo[(int64_t)c * sp.ldm + p] = !enough ? NaN : (haszero ? zzero[c] : swz[c] / sw);
-      if (c0 == 0) {
-        aux_out[p] = !enough ? NaN : (haszero ? 0.0 : metric_dist(sp.metric, dmin2, sp.mparam));
-        status_out[p] = enough ? GSS_PT_OK : GSS_PT_MISSING;
-      }
-    }
-    continue;
-  }
-  // sweep 2 (LWR): moments with delta = d / dmax over the same eligible samples
-  const double dmax = metric_dist(sp.metric, dmax2, sp.mparam);
-  double S1[NT], S2[NT], b[ZC][NP];
-#pragma unroll
-  for (int e = 0; e < NT; ++e) S1[e] = S2[e] = 0.0;
-#pragma unroll
-  for (int c = 0; c < ZC; ++c)
-#pragma unroll
-    for (int e = 0; e < NP; ++e) b[c][e] = 0.0;
-  for (int t0 = 0; t0 < n; t0 += EST_TILE) {
-    const int tn = (n - t0) < EST_TILE ? (n - t0) : EST_TILE;
-    __syncthreads();
-    for (int e = threadIdx.x; e < tn * DIM; e += 256) sx[e] = xdata[(int64_t)t0 * DIM + e];
-    for (int e = threadIdx.x; e < tn; e += 256) sf[e] = fold[t0 + e];
-#pragma unroll
-    for (int c = 0; c < ZC; ++c)
-      if (c < ncz)
-        for (int e = threadIdx.x; e < tn; e += 256) sz[c][e] = zc[(int64_t)c * sp.ldz + t0 + e];
-    __syncthreads();
-    const bool gauss_w = sp.wkind == GSS_WEIGHT_EXP && sp.wp == 2.0;  // exp(-a delta^2): no square root needed
-    const double inv_dmax2 = 1.0 / dmax2;
-    for (int j = 0; j < tn; ++j) {
-      const double d2 = euclid ? sqdist_nofma<DIM>(&sx[j * DIM], qc, ir, aniso != 0)
-                               : est_key<DIM>(sp.metric, &sx[j * DIM], qc, ir, aniso != 0);
-      if (!(sf[j] != myfold && d2 > ex && (!use_ball || d2 <= r2))) continue;
-      double w;
-      if (euclid && gauss_w) w = gss_exp(-sp.wa * (d2 * inv_dmax2));
-      else if (euclid) w = lwr_weight(sp.wkind, sp.wa, sp.wp, gss_sqrt(d2 * inv_dmax2));
-      else w = lwr_weight(sp.wkind, sp.wa, sp.wp, metric_dist(sp.metric, d2, sp.mparam) / dmax);
-      double u[NP];
-      u[0] = 1.0;
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) u[a + 1] = sx[j * DIM + a] - qc[a];
-#pragma unroll
-      for (int r = 0; r < NP; ++r) {
-        const double wu = w * u[r];
-#pragma unroll
-        for (int c = 0; c < ZC; ++c)
-          if (c < ncz) b[c][r] += wu * sz[c][j];
-#pragma unroll
-        for (int q = 0; q <= r; ++q) {
-          const double t = wu * u[q];
-          S1[r * (r + 1) / 2 + q] += t;
-          S2[r * (r + 1) / 2 + q] += w * t;
-        }
-      }
-    }
-  }
-  if (live) {
-    bool ok = enough && dmax > 0.0;
-    double var = 0.0;
-#pragma unroll
-    for (int c = 0; c < ZC; ++c) {
-      if (c < ncz) {
-        double mu = 0.0;
-        ok = ok && lwr_solve<NP>(S1, S2, b[c], &mu, &var);
-        mo[(int64_t)c * sp.ldm + p] = ok ? mu : NaN;
-      }
-    }
-    if (c0 == 0) {
-      aux_out[p] = ok ? var : NaN;
-      status_out[p] = !enough ? GSS_PT_MISSING : (ok ? GSS_PT_OK : GSS_PT_SINGULAR);
-    }
-  }
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -938,13 +756,7 @@ __global__ __launch_bounds__(256) void est_list_kernel(EstSpec sp, const double*
       dmax2 = est_key<DIM>(sp.metric, xl, qc, ir, aniso != 0);
     }
     const double dmax = metric_dist(sp.metric, dmax2, sp.mparam);
-    double S1[NT], S2[NT], b[ZC][NP];
-#pragma unroll
-    for (int e = 0; e < NT; ++e) S1[e] = S2[e] = 0.0;
-#pragma unroll
-    for (int c = 0; c < ZC; ++c)
-#pragma unroll
-      for (int e = 0; e < NP; ++e) b[c][e] = 0.0;
+    double S1[NT] = {}, S2[NT] = {}, b[ZC][NP] = {};
     for (int j = 0; j < cnt; ++j) {
       const int nj = nb[j];
       double xj[DIM];
@@ -957,19 +769,7 @@ __global__ __launch_bounds__(256) void est_list_kernel(EstSpec sp, const double*
       u[0] = 1.0;
 #pragma unroll
       for (int a = 0; a < DIM; ++a) u[a + 1] = xj[a] - qc[a];
-#pragma unroll
-      for (int r = 0; r < NP; ++r) {
-        const double wu = w * u[r];
-#pragma unroll
-        for (int c = 0; c < ZC; ++c)
-          if (c < ncz) b[c][r] += wu * zc[(int64_t)c * sp.ldz + nj];
-#pragma unroll
-        for (int q = 0; q <= r; ++q) {
-          const double t = wu * u[q];
-          S1[r * (r + 1) / 2 + q] += t;
-          S2[r * (r + 1) / 2 + q] += w * t;
-        }
-      }
+      lwr_moments<NP, ZC>(w, u, ncz, [&](int c) { return zc[(int64_t)c * sp.ldz + nj]; }, S1, S2, b);
     }
     bool ok = sp.wsup != nullptr || dmax > 0.0;
     double var = 0.0;
@@ -985,6 +785,17 @@ __global__ __launch_bounds__(256) void est_list_kernel(EstSpec sp, const double*
       aux_out[p] = ok ? var : NaN;
       status_out[p] = ok ? GSS_PT_OK : GSS_PT_SINGULAR;
     }
+  }
+}
+
+// Run-time dim (1 .. 3) to a compile-time argument: f(std::integral_constant<int, DIM>), as in knn.hip.  Every launch of
+// this file goes through it.
+template <class F>
+static void with_dim(int dim, F&& f) {
+  switch (dim) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 3>{}); break;
   }
 }
 
@@ -1017,93 +828,41 @@ static int32_t est_local_dev(const EstSpec& sp, Searcher& sr, const double* z, c
   const char* pname = sp.method == 0 ? (cv ? "idw_cv" : "idw") : (cv ? "lwr_cv" : "lwr");
   int* const idx_out = cv ? cv->idx_out : nullptr;
   int* const count_out = cv ? cv->count_out : nullptr;
-
-  if (k > 64 && (int64_t)k < n) {
-    // 65 .. n - 1 neighbours (ui.jl:16-23 accepts any count): the search runs in passes of 64, the estimator walks
-    // the lists with one thread per point
-    int64_t chunk = k > 512 ? (1 << 16) : (1 << 19);
-    if (cv) chunk = est_cv_chunk_cap(chunk);
-    DevBuf idx_s, cnt_s;
-    if (!idx_out) GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
-    if (!count_out) GSS_TRY(cnt_s.alloc(sizeof(int) * (size_t)(m < chunk ? m : chunk)));
-    for (int64_t off = 0; off < m; off += chunk) {
-      const int64_t mv = (m - off) < chunk ? (m - off) : chunk;
-      int* idx = idx_out ? idx_out + off * k : idx_s.as<int>();
-      int* cnt = count_out ? count_out + off : cnt_s.as<int>();
-      {
-        ProfScope ps("knn", s);
-        const KnnMask mk = cv ? cv->mask.from(off) : KnnMask();   // cross-validation: the query folds of this chunk
-        GSS_TRY(sr.query(x0 + off * dim, nullptr, mv, k, idx, cnt, s, cv ? &mk : nullptr));
-      }
-      ProfScope pl(pname, s);
-      const dim3 grid((unsigned)((mv + 255) / 256));
-#define GSS_EST_LIST_ARGS sp, xdata, z, x0 + off * dim, mv, k, minneighbors, idx, cnt, aniso, \
-                          ir[0], ir[1], ir[2], mean + off, aux + off, status + off, 0
-#define GSS_EST_LIST(D)                                                                                      \
-  if (sp.nz > 1) hipLaunchKernelGGL((est_list_kernel<D, 4>), grid, dim3(256), 0, s, GSS_EST_LIST_ARGS);      \
-  else hipLaunchKernelGGL((est_list_kernel<D, 1>), grid, dim3(256), 0, s, GSS_EST_LIST_ARGS)
-      switch (dim) {
-        case 1: GSS_EST_LIST(1); break;
-        case 2: GSS_EST_LIST(2); break;
-        default: GSS_EST_LIST(3); break;
-      }
-#undef GSS_EST_LIST
-#undef GSS_EST_LIST_ARGS
-      GSS_HIP(hipGetLastError());
-    }
-    GSS_HIP(hipStreamSynchronize(s));  // scratch and the search index are released on return
-    return GSS_OK;
-  }
-  if (k > 64) {
+  if (k > 64 && (int64_t)k == n) {   // every sample: no search
     ProfScope ps(pname, s);
-    dim3 grid((unsigned)((m + 255) / 256));
-    // (the two dedicated kernels carry one value column; several columns share the sweeps of the general kernel)
-    if (sp.nz == 1 && sp.method == 0 && sp.metric == GSS_METRIC_EUCLIDEAN && !use_ball &&
-        (sp.exponent == 1.0 || sp.exponent == 2.0) && minneighbors <= n) {
-#define GSS_IDW_FAST(D)                                                                                               \
-  if (sp.exponent == 1.0)                                                                                            \
-    hipLaunchKernelGGL((idw_all_fast_kernel<D, true>), grid, dim3(256), 0, s, xdata, z, (int)n, x0, m, mean, aux,     \
-                       status);                                                                                      \
-  else                                                                                                               \
-    hipLaunchKernelGGL((idw_all_fast_kernel<D, false>), grid, dim3(256), 0, s, xdata, z, (int)n, x0, m, mean, aux,    \
-                       status)
-      switch (dim) {
-        case 1: GSS_IDW_FAST(1); break;
-        case 2: GSS_IDW_FAST(2); break;
-        default: GSS_IDW_FAST(3); break;
+    const dim3 grid((unsigned)((m + 255) / 256));
+    with_dim(dim, [&](auto D) {
+      constexpr int DIM = decltype(D)::value;
+      // (the two dedicated kernels carry one value column; several columns share the sweeps of the general kernel)
+      auto fast = [&](auto kernel, auto... head) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, head..., xdata, z, (int)n, x0, m, mean, aux, status);
+      };
+      auto general = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sp, xdata, z, (int)n, x0, m, minneighbors, r2, use_ball, aniso,
+                           ir[0], ir[1], ir[2], mean, aux, status);
+      };
+      if (sp.nz == 1 && sp.method == 0 && sp.metric == GSS_METRIC_EUCLIDEAN && !use_ball &&
+          (sp.exponent == 1.0 || sp.exponent == 2.0) && minneighbors <= n) {
+        if (sp.exponent == 1.0) fast(idw_all_fast_kernel<DIM, true>);
+        else fast(idw_all_fast_kernel<DIM, false>);
+      } else if (sp.nz == 1 && sp.method == 1 && sp.metric == GSS_METRIC_EUCLIDEAN && !use_ball &&
+                 sp.wkind == GSS_WEIGHT_EXP && sp.wp == 2.0 && minneighbors <= n) {
+        fast(lwr_all_fast_kernel<DIM>, sp.wa);
+      } else if (sp.nz > 1) {
+        general(est_all_kernel<DIM, 4>);
+      } else {
+        general(est_all_kernel<DIM, 1>);
       }
-#undef GSS_IDW_FAST
-      GSS_HIP(hipGetLastError());
-      return GSS_OK;
-    }
-    if (sp.nz == 1 && sp.method == 1 && sp.metric == GSS_METRIC_EUCLIDEAN && !use_ball && sp.wkind == GSS_WEIGHT_EXP &&
-        sp.wp == 2.0 && minneighbors <= n) {
-      switch (dim) {
-        case 1: hipLaunchKernelGGL((lwr_all_fast_kernel<1>), grid, dim3(256), 0, s, sp.wa, xdata, z, (int)n, x0, m, mean, aux, status); break;
-        case 2: hipLaunchKernelGGL((lwr_all_fast_kernel<2>), grid, dim3(256), 0, s, sp.wa, xdata, z, (int)n, x0, m, mean, aux, status); break;
-        default: hipLaunchKernelGGL((lwr_all_fast_kernel<3>), grid, dim3(256), 0, s, sp.wa, xdata, z, (int)n, x0, m, mean, aux, status); break;
-      }
-      GSS_HIP(hipGetLastError());
-      return GSS_OK;
-    }
-#define GSS_EST_ALL_ARGS sp, xdata, z, (int)n, x0, m, minneighbors, r2, use_ball, aniso, ir[0], ir[1], ir[2], mean, \
-                         aux, status
-#define GSS_EST_ALL(D)                                                                                     \
-  if (sp.nz > 1) hipLaunchKernelGGL((est_all_kernel<D, 4>), grid, dim3(256), 0, s, GSS_EST_ALL_ARGS);      \
-  else hipLaunchKernelGGL((est_all_kernel<D, 1>), grid, dim3(256), 0, s, GSS_EST_ALL_ARGS)
-    switch (dim) {
-      case 1: GSS_EST_ALL(1); break;
-      case 2: GSS_EST_ALL(2); break;
-      default: GSS_EST_ALL(3); break;
-    }
-#undef GSS_EST_ALL
-#undef GSS_EST_ALL_ARGS
+    });
     GSS_HIP(hipGetLastError());
     return GSS_OK;
   }
 
-  const bool piped = pipe && pipe->on;   // host arrays of the domain arrive and leave piece by piece (gss_internal.h)
-  int64_t chunk = piped ? HostPipe::PIECE : (1 << 20);
+  // k < n (or k = n <= 64): the search, chunk by chunk, in front of a list estimator.  k <= 64: one wave (k <= 16: a
+  // quarter of one) per point; 65 .. n - 1 (ui.jl:16-23 accepts any count): the search runs in passes of 64 and the
+  // estimator walks the lists with one thread per point
+  const bool piped = k <= 64 && pipe && pipe->on;   // host arrays of the domain arrive and leave piece by piece
+  int64_t chunk = k <= 64 ? (piped ? HostPipe::PIECE : (1 << 20)) : (k > 512 ? (1 << 16) : (1 << 19));
   if (cv) chunk = est_cv_chunk_cap(chunk);
   DevBuf idx_s, cnt_s;
   if (!idx_out) GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)((m < chunk ? m : chunk) * k)));
@@ -1119,24 +878,18 @@ static int32_t est_local_dev(const EstSpec& sp, Searcher& sr, const double* z, c
       GSS_TRY(sr.query(x0 + off * dim, nullptr, mv, k, idx, cnt, s, cv ? &mk : nullptr));
     }
     ProfScope pl(pname, s);
-#define GSS_EST_KNN_ARGS sp, xdata, z, x0 + off * dim, mv, k, minneighbors, idx, cnt, aniso, \
-                         ir[0], ir[1], ir[2], mean + off, aux + off, status + off
-    if (k <= 16) {  // sixteen lanes per point, sixteen points per workgroup
-      dim3 grid((unsigned)((mv + 15) / 16));
-      switch (dim) {
-        case 1: hipLaunchKernelGGL((est_knn_kernel<1, 16>), grid, dim3(256), 0, s, GSS_EST_KNN_ARGS); break;
-        case 2: hipLaunchKernelGGL((est_knn_kernel<2, 16>), grid, dim3(256), 0, s, GSS_EST_KNN_ARGS); break;
-        default: hipLaunchKernelGGL((est_knn_kernel<3, 16>), grid, dim3(256), 0, s, GSS_EST_KNN_ARGS); break;
-      }
-    } else {
-      dim3 grid((unsigned)((mv + 3) / 4));
-      switch (dim) {
-        case 1: hipLaunchKernelGGL((est_knn_kernel<1, 64>), grid, dim3(256), 0, s, GSS_EST_KNN_ARGS); break;
-        case 2: hipLaunchKernelGGL((est_knn_kernel<2, 64>), grid, dim3(256), 0, s, GSS_EST_KNN_ARGS); break;
-        default: hipLaunchKernelGGL((est_knn_kernel<3, 64>), grid, dim3(256), 0, s, GSS_EST_KNN_ARGS); break;
-      }
-    }
-#undef GSS_EST_KNN_ARGS
+    with_dim(dim, [&](auto D) {
+      constexpr int DIM = decltype(D)::value;
+      auto launch = [&](auto kernel, int per_block, auto... ncheck) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((mv + per_block - 1) / per_block)), dim3(256), 0, s, sp, xdata, z,
+                           x0 + off * dim, mv, k, minneighbors, idx, cnt, aniso, ir[0], ir[1], ir[2], mean + off,
+                           aux + off, status + off, ncheck...);
+      };
+      if (k <= 16) launch(est_knn_kernel<DIM, 16>, 16);   // sixteen lanes per point, sixteen points per workgroup
+      else if (k <= 64) launch(est_knn_kernel<DIM, 64>, 4);
+      else if (sp.nz > 1) launch(est_list_kernel<DIM, 4>, 256, 0);
+      else launch(est_list_kernel<DIM, 1>, 256, 0);
+    });
     GSS_HIP(hipGetLastError());
     if (piped) GSS_TRY(pipe->deliver(off, mv, s));
   }
@@ -1213,34 +966,21 @@ static int32_t est_cv_all_dev(const EstSpec& sp, const Searcher& sr, const doubl
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t mv = (n - off) < chunk ? (n - off) : chunk;
     const dim3 grid((unsigned)((mv + 255) / 256));
-    if (fast) {
-#define GSS_IDW_CV_FAST(D)                                                                                         \
-  if (sp.exponent == 1.0)                                                                                          \
-    hipLaunchKernelGGL((idw_cv_all_fast_kernel<D, true>), grid, dim3(256), 0, s, xdata, z, fold, (int)n, off, mv,  \
-                       minneighbors, mean + off, aux + off, status + off);                                         \
-  else                                                                                                             \
-    hipLaunchKernelGGL((idw_cv_all_fast_kernel<D, false>), grid, dim3(256), 0, s, xdata, z, fold, (int)n, off, mv, \
-                       minneighbors, mean + off, aux + off, status + off)
-      switch (dim) {
-        case 1: GSS_IDW_CV_FAST(1); break;
-        case 2: GSS_IDW_CV_FAST(2); break;
-        default: GSS_IDW_CV_FAST(3); break;
-      }
-#undef GSS_IDW_CV_FAST
-    } else {
-#define GSS_EST_CV_ALL_ARGS sp, xdata, z, fold, (int)n, off, mv, minneighbors, ex, r2, use_ball, aniso, ir[0], ir[1], \
-                            ir[2], mean + off, aux + off, status + off
-#define GSS_EST_CV_ALL(D)                                                                                        \
-  if (sp.nz > 1) hipLaunchKernelGGL((est_cv_all_kernel<D, 4>), grid, dim3(256), 0, s, GSS_EST_CV_ALL_ARGS);      \
-  else hipLaunchKernelGGL((est_cv_all_kernel<D, 1>), grid, dim3(256), 0, s, GSS_EST_CV_ALL_ARGS)
-      switch (dim) {
-        case 1: GSS_EST_CV_ALL(1); break;
-        case 2: GSS_EST_CV_ALL(2); break;
-        default: GSS_EST_CV_ALL(3); break;
-      }
-#undef GSS_EST_CV_ALL
-#undef GSS_EST_CV_ALL_ARGS
-    }
+    with_dim(dim, [&](auto D) {
+      constexpr int DIM = decltype(D)::value;
+      auto masked_fast = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, xdata, z, fold, (int)n, off, mv, minneighbors, mean + off,
+                           aux + off, status + off);
+      };
+      auto general = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sp, xdata, z, fold, (int)n, off, mv, minneighbors, ex, r2,
+                           use_ball, aniso, ir[0], ir[1], ir[2], mean + off, aux + off, status + off);
+      };
+      if (fast && sp.exponent == 1.0) masked_fast(idw_cv_all_fast_kernel<DIM, true>);
+      else if (fast) masked_fast(idw_cv_all_fast_kernel<DIM, false>);
+      else if (sp.nz > 1) general(est_cv_all_kernel<DIM, 4>);
+      else general(est_cv_all_kernel<DIM, 1>);
+    });
     GSS_HIP(hipGetLastError());
   }
   if (own.p) GSS_HIP(hipStreamSynchronize(s));   // the indices are released on return
@@ -1310,6 +1050,32 @@ static int32_t est_cv(EstSpec sp, const char* who, const double* xdata, const do
   return GSS_OK;
 }
 
+// The estimator of a predict or cross-validation call, its parameters checked (columns and strides: est_predict / est_cv)
+static int32_t idw_spec(EstSpec* sp, int32_t metric, double metric_param, double exponent) {
+  GSS_REQUIRE(exponent > 0.0, "exponent must be positive");  // idw.jl:96
+  std::memset(sp, 0, sizeof(*sp));
+  sp->method = 0;
+  sp->exponent = exponent;
+  sp->metric = metric;
+  sp->mparam = metric_param;
+  return GSS_OK;
+}
+
+static int32_t lwr_spec(EstSpec* sp, int32_t metric, double metric_param, int32_t weight_kind, double weight_a,
+                        double weight_p) {
+  GSS_REQUIRE(weight_kind == GSS_WEIGHT_EXP || weight_kind == GSS_WEIGHT_TRICUBE, "unknown weight function %d",
+              weight_kind);
+  GSS_REQUIRE(weight_kind != GSS_WEIGHT_EXP || weight_p > 0.0, "weight exponent must be positive");
+  std::memset(sp, 0, sizeof(*sp));
+  sp->method = 1;
+  sp->wkind = weight_kind;
+  sp->wa = weight_a;
+  sp->wp = weight_p;
+  sp->metric = metric;
+  sp->mparam = metric_param;
+  return GSS_OK;
+}
+
 }  // namespace gss
 
 using namespace gss;
@@ -1321,13 +1087,8 @@ int32_t gss_idw_predict_cols(const double* xdata, const double* z, int64_t n, in
                              const double* inv_radii, int32_t metric, double metric_param, double exponent, double* mean,
                              double* dist, uint8_t* status, int32_t mem, void* stream) {
   GSS_ENTRY();
-  GSS_REQUIRE(exponent > 0.0, "exponent must be positive");  // idw.jl:96
   EstSpec sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.method = 0;
-  sp.exponent = exponent;
-  sp.metric = metric;
-  sp.mparam = metric_param;
+  GSS_TRY(idw_spec(&sp, metric, metric_param, exponent));
   return est_predict(sp, xdata, z, n, dim, nz, xdom, m, k, minneighbors, radius, inv_radii, mean, dist, status, mem,
                      stream);
 }
@@ -1375,14 +1136,11 @@ int32_t gss_lwr_predict_weights(const double* xdata, const double* z, int64_t n,
   sp.ldz = n;
   sp.ldm = m;
   const dim3 grid((unsigned)((m + 255) / 256));
-#define GSS_LWRW_ARGS sp, sxd.as<double>(), sz.as<double>(), sx.as<double>(), m, (int)k, (int)minneighbors, si.as<int>(), \
-                      sc.as<int>(), 0, 1.0, 1.0, 1.0, smean.as<double>(), svar.as<double>(), st, (int)n
-  switch (dim) {
-    case 1: hipLaunchKernelGGL((est_list_kernel<1, 1>), grid, dim3(256), 0, s, GSS_LWRW_ARGS); break;
-    case 2: hipLaunchKernelGGL((est_list_kernel<2, 1>), grid, dim3(256), 0, s, GSS_LWRW_ARGS); break;
-    default: hipLaunchKernelGGL((est_list_kernel<3, 1>), grid, dim3(256), 0, s, GSS_LWRW_ARGS); break;
-  }
-#undef GSS_LWRW_ARGS
+  with_dim(dim, [&](auto D) {   // (the lists are the caller's: the kernel checks every entry against n)
+    hipLaunchKernelGGL((est_list_kernel<decltype(D)::value, 1>), grid, dim3(256), 0, s, sp, sxd.as<double>(),
+                       sz.as<double>(), sx.as<double>(), m, (int)k, (int)minneighbors, si.as<int>(), sc.as<int>(), 0, 1.0,
+                       1.0, 1.0, smean.as<double>(), svar.as<double>(), st, (int)n);
+  });
   GSS_HIP(hipGetLastError());
   GSS_TRY(smean.back(s));
   GSS_TRY(svar.back(s));
@@ -1405,17 +1163,8 @@ int32_t gss_lwr_predict_cols(const double* xdata, const double* z, int64_t n, in
                              double weight_a, double weight_p, double* mean, double* var, uint8_t* status, int32_t mem,
                              void* stream) {
   GSS_ENTRY();
-  GSS_REQUIRE(weight_kind == GSS_WEIGHT_EXP || weight_kind == GSS_WEIGHT_TRICUBE, "unknown weight function %d",
-              weight_kind);
-  GSS_REQUIRE(weight_kind != GSS_WEIGHT_EXP || weight_p > 0.0, "weight exponent must be positive");
   EstSpec sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.method = 1;
-  sp.wkind = weight_kind;
-  sp.wa = weight_a;
-  sp.wp = weight_p;
-  sp.metric = metric;
-  sp.mparam = metric_param;
+  GSS_TRY(lwr_spec(&sp, metric, metric_param, weight_kind, weight_a, weight_p));
   return est_predict(sp, xdata, z, n, dim, nz, xdom, m, k, minneighbors, radius, inv_radii, mean, var, status, mem,
                      stream);
 }
@@ -1426,13 +1175,8 @@ int32_t gss_idw_cv(const double* xdata, const double* z, int64_t n, int32_t dim,
                    int32_t metric, double metric_param, double exponent, double* pred, double* dist, uint8_t* status,
                    int32_t* idx_out, int32_t* count_out, int32_t mem, void* stream) {
   GSS_ENTRY();
-  GSS_REQUIRE(exponent > 0.0, "exponent must be positive");  // idw.jl:96
   EstSpec sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.method = 0;
-  sp.exponent = exponent;
-  sp.metric = metric;
-  sp.mparam = metric_param;
+  GSS_TRY(idw_spec(&sp, metric, metric_param, exponent));
   return est_cv(sp, "gss_idw_cv", xdata, z, n, dim, nz, fold, exclude_radius, k, minneighbors, radius, inv_radii, pred,
                 dist, status, idx_out, count_out, mem, stream);
 }
@@ -1443,17 +1187,8 @@ int32_t gss_lwr_cv(const double* xdata, const double* z, int64_t n, int32_t dim,
                    double* pred, double* var, uint8_t* status, int32_t* idx_out, int32_t* count_out, int32_t mem,
                    void* stream) {
   GSS_ENTRY();
-  GSS_REQUIRE(weight_kind == GSS_WEIGHT_EXP || weight_kind == GSS_WEIGHT_TRICUBE, "unknown weight function %d",
-              weight_kind);
-  GSS_REQUIRE(weight_kind != GSS_WEIGHT_EXP || weight_p > 0.0, "weight exponent must be positive");
   EstSpec sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.method = 1;
-  sp.wkind = weight_kind;
-  sp.wa = weight_a;
-  sp.wp = weight_p;
-  sp.metric = metric;
-  sp.mparam = metric_param;
+  GSS_TRY(lwr_spec(&sp, metric, metric_param, weight_kind, weight_a, weight_p));
   return est_cv(sp, "gss_lwr_cv", xdata, z, n, dim, nz, fold, exclude_radius, k, minneighbors, radius, inv_radii, pred,
                 var, status, idx_out, count_out, mem, stream);
 }

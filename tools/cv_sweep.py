@@ -16,7 +16,9 @@
     gss_idw_predict / gss_lwr_predict with xdom = xdata and the same k in the same session, alternating; the "knn" /
     estimator split of each comes from gss_profile_read ("idw_cv" / "lwr_cv" beside "idw" / "lwr"), and the k = n rows
     report the pair rate of the masked self-join beside the unmasked all-sample kernel, the latter also at a domain of
-    other points (at xdom = xdata each of its points hits its own sample and rescans).
+    other points (at xdom = xdata each of its points hits its own sample and rescans).  At 100 000 samples two more
+    rows with exponent 3, k = n: the general est_all_kernel (predict at the other points) and est_cv_all_kernel
+    (leave-one-out), which the fast kernels of exponent 1 and 2 leave the call to.
 
 Method: warm-up, then `--reps` timed runs bracketed by events on the stream; the median is reported.  One JSON line per
 row on stdout.  python tools/cv_sweep.py [--reps 5] [--max-n 1000000]"""
@@ -243,6 +245,24 @@ def estimator_rows(reps, max_n):
                 row["predict_pairs_per_s"] = float("%.4g" % (n * float(n) / (ps[1] * 1e-3)))
                 row["kernel_ratio"] = round(cs[1] / ps[1], 3)
             print(json.dumps(row), flush=True)
+        if n == 100_000:
+            # exponent 3 is not one of the fast kernels': est_all_kernel (predict at the other points) and
+            # est_cv_all_kernel (leave-one-out) take these two calls
+            def general():
+                HipEngine.idw(x, z, xo, n, exponent=3.0)
+
+            def general_cv():
+                HipEngine.idw_cv(x, z, n, device=True, exponent=3.0)
+            tg, tc = [], []
+            for _ in range(3):                          # alternating blocks
+                tg.append(timed(general, reps))
+                tc.append(timed(general_cv, reps))
+            for what, fn, t, scope in (("idw_general_predict_other_points", general, tg, "idw"),
+                                       ("idw_general_cv", general_cv, tc, "idw_cv")):
+                ms, est_ms = statistics.median(t), parts(fn, (scope,))[0]
+                print(json.dumps({"what": what, "n": n, "k": "n", "exponent": 3.0, "folds": "loo", "ms": round(ms, 4),
+                                  "estimator_ms": est_ms,
+                                  "pairs_per_s": float("%.4g" % (n * float(n) / (est_ms * 1e-3)))}), flush=True)
 
 
 def main():
