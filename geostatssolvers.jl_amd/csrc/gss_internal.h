@@ -6,6 +6,7 @@
 #include <stddef.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "gss.h"
 
@@ -268,6 +269,24 @@ struct OutStream {
 // left behind at its exit (EntryGuard above): one stream wait, nothing when the process keeps to one stream.
 hipStream_t to_stream(void* s);
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
+
+// Run-time dim (1 .. 3) to a compile-time argument: f(std::integral_constant<int, DIM>{}).  The launches of knn.hip,
+// idw_lwr.hip and the SGS files go through it.
+template <class F>
+void with_dim(int dim, F&& f) {
+  switch (dim) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 3>{}); break;
+  }
+}
+
+// sum over the 64 lanes of a wave, in every lane
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
 
 // ---------------------------------------------------------------------------------------------
 // variogram on device

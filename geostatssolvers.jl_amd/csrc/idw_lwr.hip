@@ -13,8 +13,8 @@
 // est_all_body<DIM, ZC, CV> behind est_all_kernel / est_cv_all_kernel, idw_all_fast_body<DIM, E1, CV> behind
 // idw_all_fast_kernel / idw_cv_all_fast_kernel; the __global__ wrappers only load the query (and its fold).  Shared
 // pieces: idw_recip (the rsq / rcp Newton steps), lwr_moments (the S1 / S2 / b update, est_list_kernel too),
-// est_stage_tile (the LDS tile of the general sweep), sqdist_fma.  Host side: with_dim turns dim into a template
-// argument for every launch; idw_spec / lwr_spec build the EstSpec of the predict and the cv entry points.
+// est_stage_tile (the LDS tile of the general sweep), sqdist_fma.  Host side: with_dim (gss_internal.h) turns dim into a
+// template argument for every launch; idw_spec / lwr_spec build the EstSpec of the predict and the cv entry points.
 // LWR solves its (d+1) x (d+1) normal equations about the estimation point (same predictor, better conditioned
 // than the raw coordinates the reference uses) with an unpivoted Cholesky; a non-positive pivot is reported as
 // GSS_PT_SINGULAR where the reference's `\` would throw.
@@ -785,17 +785,6 @@ __global__ __launch_bounds__(256) void est_list_kernel(EstSpec sp, const double*
       aux_out[p] = ok ? var : NaN;
       status_out[p] = ok ? GSS_PT_OK : GSS_PT_SINGULAR;
     }
-  }
-}
-
-// Run-time dim (1 .. 3) to a compile-time argument: f(std::integral_constant<int, DIM>), as in knn.hip.  Every launch of
-// this file goes through it.
-template <class F>
-static void with_dim(int dim, F&& f) {
-  switch (dim) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    default: f(std::integral_constant<int, 3>{}); break;
   }
 }
 

@@ -770,18 +770,11 @@ int32_t Searcher::index(hipStream_t s, const KnnIndex** out) {
   return GSS_OK;
 }
 
-// Run-time (dim in 1..3, metric) to compile-time arguments: f(integral_constant dim[, integral_constant metric]).
-// Only the exhaustive kernel has a Haversine copy; without HAVERSINE that metric is not instantiated.
+// Run-time (dim in 1..3, metric) to compile-time arguments: f(integral_constant dim, integral_constant metric), on top
+// of with_dim (gss_internal.h).  Only the exhaustive kernel has a Haversine copy; without HAVERSINE that metric is not
+// instantiated.
 template <int V>
 using Int = std::integral_constant<int, V>;
-template <class F>
-static void with_dim(int dim, F&& f) {
-  switch (dim) {
-    case 1: f(Int<1>{}); break;
-    case 2: f(Int<2>{}); break;
-    default: f(Int<3>{}); break;
-  }
-}
 template <bool HAVERSINE, class F>
 static void with_dim_metric(int dim, int metric, F&& f) {
   with_dim(dim, [&](auto D) {

@@ -25,12 +25,6 @@ namespace gss {
 
 __device__ __forceinline__ int tri(int i) { return (i * (i + 1)) >> 1; }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // More than 64 neighbours (maxneighbors in 65 .. n - 1; krig.jl:201-210 and ui.jl:16-23 accept any count).
 // One workgroup of 256 threads per estimation point, same mathematics as the MFMA-tile kernel below with the

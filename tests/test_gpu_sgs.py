@@ -60,7 +60,8 @@ def test_realisations_match_oracle(dims, vgspec, mean, k, nmin, ball, nd, rpath,
 
 
 @pytest.mark.parametrize("mask_after", [True, False])
-@pytest.mark.parametrize("dims,k,rpath,nd", [((30, 20), 80, False, 5), ((14, 12, 6), 100, True, 0), ((40, 25), 200, True, 7)])
+@pytest.mark.parametrize("dims,k,rpath,nd", [((30, 20), 80, False, 5), ((14, 12, 6), 100, True, 0), ((40, 25), 200, True, 7),
+                                             ((400,), 70, False, 5)])       # 1-D: sgs_weights_big_kernel<1>
 def test_more_than_64_neighbours(dims, k, rpath, nd, mask_after):
     """seq.jl:91-98 accepts any maxneighbors.  Beyond 64 the search -- unmasked for `mask = simulated` applied after
     the search (the front-ends' default), masked otherwise -- runs in passes of 64; the weights come from the
@@ -331,7 +332,8 @@ def test_short_levels_in_one_launch_are_bit_identical_to_both_other_sweeps():
     lists and normals staged by LDS-direct loads).  Forced on (GSS_SGS_TEAM=1) it must give, bit for bit, the fields of
     the launch-per-level sweep (GSS_SGS_TEAM=0) and of the wave that walks the path (GSS_SGS_LEVELS=0): 2-D and 3-D
     grids, 4 ... 20 neighbours (10, the reference's default, and 7: lists that are not a multiple of four), conditioning data, realisation counts that do not fill the last group, a random order
-    (long levels: several chunks and rounds per level), supplied normals."""
+    (long levels: several chunks and rounds per level), supplied normals, and 693 cells (no multiple of 64) with 5
+    neighbours and 65 realisations and with 1 neighbour: the remainder loops of the sweeps and a partial last block."""
     import os
     import subprocess
     import sys
@@ -342,7 +344,8 @@ def test_short_levels_in_one_launch_are_bit_identical_to_both_other_sweeps():
             "res = []\n"
             "for dims, k, R, order in (((96, 80), 16, 67, None), ((70, 50), 12, 8, None), ((24, 18, 10), 20, 130, None),\n"
             "                          ((64, 64), 4, 9, None), ((90, 70), 16, 33, 'random'), ((40, 30), 8, 3, 'noise'),\n"
-            "                          ((60, 45), 10, 5, None), ((50, 40), 7, 3, None)):\n"
+            "                          ((60, 45), 10, 5, None), ((50, 40), 7, 3, None),\n"
+            "                          ((33, 21), 5, 65, None), ((33, 21), 1, 3, None)):\n"
             "    N = int(np.prod(dims)); rng = np.random.default_rng(N)\n"
             "    g = np.meshgrid(*[np.arange(d) + 0.5 for d in dims], indexing='ij')\n"
             "    cent = np.stack([a.ravel(order='F') for a in g], 1)\n"
@@ -363,7 +366,7 @@ def test_short_levels_in_one_launch_are_bit_identical_to_both_other_sweeps():
             subprocess.run([sys.executable, "-c", code, out], check=True, env=env, timeout=600)
             with np.load(out) as f:
                 outs.append([f[k] for k in f.files])
-    assert len(outs[0]) == 8
+    assert len(outs[0]) == 10
     for a, b, c in zip(*outs):
         assert a.shape == b.shape == c.shape and np.isfinite(a).all()
         assert np.array_equal(a, b) and np.array_equal(a, c)
