@@ -209,6 +209,55 @@ void DevBuf::release() {
   cap = 0;
 }
 
+// Fit slots (gss_internal.h, FitSlot): free list of the process, newest first.
+static std::vector<FitSlot> g_fit_slots;
+static std::mutex g_fit_slots_mu;
+static std::atomic<int64_t> g_fit_slot_allocs{0};
+
+int32_t fit_slot_acquire(FitSlot* out) {
+  {
+    std::lock_guard<std::mutex> lock(g_fit_slots_mu);
+    if (!g_fit_slots.empty()) {
+      *out = g_fit_slots.back();
+      g_fit_slots.pop_back();
+      return GSS_OK;
+    }
+  }
+  FitSlot sl;
+  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&sl.info), 2 * sizeof(int), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.fork, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
+  if (e != hipSuccess) {   // (the status is kept: the calls that clean up would replace it)
+    if (sl.fork) (void)hipEventDestroy(sl.fork);
+    if (sl.info) (void)hipHostFree(sl.info);
+    (void)hipGetLastError();
+    set_error("kriging fit: no pinned status slot / event (%s)", hipGetErrorString(e));
+    return GSS_ERR_HIP;
+  }
+  g_fit_slot_allocs.fetch_add(1);
+  *out = sl;
+  return GSS_OK;
+}
+
+void fit_slot_release(FitSlot* slot) {
+  if (slot->info) {
+    std::lock_guard<std::mutex> lock(g_fit_slots_mu);
+    g_fit_slots.push_back(*slot);
+  }
+  *slot = FitSlot();
+}
+
+// with the cached blocks (gss_shutdown, gss_trim_pool): slots that live handles hold stay theirs
+static void fit_slots_free() {
+  std::lock_guard<std::mutex> lock(g_fit_slots_mu);
+  for (auto& sl : g_fit_slots) {
+    (void)hipEventDestroy(sl.fork);
+    (void)hipEventDestroy(sl.done);
+    (void)hipHostFree(sl.info);
+  }
+  g_fit_slots.clear();
+}
+
 int32_t Staged::in(const void* src, size_t bytes, int32_t mem, hipStream_t s) {
   if (src == nullptr) {
     p = nullptr;
@@ -870,6 +919,7 @@ int32_t gss_shutdown(void) {
   for (auto& b : g_pool) (void)hipFree(b.p);
   g_pool.clear();
   g_pool_bytes = 0;
+  fit_slots_free();
   return GSS_OK;
 }
 
@@ -920,6 +970,7 @@ int32_t gss_trim_pool(void) {
   for (auto& b : g_pool) (void)hipFree(b.p);
   g_pool.clear();
   g_pool_bytes = 0;
+  fit_slots_free();
   return GSS_OK;
 }
 
@@ -932,6 +983,8 @@ int32_t gss_stat(const char* name, int64_t* value) {
     *value = g_stat_ring_bytes.load();
   } else if (!std::strcmp(name, "out_chunks")) {
     *value = g_stat_chunks.load();
+  } else if (!std::strcmp(name, "fit_slot_allocs")) {
+    *value = g_fit_slot_allocs.load();   // pinned status slots allocated so far (steady state: constant)
   } else if (!std::strcmp(name, "panel_giveups")) {
     *value = panel_giveups();
   } else if (!std::strcmp(name, "gemm_launches_128")) {

@@ -971,6 +971,18 @@ struct ScopedEvent {
   operator hipEvent_t() const { return e; }
 };
 
+// What a kriging fit in flight borrows from the process (common.hip): two pinned status words and two events
+// (timing disabled) -- `fork` orders an asynchronous fit behind the caller's stream, `done` marks its end.  The slots are
+// allocated on demand and go back to a free list, so that a handle per solve costs no pinned allocation, no
+// hipHostFree (which waits for every stream of the device) and no event creation in steady state; the free list is
+// released where the block pool is (gss_shutdown, gss_trim_pool).  gss_stat "fit_slot_allocs": pinned allocations so far.
+struct FitSlot {
+  int* info = nullptr;
+  hipEvent_t fork = nullptr, done = nullptr;
+};
+int32_t fit_slot_acquire(FitSlot* out);
+void fit_slot_release(FitSlot* slot);   // the caller has waited for `done` (or never recorded it); clears *slot
+
 // the process's low-priority helper stream of those look-aheads (nullptr if it cannot be created); work put on it
 // must be fenced by events against the caller's stream on both sides
 // helper streams of the process (common.hip), created together in a fixed order

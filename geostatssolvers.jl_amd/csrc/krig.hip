@@ -774,12 +774,10 @@ int32_t gss::krig_factorize(gss_krig* h, hipStream_t s, bool async) {
       fs = s;
     }
   }
+  if (!h->fit_slot.info) GSS_TRY(fit_slot_acquire(&h->fit_slot));   // (a retry finds the slot given back by its join)
   if (async) {
-    ScopedEvent e0;
-    GSS_HIP(e0.create());
-    GSS_HIP(hipEventRecord(e0, s));
-    GSS_HIP(hipStreamWaitEvent(fs, e0, 0));
-    if (!h->fit_info_host) GSS_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->fit_info_host), 2 * sizeof(int), hipHostMallocDefault));
+    GSS_HIP(hipEventRecord(h->fit_slot.fork, s));
+    GSS_HIP(hipStreamWaitEvent(fs, h->fit_slot.fork, 0));
   }
   FitPlan fp;
   GSS_TRY(krig_fit_plan(h, &fp));
@@ -787,9 +785,11 @@ int32_t gss::krig_factorize(gss_krig* h, hipStream_t s, bool async) {
   h->fit_info = fp.info;
   h->fit_stream = fs;
   h->fit_async = async;
-  if (async) GSS_HIP(hipMemcpyAsync(h->fit_info_host, fp.info, 2 * sizeof(int), hipMemcpyDeviceToHost, fs));
-  if (!h->fit_done) GSS_HIP(hipEventCreateWithFlags(&h->fit_done, hipEventDisableTiming));
-  GSS_HIP(hipEventRecord(h->fit_done, fs));
+  if (async) GSS_HIP(hipMemcpyAsync(h->fit_slot.info, fp.info, 2 * sizeof(int), hipMemcpyDeviceToHost, fs));
+  const hipError_t rec = hipEventRecord(h->fit_slot.done, fs);
+  // no event to wait for: the copy into the slot's words must not outlive this call (the slot goes back to the free list)
+  if (rec != hipSuccess) (void)hipStreamSynchronize(fs);
+  GSS_HIP(rec);
   h->fit_pending = true;
   h->factored = true;
   return GSS_OK;
@@ -797,7 +797,7 @@ int32_t gss::krig_factorize(gss_krig* h, hipStream_t s, bool async) {
 
 // device side of the join: what `s` receives next runs behind the fit
 int32_t gss::krig_join_device(gss_krig* h, hipStream_t s) {
-  if (h->fit_pending && h->fit_done && h->fit_stream != s) GSS_HIP(hipStreamWaitEvent(s, h->fit_done, 0));
+  if (h->fit_pending && h->fit_slot.done && h->fit_stream != s) GSS_HIP(hipStreamWaitEvent(s, h->fit_slot.done, 0));
   return GSS_OK;
 }
 
@@ -805,14 +805,15 @@ int32_t gss::krig_join_device(gss_krig* h, hipStream_t s) {
 int32_t gss::krig_fit_wait(gss_krig* h) {
   if (!h->fit_pending) return GSS_OK;
   h->fit_pending = false;
-  GSS_HIP(hipEventSynchronize(h->fit_done));
+  GSS_HIP(hipEventSynchronize(h->fit_slot.done));
   int hinfo[2] = {0, 0};
   if (h->fit_async) {   // the words were copied on the fit stream in front of the event: no blocking copy (it would
-    hinfo[0] = h->fit_info_host[0];   // wait for the caller's stream as well)
-    hinfo[1] = h->fit_info_host[1];
+    hinfo[0] = h->fit_slot.info[0];   // wait for the caller's stream as well)
+    hinfo[1] = h->fit_slot.info[1];
   } else {
     GSS_HIP(hipMemcpy(hinfo, h->fit_info, 2 * sizeof(int), hipMemcpyDeviceToHost));
   }
+  fit_slot_release(&h->fit_slot);
   h->fit_ws.release();
   h->fit_info = nullptr;
   if (hinfo[0] < 0) {

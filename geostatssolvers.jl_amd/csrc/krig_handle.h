@@ -38,20 +38,19 @@ struct gss_krig {
   gss::Frame fr;
   gss::DevBuf xraw;
   gss::DevBuf factor;  // W' (ldw x N1pad, column-major) followed by wd (N1pad)
-  // fit in flight: workspace, completion event and status words (joined by krig_fit_wait)
+  // fit in flight: workspace, status words, and the slot borrowed from the process (its `done` event ends the fit;
+  // joined and handed back by krig_fit_wait, or by the destructor of a handle whose fit nobody joined)
   gss::DevBuf fit_ws;
-  hipEvent_t fit_done = nullptr;
+  gss::FitSlot fit_slot;
   bool fit_pending = false;
   int* fit_info = nullptr;
   hipStream_t fit_stream = nullptr;  // stream of the fit in flight (a retry goes back on it)
   // GSS_KRIG_ASYNC_FIT: the fit runs on the library's fit stream beside whatever the caller queues next (K1 of the
-  // first prediction); its two status words travel to pinned host memory on that stream, in front of fit_done
+  // first prediction); its two status words travel to the slot's pinned words on that stream, in front of `done`
   bool fit_async = false;
-  int* fit_info_host = nullptr;
   ~gss_krig() {
-    if (fit_pending && fit_done) (void)hipEventSynchronize(fit_done);
-    if (fit_done) (void)hipEventDestroy(fit_done);
-    if (fit_info_host) (void)hipHostFree(fit_info_host);
+    if (fit_pending && fit_slot.done) (void)hipEventSynchronize(fit_slot.done);
+    gss::fit_slot_release(&fit_slot);
   }
   bool factored = false;
   // block support (gss_krig_set_block_support): right-hand sides regularised over a cell of size `cell` sampled at

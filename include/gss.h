@@ -143,7 +143,8 @@ int32_t gss_dev_to_host(void* dst, const void* src_dev, int64_t bytes, void* str
  * program whose own allocator (torch, RCCL, rocFFT) has just failed.  Synchronises the device. */
 int32_t gss_trim_pool(void);
 /* Counters for tests and diagnostics: "pool_bytes" (device bytes in the block cache), "out_ring_bytes" (HBM staged for
- * the host outputs of the last simulation call), "out_chunks" (chunks that call moved), "panel_giveups" (times a
+ * the host outputs of the last simulation call), "out_chunks" (chunks that call moved), "fit_slot_allocs" (pinned status
+ * slots allocated so far for kriging fits: constant once handles are created and closed at a steady rate), "panel_giveups" (times a
  * single-launch factorisation left through its bounded wait and was repeated on the launch-per-block path),
  * "gemm_launches_128" / "gemm_launches_64" (FP64 matrix products launched so far on the 128 x 128 and on the 64 x 64
  * tile kernel: which of the two a given shape ran on),
