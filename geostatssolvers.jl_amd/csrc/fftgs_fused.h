@@ -19,16 +19,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fftgs_common.h"
 #include "gss_internal.h"
 #include "philox.h"
 
 namespace gss {
 
-// source of the real input of P1
-enum { FF_SRC_PHILOX = 0,   // uniform noise generated in registers (fft.jl:163 `rand(rng, V, dims)`)
-       FF_SRC_ARRAY = 1,    // caller-supplied noise
-       FF_SRC_COV = 2,      // covariance to the centre cell (fft.jl:96-99): the spectrum build runs on the same passes
-       FF_SRC_COV_ROT = 3 };  // the same for a rotated variogram: lag := R^T lag, `noise` carries R (row-major 3 x 3)
 struct CovSrc {
   VgDev vg;
   int c1, c2, c3;     // 0-based centre cell
@@ -40,23 +36,7 @@ constexpr int FF_TX = 1 << FF_TX_LOG;  // lines per tile in the strided passes: 
                                        // 2u + 1 (the two halves of a 128-B line) are given to workgroups b and b + 8,
                                        // which share an XCD and are dispatched together, so the L2 merges the halves
 constexpr int FF_PITCH_ALIGN = 8;      // rows of the half-spectrum buffer start on 128-B boundaries
-constexpr int FF_ROWS = 4;      // x lines per workgroup in P1 / P5 (4 keeps 4+ workgroups per CU resident)
-constexpr int FF_THREADS = 256;   // strided passes
-constexpr int FF_XTHREADS = 256;  // x-line passes (128 threads measured slower: fewer waves to hide latency)
 
-struct FusedGrid {
-  int n1, n2, n3;      // n1 fastest; all powers of two
-  int l1, l2, l3;      // log2
-  int nh;              // n1 / 2 + 1
-  int nhp;             // row pitch of the half-spectrum buffer: nh rounded up to FF_PITCH_ALIGN
-  int ntx;             // nhp / FF_TX
-  int slab_t0, slab_nt;  // strided passes restricted to the x tiles slab_t0 .. slab_t0 + slab_nt - 1 (slab_nt = 0: all)
-};
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 cconj(double2 a) { return make_double2(a.x, -a.y); }
 __device__ __forceinline__ int brev_bits(int k, int bits) { return (int)(__brev((unsigned)k) >> (32 - bits)); }
 // =====================================================================================================
 // x passes, second generation (ff_x_fwd2_kernel / ff_x_inv2_kernel): Stockham autosort passes.
@@ -72,53 +52,6 @@ __device__ __forceinline__ int brev_bits(int k, int bits) { return (int)(__brev(
 // LDS image of a line: element i at i ^ ((i >> 3) & 7): the stride-8 stores of the first pass and the
 // unit-stride accesses of the others both spread over the banks.
 __device__ __forceinline__ int xs_phys(int i) { return i ^ ((i >> 3) & 7); }
-
-template <bool INV>
-__device__ __forceinline__ double2 mul_mi(double2 a) {   // forward: a * (-i); inverse: a * (+i)
-  return INV ? make_double2(-a.y, a.x) : make_double2(a.y, -a.x);
-}
-
-template <bool INV>
-__device__ __forceinline__ void x_dft4(double2& a0, double2& a1, double2& a2, double2& a3) {
-  const double2 s0 = make_double2(a0.x + a2.x, a0.y + a2.y), s1 = make_double2(a0.x - a2.x, a0.y - a2.y);
-  const double2 s2 = make_double2(a1.x + a3.x, a1.y + a3.y);
-  const double2 s3 = mul_mi<INV>(make_double2(a1.x - a3.x, a1.y - a3.y));
-  a0 = make_double2(s0.x + s2.x, s0.y + s2.y);
-  a2 = make_double2(s0.x - s2.x, s0.y - s2.y);
-  a1 = make_double2(s1.x + s3.x, s1.y + s3.y);
-  a3 = make_double2(s1.x - s3.x, s1.y - s3.y);
-}
-
-// v <- DFT_R(v), R = 2^NS, outputs in natural order
-template <int NS, bool INV>
-__device__ __forceinline__ void x_dft(double2 (&v)[1 << NS]) {
-  if (NS == 1) {
-    const double2 a = v[0], b = v[1];
-    v[0] = make_double2(a.x + b.x, a.y + b.y);
-    v[1] = make_double2(a.x - b.x, a.y - b.y);
-  } else if (NS == 2) {
-    x_dft4<INV>(v[0], v[1], v[2], v[3]);
-  } else {
-    const double h = 0.70710678118654752440;
-    double2 t0 = make_double2(v[0].x + v[4].x, v[0].y + v[4].y), u0 = make_double2(v[0].x - v[4].x, v[0].y - v[4].y);
-    double2 t1 = make_double2(v[1].x + v[5].x, v[1].y + v[5].y), u1 = make_double2(v[1].x - v[5].x, v[1].y - v[5].y);
-    double2 t2 = make_double2(v[2].x + v[6].x, v[2].y + v[6].y), u2 = make_double2(v[2].x - v[6].x, v[2].y - v[6].y);
-    double2 t3 = make_double2(v[3].x + v[7].x, v[3].y + v[7].y), u3 = make_double2(v[3].x - v[7].x, v[3].y - v[7].y);
-    // u_q *= W8^q (forward: exp(-i pi q / 4); inverse: conjugate)
-    if (INV) {
-      u1 = make_double2((u1.x - u1.y) * h, (u1.x + u1.y) * h);
-      u3 = make_double2((-u3.x - u3.y) * h, (u3.x - u3.y) * h);
-    } else {
-      u1 = make_double2((u1.x + u1.y) * h, (u1.y - u1.x) * h);
-      u3 = make_double2((u3.y - u3.x) * h, (-u3.x - u3.y) * h);
-    }
-    u2 = mul_mi<INV>(u2);
-    x_dft4<INV>(t0, t1, t2, t3);   // -> V0, V2, V4, V6
-    x_dft4<INV>(u0, u1, u2, u3);   // -> V1, V3, V5, V7
-    v[0] = t0; v[2] = t1; v[4] = t2; v[6] = t3;
-    v[1] = u0; v[3] = u1; v[5] = u2; v[7] = u3;
-  }
-}
 
 // twiddle multiply of inputs 1 .. R-1 by T[(r-1) Ns + k] (conjugated for the inverse)
 template <int NS, bool INV>

@@ -21,28 +21,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fftgs_fused.h"
+#include "fftgs_common.h"
 #include "gss_internal.h"
 #include "philox.h"
 
 namespace gss {
-
-constexpr int GEN_MAX_PASSES = 12;
-struct GenPlan {          // one axis: radices of the Stockham passes and where each pass's twiddles start in its table
-  int L;                  // line length (x: n1 / 2)
-  int npass;
-  int radix[GEN_MAX_PASSES];
-  int toff[GEN_MAX_PASSES];
-  int tlen;               // complex entries of the table: sum over the passes of (R - 1) * Ns
-  int has7;               // a radix-7 pass: tiles of this line hold at most 7 elements per thread (g_pass)
-};
-struct GenGrid {
-  int n1, n2, n3;         // n1 fastest; n3 = 1 on 2-D grids
-  int nh, nhp;            // n1 / 2 + 1 and the row pitch of the half-spectrum buffer (a multiple of 8)
-  int ndim;
-  int c1, c2, c3;         // centre cell (covariance source)
-  double s1, s2, s3;
-};
 
 // ---- in-register DFTs ------------------------------------------------------------------------------------------------
 template <bool INV>
@@ -406,12 +389,6 @@ __global__ __launch_bounds__(GEN_ANT) void gen_axis_kernel(GenGrid g, GenPlan pl
 // i.e. the pass GP3 of a 2-D grid becomes three trips over the buffer (five passes per realisation in all); the rows of
 // every tile are 128-byte pieces exactly as in the other strided passes.  twl = exp(-2 pi i k / n2), k < n2 (global; b c <
 // L2 L1 = n2, so the product indexes it directly).
-struct GenLong {
-  int L1, L2;      // n2 = L1 * L2
-  int NB;          // values of b per outer tile (divides L2; TX * L1 * NB <= 4 096)
-  int NC;          // values of c per inner tile (divides L1; TX * L2 * NC <= 4 096)
-};
-
 template <bool INV>
 __global__ __launch_bounds__(GEN_ANT) void gen_long_outer_kernel(GenGrid g, GenPlan pl, GenLong lg,
                                                                  const double2* __restrict__ atw, const double2* __restrict__ twl,

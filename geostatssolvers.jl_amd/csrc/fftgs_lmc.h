@@ -4,23 +4,13 @@
 //     Z_a = means[a] + sum_j L1[a][j] Y_j + sum_j L0[a][j] E_j .
 // The fields Y_j come from the realisation pipelines of fftgs.hip, which also holds the driver and the two entries.
 #pragma once
+#include "fftgs_common.h"
 #include "gss_internal.h"
 #include "philox.h"
 
 #include <cmath>
 
 namespace gss {
-
-constexpr int LMC_MAXZ = 8;   // the limit of gss_variogram_cross and gss_cokrig_create
-
-// What the mixing kernel reads per cell besides the fields.  Passed by value: the coefficients are scalar operands of
-// the multiplies, not loads from HBM.
-struct LmcCoef {
-  double L0[LMC_MAXZ * LMC_MAXZ];   // lower factor of (b0 + b0^T) / 2, row-major with stride LMC_MAXZ
-  double L1[LMC_MAXZ * LMC_MAXZ];   // ... of (b1 + b1^T) / 2
-  double means[LMC_MAXZ];
-  uint32_t live0, live1;            // bit j: column j of the factor is not a zero column
-};
 
 // Left-looking Cholesky without pivoting of the symmetric n x n matrix B (row-major, stride LMC_MAXZ) into L (same
 // layout, zero above the diagonal).  With d the largest diagonal entry, a pivot <= 1e-12 d makes its column a zero

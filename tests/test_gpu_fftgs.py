@@ -251,6 +251,39 @@ def test_slab_order_of_the_strided_passes_changes_nothing():
     assert abs(float(outs[0].split()[2]) - 1.0) < 0.05
 
 
+def test_generic_slab_order_changes_nothing():
+    """The generic passes of a 3-D grid can run their three strided passes in the slab order of the power-of-two pipeline
+    (GSS_FFTGS_GEN_SLAB, an A/B switch that is off by default, read once per process): the realisations must be bit for
+    bit those of one launch per pass.  The branch needs 8-column tiles on both strided axes, one realisation per launch
+    and a half-spectrum buffer over 200 MiB: 240 x 360 x 360 is the smallest non-power-of-two grid that has them (128 x
+    360 x 360 complex = 265 MB, so g_batch = 1; 360-point lines).  GSS_FFTGS_GEN_SLAB=3 gives 6 of the 16 x tiles per
+    slab, so the last slab is ragged.  Two subprocesses."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (
+        "import sys, hashlib, torch\n"
+        "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "import gss\n"
+        "from gss.engine import FFTGSHandle\n"
+        "h = FFTGSHandle(gss.ExponentialVariogram(range=9.0), (240, 360, 360), mean=0.5)\n"
+        "z = h.realize(11, 3, 2, device=True)\n"
+        "torch.cuda.synchronize()\n"
+        "print('DIGEST', hashlib.sha256(z.cpu().numpy().tobytes()).hexdigest(), float(z.std()))\n"
+    ) % (root, os.path.join(root, "geostatssolvers.jl_amd"))
+    outs = []
+    for env_slab in (None, "3"):
+        env = {k: v for k, v in os.environ.items() if k != "GSS_FFTGS_GEN_SLAB"}
+        if env_slab is not None:
+            env["GSS_FFTGS_GEN_SLAB"] = env_slab
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append([l for l in r.stdout.splitlines() if l.startswith("DIGEST")][0])
+    assert outs[0] == outs[1]
+    assert abs(float(outs[0].split()[2]) - 1.0) < 0.05
+
+
 @pytest.mark.parametrize("dims", POW2_GRIDS)
 def test_fused_spectrum_matches_oracle(dims, monkeypatch):
     """On power-of-two 3-D grids gss_fftgs_create builds F on the library's own passes (covariance rows generated
@@ -293,16 +326,26 @@ def test_state_broadcast_adopt(dims):
     b.close()
 
 
-def test_pipelined_realisations_equal_single_calls():
-    """One gss_fftgs_realize call with several realisations runs them as a two-stream pipeline (noise / x pass of
-    r + 1 on a helper stream beside the strided passes of r, two half-spectrum buffers).  The fields must be
-    bit-identical to one call per realisation, also on the second call (buffers and events re-used) and with an
-    index view."""
+@pytest.mark.parametrize("overlap", [None, "1"])
+def test_pipelined_realisations_equal_single_calls(overlap, monkeypatch):
+    """With GSS_FFTGS_OVERLAP=1 one gss_fftgs_realize call with several realisations runs them on the fused passes as a
+    two-stream pipeline (noise / x pass of r + 1 on a helper stream beside the strided passes of r, two half-spectrum
+    buffers); with the variable unset (the default) the same call runs them one after the other on the caller's stream.
+    Both are read when the handle is created, as is GSS_FFTGS_PATH=fused, without which this grid goes to the generic
+    passes.  In both runs the fields must be bit-identical to one call per realisation on a handle created without the
+    overlap, also on the second call (buffers and events re-used) and with an index view."""
     import gss
     from gss.engine import FFTGSHandle
     dims = (64, 32, 32)
-    h = FFTGSHandle(gss.ExponentialVariogram(range=9.0, sill=2.0, nugget=0.1), dims, mean=0.5)
-    single = np.stack([h.realize(21, r, 1)[0] for r in range(7)])
+    vg = gss.ExponentialVariogram(range=9.0, sill=2.0, nugget=0.1)
+    monkeypatch.setenv("GSS_FFTGS_PATH", "fused")
+    monkeypatch.delenv("GSS_FFTGS_OVERLAP", raising=False)
+    h0 = FFTGSHandle(vg, dims, mean=0.5)
+    single = np.stack([h0.realize(21, r, 1)[0] for r in range(7)])
+    h0.close()
+    if overlap is not None:
+        monkeypatch.setenv("GSS_FFTGS_OVERLAP", overlap)
+    h = FFTGSHandle(vg, dims, mean=0.5)
     for _ in range(2):
         assert np.array_equal(h.realize(21, 0, 7), single)
         assert np.array_equal(h.realize(21, 2, 5), single[2:])
@@ -313,7 +356,7 @@ def test_pipelined_realisations_equal_single_calls():
 
 def test_rocfft_kernels_are_kept_for_later_processes():
     """Grids outside the fused passes go through rocFFT, which compiles its kernels at run time; unless the user chose
-    a place, the library points ROCFFT_RTC_CACHE_PATH at ~/.cache/gss_hip (fftgs.hip) so that a later process finds
+    a place, the library points ROCFFT_RTC_CACHE_PATH at ~/.cache/gss_hip (fftgs_rocfft.hip) so that a later process finds
     them (0.1 s instead of 1.7 s for its first plan)."""
     import ctypes
     import os
