@@ -30,6 +30,7 @@ LUGS_NO_FACTOR = 1
 LUGS_FACT_LU = 2
 SGS_MASK_AFTER_SEARCH = 1
 SGS_METRIC_SHIFT = 4
+NSCORE_FORWARD, NSCORE_INVERSE = 0, 1
 
 
 class GSSError(RuntimeError):
@@ -139,6 +140,11 @@ SIGNATURES = {
     "gss_lugs_state_buffer": [_p, C.POINTER(_p), C.POINTER(_i64)],
     "gss_lugs_adopt_state": [_p],
     "gss_lugs_realize": [_p, _u64, _i64, _i64, _p, _f64, _p, _p, _p, _i32, _p],
+    "gss_nscore_create": [C.POINTER(_p), _p, _p, _i64, _f64, _f64, _f64, _f64, _p],
+    "gss_nscore_destroy": [_p],
+    "gss_nscore_info": [_p, C.POINTER(_i64)],
+    "gss_nscore_table": [_p, _p, _p, _i32, _p],
+    "gss_nscore_apply": [_p, _i32, _p, _p, _i64, _i64, _i64, _i64, _i32, _p],
     "gss_philox_uniform": [_u64, _i64, _i64, _p, _i32, _p],
     "gss_philox_normal": [_u64, _i64, _i64, _p, _i32, _p],
     "gss_dev_potrf": [_p, _i64, _i64, _p],

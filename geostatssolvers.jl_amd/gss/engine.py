@@ -711,6 +711,138 @@ class SGSHandle:
         return out
 
 
+def _runs(shape, strides):
+    """(nblocks, len, stride) of an array with element `strides` if it is `nblocks` contiguous runs of `len` elements
+    that start `stride` elements apart -- a contiguous array, or a view strided along its first axes --, else None."""
+    size = 1
+    for n in shape:
+        size *= n
+    if size == 0:
+        return None
+    nd = len(shape)
+    j, run = nd, 1
+    while j > 0 and (shape[j - 1] == 1 or strides[j - 1] == run):     # trailing axes that are contiguous
+        run *= shape[j - 1]
+        j -= 1
+    lead = [(n, s) for n, s in zip(shape[:j], strides[:j]) if n != 1]
+    if not lead:
+        return 1, run, run
+    for (n0, s0), (n1, s1) in zip(lead, lead[1:]):                    # leading axes that collapse into one stride
+        if s0 != n1 * s1:
+            return None
+    nb = 1
+    for n, _ in lead:
+        nb *= n
+    st = lead[-1][1]
+    return (nb, run, st) if st >= run else None
+
+
+def _elem_strides(a):
+    if is_torch(a):
+        return tuple(a.stride())
+    return tuple(s // a.itemsize if s % a.itemsize == 0 else -1 for s in a.strides)
+
+
+class NScoreHandle:
+    """gss_nscore_t*: the knots of a normal-score transform and their guide tables in HBM (gss.h).
+
+    `values` / `weights`: host arrays (the fit is preprocess); `tails`: (zmin, zmax), None or NaN entries meaning the
+    smallest / largest value; `tail_power`: (lower, upper).  `forward` and `inverse` take numpy arrays (host: staged in
+    chunks) or CUDA tensors (device: one launch on torch's current stream) of any shape and return the same kind; a
+    float64 view that is strided along its first axes only -- variable a of an (nreals, nz, N) ensemble -- is
+    transformed where it lies, anything else is made contiguous first.  `out=x` transforms in place; an `out` that is
+    not such runs, or not the runs of the input, is filled from a contiguous temporary."""
+
+    def __init__(self, values, weights=None, tails=None, tail_power=(1.0, 1.0)):
+        z = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        if w is not None and w.size != z.size:
+            raise ValueError(f"{w.size} weights for {z.size} values")
+        lo, hi = (None, None) if tails is None else tails
+        self._l = _lib.lib()
+        h = C.c_void_p()
+        check(self._l.gss_nscore_create(C.byref(h), ptr(z), ptr(w), z.size, float("nan") if lo is None else float(lo),
+                                        float("nan") if hi is None else float(hi), float(tail_power[0]),
+                                        float(tail_power[1]), current_stream()))
+        self._h = h
+        k = C.c_int64()
+        check(self._l.gss_nscore_info(h, C.byref(k)))
+        self.nknots = k.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.gss_nscore_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def table(self):
+        """(v, y): the distinct values and their scores, read back from the device tables."""
+        v, y = np.empty(self.nknots), np.empty(self.nknots)
+        check(self._l.gss_nscore_table(self._h, ptr(v), ptr(y), MEM_HOST, current_stream()))
+        return v, y
+
+    @staticmethod
+    def _as_runs(a):
+        """`a` as it is when the library can walk it, else a contiguous float64 copy; and its (nblocks, len, stride)."""
+        if is_torch(a):
+            import torch
+            if not a.is_cuda:
+                a = a.numpy()
+            else:
+                r = _runs(tuple(a.shape), _elem_strides(a)) if a.dtype == torch.float64 else None
+                if r is None:
+                    a = a.to(torch.float64).contiguous()
+                    r = (1, a.numel(), a.numel())
+                return a, r
+        a = np.asarray(a)
+        r = _runs(a.shape, _elem_strides(a)) if a.dtype == np.float64 and a.ctypes.data % 8 == 0 else None
+        if r is None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            r = (1, a.size, a.size)
+        return a, r
+
+    def _apply(self, direction, x, out):
+        x, (nb, ln, si) = self._as_runs(x)
+        if out is None:
+            out = _empty_like_space(x if is_torch(x) else None, tuple(x.shape), np.float64)
+            so = ln
+        else:
+            if is_torch(out) and not out.is_cuda:
+                out = out.numpy()
+            if tuple(out.shape) != tuple(x.shape) or _space(out) != _space(x):
+                raise ValueError("out must have the shape of the input and live where it lives")
+            if nb * ln == 0:
+                return out
+            f64 = str(out.dtype).endswith("float64")
+            r = _runs(tuple(out.shape), _elem_strides(out)) if f64 else None
+            if r is not None and r[0] == 1 and nb > 1:   # a contiguous side is the runs of the other side, back to back
+                r = (nb, ln, ln)
+            elif r is not None and nb == 1 and r[0] > 1:
+                nb, ln, si = r[0], r[1], r[1]
+            if r is None or (r[0], r[1]) != (nb, ln):
+                # `out` is no such runs, or other runs than the input: through a contiguous temporary
+                tmp = self._apply(direction, x, None)
+                if is_torch(out):
+                    out.copy_(tmp)
+                else:
+                    out[...] = tmp
+                return out
+            so = r[2]
+        if nb * ln:
+            check(self._l.gss_nscore_apply(self._h, direction, ptr(x), ptr(out), nb, ln, si, so, _space(x),
+                                           current_stream()))
+        return out
+
+    def forward(self, x, out=None):
+        """Values to scores: linear between the knots, y_1 below the smallest value and y_K above the largest."""
+        return self._apply(_lib.NSCORE_FORWARD, x, out)
+
+    def inverse(self, y, out=None):
+        """Scores to values: linear between the knots, the tail model outside [y_1, y_K]."""
+        return self._apply(_lib.NSCORE_INVERSE, y, out)
+
+
 class HipEngine:
     """The product engine: every call lands in a gfx950 kernel."""
     name = "hip"
@@ -721,6 +853,11 @@ class HipEngine:
     FFTGS_LMC = FFTGSHandle.lmc
     LUGS = LUGSHandle
     SGS = SGSHandle
+
+    @staticmethod
+    def nscore(values, weights=None, tails=None, tail_power=(1.0, 1.0)):
+        """A normal-score transform fitted to `values` (NScoreHandle): `.forward(x)`, `.inverse(y)`, `.table()`."""
+        return NScoreHandle(values, weights=weights, tails=tails, tail_power=tail_power)
 
     @staticmethod
     def cokrig(structure, B0, B1, variant, xdata, z, var, means=None, async_fit=False, factor=True):

@@ -902,6 +902,42 @@ int32_t gss_sgs_weights(gss_sgs_t* h, int32_t* idx, int32_t* ncond, double* w, d
 int32_t gss_sgs_realize(gss_sgs_t* h, uint64_t seed, int64_t first_real, int64_t nreals, const double* noise,
                         double* out, int32_t mem, void* stream);
 
+/* ---- normal-score transform: skewed data into Gaussian space and realisations back (GSLIB nscore / backtr, the
+ * reversible Quantile() step of a GeoStats pipeline).  Not in the reference's solvers; DESIGN.md section 4.
+ *   Fit (host, preprocess): n >= 1 finite values z with optional weights w (finite, > 0; NULL = 1) are sorted stably,
+ * equal values merged into distinct v_1 < ... < v_K with class weights W_k; cumulative weights are summed in long
+ * double from both ends.  With B_k the weight strictly below v_k, A_k strictly above and T the total,
+ *     y_k = Phi^-1((B_k + W_k / 2) / T)  if B_k <= A_k,   y_k = -Phi^-1((A_k + W_k / 2) / T)  otherwise
+ * (the survival form keeps the upper tail as accurate as the lower one).  Phi^-1: a rational start and one correction
+ * step on erfc.  Scores that rounding leaves non-increasing give GSS_ERR_INVALID (the message names the knot).
+ *   FORWARD z -> y: z <= v_1 gives y_1, z >= v_K gives y_K, otherwise linear between the bracketing knots; a datum
+ * gets exactly its class score.  INVERSE y -> z: inside [y_1, y_K] linear with the roles swapped;
+ *     y < y_1:  z = zmin + (v_1 - zmin) t^power_lo,  t = Q(-y) / Q(-y_1),   Q(x) = erfc(x / sqrt 2) / 2
+ *     y > y_K:  z = zmax - (zmax - v_K) t^power_hi,  t = Q(y) / Q(y_K)
+ * (GSLIB's linear / power tails, written so that no probability near 1 is subtracted).  zmin / zmax = NaN mean v_1 /
+ * v_K (clamp).  -inf gives zmin, +inf zmax, NaN gives NaN in both directions.  K = 1: forward is 0 everywhere and the
+ * inverse is the two tails around y_1 = 0.
+ *   gss_nscore_create takes HOST arrays and validates before it touches the device: n < 1, a non-finite value, a
+ * weight that is not finite and positive, zmin > v_1, zmax < v_K, a power <= 0 and K > 2^24 are GSS_ERR_INVALID.
+ * gss_nscore_table copies the knots (K doubles each) out of the device tables.
+ *   gss_nscore_apply transforms nblocks runs of len doubles that start in_stride / out_stride elements apart (variable
+ * a of every realisation of a gss_fftgs_realize_lmc output: nblocks = nreals, stride = nz N, one launch).  out == in
+ * with equal strides is allowed; any other overlap, or a stride < len with nblocks > 1, is GSS_ERR_INVALID.
+ * GSS_MEM_DEVICE: one launch in stream order, no allocation.  GSS_MEM_HOST: chunk by chunk through staged images;
+ * the environment variable GSS_NSCORE_CHUNK_ELEMS caps the elements per chunk, for tests, like
+ * GSS_COKRIG_CHUNK_POINTS: the results are the same bits.  Tables of up to 1 280 knots are searched in LDS, larger ones
+ * in global memory; GSS_NSCORE_LDS_KNOTS (tests; at most 2 048, 0 = never) moves that threshold.  Both find exactly
+ * the interval of a binary search and give the same bits.  Profile scope: "nscore_apply". */
+typedef struct gss_nscore gss_nscore_t;
+int32_t gss_nscore_create(gss_nscore_t** out, const double* z, const double* w, int64_t n, double zmin, double zmax,
+                          double power_lo, double power_hi, void* stream);
+int32_t gss_nscore_destroy(gss_nscore_t* h);
+int32_t gss_nscore_info(const gss_nscore_t* h, int64_t* nknots);
+int32_t gss_nscore_table(gss_nscore_t* h, double* v, double* y, int32_t mem, void* stream);
+enum { GSS_NSCORE_FORWARD = 0, GSS_NSCORE_INVERSE = 1 };
+int32_t gss_nscore_apply(gss_nscore_t* h, int32_t direction, const double* in, double* out, int64_t nblocks,
+                         int64_t len, int64_t in_stride, int64_t out_stride, int32_t mem, void* stream);
+
 /* ---- noise (test support): the Philox streams used above, n values for one realisation ----- */
 int32_t gss_philox_uniform(uint64_t seed, int64_t real, int64_t n, double* out, int32_t mem, void* stream);
 int32_t gss_philox_normal(uint64_t seed, int64_t real, int64_t n, double* out, int32_t mem, void* stream);
