@@ -403,6 +403,8 @@ static int32_t sgs_path(gss_sgs* h, SgsStageA* a, int64_t pp, hipStream_t s) {
         GSS_TRY(a->bigscr.alloc(sizeof(double) * (size_t)(need * nwg)));
       }
     }
+    h->big = 1;
+    h->big_lds = use_lds;
     const size_t lds = use_lds ? sizeof(double) * (size_t)need : 0;
     if (lds > 48 * 1024)
       GSS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sgs_weights_big_kernel<DIM>),
@@ -514,6 +516,21 @@ int32_t gss_sgs_weights(gss_sgs_t* h, int32_t* idx, int32_t* ncond, double* w, d
   if (w) GSS_HIP(hipMemcpyAsync(w, h->w.p, sizeof(double) * nk, kind, s));
   if (sigma) GSS_HIP(hipMemcpyAsync(sigma, h->sigma.p, sizeof(double) * n1, kind, s));
   if (mem == GSS_MEM_HOST) GSS_HIP(hipStreamSynchronize(s));
+  return GSS_OK;
+}
+
+int32_t gss_sgs_schedule(gss_sgs_t* h, int32_t* out, int32_t n) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr && out != nullptr, "NULL argument");
+  GSS_REQUIRE(n >= GSS_SGS_SCHEDULE_WORDS, "gss_sgs_schedule: room for %d words, %d needed", n, GSS_SGS_SCHEDULE_WORDS);
+  const bool team = h->team_chunks > 0;   // (team_rl is chosen before the chunks: it only counts where they exist)
+  out[0] = (int32_t)h->npaths;
+  out[1] = h->lvl_off.empty() ? 0 : (int32_t)h->lvl_off.size() - 2;
+  out[2] = h->team_chunks;
+  out[3] = team ? h->team_rl : 0;
+  out[4] = team ? h->team_cap : 0;
+  out[5] = h->big;
+  out[6] = h->big_lds;
   return GSS_OK;
 }
 

@@ -20,6 +20,7 @@ struct gss_sgs {
   // short levels (sgs_level_team_kernel): schedule-ordered padded lists / weights / sigma, chunk boundaries in `order`
   gss::DevBuf nb_sched, w_sched, sg_sched, inv_sched, chunk_off;
   int team_chunks = 0, team_cap = 0, team_rl = 0;
+  int big = 0, big_lds = 0;   // stage A ran sgs_weights_big_kernel; with the triangle in LDS (gss_sgs_schedule)
 };
 
 namespace gss {

@@ -125,6 +125,7 @@ SIGNATURES = {
     "gss_sgs_destroy": [_p],
     "gss_sgs_weights": [_p, _p, _p, _p, _p, _i32, _p],
     "gss_sgs_realize": [_p, _u64, _i64, _i64, _p, _p, _i32, _p],
+    "gss_sgs_schedule": [_p, _p, _i32],
     "gss_fftgs_create": [C.POINTER(_p), _VG, _i32, _p, _p, _f64, _i32, _p],
     "gss_fftgs_destroy": [_p],
     "gss_fftgs_spectrum": [_p, _p, _i32, _p],

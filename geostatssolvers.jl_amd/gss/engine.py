@@ -696,6 +696,13 @@ class SGSHandle:
         check(self._l.gss_sgs_weights(self._h, ptr(idx), ptr(nc), ptr(w), ptr(sg), MEM_HOST, current_stream()))
         return idx, nc, w, sg
 
+    def schedule(self):
+        """gss_sgs_schedule: which kernels the handle was built with and sweeps with (launches nothing)."""
+        o = np.zeros(7, dtype=np.int32)
+        check(self._l.gss_sgs_schedule(self._h, ptr(o), o.size))
+        return dict(npaths=int(o[0]), levels=int(o[1]), team_chunks=int(o[2]), team_rl=int(o[3]), team_cap=int(o[4]),
+                    big=bool(o[5]), big_lds=bool(o[6]))
+
     def realize(self, seed, first_real, nreals, noise=None, device=False, out=None):
         noise = _prep_in(noise)
         if out is not None:

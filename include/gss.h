@@ -901,6 +901,13 @@ int32_t gss_sgs_weights(gss_sgs_t* h, int32_t* idx, int32_t* ncond, double* w, d
                         void* stream);
 int32_t gss_sgs_realize(gss_sgs_t* h, uint64_t seed, int64_t first_real, int64_t nreals, const double* noise,
                         double* out, int32_t mem, void* stream);
+/* gss_sgs_schedule (test support; launches nothing): which kernels the handle was built with and will sweep with.
+ * out[0..6] (n >= GSS_SGS_SCHEDULE_WORDS): the number of visiting orders; the number of levels of the schedule (0: stage B
+ * walks the path); the chunks, the realisations per team and the nodes per chunk of the team schedule (all 0 where the
+ * sweep is not the team kernel's); 1 if the weights came from the workgroup-per-node kernel (more than 64 neighbours);
+ * 1 if that kernel kept its covariance triangle in LDS, 0 in HBM. */
+#define GSS_SGS_SCHEDULE_WORDS 7
+int32_t gss_sgs_schedule(gss_sgs_t* h, int32_t* out, int32_t n);
 
 /* ---- normal-score transform: skewed data into Gaussian space and realisations back (GSLIB nscore / backtr, the
  * reversible Quantile() step of a GeoStats pipeline).  Not in the reference's solvers; DESIGN.md section 4.

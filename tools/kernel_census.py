@@ -7,8 +7,9 @@ With the kernel-stats CSV of a `rocprofv3 --kernel-trace --stats` run the listin
 kernel was launched in that run, and ends with the ones that never were.  tests/test_kernel_census.py holds the kriging
 families of this list against the case table tests/kernel_cases.py, tests/test_search_census.py the neighbour-search and
 IDW / LWR families against tests/search_cases.py, tests/test_variography_instances_host.py the pair kernels of
-variography.hip against tests/vario_cases.py, and tests/test_fftgs_census.py the FFTGS families (fused, generic and rocFFT
-pipelines, co-simulation mix) against the run table tests/fftgs_cases.py.
+variography.hip against tests/vario_cases.py, tests/test_fftgs_census.py the FFTGS families (fused, generic and rocFFT
+pipelines, co-simulation mix) against the run table tests/fftgs_cases.py, and tests/test_sgs_census.py the SGS kernels
+against the run table tests/sgs_cases.py.
 """
 import argparse
 import csv
