@@ -15,6 +15,7 @@ from .validation import (BlockValidation, CrossValidationResult, KFoldValidation
 from .variograms import (CubicVariogram, ExponentialVariogram, GaussianVariogram, MaternVariogram, MetricBall,
                          NestedVariogram, PentasphericalVariogram, PowerVariogram, SineHoleVariogram,
                          SphericalVariogram)
+from .weighting import (BlockWeighting, CellDeclustering, PolygonalWeighting, Weights, weight, wmean, wquantile, wvar)
 from .variography import (DirectionalVariogram, EmpiricalCrossVariogram, EmpiricalCrossVariogramResult,
                           EmpiricalVariogram, EmpiricalVariogramResult, EmpiricalVarioplane, EmpiricalVarioplaneResult,
                           LMCModel, fit, fit_anisotropic, fit_lmc)

@@ -31,6 +31,7 @@ LUGS_FACT_LU = 2
 SGS_MASK_AFTER_SEARCH = 1
 SGS_METRIC_SHIFT = 4
 NSCORE_FORWARD, NSCORE_INVERSE = 0, 1
+DECLUS_MIN, DECLUS_MAX = 0, 1
 
 
 class GSSError(RuntimeError):
@@ -146,6 +147,9 @@ SIGNATURES = {
     "gss_nscore_info": [_p, C.POINTER(_i64)],
     "gss_nscore_table": [_p, _p, _p, _i32, _p],
     "gss_nscore_apply": [_p, _i32, _p, _p, _i64, _i64, _i64, _i64, _i32, _p],
+    "gss_decluster_cell_counts": [_p, _i64, _i32, _p, _p, _p, C.POINTER(_i64), _i32, _p],
+    "gss_decluster_cells": [_p, _p, _i64, _i32, _p, _i32, _i32, _i32, _p, _p, C.POINTER(_i32), _i32, _p],
+    "gss_decluster_nearest": [_p, _i64, _i32, _p, _p, _p, _p, C.POINTER(_i64), _i32, _p],
     "gss_philox_uniform": [_u64, _i64, _i64, _p, _i32, _p],
     "gss_philox_normal": [_u64, _i64, _i64, _p, _i32, _p],
     "gss_dev_potrf": [_p, _i64, _i64, _p],

@@ -1135,6 +1135,79 @@ class HipEngine:
                                         MEM_DEVICE if dev else MEM_HOST, current_stream()))
         return count, lagsum, zsum, (ndup if dev else int(ndup[0]))
 
+    # ---- declustering (gss.h "declustering") ------------------------------------------------------------------
+    @staticmethod
+    def _declus_x(x):
+        x = _prep_in(x)
+        if x.ndim == 1:
+            x = x[:, None]
+        if x.ndim != 2:
+            raise ValueError("x must be (n, d) point-major coordinates")
+        return x, (is_torch(x) and x.is_cuda)
+
+    @staticmethod
+    def decluster_cell_counts(x, origin, sides):
+        """One grid: x (n, d), origin and sides (d,) on the host -> count (n,) int32 (samples in each sample's cell) in
+        the memory space of x, and the number of occupied cells (int)."""
+        l = _lib.lib()
+        x, dev = HipEngine._declus_x(x)
+        n, d = x.shape
+        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        s = np.ascontiguousarray(sides, dtype=np.float64).reshape(-1)
+        if o.size != d or s.size != d:
+            raise ValueError(f"origin and sides need {d} components each, not {o.size} and {s.size}")
+        count = _empty_like_space(x, (n,), np.int32) if dev else np.empty(n, dtype=np.int32)
+        nocc = C.c_int64()
+        check(l.gss_decluster_cell_counts(ptr(x), n, d, ptr(o), ptr(s), ptr(count), C.byref(nocc),
+                                          MEM_DEVICE if dev else MEM_HOST, current_stream()))
+        return count, nocc.value
+
+    @staticmethod
+    def decluster_cells(x, z, sides, noffsets, criterion="min"):
+        """The GSLIB sweep: x (n, d), z (n,) or None (one size only), sides (ncs, d) on the host -> weights (n,) of the
+        best size in the memory space of x, wmean (ncs,) numpy (None without z), best (int)."""
+        l = _lib.lib()
+        x, dev = HipEngine._declus_x(x)
+        n, d = x.shape
+        if z is not None:
+            if dev != (is_torch(z) and z.is_cuda):
+                raise ValueError("x and z must live in the same memory space")
+            z = _prep_in(z).reshape(-1)
+            if z.shape[0] != n:
+                raise ValueError(f"{z.shape[0]} values for {n} samples")
+        s = np.ascontiguousarray(sides, dtype=np.float64)
+        if s.ndim == 1:
+            s = s[None, :]
+        if s.ndim != 2 or s.shape[1] != d:
+            raise ValueError(f"sides must be (ncs, {d}), not {s.shape}")
+        if criterion not in ("min", "max"):
+            raise ValueError(f"criterion {criterion!r}: 'min' or 'max'")
+        w = _empty_like_space(x, (n,), np.float64) if dev else np.empty(n)
+        wmean = None if z is None else np.empty(s.shape[0])
+        best = C.c_int32()
+        check(l.gss_decluster_cells(ptr(x), ptr(z), n, d, ptr(s), s.shape[0], int(noffsets),
+                                    _lib.DECLUS_MIN if criterion == "min" else _lib.DECLUS_MAX, ptr(w), ptr(wmean),
+                                    C.byref(best), MEM_DEVICE if dev else MEM_HOST, current_stream()))
+        return w, wmean, best.value
+
+    @staticmethod
+    def decluster_nearest(x, lo, step, dims):
+        """Polygonal declustering by discretisation: every point lo + (j + 1/2) step of the `dims` lattice goes to its
+        nearest sample -> weights (n,) in the memory space of x, nzero (samples without a point)."""
+        l = _lib.lib()
+        x, dev = HipEngine._declus_x(x)
+        n, d = x.shape
+        lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(-1)
+        step = np.ascontiguousarray(step, dtype=np.float64).reshape(-1)
+        dims = np.ascontiguousarray(dims, dtype=np.int64).reshape(-1)
+        if not (lo.size == step.size == dims.size == d):
+            raise ValueError(f"lo, step and dims need {d} components each")
+        w = _empty_like_space(x, (n,), np.float64) if dev else np.empty(n)
+        nzero = C.c_int64()
+        check(l.gss_decluster_nearest(ptr(x), n, d, ptr(lo), ptr(step), ptr(dims), ptr(w), C.byref(nzero),
+                                      MEM_DEVICE if dev else MEM_HOST, current_stream()))
+        return w, nzero.value
+
     @staticmethod
     def variogram_fit(h, gamma, count, kinds, nu=1.0, weighting=0, max_nugget_frac=1.0):
         """gss_variogram_fit (host code of the library, no device): -> (kind name, sill, nugget, range, nu,

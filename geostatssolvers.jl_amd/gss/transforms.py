@@ -20,7 +20,9 @@ class NormalScore:
 
     `NormalScore.fit(values, weights=None, tails=None, tail_power=(1.0, 1.0))`: rows whose value is NaN are dropped
     (with their weights); equal values are merged into one class, not despiked; `weights` (finite, > 0) are what a
-    declustering step supplies; `tails = (zmin, zmax)` are the bounds the back-transform extrapolates to below the
+    declustering step supplies -- `gss.weight(data, method, var)` marks the rows it left out (NaN in `var`) with a NaN
+    weight, and those are exactly the rows dropped here, so its result goes in as it is; `tails = (zmin, zmax)` are the
+    bounds the back-transform extrapolates to below the
     smallest and above the largest datum (None: clamp at the datum) and `tail_power` the exponents of the GSLIB
     power model on either side (1: linear).  The device tables are built at the first transform."""
 

@@ -945,6 +945,48 @@ enum { GSS_NSCORE_FORWARD = 0, GSS_NSCORE_INVERSE = 1 };
 int32_t gss_nscore_apply(gss_nscore_t* h, int32_t direction, const double* in, double* out, int64_t nblocks,
                          int64_t len, int64_t in_stride, int64_t out_stride, int32_t mem, void* stream);
 
+/* ---- declustering: weights for preferentially sampled data, the first link of the chain (GSLIB declus, the
+ * ecosystem's weight(data, BlockWeighting(sides)); what gss_nscore_create takes as w).  Not in the reference's solvers;
+ * DESIGN.md section 4.  x is n x dim point-major, dim 1 .. 3, 1 <= n < 2^31 - 1, every coordinate finite.
+ *   A cell.  For an origin o and sides s (one per axis, finite, > 0) the index of sample x along axis a is
+ *     floor((x_a - o_a) / s_a)
+ * in FP64: one subtraction and one IEEE division, no reciprocal, nothing fused.  A sample exactly on an edge therefore
+ * belongs to the upper cell.  Every sample's index along every axis must lie in [0, 2^21) (a cell id then fits 63
+ * bits); otherwise the call returns GSS_ERR_INVALID and the message names the axis.
+ *   gss_decluster_cell_counts, one grid: count[i] = samples in the cell of sample i (itself included), *noccupied (a host
+ * word) = distinct occupied cells.  The integer core of block weighting: w_i = n / (noccupied count[i]).
+ *   gss_decluster_cells, the GSLIB sweep: sides is ncs x dim (1 <= ncs <= 256), each size is laid noff times
+ * (1 <= noff <= 64).  With lo_a the smallest coordinate along axis a, offset k = 0 .. noff - 1 of size c has the origin
+ *     o_a = lo_a - (s_a k) / noff          (the product and the quotient each rounded once).
+ * The weights of one grid are n / (noccupied count_i): the integer product formed exactly (64 bits), converted to FP64
+ * (exact below 2^53) and one division.  The weights of a size are the mean over its grids: summed in ascending k from
+ * 0, then one division by noff.  wmean[c] = (sum_i w_i z_i) / n, reduced in a fixed order without floating-point
+ * atomics: two calls on the same input give the same bits.  *best = the first c that attains the minimum
+ * (GSS_DECLUS_MIN) or the maximum (GSS_DECLUS_MAX) of wmean, and w receives the weights of that size.  z must be
+ * finite; z == NULL is allowed with ncs == 1 only: wmean is then untouched and *best = 0.  wmean and best are host
+ * memory whatever `mem` says.
+ *   The grids are counted in batches (a radix sort of (cell, sample) pairs and a scan per batch) of at most 2^24 pairs,
+ * with scratch from the block pool.  The environment variable GSS_DECLUS_CHUNK_GRIDS caps the grids per batch, for
+ * tests, like GSS_COKRIG_CHUNK_POINTS: the results are the same bits whatever the batching.
+ *   gss_decluster_nearest, polygonal (Voronoi) declustering by discretisation: the M = prod dims points
+ *     lo_a + (j_a + 1/2) step_a,   0 <= j_a < dims_a   (product and sum each rounded once; step finite, > 0; M <= 2^53)
+ * are formed in HBM in pieces of 2^22 (GSS_DECLUS_CHUNK_QUERIES lowers that, for tests: same results), each is given
+ * to its nearest sample by the searcher of gss_knn_search (k = 1, Euclidean, ties to the lower index), the hits are
+ * counted with 64-bit integer atomics, and w_i = (n hits_i) / M.  *nzero (a host word) = samples nobody chose, whose
+ * weight is 0: a finer lattice is needed before such weights go into gss_nscore_create.
+ *   All three validate before they touch the device what can be checked without it: sizes, sides, steps, and for
+ * GSS_MEM_HOST arrays also the coordinates, the values and the index range (device arrays are checked on the device).
+ * Profile scopes: "declus_cell_counts", "declus_cells", "declus_nearest"; "declus_sort" is the radix sorts inside the
+ * first two. */
+enum { GSS_DECLUS_MIN = 0, GSS_DECLUS_MAX = 1 };
+int32_t gss_decluster_cell_counts(const double* x, int64_t n, int32_t dim, const double* origin, const double* sides,
+                                  int32_t* count, int64_t* noccupied, int32_t mem, void* stream);
+int32_t gss_decluster_cells(const double* x, const double* z, int64_t n, int32_t dim, const double* sides, int32_t ncs,
+                            int32_t noff, int32_t criterion, double* w, double* wmean, int32_t* best, int32_t mem,
+                            void* stream);
+int32_t gss_decluster_nearest(const double* x, int64_t n, int32_t dim, const double* lo, const double* step,
+                              const int64_t* dims, double* w, int64_t* nzero, int32_t mem, void* stream);
+
 /* ---- noise (test support): the Philox streams used above, n values for one realisation ----- */
 int32_t gss_philox_uniform(uint64_t seed, int64_t real, int64_t n, double* out, int32_t mem, void* stream);
 int32_t gss_philox_normal(uint64_t seed, int64_t real, int64_t n, double* out, int32_t mem, void* stream);
