@@ -9,6 +9,7 @@ from .geo import (CartesianGrid, Composition, DomainView, Ensemble, GeoTable, Po
 from .problems import EstimationProblem, SimulationProblem
 from .solvers import (FFTGS, LUGS, SGS, CoKrigingSolver, ExpWeight, IDWSolver, KrigingSolver, LWRSolver, TricubeWeight,
                       kriging_ui, searcher_ui, simulate_with_generic_loop, solve)
+from .indicator import IndicatorKrigingSolver, postik
 from .transforms import InNormalScores, NormalScore
 from .validation import (BlockValidation, CrossValidationResult, KFoldValidation, LeaveBallOut, LeaveOneOut,
                          cross_validate, cverror)

@@ -150,6 +150,10 @@ SIGNATURES = {
     "gss_decluster_cell_counts": [_p, _i64, _i32, _p, _p, _p, C.POINTER(_i64), _i32, _p],
     "gss_decluster_cells": [_p, _p, _i64, _i32, _p, _i32, _i32, _i32, _p, _p, C.POINTER(_i32), _i32, _p],
     "gss_decluster_nearest": [_p, _i64, _i32, _p, _p, _p, _p, C.POINTER(_i64), _i32, _p],
+    "gss_ik_predict_knn": [_p, _p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _i32, _i32, _f64, _p, _i32, _f64, _p, _i64,
+                           _p, _p, _p, _p, _p, _i32, _p],
+    "gss_ik_order_relations": [_p, _i64, _i32, C.POINTER(_i64), C.POINTER(_f64), _i32, _p],
+    "gss_ik_post": [_p, _i64, _i32, _p, _f64, _f64, _f64, _f64, _p, _i32, _p, _i32, _p, _p, _p, _p, _i32, _p],
     "gss_philox_uniform": [_u64, _i64, _i64, _p, _i32, _p],
     "gss_philox_normal": [_u64, _i64, _i64, _p, _i32, _p],
     "gss_dev_potrf": [_p, _i64, _i64, _p],

@@ -874,6 +874,102 @@ class HipEngine:
         return CoKrigHandle(structure, B0, B1, variant, xdata, z, var, means=means, async_fit=async_fit, factor=factor)
 
     @staticmethod
+    def ik_predict_knn(xdata, z, xdom, cutoffs, variograms, k, minneighbors=1, fstar=None, radius=None, radii=None,
+                       distance=None, rotation=None, return_raw=False, return_idx=False):
+        """Indicator kriging under a moving neighbourhood (gss.h, gss_ik_predict_knn).  `variograms`: one model (median
+        form) or a sequence of one per cutoff (full form).  `fstar=None`: the ordinary variant; K global proportions:
+        simple kriging about them.  Host arrays in -> host arrays out; with a CUDA `xdom` everything stays in HBM.
+        -> ccdf[m, K] (corrected), status[m][, raw[m, K]][, idx[m, k], count[m]]."""
+        l = _lib.lib()
+        dev = is_torch(xdom) and xdom.is_cuda
+        if dev:
+            import torch
+            x = xdata if is_torch(xdata) else torch.as_tensor(np.asarray(xdata, dtype=np.float64), device="cuda")
+            x = _prep_in(x.reshape(x.shape[0], -1))
+            zz = _prep_in(z if is_torch(z) else torch.as_tensor(np.asarray(z, dtype=np.float64), device="cuda"))
+            c = _prep_in(xdom.reshape(-1, x.shape[1]))
+        else:
+            x = np.ascontiguousarray(xdata, dtype=np.float64)
+            if x.ndim == 1:
+                x = x[:, None]
+            zz = np.ascontiguousarray(z, dtype=np.float64)
+            c = np.ascontiguousarray(xdom, dtype=np.float64).reshape(-1, x.shape[1])
+        n, d = int(x.shape[0]), int(x.shape[1])
+        m = int(c.shape[0])
+        if zz.ndim != 1 or zz.shape[0] != n:
+            raise ValueError("z must have shape (n,)")
+        cut = np.ascontiguousarray(cutoffs, dtype=np.float64).reshape(-1)
+        K = int(cut.size)
+        models = list(variograms) if isinstance(variograms, (list, tuple)) else [variograms]
+        vgs = (_lib.Variogram * len(models))(*[_vg_struct(v, d) for v in models])
+        fs = None if fstar is None else np.ascontiguousarray(fstar, dtype=np.float64).reshape(-1)
+        if fs is not None and fs.size != K:
+            raise ValueError(f"fstar has {fs.size} values for {K} cutoffs")
+        ccdf = _empty_like_space(c, (m, K), np.float64)
+        raw = _empty_like_space(c, (m, K), np.float64) if return_raw else None
+        st = _empty_like_space(c, (m,), np.uint8)
+        idx = _empty_like_space(c, (m, int(k)), np.int32) if return_idx else None
+        cnt = _empty_like_space(c, (m,), np.int32) if return_idx else None
+        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
+        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
+        met, mpar = _lib.metric_spec(distance)
+        met, ir = _ball_metric(met, ir, radii, rotation)
+        check(l.gss_ik_predict_knn(ptr(x), ptr(zz), n, d, ptr(cut), K, vgs, len(models), SK if fs is not None else OK,
+                                   ptr(fs), int(k), int(minneighbors), r, ptr(ir), met, mpar, ptr(c), m, ptr(ccdf),
+                                   ptr(raw), ptr(st), ptr(idx), ptr(cnt), MEM_DEVICE if dev else MEM_HOST,
+                                   current_stream()))
+        out = (ccdf, st)
+        if return_raw:
+            out += (raw,)
+        if return_idx:
+            out += (idx, cnt)
+        return out
+
+    @staticmethod
+    def ik_order_relations(ccdf):
+        """GSLIB's order-relation correction of m x K rows, IN PLACE (gss.h, gss_ik_order_relations; numpy array or CUDA
+        tensor, contiguous float64) -> (ccdf, ncorrected, maxcorr)."""
+        l = _lib.lib()
+        dev = is_torch(ccdf) and ccdf.is_cuda
+        ok = ccdf.is_contiguous() if is_torch(ccdf) else (ccdf.flags.c_contiguous and ccdf.dtype == np.float64)
+        if len(ccdf.shape) != 2 or not ok:
+            raise ValueError("ccdf must be a contiguous float64 array of shape (m, K)")
+        nc, mx = C.c_int64(0), C.c_double(0.0)
+        check(l.gss_ik_order_relations(ptr(ccdf), int(ccdf.shape[0]), int(ccdf.shape[1]), C.byref(nc), C.byref(mx),
+                                       MEM_DEVICE if dev else MEM_HOST, current_stream()))
+        return ccdf, int(nc.value), float(mx.value)
+
+    @staticmethod
+    def ik_post(ccdf, cutoffs, zmin, zmax, tail_power=(1.0, 1.0), thresholds=(), probs=(), moments=True):
+        """Post-processing of corrected ccdf rows (gss.h, gss_ik_post) -> dict with `etype`[m] and `cvar`[m] (when
+        `moments`), `pabove`[m, nthr] (when thresholds are given) and `quant`[m, nq] (when probs are given), in the
+        memory space of `ccdf`."""
+        l = _lib.lib()
+        dev = is_torch(ccdf) and ccdf.is_cuda
+        f = _prep_in(ccdf) if dev else np.ascontiguousarray(ccdf, dtype=np.float64)
+        if len(f.shape) != 2:
+            raise ValueError("ccdf must have shape (m, K)")
+        m, K = int(f.shape[0]), int(f.shape[1])
+        cut = np.ascontiguousarray(cutoffs, dtype=np.float64).reshape(-1)
+        if cut.size != K:
+            raise ValueError(f"{cut.size} cutoffs for rows of {K}")
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = {}
+        if moments:
+            out["etype"] = _empty_like_space(f, (m,), np.float64)
+            out["cvar"] = _empty_like_space(f, (m,), np.float64)
+        if thr.size:
+            out["pabove"] = _empty_like_space(f, (m, thr.size), np.float64)
+        if pr.size:
+            out["quant"] = _empty_like_space(f, (m, pr.size), np.float64)
+        check(l.gss_ik_post(ptr(f), m, K, ptr(cut), float(zmin), float(zmax), float(tail_power[0]), float(tail_power[1]),
+                            ptr(thr) if thr.size else None, int(thr.size), ptr(pr) if pr.size else None, int(pr.size),
+                            ptr(out.get("etype")), ptr(out.get("cvar")), ptr(out.get("pabove")), ptr(out.get("quant")),
+                            MEM_DEVICE if dev else MEM_HOST, current_stream()))
+        return out
+
+    @staticmethod
     def cov_pairwise(vg, a, b=None):
         l = _lib.lib()
         a = np.ascontiguousarray(a, dtype=np.float64)

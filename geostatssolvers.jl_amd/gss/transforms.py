@@ -129,7 +129,8 @@ class InNormalScores:
     def __init__(self, solver, **transforms):
         if not hasattr(solver, "solvesingle"):
             raise TypeError(f"{type(solver).__name__} is not a simulation solver: the back-transform of an estimate "
-                            f"(a kriging mean) is biased, so estimation in normal scores is refused")
+                            f"(a kriging mean) is biased, so estimation in normal scores is refused; for the local "
+                            f"distribution of skewed data use IndicatorKrigingSolver and postik")
         if not transforms:
             raise ValueError("InNormalScores needs at least one variable: InNormalScores(solver, z=None)")
         for var, t in transforms.items():

@@ -987,6 +987,56 @@ int32_t gss_decluster_cells(const double* x, const double* z, int64_t n, int32_t
 int32_t gss_decluster_nearest(const double* x, int64_t n, int32_t dim, const double* lo, const double* step,
                               const int64_t* dims, double* w, int64_t* nzero, int32_t mem, void* stream);
 
+/* ---- indicator kriging: the local distribution of a continuous variable without a Gaussian model (GSLIB ik3d +
+ *      postik).  (The reference has no indicator solver; the conventions are this library's own.)
+ *
+ * Cutoffs      c_0 < c_1 < .. < c_{K-1}, 1 <= K <= 16, finite and strictly increasing (GSS_ERR_INVALID otherwise).
+ * Indicator    i_jq = (z_j <= c_q) ? 1 : 0, formed in the kernel from z: a sample exactly on a cutoff counts as below it.
+ * Variant      GSS_KRIG_ORDINARY: weights sum to one.  GSS_KRIG_SIMPLE about the global proportions fstar (K doubles in
+ *              [0, 1], HOST memory like cutoffs): F_q = F*_q + sum_j lambda_j (i_jq - F*_q).  No drift variants.
+ * Variograms   vgs / nvg, HOST memory.  nvg = 1: median indicator kriging, one system per point serves the K cutoffs.
+ *              nvg = K: full indicator kriging, one system per cutoff and point on the same neighbour list.  Every
+ *              stationary model of gss_krig_predict_knn, nested ones included; GSS_VG_POWER -> GSS_ERR_UNSUPPORTED.
+ *              Rotated structures go through the frame contract of gss_variogram_t::rotation; the rotated models of one
+ *              call must share one rotation and the others must not depend on a frame (isotropic structures, or equal
+ *              radii): GSS_ERR_UNSUPPORTED otherwise.
+ * Order relations (GSLIB, continuous variable)  clip each value to [0, 1]; upward pass U_q = max(U_{q-1}, F_q); downward
+ *              pass from the top D_q = min(D_{q+1}, F_q); result (U_q + D_q) / 2.  Pure FP64 in a fixed order.  A row
+ *              that holds a NaN stays all NaN.
+ *
+ * gss_ik_predict_knn: samples xdata (n x dim, point-major) and z (n), domain xdom (m x dim), all in `mem`.  k (1 .. 64,
+ *   <= n; more than 64 -> GSS_ERR_UNSUPPORTED, the limit of the cokriging moving neighbourhood), minneighbors, radius,
+ *   inv_radii, metric, metric_param: as gss_krig_predict_knn, one search per call.  Outputs: ccdf (m x K, point-major,
+ *   corrected), raw (m x K, before the correction; may be NULL), status (m; may be NULL), idx_out (m x k) and
+ *   count_out (m) as gss_krig_predict_knn (may be NULL).  Fewer than max(minneighbors, 1) neighbours: GSS_PT_MISSING
+ *   and NaN in the K outputs; a non-positive pivot in any of the point's factorisations (or in the constraint's Schur
+ *   complement): GSS_PT_SINGULAR and NaN.  No kriging variance is formed.  Profile scopes: "knn", "ik_local".
+ *
+ * gss_ik_order_relations: the correction alone, in place on m x K rows (for ccdfs assembled elsewhere, e.g. from the
+ *   global neighbourhood).  *ncorrected (host word, may be NULL): the (point, cutoff) values it changed; *maxcorr
+ *   (host word, may be NULL): the largest absolute change; a row that holds a NaN becomes all NaN and counts in neither
+ *   figure.  gss_ik_predict_knn applies the same device function.
+ *
+ * gss_ik_post: from corrected rows, under the ccdf model
+ *     inside a class (c_{q-1}, c_q]   F linear
+ *     below c_0                       F(z) = F_0 ((z - zmin) / (c_0 - zmin))^w_lo
+ *     above c_{K-1}                   F(z) = 1 - (1 - F_{K-1}) ((zmax - z) / (zmax - c_{K-1}))^w_hi
+ *   (w = 1: linear tails; no hyperbolic tail, whose mean need not exist), any of: etype[m] (mean) and cvar[m]
+ *   (variance, clamped at 0) from the closed-form class moments of DESIGN.md section 4; pabove[m x nthr] = 1 - F(t_i);
+ *   quant[m x nq] = the smallest z with F(z) >= p_i (a flat segment returns its left end).  A row with a NaN gives
+ *   NaNs.  zmin < c_0, zmax > c_{K-1}, w > 0, 0 < p < 1, thresholds inside [zmin, zmax], nthr and nq at most 16
+ *   (GSS_ERR_INVALID otherwise); cutoffs, thresholds and probs are HOST arrays.  Profile scope: "ik_post". */
+int32_t gss_ik_predict_knn(const double* xdata, const double* z, int64_t n, int32_t dim, const double* cutoffs,
+                           int32_t K, const gss_variogram_t* vgs, int32_t nvg, int32_t variant, const double* fstar,
+                           int32_t k, int32_t minneighbors, double radius, const double* inv_radii, int32_t metric,
+                           double metric_param, const double* xdom, int64_t m, double* ccdf, double* raw,
+                           uint8_t* status, int32_t* idx_out, int32_t* count_out, int32_t mem, void* stream);
+int32_t gss_ik_order_relations(double* ccdf, int64_t m, int32_t K, int64_t* ncorrected, double* maxcorr, int32_t mem,
+                               void* stream);
+int32_t gss_ik_post(const double* ccdf, int64_t m, int32_t K, const double* cutoffs, double zmin, double zmax,
+                    double w_lo, double w_hi, const double* thresholds, int32_t nthr, const double* probs, int32_t nq,
+                    double* etype, double* cvar, double* pabove, double* quant, int32_t mem, void* stream);
+
 /* ---- noise (test support): the Philox streams used above, n values for one realisation ----- */
 int32_t gss_philox_uniform(uint64_t seed, int64_t real, int64_t n, double* out, int32_t mem, void* stream);
 int32_t gss_philox_normal(uint64_t seed, int64_t real, int64_t n, double* out, int32_t mem, void* stream);
