@@ -13,7 +13,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import MEM_DEVICE, MEM_HOST, check, current_stream, is_torch, make_variogram, ptr
+from . import _staging as st
+from ._lib import MEM_HOST, check, current_stream, is_torch, make_variogram, ptr
 
 SK, OK, UK, EDK = 0, 1, 2, 3
 
@@ -48,17 +49,6 @@ def _vg_struct(vg, dim, extent=None):
                           rotation=getattr(vg, "rotation", None))
 
 
-def _ball_metric(met, ir, radii, rotation):
-    """A rotated search ball: GSS_METRIC_ROTATED_BALL with the 12-double inv_radii (gss.h, gss_knn_search)."""
-    if rotation is None:
-        return met, ir
-    if radii is None:
-        raise ValueError("a rotation needs an anisotropic ball (radii)")
-    if met != 0:
-        raise ValueError("a search ball cannot be combined with a non-Euclidean distance")
-    return _lib.METRIC_ROTATED_BALL, _lib.rotated_ball_spec(radii, rotation)
-
-
 def _extent(x):
     """Diameter of the bounding box of point-major coordinates (numpy or CUDA tensor)."""
     if is_torch(x):
@@ -67,39 +57,11 @@ def _extent(x):
     return float(np.sqrt(((x.max(axis=0) - x.min(axis=0)) ** 2).sum()))
 
 
-def _space(x):
-    """MEM_DEVICE for CUDA tensors; numpy arrays and CPU tensors (pinned ones included) are host memory."""
-    return MEM_DEVICE if is_torch(x) and x.is_cuda else MEM_HOST
-
-
-def _empty_like_space(ref, shape, dtype):
-    if is_torch(ref):
-        import torch
-        tdt = {np.float64: torch.float64, np.uint8: torch.uint8, np.int32: torch.int32}[dtype]
-        return torch.empty(shape, dtype=tdt, device=ref.device)
-    return np.empty(shape, dtype=dtype)
-
-
-def _prep_in(x, dtype=np.float64):
-    """Contiguous array of the right dtype in the space it already lives in."""
-    if x is None:
-        return None
-    if is_torch(x):
-        import torch
-        tdt = {np.float64: torch.float64, np.int64: torch.int64}[dtype]
-        if not x.is_cuda:
-            return np.ascontiguousarray(x.numpy(), dtype=dtype)
-        return x.to(tdt).contiguous()
-    return np.ascontiguousarray(x, dtype=dtype)
-
-
 def to_host(t):
     """numpy copy of a contiguous CUDA tensor through the library's transfer path (gss_dev_to_host: pinned bounce
     buffers, ~45 GB/s into pageable memory where `tensor.cpu()` manages ~10)."""
-    import torch
     t = t.contiguous()
-    dt = {torch.float64: np.float64, torch.int32: np.int32, torch.uint8: np.uint8, torch.int64: np.int64}[t.dtype]
-    out = np.empty(tuple(t.shape), dtype=dt)
+    out = np.empty(tuple(t.shape), dtype={v: k for k, v in st.torch_dtypes().items()}[t.dtype])
     check(_lib.lib().gss_dev_to_host(ptr(out), C.c_void_p(t.data_ptr()), out.nbytes, current_stream()))
     return out
 
@@ -126,7 +88,8 @@ class _NativeState:
         _lib.state_bcast(self._STATE_KIND, self._h, root)
 
     def export_state(self) -> bytes:
-        """80-byte token another process passes to `import_state` (keep this handle alive until it has)."""
+        """Token of `_lib.IPC_TOKEN_BYTES` (96) bytes that another process passes to `import_state` (keep this handle
+        alive until it has)."""
         return _lib.state_ipc_export(self._STATE_KIND, self._h)
 
     def import_state(self, token: bytes):
@@ -144,9 +107,7 @@ class KrigHandle(_NativeState):
         prediction assembles its right-hand sides beside it and reports the fit's status itself (the order of
         `solve`: fit, then predict, krig.jl:166-186)."""
         self._l = _lib.lib()
-        x = np.ascontiguousarray(xdata, dtype=np.float64)
-        if x.ndim == 1:
-            x = x[:, None]
+        x = st.samples(xdata)
         self.n, self.dim = x.shape
         zz = np.ascontiguousarray(z, dtype=np.float64)
         dd = None if drift_data is None else np.ascontiguousarray(drift_data, dtype=np.float64).reshape(self.n, -1)
@@ -185,81 +146,44 @@ class KrigHandle(_NativeState):
         check(self._l.gss_krig_set_block_support(self._h, ptr(c), int(nsub or 0), current_stream()))
 
     def predict_global(self, xdom, drift_dom=None):
-        xdom = _prep_in(xdom)
+        xdom = st.prep(xdom)
         m = xdom.shape[0]
-        mem = _space(xdom)
-        mean = _empty_like_space(xdom, (m,), np.float64)
-        var = _empty_like_space(xdom, (m,), np.float64)
-        status = _empty_like_space(xdom, (m,), np.uint8)
-        dd = _prep_in(drift_dom)
+        mean, var, status = st.estimate_out(xdom, (m,), (m,))[:3]
+        dd = st.prep(drift_dom)
         check(self._l.gss_krig_predict_global(self._h, ptr(xdom), ptr(dd), m, ptr(mean), ptr(var), ptr(status),
-                                              mem, current_stream()))
+                                              st.mem_flag(xdom), current_stream()))
         return mean, var, status
 
     def predict_knn(self, xdom, k, minneighbors=1, radius=None, radii=None, drift_dom=None, return_idx=False,
                     distance=None, rotation=None):
         """`rotation`: of the search ball `radii` (MetricBall.rotation; GSS_METRIC_ROTATED_BALL)."""
-        xdom = _prep_in(xdom)
+        xdom = st.prep(xdom)
         m = xdom.shape[0]
-        mem = _space(xdom)
-        mean = _empty_like_space(xdom, (m,), np.float64)
-        var = _empty_like_space(xdom, (m,), np.float64)
-        status = _empty_like_space(xdom, (m,), np.uint8)
-        idx = _empty_like_space(xdom, (m, k), np.int32) if return_idx else None
-        cnt = _empty_like_space(xdom, (m,), np.int32) if return_idx else None
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        dd = _prep_in(drift_dom)
-        met, mpar = _lib.metric_spec(distance)
-        met, ir = _ball_metric(met, ir, radii, rotation)
+        out = st.estimate_out(xdom, (m,), (m,), ((m, k), (m,)) if return_idx else None)
+        mean, var, status, idx, cnt = out
+        dd = st.prep(drift_dom)
+        r, ir, met, mpar = st.search_args(radius, radii, distance, rotation)
         check(self._l.gss_krig_predict_knn(self._h, ptr(xdom), ptr(dd), m, int(k), int(minneighbors), r, ptr(ir),
-                                           met, mpar, ptr(mean), ptr(var), ptr(status), ptr(idx), ptr(cnt), mem,
-                                           current_stream()))
-        if return_idx:
-            return mean, var, status, idx, cnt
-        return mean, var, status
-
-    def _cv_out(self, device, k=None):
-        """Output arrays of a cross-validation call: numpy, or CUDA tensors when `device`."""
-        if device:
-            import torch
-            dev = f"cuda:{torch.cuda.current_device()}"
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)   # noqa: E731
-            out = [mk((self.n,), torch.float64), mk((self.n,), torch.float64), mk((self.n,), torch.uint8)]
-            if k is not None:
-                out += [mk((self.n, k), torch.int32), mk((self.n,), torch.int32)]
-            return out
-        out = [np.empty(self.n), np.empty(self.n), np.empty(self.n, dtype=np.uint8)]
-        if k is not None:
-            out += [np.empty((self.n, k), dtype=np.int32), np.empty(self.n, dtype=np.int32)]
-        return out
+                                           met, mpar, ptr(mean), ptr(var), ptr(status), ptr(idx), ptr(cnt),
+                                           st.mem_flag(xdom), current_stream()))
+        return st.estimate_result(out, return_idx)
 
     def cv_global(self, device=False):
         """Leave-one-out predictions of every sample under the global neighbourhood, from the factor of the handle
         (gss.h, gss_krig_cv_global) -> (pred, variance, status)."""
-        pred, var, status = self._cv_out(device)
-        check(self._l.gss_krig_cv_global(self._h, ptr(pred), ptr(var), ptr(status),
-                                         MEM_DEVICE if device else MEM_HOST, current_stream()))
+        pred, var, status = st.estimate_out(bool(device), (self.n,), (self.n,))[:3]
+        check(self._l.gss_krig_cv_global(self._h, ptr(pred), ptr(var), ptr(status), st.mem_flag(bool(device)),
+                                         current_stream()))
         return pred, var, status
 
     def cv_global_folds(self, fold, device=False):
         """Every sample predicted from all samples outside its own fold under the global neighbourhood, from the factor
         of the handle (gss.h, gss_krig_cv_global_folds).  `fold`: n ids >= 0, arbitrary (numpy: host arrays out; CUDA
         int32 tensor: everything stays in HBM) or None for leave-one-out (`cv_global`).  -> (pred, variance, status)."""
-        device = bool(device) or (is_torch(fold) and fold.is_cuda)
-        if device and fold is not None and not (is_torch(fold) and fold.is_cuda):
-            raise ValueError("device=True needs the fold ids as a CUDA tensor")
-        if fold is not None:
-            if device:
-                import torch
-                fold = fold.to(torch.int32).contiguous()
-            else:
-                fold = np.ascontiguousarray(fold, dtype=np.int32)
-            if fold.shape != (self.n,):
-                raise ValueError(f"fold must hold one id per sample ({self.n}), got shape {tuple(fold.shape)}")
-        pred, var, status = self._cv_out(device)
+        fold, device = st.fold_arg(fold, self.n, device)
+        pred, var, status = st.estimate_out(device, (self.n,), (self.n,))[:3]
         check(self._l.gss_krig_cv_global_folds(self._h, ptr(fold), ptr(pred), ptr(var), ptr(status),
-                                               MEM_DEVICE if device else MEM_HOST, current_stream()))
+                                               st.mem_flag(device), current_stream()))
         return pred, var, status
 
     def cv_knn(self, k, fold=None, exclude_radius=None, minneighbors=1, radius=None, radii=None, return_idx=False,
@@ -267,38 +191,23 @@ class KrigHandle(_NativeState):
         """Every sample predicted from its k nearest samples outside its own fold (gss.h, gss_krig_cv_knn).  `fold`: n
         ids >= 0 (numpy: host arrays out; CUDA int32 tensor, or `device=True` without folds: everything stays in HBM)
         or None for leave-one-out; `exclude_radius`: leave-ball-out.  -> (pred, variance, status[, idx, count])."""
-        device = bool(device) or (is_torch(fold) and fold.is_cuda)
-        if device and fold is not None and not (is_torch(fold) and fold.is_cuda):
-            raise ValueError("device=True needs the fold ids as a CUDA tensor")
-        if fold is not None:
-            if device:
-                import torch
-                fold = fold.to(torch.int32).contiguous()
-            else:
-                fold = np.ascontiguousarray(fold, dtype=np.int32)
-            if fold.shape != (self.n,):
-                raise ValueError(f"fold must hold one id per sample ({self.n}), got shape {tuple(fold.shape)}")
-        out = self._cv_out(device, int(k) if return_idx else None)
-        pred, var, status = out[:3]
-        idx, cnt = (out[3], out[4]) if return_idx else (None, None)
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        met, mpar = _lib.metric_spec(distance)
-        met, ir = _ball_metric(met, ir, radii, rotation)
+        fold, device = st.fold_arg(fold, self.n, device)
+        out = st.estimate_out(device, (self.n,), (self.n,), ((self.n, int(k)), (self.n,)) if return_idx else None)
+        pred, var, status, idx, cnt = out
+        r, ir, met, mpar = st.search_args(radius, radii, distance, rotation)
         check(self._l.gss_krig_cv_knn(self._h, ptr(fold), -1.0 if exclude_radius is None else float(exclude_radius),
                                       int(k), int(minneighbors), r, ptr(ir), met, mpar, ptr(pred), ptr(var), ptr(status),
-                                      ptr(idx), ptr(cnt), MEM_DEVICE if device else MEM_HOST, current_stream()))
-        return tuple(out)
+                                      ptr(idx), ptr(cnt), st.mem_flag(device), current_stream()))
+        return st.estimate_result(out, return_idx)
 
     def predict_global_batch(self, xdom, zbatch):
-        xdom = _prep_in(xdom)
-        zb = _prep_in(zbatch)
-        if _space(zb) != _space(xdom):
-            raise ValueError("xdom and zbatch must live in the same memory space")
+        xdom = st.prep(xdom)
+        zb = st.prep(zbatch)
+        st.same_space("xdom and zbatch", xdom, zb)
         nb = zb.shape[0]
         m = xdom.shape[0]
-        out = _empty_like_space(xdom, (nb, m), np.float64)
-        check(self._l.gss_krig_predict_global_batch(self._h, ptr(xdom), m, ptr(zb), nb, ptr(out), _space(xdom),
+        out = st.empty(xdom, (nb, m))
+        check(self._l.gss_krig_predict_global_batch(self._h, ptr(xdom), m, ptr(zb), nb, ptr(out), st.mem_flag(xdom),
                                                     current_stream()))
         return out
 
@@ -314,9 +223,7 @@ class CoKrigHandle(KrigHandle):
         """`factor=False`: gss_cokrig_create_local -- no system, no factor; the handle serves `predict_knn` and `cv_knn` only
         (at most four variables)."""
         self._l = _lib.lib()
-        x = np.ascontiguousarray(xdata, dtype=np.float64)
-        if x.ndim == 1:
-            x = x[:, None]
+        x = st.samples(xdata)
         self.n, self.dim = x.shape
         zz = np.ascontiguousarray(z, dtype=np.float64)
         vv = np.ascontiguousarray(var, dtype=np.int32)
@@ -348,12 +255,10 @@ class CoKrigHandle(KrigHandle):
 
     def predict_global(self, xdom):
         """-> (mean[nz, m], variance[nz, m], status[nz, m]); numpy in, numpy out; CUDA tensors stay in HBM."""
-        xdom = _prep_in(xdom)
+        xdom = st.prep(xdom)
         m = xdom.shape[0]
-        mean = _empty_like_space(xdom, (self.nz, m), np.float64)
-        var = _empty_like_space(xdom, (self.nz, m), np.float64)
-        status = _empty_like_space(xdom, (self.nz, m), np.uint8)
-        check(self._l.gss_cokrig_predict_global(self._h, ptr(xdom), m, ptr(mean), ptr(var), ptr(status), _space(xdom),
+        mean, var, status = st.estimate_out(xdom, (self.nz, m), (self.nz, m))[:3]
+        check(self._l.gss_cokrig_predict_global(self._h, ptr(xdom), m, ptr(mean), ptr(var), ptr(status), st.mem_flag(xdom),
                                                 current_stream()))
         return mean, var, status
 
@@ -362,18 +267,17 @@ class CoKrigHandle(KrigHandle):
         gss_cokrig_predict_global_batch).  `zbatch`: (nbatch, n) in the row order the handle was created with (one
         vector: (n,)); numpy in, numpy out; CUDA tensors stay in HBM.  -> mean[nbatch, nz, m].  (The inherited
         `predict_global_batch` is the single-variable call, which the library refuses for a cokriging system.)"""
-        xdom = _prep_in(xdom)
-        zb = _prep_in(zbatch)
+        xdom = st.prep(xdom)
+        zb = st.prep(zbatch)
         if zb.ndim == 1:
             zb = zb[None, :]
-        if _space(zb) != _space(xdom):
-            raise ValueError("xdom and zbatch must live in the same memory space")
+        st.same_space("xdom and zbatch", xdom, zb)
         if zb.ndim != 2 or zb.shape[1] != self.n:
             raise ValueError(f"zbatch must hold one value per stacked sample ({self.n}) in every row, got shape "
                              f"{tuple(zb.shape)}")
         nb, m = zb.shape[0], xdom.shape[0]
-        out = _empty_like_space(xdom, (nb, self.nz, m), np.float64)
-        check(self._l.gss_cokrig_predict_global_batch(self._h, ptr(xdom), m, ptr(zb), nb, ptr(out), _space(xdom),
+        out = st.empty(xdom, (nb, self.nz, m))
+        check(self._l.gss_cokrig_predict_global_batch(self._h, ptr(xdom), m, ptr(zb), nb, ptr(out), st.mem_flag(xdom),
                                                       current_stream()))
         return out
 
@@ -381,24 +285,18 @@ class CoKrigHandle(KrigHandle):
         """Moving neighbourhood (gss.h, gss_cokrig_predict_knn): the `k[a]` nearest samples of every variable a, each
         variable searched on its own.  `k`: one count per variable, or an int for all of them.
         -> (mean[nz, m], variance[nz, m], status[nz, m][, idx[m, sum k], count[m, nz]])."""
-        xdom = _prep_in(xdom)
+        xdom = st.prep(xdom)
         m = xdom.shape[0]
         kk = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.int32), (self.nz,)))
         ksum = int(kk.sum())
-        mean = _empty_like_space(xdom, (self.nz, m), np.float64)
-        var = _empty_like_space(xdom, (self.nz, m), np.float64)
-        status = _empty_like_space(xdom, (self.nz, m), np.uint8)
-        idx = _empty_like_space(xdom, (m, max(ksum, 0)), np.int32) if return_idx else None
-        cnt = _empty_like_space(xdom, (m, self.nz), np.int32) if return_idx else None
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        met, ir = _ball_metric(0, ir, radii, rotation)
-        check(self._l.gss_cokrig_predict_knn(self._h, ptr(xdom), m, ptr(kk), int(minneighbors), r, ptr(ir), met, 0.0,
-                                             ptr(mean), ptr(var), ptr(status), ptr(idx), ptr(cnt), _space(xdom),
+        out = st.estimate_out(xdom, (self.nz, m), (self.nz, m),
+                              ((m, max(ksum, 0)), (m, self.nz)) if return_idx else None)
+        mean, var, status, idx, cnt = out
+        r, ir, met, mpar = st.search_args(radius, radii, rotation=rotation)     # cokriging searches Euclidean only
+        check(self._l.gss_cokrig_predict_knn(self._h, ptr(xdom), m, ptr(kk), int(minneighbors), r, ptr(ir), met, mpar,
+                                             ptr(mean), ptr(var), ptr(status), ptr(idx), ptr(cnt), st.mem_flag(xdom),
                                              current_stream()))
-        if return_idx:
-            return mean, var, status, idx, cnt
-        return mean, var, status
+        return st.estimate_result(out, return_idx)
 
     def cv_knn(self, k, fold=None, exclude_radius=None, minneighbors=1, radius=None, radii=None, return_idx=False,
                rotation=None, device=False):
@@ -412,39 +310,19 @@ class CoKrigHandle(KrigHandle):
         if np.ndim(k) == 0:
             return KrigHandle.cv_knn(self, k, fold, exclude_radius, minneighbors, radius, radii, return_idx,
                                      rotation=rotation, device=device)
-        device = bool(device) or (is_torch(fold) and fold.is_cuda)
-        if device and fold is not None and not (is_torch(fold) and fold.is_cuda):
-            raise ValueError("device=True needs the fold ids as a CUDA tensor")
-        if fold is not None:
-            if device:
-                import torch
-                fold = fold.to(torch.int32).contiguous()
-            else:
-                fold = np.ascontiguousarray(fold, dtype=np.int32)
-            if fold.shape != (self.n,):
-                raise ValueError(f"fold must hold one id per sample ({self.n}), got shape {tuple(fold.shape)}")
+        fold, device = st.fold_arg(fold, self.n, device)
         kk = np.ascontiguousarray(k, dtype=np.int32)
         if kk.shape != (self.nz,):
             raise ValueError(f"k must hold one count per variable ({self.nz}), got shape {kk.shape}")
         ksum = int(kk.sum())
-        out = self._cv_out(device)
-        if return_idx:
-            if device:
-                import torch
-                out += [torch.empty((self.n, max(ksum, 0)), dtype=torch.int32, device=out[0].device),
-                        torch.empty((self.n, self.nz), dtype=torch.int32, device=out[0].device)]
-            else:
-                out += [np.empty((self.n, max(ksum, 0)), dtype=np.int32), np.empty((self.n, self.nz), dtype=np.int32)]
-        pred, var, status = out[:3]
-        idx, cnt = (out[3], out[4]) if return_idx else (None, None)
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        met, ir = _ball_metric(0, ir, radii, rotation)
+        out = st.estimate_out(device, (self.n,), (self.n,),
+                              ((self.n, max(ksum, 0)), (self.n, self.nz)) if return_idx else None)
+        pred, var, status, idx, cnt = out
+        r, ir, met, mpar = st.search_args(radius, radii, rotation=rotation)     # cokriging searches Euclidean only
         check(self._l.gss_cokrig_cv_knn(self._h, ptr(fold), -1.0 if exclude_radius is None else float(exclude_radius),
-                                        ptr(kk), int(minneighbors), r, ptr(ir), met, 0.0, ptr(pred), ptr(var),
-                                        ptr(status), ptr(idx), ptr(cnt), MEM_DEVICE if device else MEM_HOST,
-                                        current_stream()))
-        return tuple(out)
+                                        ptr(kk), int(minneighbors), r, ptr(ir), met, mpar, ptr(pred), ptr(var),
+                                        ptr(status), ptr(idx), ptr(cnt), st.mem_flag(device), current_stream()))
+        return st.estimate_result(out, return_idx)
 
 
 class FFTGSHandle(_NativeState):
@@ -517,35 +395,36 @@ class FFTGSHandle(_NativeState):
         check(self._l.gss_fftgs_spectrum(self._h, ptr(out), MEM_HOST, current_stream()))
         return out
 
+    @staticmethod
+    def _inds(inds, out):
+        """Cell indices of a partial realisation, in the memory space of `out`."""
+        if inds is None:
+            return None
+        if st.on_device(out):
+            import torch
+            return torch.as_tensor(np.asarray(inds, dtype=np.int64), device=out.device)
+        return np.ascontiguousarray(inds, dtype=np.int64)
+
     def realize(self, seed, first_real, nreals, noise=None, inds=None, out=None, device=False, pinned=False):
         """nreals x npts realisations; `device=True` (or a CUDA `out`/`noise`) keeps them in HBM.  Host results leave
         the device chunk by chunk while the next realisations are computed (at most three chunks of ~256 MiB staged in
         HBM, csrc OutStream); `pinned=True` returns a numpy view of page-locked memory, which the DMA engine writes
         directly (a pageable array goes through the library's pinned bounce buffers); `out` may be a numpy array or a
         CPU / pinned / CUDA tensor of shape (nreals, npts)."""
-        noise = _prep_in(noise)
+        noise = st.prep(noise)
         npts = self.N if inds is None else len(inds)
         if out is None:
-            if device or (is_torch(noise) and noise.is_cuda):
-                import torch
-                out = torch.empty((nreals, npts), dtype=torch.float64, device="cuda")
-            elif pinned:
+            dev = bool(device) or st.on_device(noise)
+            if pinned and not dev:
                 import torch
                 out = torch.empty((nreals, npts), dtype=torch.float64, pin_memory=True)
             else:
-                out = np.empty((nreals, npts))
-        mem = _space(out)
-        if noise is not None and _space(noise) != mem:
-            raise ValueError("noise and out must live in the same memory space")
-        ii = None
-        if inds is not None:
-            if mem == MEM_DEVICE:
-                import torch
-                ii = torch.as_tensor(np.asarray(inds, dtype=np.int64), device=out.device)
-            else:
-                ii = np.ascontiguousarray(inds, dtype=np.int64)
+                out = st.empty(dev, (nreals, npts))
+        if noise is not None:
+            st.same_space("noise and out", out, noise)
+        ii = self._inds(inds, out)
         check(self._l.gss_fftgs_realize(self._h, int(seed), int(first_real), int(nreals), ptr(noise), ptr(ii),
-                                        0 if inds is None else npts, ptr(out), mem, current_stream()))
+                                        0 if inds is None else npts, ptr(out), st.mem_flag(out), current_stream()))
         return out.numpy() if pinned and is_torch(out) and not out.is_cuda else out
 
     def realize_lmc(self, seed, first_real, nreals, noise=None, nugget_noise=None, inds=None, out=None, device=False):
@@ -553,30 +432,18 @@ class FFTGSHandle(_NativeState):
         (nreals, nz, N) uniforms for the unit fields, `nugget_noise`: (nreals, nz, N) normals for the nugget, each
         optional (parity checks); `device=True` (or a CUDA `out` / noise array) keeps everything in HBM, where the
         fields are mixed in place in `out`."""
-        noise, nugget_noise = _prep_in(noise), _prep_in(nugget_noise)
+        noise, nugget_noise = st.prep(noise), st.prep(nugget_noise)
         npts = self.N if inds is None else len(inds)
         given = [a for a in (noise, nugget_noise) if a is not None]
         if out is None:
-            if device or any(is_torch(a) and a.is_cuda for a in given):
-                import torch
-                out = torch.empty((nreals, self.nz, npts), dtype=torch.float64, device="cuda")
-            else:
-                out = np.empty((nreals, self.nz, npts))
-        mem = _space(out)
-        if any(_space(a) != mem for a in given):
-            raise ValueError("noise, nugget_noise and out must live in the same memory space")
+            out = st.empty(bool(device) or any(st.on_device(a) for a in given), (nreals, self.nz, npts))
+        st.same_space("noise, nugget_noise and out", out, *given)
         if any(tuple(a.shape) != (nreals, self.nz, self.N) for a in given):
             raise ValueError(f"noise and nugget_noise have the shape (nreals, nz, N) = {(nreals, self.nz, self.N)}")
-        ii = None
-        if inds is not None:
-            if mem == MEM_DEVICE:
-                import torch
-                ii = torch.as_tensor(np.asarray(inds, dtype=np.int64), device=out.device)
-            else:
-                ii = np.ascontiguousarray(inds, dtype=np.int64)
+        ii = self._inds(inds, out)
         check(self._l.gss_fftgs_realize_lmc(self._h, int(seed), int(first_real), int(nreals), ptr(noise),
-                                            ptr(nugget_noise), ptr(ii), 0 if inds is None else npts, ptr(out), mem,
-                                            current_stream()))
+                                            ptr(nugget_noise), ptr(ii), 0 if inds is None else npts, ptr(out),
+                                            st.mem_flag(out), current_stream()))
         return out
 
 
@@ -591,9 +458,7 @@ class LUGSHandle(_NativeState):
         if factorization not in ("cholesky", "lu"):
             raise ValueError(f"factorization={factorization!r}: 'cholesky' or 'lu'")
         self._l = _lib.lib()
-        c = np.ascontiguousarray(centroids, dtype=np.float64)
-        if c.ndim == 1:
-            c = c[:, None]
+        c = st.samples(centroids)
         self.N, dim = c.shape
         dl = np.ascontiguousarray(dlocs, dtype=np.int64)
         zz = np.ascontiguousarray(z1, dtype=np.float64)
@@ -629,17 +494,12 @@ class LUGSHandle(_NativeState):
         return l22.T.copy(), d2          # column-major on the wire -> numpy (row, col)
 
     def realize(self, seed, first_real, nreals, noise=None, rho=None, w1=None, device=False):
-        noise = _prep_in(noise)
-        w1 = _prep_in(w1)
-        if device or is_torch(noise) or is_torch(w1):
-            import torch
-            out = torch.empty((nreals, self.N), dtype=torch.float64, device="cuda")
-            wout = torch.empty((nreals, self.ns), dtype=torch.float64, device="cuda")
-        else:
-            out = np.empty((nreals, self.N))
-            wout = np.empty((nreals, self.ns))
+        noise = st.prep(noise)
+        w1 = st.prep(w1)
+        dev = bool(device) or is_torch(noise) or is_torch(w1)
+        out, wout = st.empty(dev, (nreals, self.N)), st.empty(dev, (nreals, self.ns))
         check(self._l.gss_lugs_realize(self._h, int(seed), int(first_real), int(nreals), ptr(noise),
-                                       0.0 if rho is None else float(rho), ptr(w1), ptr(out), ptr(wout), _space(out),
+                                       0.0 if rho is None else float(rho), ptr(w1), ptr(out), ptr(wout), st.mem_flag(out),
                                        current_stream()))
         return out, wout
 
@@ -656,9 +516,7 @@ class SGSHandle:
         ones) instead of the k nearest among the simulated cells.  `distance`: the search metric (euclidean,
         cityblock, chebyshev)."""
         self._l = _lib.lib()
-        c = np.ascontiguousarray(centroids, dtype=np.float64)
-        if c.ndim == 1:
-            c = c[:, None]
+        c = st.samples(centroids)
         self.N, dim = c.shape
         self.k = int(maxneighbors)
         pa = None if path is None else np.ascontiguousarray(path, dtype=np.int64)
@@ -669,9 +527,7 @@ class SGSHandle:
                 raise ValueError(f"paths must have {self.N} cells each")
         dl = np.ascontiguousarray(dlocs if dlocs is not None else [], dtype=np.int64)
         zd = np.ascontiguousarray(zdata if zdata is not None else [], dtype=np.float64)
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        met, ir = _ball_metric(_lib.metric_spec(distance)[0], ir, radii, rotation)
+        r, ir, met, _ = st.search_args(radius, radii, distance, rotation)   # the flags word carries the metric id only
         v = _vg_struct(vg, dim)
         h = C.c_void_p()
         check(self._l.gss_sgs_create_paths(C.byref(h), C.byref(v), float(mean), ptr(c), self.N, dim, ptr(pa), npaths,
@@ -704,17 +560,14 @@ class SGSHandle:
                     big=bool(o[5]), big_lds=bool(o[6]))
 
     def realize(self, seed, first_real, nreals, noise=None, device=False, out=None):
-        noise = _prep_in(noise)
+        noise = st.prep(noise)
         if out is not None:
             if tuple(out.shape) != (nreals, self.N):
                 raise ValueError(f"out must have shape ({nreals}, {self.N})")
-        elif device or is_torch(noise):
-            import torch
-            out = torch.empty((nreals, self.N), dtype=torch.float64, device="cuda")
         else:
-            out = np.empty((nreals, self.N))
+            out = st.empty(bool(device) or is_torch(noise), (nreals, self.N))
         check(self._l.gss_sgs_realize(self._h, int(seed), int(first_real), int(nreals), ptr(noise), ptr(out),
-                                      _space(out), current_stream()))
+                                      st.mem_flag(out), current_stream()))
         return out
 
 
@@ -812,12 +665,12 @@ class NScoreHandle:
     def _apply(self, direction, x, out):
         x, (nb, ln, si) = self._as_runs(x)
         if out is None:
-            out = _empty_like_space(x if is_torch(x) else None, tuple(x.shape), np.float64)
+            out = st.empty(x, tuple(x.shape))
             so = ln
         else:
             if is_torch(out) and not out.is_cuda:
                 out = out.numpy()
-            if tuple(out.shape) != tuple(x.shape) or _space(out) != _space(x):
+            if tuple(out.shape) != tuple(x.shape) or st.mem_flag(out) != st.mem_flag(x):
                 raise ValueError("out must have the shape of the input and live where it lives")
             if nb * ln == 0:
                 return out
@@ -837,7 +690,7 @@ class NScoreHandle:
                 return out
             so = r[2]
         if nb * ln:
-            check(self._l.gss_nscore_apply(self._h, direction, ptr(x), ptr(out), nb, ln, si, so, _space(x),
+            check(self._l.gss_nscore_apply(self._h, direction, ptr(x), ptr(out), nb, ln, si, so, st.mem_flag(x),
                                            current_stream()))
         return out
 
@@ -881,19 +734,9 @@ class HipEngine:
         simple kriging about them.  Host arrays in -> host arrays out; with a CUDA `xdom` everything stays in HBM.
         -> ccdf[m, K] (corrected), status[m][, raw[m, K]][, idx[m, k], count[m]]."""
         l = _lib.lib()
-        dev = is_torch(xdom) and xdom.is_cuda
-        if dev:
-            import torch
-            x = xdata if is_torch(xdata) else torch.as_tensor(np.asarray(xdata, dtype=np.float64), device="cuda")
-            x = _prep_in(x.reshape(x.shape[0], -1))
-            zz = _prep_in(z if is_torch(z) else torch.as_tensor(np.asarray(z, dtype=np.float64), device="cuda"))
-            c = _prep_in(xdom.reshape(-1, x.shape[1]))
-        else:
-            x = np.ascontiguousarray(xdata, dtype=np.float64)
-            if x.ndim == 1:
-                x = x[:, None]
-            zz = np.ascontiguousarray(z, dtype=np.float64)
-            c = np.ascontiguousarray(xdom, dtype=np.float64).reshape(-1, x.shape[1])
+        dev = st.on_device(xdom)
+        x, zz = st.samples(xdata, dev), st.values(z, dev)
+        c = st.centres(xdom, x.shape[1], dev)
         n, d = int(x.shape[0]), int(x.shape[1])
         m = int(c.shape[0])
         if zz.ndim != 1 or zz.shape[0] != n:
@@ -905,20 +748,16 @@ class HipEngine:
         fs = None if fstar is None else np.ascontiguousarray(fstar, dtype=np.float64).reshape(-1)
         if fs is not None and fs.size != K:
             raise ValueError(f"fstar has {fs.size} values for {K} cutoffs")
-        ccdf = _empty_like_space(c, (m, K), np.float64)
-        raw = _empty_like_space(c, (m, K), np.float64) if return_raw else None
-        st = _empty_like_space(c, (m,), np.uint8)
-        idx = _empty_like_space(c, (m, int(k)), np.int32) if return_idx else None
-        cnt = _empty_like_space(c, (m,), np.int32) if return_idx else None
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        met, mpar = _lib.metric_spec(distance)
-        met, ir = _ball_metric(met, ir, radii, rotation)
+        ccdf = st.empty(c, (m, K))
+        raw = st.empty(c, (m, K)) if return_raw else None
+        status = st.empty(c, (m,), np.uint8)
+        idx = st.empty(c, (m, int(k)), np.int32) if return_idx else None
+        cnt = st.empty(c, (m,), np.int32) if return_idx else None
+        r, ir, met, mpar = st.search_args(radius, radii, distance, rotation)
         check(l.gss_ik_predict_knn(ptr(x), ptr(zz), n, d, ptr(cut), K, vgs, len(models), SK if fs is not None else OK,
                                    ptr(fs), int(k), int(minneighbors), r, ptr(ir), met, mpar, ptr(c), m, ptr(ccdf),
-                                   ptr(raw), ptr(st), ptr(idx), ptr(cnt), MEM_DEVICE if dev else MEM_HOST,
-                                   current_stream()))
-        out = (ccdf, st)
+                                   ptr(raw), ptr(status), ptr(idx), ptr(cnt), st.mem_flag(dev), current_stream()))
+        out = (ccdf, status)
         if return_raw:
             out += (raw,)
         if return_idx:
@@ -930,13 +769,12 @@ class HipEngine:
         """GSLIB's order-relation correction of m x K rows, IN PLACE (gss.h, gss_ik_order_relations; numpy array or CUDA
         tensor, contiguous float64) -> (ccdf, ncorrected, maxcorr)."""
         l = _lib.lib()
-        dev = is_torch(ccdf) and ccdf.is_cuda
         ok = ccdf.is_contiguous() if is_torch(ccdf) else (ccdf.flags.c_contiguous and ccdf.dtype == np.float64)
         if len(ccdf.shape) != 2 or not ok:
             raise ValueError("ccdf must be a contiguous float64 array of shape (m, K)")
         nc, mx = C.c_int64(0), C.c_double(0.0)
         check(l.gss_ik_order_relations(ptr(ccdf), int(ccdf.shape[0]), int(ccdf.shape[1]), C.byref(nc), C.byref(mx),
-                                       MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                                       st.mem_flag(ccdf), current_stream()))
         return ccdf, int(nc.value), float(mx.value)
 
     @staticmethod
@@ -945,8 +783,7 @@ class HipEngine:
         `moments`), `pabove`[m, nthr] (when thresholds are given) and `quant`[m, nq] (when probs are given), in the
         memory space of `ccdf`."""
         l = _lib.lib()
-        dev = is_torch(ccdf) and ccdf.is_cuda
-        f = _prep_in(ccdf) if dev else np.ascontiguousarray(ccdf, dtype=np.float64)
+        f = st.values(ccdf, st.on_device(ccdf))
         if len(f.shape) != 2:
             raise ValueError("ccdf must have shape (m, K)")
         m, K = int(f.shape[0]), int(f.shape[1])
@@ -957,25 +794,23 @@ class HipEngine:
         pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
         out = {}
         if moments:
-            out["etype"] = _empty_like_space(f, (m,), np.float64)
-            out["cvar"] = _empty_like_space(f, (m,), np.float64)
+            out["etype"] = st.empty(f, (m,))
+            out["cvar"] = st.empty(f, (m,))
         if thr.size:
-            out["pabove"] = _empty_like_space(f, (m, thr.size), np.float64)
+            out["pabove"] = st.empty(f, (m, thr.size))
         if pr.size:
-            out["quant"] = _empty_like_space(f, (m, pr.size), np.float64)
+            out["quant"] = st.empty(f, (m, pr.size))
         check(l.gss_ik_post(ptr(f), m, K, ptr(cut), float(zmin), float(zmax), float(tail_power[0]), float(tail_power[1]),
                             ptr(thr) if thr.size else None, int(thr.size), ptr(pr) if pr.size else None, int(pr.size),
                             ptr(out.get("etype")), ptr(out.get("cvar")), ptr(out.get("pabove")), ptr(out.get("quant")),
-                            MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                            st.mem_flag(f), current_stream()))
         return out
 
     @staticmethod
     def cov_pairwise(vg, a, b=None):
         l = _lib.lib()
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if a.ndim == 1:
-            a = a[:, None]
-        bb = a if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1, a.shape[1])
+        a = st.samples(a)
+        bb = a if b is None else st.centres(b, a.shape[1])
         out = np.empty((a.shape[0], bb.shape[0]))
         v = _vg_struct(vg, a.shape[1])
         check(l.gss_cov_pairwise(C.byref(v), ptr(a), a.shape[0], None if b is None else ptr(bb), bb.shape[0],
@@ -986,30 +821,15 @@ class HipEngine:
     def knn_search(xdata, centers, k, radius=None, radii=None, distance=None, rotation=None):
         """Host arrays in -> host arrays out; CUDA tensors for both point sets keep the search in HBM."""
         l = _lib.lib()
-        met, mpar = _lib.metric_spec(distance)
-        dev = is_torch(xdata) and xdata.is_cuda
-        if dev != (is_torch(centers) and centers.is_cuda):
-            raise ValueError("xdata and centers must live in the same memory space")
-        if dev:
-            import torch
-            x = _prep_in(xdata.reshape(xdata.shape[0], -1))
-            c = _prep_in(centers.reshape(-1, x.shape[1]))
-            m = c.shape[0]
-            idx = torch.empty((m, k), dtype=torch.int32, device=x.device)
-            cnt = torch.empty(m, dtype=torch.int32, device=x.device)
-        else:
-            x = np.ascontiguousarray(xdata, dtype=np.float64)
-            if x.ndim == 1:
-                x = x[:, None]
-            c = np.ascontiguousarray(centers, dtype=np.float64).reshape(-1, x.shape[1])
-            m = c.shape[0]
-            idx = np.empty((m, k), dtype=np.int32)
-            cnt = np.empty(m, dtype=np.int32)
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        met, ir = _ball_metric(met, ir, radii, rotation)
+        # (the search is parsed, and a bad one refused, before the arrays are looked at)
+        r, ir, met, mpar = st.search_args(radius, radii, distance, rotation)
+        dev = st.same_space("xdata and centers", xdata, centers)
+        x = st.samples(xdata, dev)
+        c = st.centres(centers, x.shape[1], dev)
+        m = c.shape[0]
+        idx, cnt = st.empty(x, (m, k), np.int32), st.empty(x, m, np.int32)
         check(l.gss_knn_search(ptr(x), x.shape[0], x.shape[1], ptr(c), m, int(k), r, ptr(ir), met, mpar, ptr(idx),
-                               ptr(cnt), MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                               ptr(cnt), st.mem_flag(dev), current_stream()))
         return idx, cnt
 
     @staticmethod
@@ -1018,42 +838,23 @@ class HipEngine:
         one value column; (nz, n) is nz columns that share the search and the weights (gss_*_predict_cols: the mean
         comes back as (nz, m), distance / variance / status per point)."""
         l = _lib.lib()
-        dev = is_torch(xdom) and xdom.is_cuda
-        if dev:
-            import torch
-            x = xdata if is_torch(xdata) else torch.as_tensor(np.asarray(xdata, dtype=np.float64), device="cuda")
-            x = _prep_in(x.reshape(x.shape[0], -1))
-            zz = _prep_in(z if is_torch(z) else torch.as_tensor(np.asarray(z, dtype=np.float64), device="cuda"))
-            c = _prep_in(xdom.reshape(-1, x.shape[1]))
-            m = c.shape[0]
-            mshape = (m,) if zz.ndim == 1 else (zz.shape[0], m)
-            mean = torch.empty(mshape, dtype=torch.float64, device="cuda")
-            aux = torch.empty(m, dtype=torch.float64, device="cuda")
-            st = torch.empty(m, dtype=torch.uint8, device="cuda")
-        else:
-            x = np.ascontiguousarray(xdata, dtype=np.float64)
-            if x.ndim == 1:
-                x = x[:, None]
-            zz = np.ascontiguousarray(z, dtype=np.float64)
-            c = np.ascontiguousarray(xdom, dtype=np.float64).reshape(-1, x.shape[1])
-            m = c.shape[0]
-            mean = np.empty((m,) if zz.ndim == 1 else (zz.shape[0], m))
-            aux, st = np.empty(m), np.empty(m, dtype=np.uint8)
+        dev = st.on_device(xdom)
+        x, zz = st.samples(xdata, dev), st.values(z, dev)
+        c = st.centres(xdom, x.shape[1], dev)
+        m = c.shape[0]
+        mean, aux, status = st.estimate_out(dev, (m,) if zz.ndim == 1 else (zz.shape[0], m), m)[:3]
         if zz.ndim not in (1, 2) or zz.shape[-1] != x.shape[0]:
             raise ValueError("z must have shape (n,) or (nz, n)")
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        met, mpar = _lib.metric_spec(distance)
-        met, ir = _ball_metric(met, ir, radii, rotation)
+        r, ir, met, mpar = st.search_args(radius, radii, distance, rotation)
         if zz.ndim == 1:
             check(getattr(l, fn_name)(ptr(x), ptr(zz), x.shape[0], x.shape[1], ptr(c), m, int(k), int(minneighbors), r,
-                                      ptr(ir), met, mpar, *extra, ptr(mean), ptr(aux), ptr(st),
-                                      MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                                      ptr(ir), met, mpar, *extra, ptr(mean), ptr(aux), ptr(status),
+                                      st.mem_flag(dev), current_stream()))
         else:
             check(getattr(l, fn_name + "_cols")(ptr(x), ptr(zz), x.shape[0], x.shape[1], int(zz.shape[0]), ptr(c), m, int(k),
                                                 int(minneighbors), r, ptr(ir), met, mpar, *extra, ptr(mean), ptr(aux),
-                                                ptr(st), MEM_DEVICE if dev else MEM_HOST, current_stream()))
-        return mean, aux, st
+                                                ptr(status), st.mem_flag(dev), current_stream()))
+        return mean, aux, status
 
     @staticmethod
     def idw(xdata, z, xdom, k, minneighbors=1, exponent=1.0, radius=None, radii=None, distance=None, rotation=None):
@@ -1078,45 +879,21 @@ class HipEngine:
         vector per sample (`pred` comes back in the shape of `z`).  `k == n`: every eligible sample, no search (no
         lists: `return_idx` is refused).  -> (pred, aux, status[, idx, count])."""
         l = _lib.lib()
-        device = bool(device) or (is_torch(fold) and fold.is_cuda)
-        if device:
-            import torch
-            if fold is not None and not (is_torch(fold) and fold.is_cuda):
-                raise ValueError("device=True needs the fold ids as a CUDA tensor")
-            x = xdata if is_torch(xdata) else torch.as_tensor(np.asarray(xdata, dtype=np.float64), device="cuda")
-            x = _prep_in(x.reshape(x.shape[0], -1))
-            zz = _prep_in(z if is_torch(z) else torch.as_tensor(np.asarray(z, dtype=np.float64), device="cuda"))
-            if fold is not None:
-                fold = fold.to(torch.int32).contiguous()
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=x.device)   # noqa: E731
-            f64, u8, i32 = torch.float64, torch.uint8, torch.int32
-        else:
-            x = np.ascontiguousarray(xdata, dtype=np.float64)
-            if x.ndim == 1:
-                x = x[:, None]
-            zz = np.ascontiguousarray(z, dtype=np.float64)
-            if fold is not None:
-                fold = np.ascontiguousarray(fold, dtype=np.int32)
-            mk = lambda shape, dt: np.empty(shape, dtype=dt)   # noqa: E731
-            f64, u8, i32 = np.float64, np.uint8, np.int32
-        n = x.shape[0]
+        n = len(xdata)
+        fold, device = st.fold_arg(fold, n, device)
+        x, zz = st.samples(xdata, device), st.values(z, device)
         if zz.ndim not in (1, 2) or zz.shape[-1] != n:
             raise ValueError("z must have shape (n,) or (nz, n)")
-        if fold is not None and tuple(fold.shape) != (n,):
-            raise ValueError(f"fold must hold one id per sample ({n}), got shape {tuple(fold.shape)}")
         if return_idx and int(k) >= n:
             raise ValueError("maxneighbors = n takes every eligible sample and runs no search: there are no lists")
-        pred, aux, st = mk(tuple(zz.shape), f64), mk((n,), f64), mk((n,), u8)
-        idx, cnt = (mk((n, int(k)), i32), mk((n,), i32)) if return_idx else (None, None)
-        ir = None if radii is None else np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64))
-        r = -1.0 if radius is None and radii is None else (1.0 if radii is not None else float(radius))
-        met, mpar = _lib.metric_spec(distance)
-        met, ir = _ball_metric(met, ir, radii, rotation)
+        out = st.estimate_out(x if device else False, tuple(zz.shape), (n,), ((n, int(k)), (n,)) if return_idx else None)
+        pred, aux, status, idx, cnt = out
+        r, ir, met, mpar = st.search_args(radius, radii, distance, rotation)
         check(getattr(l, fn_name)(ptr(x), ptr(zz), n, x.shape[1], 1 if zz.ndim == 1 else int(zz.shape[0]), ptr(fold),
                                   -1.0 if exclude_radius is None else float(exclude_radius), int(k), int(minneighbors),
-                                  r, ptr(ir), met, mpar, *extra, ptr(pred), ptr(aux), ptr(st), ptr(idx), ptr(cnt),
-                                  MEM_DEVICE if device else MEM_HOST, current_stream()))
-        return (pred, aux, st, idx, cnt) if return_idx else (pred, aux, st)
+                                  r, ptr(ir), met, mpar, *extra, ptr(pred), ptr(aux), ptr(status), ptr(idx), ptr(cnt),
+                                  st.mem_flag(device), current_stream()))
+        return st.estimate_result(out, return_idx)
 
     @staticmethod
     def idw_cv(xdata, z, k, fold=None, exclude_radius=None, minneighbors=1, exponent=1.0, radius=None, radii=None,
@@ -1140,33 +917,30 @@ class HipEngine:
         """LWR with an arbitrary `weightfun` callable (lwr.jl:58,136): the search runs on the device, delta = d / max d
         and w = weightfun(delta) are evaluated here on the host (the callable cannot cross the C-ABI), the normal
         equations and norm(r) on the device again (gss_lwr_predict_weights).  Host arrays."""
-        x = np.ascontiguousarray(xdata, dtype=np.float64)
-        if x.ndim == 1:
-            x = x[:, None]
-        zz = np.ascontiguousarray(z, dtype=np.float64)
-        c = np.ascontiguousarray(xdom, dtype=np.float64).reshape(-1, x.shape[1])
+        x, zz = st.samples(xdata), st.values(z)
+        c = st.centres(xdom, x.shape[1])
         m = c.shape[0]
         idx, cnt = HipEngine.knn_search(x, c, k, radius, radii, distance, rotation)
         valid = np.arange(k)[None, :] < cnt[:, None]
         nb = np.where(valid, idx, 0)
         diff = x[nb] - c[:, None, :]                              # m x k x d
-        name = "euclidean" if distance is None else (distance if isinstance(distance, str) else distance[0])
+        met, mpar = st.search_args(radius, radii, distance, rotation)[2:]    # as the search above parsed them
         if rotation is not None:                                 # frame of the ball: R^T (x - c) per neighbour
             diff = diff @ np.asarray(rotation, dtype=np.float64)
         if radii is not None:
             diff = diff / np.asarray(radii, dtype=np.float64)
-        if name == "euclidean":
+        if met in (_lib.METRICS["euclidean"], _lib.METRIC_ROTATED_BALL):
             d = np.sqrt(np.sum(diff * diff, axis=-1))
-        elif name == "cityblock":
+        elif met == _lib.METRICS["cityblock"]:
             d = np.sum(np.abs(diff), axis=-1)
-        elif name == "chebyshev":
+        elif met == _lib.METRICS["chebyshev"]:
             d = np.max(np.abs(diff), axis=-1)
         else:                                                    # ("haversine", r): (longitude, latitude) in degrees
             D = np.pi / 180.0
             s1 = np.sin((c[:, None, 1] - x[nb][..., 1]) * 0.5 * D)
             s2 = np.sin((c[:, None, 0] - x[nb][..., 0]) * 0.5 * D)
             key = s1 * s1 + np.cos(x[nb][..., 1] * D) * np.cos(c[:, None, 1] * D) * (s2 * s2)
-            d = 2.0 * float(distance[1]) * np.arcsin(np.minimum(np.sqrt(key), 1.0))
+            d = 2.0 * mpar * np.arcsin(np.minimum(np.sqrt(key), 1.0))
         d = np.where(valid, d, 0.0)
         with np.errstate(invalid="ignore", divide="ignore"):
             delta = d / d.max(axis=1, keepdims=True)             # lwr.jl:132
@@ -1183,63 +957,55 @@ class HipEngine:
         w = np.zeros_like(delta)
         w[valid] = wv
         w = np.ascontiguousarray(w)
-        mean, var, st = np.empty(m), np.empty(m), np.empty(m, dtype=np.uint8)
+        mean, var, status = st.estimate_out(False, m, m)[:3]
         check(_lib.lib().gss_lwr_predict_weights(ptr(x), ptr(zz), x.shape[0], x.shape[1], ptr(c), m, int(k),
                                                  int(minneighbors), ptr(np.ascontiguousarray(idx)),
-                                                 ptr(np.ascontiguousarray(cnt)), ptr(w), ptr(mean), ptr(var), ptr(st),
+                                                 ptr(np.ascontiguousarray(cnt)), ptr(w), ptr(mean), ptr(var), ptr(status),
                                                  MEM_HOST, current_stream()))
-        return mean, var, st
+        return mean, var, status
 
 
     # ---- variography (gss.h "variography") --------------------------------------------------------------------
+    @staticmethod
+    def _vario_xz(x, z):
+        """x (n, d) and z (nz, n) in their one memory space, and whether that is the device."""
+        dev = st.same_space("x and z", x, z)
+        x = st.samples(x, dev)
+        return x, st.values(z, dev).reshape(-1, x.shape[0]), dev
+
+    @staticmethod
+    def _vario_out(x, dev, shape, zshape):
+        """count, lagsum of `shape`, the sums of `zshape` and the duplicate counter beside `x`."""
+        ndup = st.empty(x, 1, np.int64) if dev else np.zeros(1, dtype=np.int64)
+        return st.empty(x, shape, np.int64), st.empty(x, shape), st.empty(x, zshape), ndup
+
     @staticmethod
     def variogram_empirical(x, z, nlags, maxlag, direction=None, dtol=float("inf"), cos_atol=0.0, estimator=0,
                             distance=None):
         """Bin sums of the empirical variogram: x (n, d), z (nz, n) -> count (nlags,) int64, lagsum (nlags,),
         zsum (nz, nlags), nduplicates.  numpy arrays in -> numpy out; CUDA tensors for x and z keep everything in HBM
         (the outputs are tensors, nduplicates a 1-element tensor).  `direction`: a unit vector (host) or None."""
-        if _lib.metric_spec(distance)[0] != 0:
+        if st.search_args(None, None, distance)[2] != 0:
             raise _lib.GSSError(_lib.ERR_UNSUPPORTED, "empirical variograms use the Euclidean distance only")
         l = _lib.lib()
-        dev = is_torch(x) and x.is_cuda
-        if dev != (is_torch(z) and z.is_cuda):
-            raise ValueError("x and z must live in the same memory space")
-        x = _prep_in(x)
-        z = _prep_in(z)
-        if x.ndim == 1:
-            x = x[:, None]
-        n, d = x.shape
-        z = z.reshape(-1, n)
-        nz = z.shape[0]
-        nlags = int(nlags)
-        if dev:
-            import torch
-            count = torch.empty(max(nlags, 0), dtype=torch.int64, device=x.device)
-            lagsum = torch.empty(max(nlags, 0), dtype=torch.float64, device=x.device)
-            zsum = torch.empty((nz, max(nlags, 0)), dtype=torch.float64, device=x.device)
-            ndup = torch.empty(1, dtype=torch.int64, device=x.device)
-        else:
-            count = np.empty(max(nlags, 0), dtype=np.int64)
-            lagsum = np.empty(max(nlags, 0))
-            zsum = np.empty((nz, max(nlags, 0)))
-            ndup = np.zeros(1, dtype=np.int64)
+        x, z, dev = HipEngine._vario_xz(x, z)
+        (n, d), nz, nlags = x.shape, z.shape[0], int(nlags)
+        count, lagsum, zsum, ndup = HipEngine._vario_out(x, dev, max(nlags, 0), (nz, max(nlags, 0)))
         u = None if direction is None else np.ascontiguousarray(direction, dtype=np.float64).reshape(-1)
         if u is not None and u.size != d:
             raise ValueError(f"direction has {u.size} components for {d}-D samples")
         check(l.gss_variogram_empirical(ptr(x), n, d, ptr(z), nz, nlags, float(maxlag), ptr(u), float(dtol),
                                         float(cos_atol), int(estimator), ptr(count), ptr(lagsum), ptr(zsum), ptr(ndup),
-                                        MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                                        st.mem_flag(dev), current_stream()))
         return count, lagsum, zsum, (ndup if dev else int(ndup[0]))
 
     # ---- declustering (gss.h "declustering") ------------------------------------------------------------------
     @staticmethod
     def _declus_x(x):
-        x = _prep_in(x)
-        if x.ndim == 1:
-            x = x[:, None]
-        if x.ndim != 2:
+        x = st.prep(x)
+        if x.ndim not in (1, 2):
             raise ValueError("x must be (n, d) point-major coordinates")
-        return x, (is_torch(x) and x.is_cuda)
+        return st.samples(x, st.on_device(x)), st.on_device(x)
 
     @staticmethod
     def decluster_cell_counts(x, origin, sides):
@@ -1252,10 +1018,10 @@ class HipEngine:
         s = np.ascontiguousarray(sides, dtype=np.float64).reshape(-1)
         if o.size != d or s.size != d:
             raise ValueError(f"origin and sides need {d} components each, not {o.size} and {s.size}")
-        count = _empty_like_space(x, (n,), np.int32) if dev else np.empty(n, dtype=np.int32)
+        count = st.empty(x, (n,), np.int32)
         nocc = C.c_int64()
         check(l.gss_decluster_cell_counts(ptr(x), n, d, ptr(o), ptr(s), ptr(count), C.byref(nocc),
-                                          MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                                          st.mem_flag(dev), current_stream()))
         return count, nocc.value
 
     @staticmethod
@@ -1266,9 +1032,8 @@ class HipEngine:
         x, dev = HipEngine._declus_x(x)
         n, d = x.shape
         if z is not None:
-            if dev != (is_torch(z) and z.is_cuda):
-                raise ValueError("x and z must live in the same memory space")
-            z = _prep_in(z).reshape(-1)
+            st.same_space("x and z", x, z)
+            z = st.prep(z).reshape(-1)
             if z.shape[0] != n:
                 raise ValueError(f"{z.shape[0]} values for {n} samples")
         s = np.ascontiguousarray(sides, dtype=np.float64)
@@ -1278,12 +1043,12 @@ class HipEngine:
             raise ValueError(f"sides must be (ncs, {d}), not {s.shape}")
         if criterion not in ("min", "max"):
             raise ValueError(f"criterion {criterion!r}: 'min' or 'max'")
-        w = _empty_like_space(x, (n,), np.float64) if dev else np.empty(n)
+        w = st.empty(x, (n,))
         wmean = None if z is None else np.empty(s.shape[0])
         best = C.c_int32()
         check(l.gss_decluster_cells(ptr(x), ptr(z), n, d, ptr(s), s.shape[0], int(noffsets),
                                     _lib.DECLUS_MIN if criterion == "min" else _lib.DECLUS_MAX, ptr(w), ptr(wmean),
-                                    C.byref(best), MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                                    C.byref(best), st.mem_flag(dev), current_stream()))
         return w, wmean, best.value
 
     @staticmethod
@@ -1298,10 +1063,10 @@ class HipEngine:
         dims = np.ascontiguousarray(dims, dtype=np.int64).reshape(-1)
         if not (lo.size == step.size == dims.size == d):
             raise ValueError(f"lo, step and dims need {d} components each")
-        w = _empty_like_space(x, (n,), np.float64) if dev else np.empty(n)
+        w = st.empty(x, (n,))
         nzero = C.c_int64()
         check(l.gss_decluster_nearest(ptr(x), n, d, ptr(lo), ptr(step), ptr(dims), ptr(w), C.byref(nzero),
-                                      MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                                      st.mem_flag(dev), current_stream()))
         return w, nzero.value
 
     @staticmethod
@@ -1328,17 +1093,8 @@ class HipEngine:
         boundaries (host), basis (3, 3) = e1, e2, normal for d = 3 (host) -> count (nangles, nlags) int64,
         lagsum (nangles, nlags), zsum (nz, nangles, nlags), nduplicates.  Memory as in variogram_empirical."""
         l = _lib.lib()
-        dev = is_torch(x) and x.is_cuda
-        if dev != (is_torch(z) and z.is_cuda):
-            raise ValueError("x and z must live in the same memory space")
-        x = _prep_in(x)
-        z = _prep_in(z)
-        if x.ndim == 1:
-            x = x[:, None]
-        n, d = x.shape
-        z = z.reshape(-1, n)
-        nz = z.shape[0]
-        nlags = int(nlags)
+        x, z, dev = HipEngine._vario_xz(x, z)
+        (n, d), nz, nlags = x.shape, z.shape[0], int(nlags)
         dirs = np.ascontiguousarray(dirs, dtype=np.float64)
         if dirs.ndim != 2 or dirs.shape[1] != 2:
             raise ValueError("dirs is an (nangles, 2) array of (cos, sin)")
@@ -1349,20 +1105,10 @@ class HipEngine:
             if b.shape != (3, 3):
                 raise ValueError("basis is a (3, 3) array: e1, e2 and the normal as rows")
         shape = (nang, max(nlags, 0))
-        if dev:
-            import torch
-            count = torch.empty(shape, dtype=torch.int64, device=x.device)
-            lagsum = torch.empty(shape, dtype=torch.float64, device=x.device)
-            zsum = torch.empty((nz,) + shape, dtype=torch.float64, device=x.device)
-            ndup = torch.empty(1, dtype=torch.int64, device=x.device)
-        else:
-            count = np.empty(shape, dtype=np.int64)
-            lagsum = np.empty(shape)
-            zsum = np.empty((nz,) + shape)
-            ndup = np.zeros(1, dtype=np.int64)
+        count, lagsum, zsum, ndup = HipEngine._vario_out(x, dev, shape, (nz,) + shape)
         check(l.gss_variogram_plane(ptr(x), n, d, ptr(z), nz, nlags, float(maxlag), nang, ptr(dirs), ptr(b), float(ptol),
                                     int(estimator), ptr(count), ptr(lagsum), ptr(zsum), ptr(ndup),
-                                    MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                                    st.mem_flag(dev), current_stream()))
         return count, lagsum, zsum, (ndup if dev else int(ndup[0]))
 
     @staticmethod
@@ -1394,35 +1140,15 @@ class HipEngine:
         nlags) -- row a nz - a (a - 1) / 2 + (b - a) holds the pair (a, b), a <= b -- and nduplicates.  Memory as in
         variogram_empirical."""
         l = _lib.lib()
-        dev = is_torch(x) and x.is_cuda
-        if dev != (is_torch(z) and z.is_cuda):
-            raise ValueError("x and z must live in the same memory space")
-        x = _prep_in(x)
-        z = _prep_in(z)
-        if x.ndim == 1:
-            x = x[:, None]
-        n, d = x.shape
-        z = z.reshape(-1, n)
-        nz = z.shape[0]
-        nlags = int(nlags)
+        x, z, dev = HipEngine._vario_xz(x, z)
+        (n, d), nz, nlags = x.shape, z.shape[0], int(nlags)
         shape = (nz * (nz + 1) // 2, max(nlags, 0))
-        if dev:
-            import torch
-            count = torch.empty(shape[1], dtype=torch.int64, device=x.device)
-            lagsum = torch.empty(shape[1], dtype=torch.float64, device=x.device)
-            csum = torch.empty(shape, dtype=torch.float64, device=x.device)
-            ndup = torch.empty(1, dtype=torch.int64, device=x.device)
-        else:
-            count = np.empty(shape[1], dtype=np.int64)
-            lagsum = np.empty(shape[1])
-            csum = np.empty(shape)
-            ndup = np.zeros(1, dtype=np.int64)
+        count, lagsum, csum, ndup = HipEngine._vario_out(x, dev, shape[1], shape)
         u = None if direction is None else np.ascontiguousarray(direction, dtype=np.float64).reshape(-1)
         if u is not None and u.size != d:
             raise ValueError(f"direction has {u.size} components for {d}-D samples")
         check(l.gss_variogram_cross(ptr(x), n, d, ptr(z), nz, nlags, float(maxlag), ptr(u), float(dtol), float(cos_atol),
-                                    ptr(count), ptr(lagsum), ptr(csum), ptr(ndup), MEM_DEVICE if dev else MEM_HOST,
-                                    current_stream()))
+                                    ptr(count), ptr(lagsum), ptr(csum), ptr(ndup), st.mem_flag(dev), current_stream()))
         return count, lagsum, csum, (ndup if dev else int(ndup[0]))
 
     @staticmethod
@@ -1454,26 +1180,19 @@ class HipEngine:
         the fields of gss_cv_summary_t, per-fold mean squared errors or None).  numpy arrays or CUDA tensors, all in
         one memory space."""
         l = _lib.lib()
-        dev = is_torch(z) and z.is_cuda
-        if dev:
-            import torch
-            z, pred, var = (a.to(torch.float64).contiguous() for a in (z, pred, var))
-            status = None if status is None else status.to(torch.uint8).contiguous()
-            fold = None if fold is None else fold.to(torch.int32).contiguous()
-        else:
-            z, pred, var = (np.ascontiguousarray(a, dtype=np.float64) for a in (z, pred, var))
-            status = None if status is None else np.ascontiguousarray(status, dtype=np.uint8)
-            fold = None if fold is None else np.ascontiguousarray(fold, dtype=np.int32)
+        dev = st.on_device(z)
+        stage = st.prep if dev else np.ascontiguousarray     # every array lies where z does
+        z, pred, var = (stage(a, dtype=np.float64) for a in (z, pred, var))
+        status = None if status is None else stage(status, dtype=np.uint8)
+        fold = None if fold is None else stage(fold, dtype=np.int32)
         n = z.shape[0]
         if any(a is not None and tuple(a.shape) != (n,) for a in (pred, var, status, fold)):
             raise ValueError("z, pred, var, status and fold must have one length")
         nf = int(nfolds) if fold is not None else 0
-        fmse = None
-        if nf > 0:
-            fmse = _empty_like_space(z, (nf,), np.float64) if dev else np.empty(nf)
+        fmse = st.empty(z, (nf,)) if nf > 0 else None
         out = _lib.CVSummary()
         check(l.gss_cv_summary(ptr(z), ptr(pred), ptr(var), ptr(status), ptr(fold), n, nf, C.byref(out), ptr(fmse),
-                               MEM_DEVICE if dev else MEM_HOST, current_stream()))
+                               st.mem_flag(dev), current_stream()))
         return {f: getattr(out, f) for f, _ in _lib.CVSummary._fields_}, fmse
 
 
