@@ -6,6 +6,7 @@
 #include "ik_kernel.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -175,6 +176,16 @@ static bool frame_free(const gss_variogram_t& v) {   // every structure a sphere
   return ok;
 }
 
+// GSS_IK_CHUNK_POINTS caps the points per chunk of gss_ik_predict_knn (tests: a chunk loop that runs more than once at a
+// small size).  Any positive count: a chunk is a launch of its own, so it need not be a multiple of IK_WAVES.
+static int64_t ik_chunk_cap(int64_t chunk) {
+  if (const char* e = std::getenv("GSS_IK_CHUNK_POINTS")) {
+    const int64_t cap = std::atoll(e);
+    if (cap > 0 && cap < chunk) chunk = cap;
+  }
+  return chunk;
+}
+
 // the kernel of one chunk by dimension, model and form
 static int32_t ik_dispatch(int dim, int kind, bool full, const IkLaunch& a) {
   if (full) {
@@ -289,7 +300,7 @@ int32_t gss_ik_predict_knn(const double* xdata, const double* z, int64_t n, int3
   Staged& scnt = *dc.out(count_out, sizeof(int32_t));
   GSS_TRY(dc.begin(mem, m, s, false, &fr));
 
-  const int64_t chunk = 1 << 20;
+  const int64_t chunk = ik_chunk_cap(1 << 20);
   const int64_t mc = m < chunk ? m : chunk;
   DevBuf idx_s, cnt_s, st_s;
   if (!idx_out) GSS_TRY(idx_s.alloc(sizeof(int) * (size_t)(mc * k)));

@@ -1010,7 +1010,9 @@ int32_t gss_decluster_nearest(const double* x, int64_t n, int32_t dim, const dou
  *   corrected), raw (m x K, before the correction; may be NULL), status (m; may be NULL), idx_out (m x k) and
  *   count_out (m) as gss_krig_predict_knn (may be NULL).  Fewer than max(minneighbors, 1) neighbours: GSS_PT_MISSING
  *   and NaN in the K outputs; a non-positive pivot in any of the point's factorisations (or in the constraint's Schur
- *   complement): GSS_PT_SINGULAR and NaN.  No kriging variance is formed.  Profile scopes: "knn", "ik_local".
+ *   complement): GSS_PT_SINGULAR and NaN.  No kriging variance is formed.  The domain is walked in chunks of 2^20
+ *   points; the environment variable GSS_IK_CHUNK_POINTS caps the points per chunk (any positive count), for tests,
+ *   like GSS_COKRIG_CHUNK_POINTS: the results are the same bits.  Profile scopes: "knn", "ik_local".
  *
  * gss_ik_order_relations: the correction alone, in place on m x K rows (for ccdfs assembled elsewhere, e.g. from the
  *   global neighbourhood).  *ncorrected (host word, may be NULL): the (point, cutoff) values it changed; *maxcorr

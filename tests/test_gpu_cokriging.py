@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cokrig_cases as CC
+import cokrig_kernel_cases as KC
 import cokrig_ref as CR
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +33,8 @@ def structure_of(s):
     """cokrig_ref structure keywords -> the package's variogram model (only its shape is read)."""
     import gss
     ctor = {"exponential": gss.ExponentialVariogram, "spherical": gss.SphericalVariogram, "matern": gss.MaternVariogram,
-            "gaussian": gss.GaussianVariogram}[s["kind"]]
+            "gaussian": gss.GaussianVariogram, "cubic": gss.CubicVariogram,
+            "pentaspherical": gss.PentasphericalVariogram}[s["kind"]]
     kw = dict(order=s["nu"]) if s["kind"] == "matern" else {}
     if s["kind"] == "gaussian":
         kw["regularize"] = False
@@ -72,6 +74,28 @@ def test_predict_matches_the_reference(name):
     assert mu.shape == var.shape == st.shape == (nz, m)
     assert not st.any()
     assert close(mu, rmu) and close(var, rvar)
+
+
+@pytest.mark.parametrize("key", sorted(KC.KERNELS), ids=lambda key: "%d_%d" % key)
+def test_every_compiled_rhs_kernel(key):
+    """Every entry of tests/cokrig_kernel_cases.py (one per compiled cokrig_rhs_kernel<DIM, KIND>;
+    tests/test_cokrig_census.py holds the table against the built library and every entry under the conditioning cap):
+    means, variances and statuses of all 517 points and every target, and the zero-key select at the points that sit
+    on a sample of one variable."""
+    c = KC.KERNELS[key]()
+    rmu, rvar = CR.predict(KC.model_of(c), c["x"], c["z"], c["var"], c["xdom"], c["variant"], c["means"])
+    h = handle_of(c)
+    mu, var, st = h.predict_global(c["xdom"])
+    h.close()
+    nz, m = c["B1"].shape[0], c["xdom"].shape[0]
+    assert mu.shape == var.shape == st.shape == (nz, m)
+    assert not st.any()
+    assert close(mu, rmu) and close(var, rvar)
+    for p, j in enumerate(c["on"]):                            # point p is the location of sample j
+        a, zj = int(c["var"][j]), float(c["z"][j])
+        assert abs(mu[a, p] - zj) <= 1e-9 * (1.0 + abs(zj)) and var[a, p] <= 1e-9
+        others = [t for t in range(nz) if t != a]
+        assert np.all(var[others, p] > 1e-3)                  # not measured there: estimated, held by the reference
 
 
 def test_handle_info_and_refusals():

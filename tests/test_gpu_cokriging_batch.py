@@ -15,6 +15,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cokrig_cases as CC
+import cokrig_kernel_cases as KC
 import cokrig_ref as CR
 
 pytestmark = pytest.mark.gpu
@@ -83,7 +84,8 @@ ALL = {**CC.CASES, **CC.GAUSSIAN, **EXTRA}
 def structure_of(s):
     import gss
     ctor = {"exponential": gss.ExponentialVariogram, "spherical": gss.SphericalVariogram, "matern": gss.MaternVariogram,
-            "gaussian": gss.GaussianVariogram, "cubic": gss.CubicVariogram}[s["kind"]]
+            "gaussian": gss.GaussianVariogram, "cubic": gss.CubicVariogram,
+            "pentaspherical": gss.PentasphericalVariogram}[s["kind"]]
     kw = dict(order=s["nu"]) if s["kind"] == "matern" else {}
     if s["kind"] == "gaussian":
         kw["regularize"] = False
@@ -139,6 +141,32 @@ def test_batched_means_match_the_reference(name):
             assert close(got, ref[:nb], tol)
     finally:
         h.close()
+
+
+@pytest.mark.parametrize("key", sorted(KC.KERNELS), ids=lambda key: "%d_%d" % key)
+def test_every_compiled_batch_mean_kernel(key):
+    """Every entry of tests/cokrig_kernel_cases.py (one per compiled cokrig_batch_mean_kernel<DIM, KIND>;
+    tests/test_cokrig_census.py holds the table against the built library): COLS + 5 value vectors, more than the columns
+    of a pass and no multiple of them, each against its own reference; the points on samples give every vector's value
+    back."""
+    c = KC.KERNELS[key]()
+    nb = COLS + 5
+    assert nb > COLS and nb % COLS != 0
+    zb = KC.batch_of(c, nb)
+    assert np.array_equal(zb[0], c["z"])
+    model = KC.model_of(c)
+    ref = np.stack([CR.predict(model, c["x"], z, c["var"], c["xdom"], c["variant"], c["means"])[0] for z in zb])
+    nz, m = c["B1"].shape[0], c["xdom"].shape[0]
+    h = handle_of(c)
+    try:
+        got = h.predict_batch(c["xdom"], zb)
+    finally:
+        h.close()
+    assert got.shape == (nb, nz, m)
+    assert close(got, ref)
+    for p, j in enumerate(c["on"]):
+        zj = zb[:, j]
+        assert np.all(np.abs(got[:, c["var"][j], p] - zj) <= 1e-9 * (1.0 + np.abs(zj)))
 
 
 def test_domain_points_on_samples_reproduce_every_value_vector():

@@ -1,5 +1,6 @@
 """Indicator kriging on the device (gss_ik_predict_knn, gss_ik_order_relations, gss_ik_post) against the numpy
-restatement tests/ik_ref.py on the cases of tests/ik_cases.py.
+restatement tests/ik_ref.py on the cases of tests/ik_cases.py and on the table tests/ik_kernel_cases.py, which has one case
+per compiled instantiation of ik_local_kernel.
 
 Raw ccdf: |device - reference| <= bar x 2^-53 max(1, sum |lambda|) per (point, cutoff), bar = 16 x the largest error of
 the FP64 restatement against the long-double one on the same inputs (ORACLE, measured on the CPU by tools/ik_oracle.py),
@@ -14,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import gss
 import ik_cases
+import ik_kernel_cases
 import ik_ref
 
 pytestmark = pytest.mark.gpu
@@ -32,6 +34,21 @@ ORACLE = {
     'route_ok': 4.57, 'route_sk': 2.32, 'route_full': 2.3,
     # the dual form of the global route (ik_ref.predict_global), in the units of the moving route
     'route_ok_global': 3.61, 'route_sk_global': 3.14, 'route_full_global': 8.44,
+    # one entry per compiled ik_local_kernel<DIM, KIND, NT, FULL> (tests/ik_kernel_cases.py; g: the general kernel)
+    'ik_2_0_1_median': 2.48, 'ik_2_0_2_median': 5.59, 'ik_2_0_4_median': 6.02, 'ik_2_1_1_median': 2.33,
+    'ik_2_1_2_median': 4.03, 'ik_2_1_4_median': 9.02, 'ik_2_2_1_median': 4.47, 'ik_2_2_2_median': 6.4,
+    'ik_2_2_4_median': 8.03, 'ik_2_30_1_median': 2.95, 'ik_2_30_2_median': 5.31, 'ik_2_30_4_median': 5.66,
+    'ik_2_31_1_median': 3.46, 'ik_2_31_2_median': 4.71, 'ik_2_31_4_median': 6.32, 'ik_2_32_1_median': 4.13,
+    'ik_2_32_2_median': 4.57, 'ik_2_32_4_median': 7.71, 'ik_3_0_1_median': 1.72, 'ik_3_0_2_median': 3.16,
+    'ik_3_0_4_median': 5.1, 'ik_3_1_1_median': 1.78, 'ik_3_1_2_median': 2.22, 'ik_3_1_4_median': 4.15,
+    'ik_3_2_1_median': 2.75, 'ik_3_2_2_median': 4.86, 'ik_3_2_4_median': 5.67, 'ik_3_30_1_median': 2.44,
+    'ik_3_30_2_median': 4.59, 'ik_3_30_4_median': 5.65, 'ik_3_31_1_median': 2.85, 'ik_3_31_2_median': 2.6,
+    'ik_3_31_4_median': 4.91, 'ik_3_32_1_median': 2.6, 'ik_3_32_2_median': 4.42, 'ik_3_32_4_median': 4.1,
+    'ik_1_g_1_median': 9.48, 'ik_1_g_1_full': 8.78, 'ik_1_g_2_median': 10.49, 'ik_1_g_2_full': 9.22,
+    'ik_1_g_4_median': 13.64, 'ik_1_g_4_full': 14.3, 'ik_2_g_1_median': 3.26, 'ik_2_g_1_full': 3.55,
+    'ik_2_g_2_median': 4.47, 'ik_2_g_2_full': 5.22, 'ik_2_g_4_median': 6.66, 'ik_2_g_4_full': 8.14, 'ik_3_g_1_median':
+    2.6, 'ik_3_g_1_full': 1.66, 'ik_3_g_2_median': 2.19, 'ik_3_g_2_full': 4.0, 'ik_3_g_4_median': 5.12,
+    'ik_3_g_4_full': 4.84,
     # post-processing: the hand-made rows, and the corrected ccdfs of the cases with ik_cases.post_args_for
     'post': 1.33, 'post_cases': 2.01,
 }
@@ -48,6 +65,9 @@ def eng():
 
 
 CASES = ik_cases.cases()
+KERNEL_CASES = {key: fn for key, fn in ik_kernel_cases.KERNELS.items()
+                if not isinstance(fn, ik_kernel_cases.UNREACHABLE)}
+CHUNK_ENV = "GSS_IK_CHUNK_POINTS"
 _REF = {}
 
 
@@ -67,9 +87,9 @@ def device_of(eng, c, **kw):
                               return_raw=True, return_idx=True, **kw)
 
 
-@pytest.mark.parametrize("name", list(CASES))
-def test_device_against_reference(eng, name):
-    c, r = CASES[name], ref_of(name)
+def check_against_reference(eng, name, c, r):
+    """One case on the device against its reference r: lists, counts and statuses equal, raw ccdf within bar(name),
+    corrected ccdf bit for bit the correction of the device's own raw values, the correction's two figures exact."""
     ccdf, st, raw, idx, cnt = device_of(eng, c)
     assert np.array_equal(cnt, r["cnt"]) and np.array_equal(idx, r["idx"])
     assert np.array_equal(st, r["status"]), (np.flatnonzero(st != r["status"]), st[st != r["status"]])
@@ -100,6 +120,64 @@ def test_device_against_reference(eng, name):
         assert np.all(ccdf[ok] == 1.0) or np.max(np.abs(ccdf[ok] - 1.0)) <= bar(name) * UNIT * r["wsum"][ok].max()
     if name == "all_above":
         assert np.all(raw[ok] == 0.0) and np.all(ccdf[ok] == 0.0)
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_device_against_reference(eng, name):
+    check_against_reference(eng, name, CASES[name], ref_of(name))
+
+
+@pytest.mark.parametrize("key", list(KERNEL_CASES), ids=lambda key: ik_kernel_cases.name_of(key))
+def test_every_compiled_kernel(eng, key):
+    """Every entry of tests/ik_kernel_cases.py (one per compiled ik_local_kernel<DIM, KIND, NT, FULL>;
+    tests/test_ik_census.py holds the table against the built library) under the assertions of
+    test_device_against_reference, no point left out (every status of these cases is 0)."""
+    c = KERNEL_CASES[key]()
+    r = ik_ref.predict(c["x"], c["z"], c["x0"], c["cutoffs"], c["models"], c["k"], fstar=c["fstar"], radius=c["radius"])
+    assert not r["status"].any()
+    check_against_reference(eng, ik_kernel_cases.name_of(key), c, r)
+
+
+def ccdf_alone(c):
+    """gss_ik_predict_knn with the corrected ccdf as its only output: raw, status, idx_out and count_out NULL (the engine
+    always asks for the status), host arrays."""
+    from gss import _lib
+    from gss import _staging as st
+    from gss.engine import OK, SK, _vg_struct
+    x, z, x0 = (np.ascontiguousarray(c[a], dtype=np.float64) for a in ("x", "z", "x0"))
+    cut = np.ascontiguousarray(c["cutoffs"], dtype=np.float64)
+    fs = None if c["fstar"] is None else np.ascontiguousarray(c["fstar"], dtype=np.float64)
+    n, d = x.shape
+    m, K = x0.shape[0], cut.size
+    vgs = (_lib.Variogram * len(c["models"]))(*[_vg_struct(v, d) for v in c["models"]])
+    r, ir, met, mpar = st.search_args(c.get("radius"), None)
+    ccdf = np.full((m, K), -7.0)
+    _lib.check(_lib.lib().gss_ik_predict_knn(_lib.ptr(x), _lib.ptr(z), n, d, _lib.ptr(cut), K, vgs, len(c["models"]),
+                                             SK if fs is not None else OK, _lib.ptr(fs), int(c["k"]),
+                                             int(c.get("minneighbors", 1)), r, _lib.ptr(ir), met, mpar, _lib.ptr(x0), m,
+                                             _lib.ptr(ccdf), None, None, None, None, _lib.MEM_HOST,
+                                             _lib.current_stream()))
+    return ccdf
+
+
+@pytest.mark.parametrize("key", [(2, 2, 2, False), (3, -1, 2, True)], ids=lambda key: ik_kernel_cases.name_of(key))
+def test_chunks(eng, key):
+    """The chunk loop of gss_ik_predict_knn past its first turn: 67 points under a cap of 16 are five chunks, the last
+    one of three points.  With every optional output (each offset by the chunk) and with none (the driver's own list,
+    count and status scratch reused by every chunk): bit for bit the one-chunk call."""
+    c = KERNEL_CASES[key]()
+    assert c["x0"].shape[0] == 67
+    one = device_of(eng, c)
+    os.environ[CHUNK_ENV] = "16"
+    try:
+        every = device_of(eng, c)
+        bare = ccdf_alone(c)
+    finally:
+        del os.environ[CHUNK_ENV]
+    assert not one[1].any() and np.isfinite(one[0]).all()
+    for a, b in zip(one, every):
+        assert np.array_equal(a, b)
+    assert np.array_equal(bare, one[0])
 
 
 def test_post_against_reference(eng):

@@ -1,5 +1,5 @@
 """How far the FP64 restatement of indicator kriging (tests/ik_ref.py) is from the same systems solved in long double,
-on the inputs of tests/ik_cases.py: the figures the error bars of tests/test_gpu_ik.py are derived from (bar = 16 x the
+on the inputs of tests/ik_cases.py and of the kernel table tests/ik_kernel_cases.py: the figures the error bars of tests/test_gpu_ik.py are derived from (bar = 16 x the
 figure, floored at 8 and capped at 1e-9, as tests/test_kernel_census.py holds the kriging bars).  CPU only.
 
 Raw ccdf: units of 2^-53 max(1, sum |lambda|) per (point, cutoff).  Post-processing: units of 2^-53 x the scale of the
@@ -17,6 +17,7 @@ for p in (ROOT, os.path.join(ROOT, "geostatssolvers.jl_amd"), os.path.join(ROOT,
     sys.path.insert(0, p)
 
 import ik_cases  # noqa: E402
+import ik_kernel_cases  # noqa: E402
 import ik_ref  # noqa: E402
 
 UNIT = 2.0 ** -53
@@ -68,6 +69,10 @@ def main():
         # post-processing of the case's corrected ccdf, with the arguments the test uses
         for w, w2 in ik_cases.POST_TAILS:
             post_cases = max(post_cases, post_error(a["ccdf"], c["cutoffs"], w, w2, **ik_cases.post_args_for(c)))
+    # the table of compiled kernels (raw ccdf only: the post-processing test runs on the cases above)
+    for key, entry in ik_kernel_cases.KERNELS.items():
+        if not isinstance(entry, ik_kernel_cases.UNREACHABLE):
+            out[ik_kernel_cases.name_of(key)] = round(raw_error(entry())[0], 2)
     rows = ik_cases.post_rows()
     out["post"] = round(max(post_error(rows, ik_cases.POST_CUTOFFS, w, w2, **ik_cases.POST_ARGS)
                             for w, w2 in ik_cases.POST_TAILS), 2)

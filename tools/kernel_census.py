@@ -8,8 +8,10 @@ kernel was launched in that run, and ends with the ones that never were.  tests/
 families of this list against the case table tests/kernel_cases.py, tests/test_search_census.py the neighbour-search and
 IDW / LWR families against tests/search_cases.py, tests/test_variography_instances_host.py the pair kernels of
 variography.hip against tests/vario_cases.py, tests/test_fftgs_census.py the FFTGS families (fused, generic and rocFFT
-pipelines, co-simulation mix) against the run table tests/fftgs_cases.py, and tests/test_sgs_census.py the SGS kernels
-against the run table tests/sgs_cases.py.
+pipelines, co-simulation mix) against the run table tests/fftgs_cases.py, tests/test_sgs_census.py the SGS kernels
+against the run table tests/sgs_cases.py, tests/test_ik_census.py the indicator-kriging kernels against
+tests/ik_kernel_cases.py, and tests/test_cokrig_census.py the global-cokriging kernels against
+tests/cokrig_kernel_cases.py.
 """
 import argparse
 import csv
