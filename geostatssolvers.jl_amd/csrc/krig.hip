@@ -270,9 +270,21 @@ __global__ __launch_bounds__(256, 2) void krig_quadform_kernel(
   }
   const int64_t p0 = (strip0 + strip) * BN;
 
-  // staging map: thread moves 2 consecutive doubles of rows kq, kq+4, kq+8, kq+12 of each operand
+  // staging map: thread moves 2 consecutive doubles of rows kq, kq+4, kq+8, kq+12 of each operand.  kq is the wave
+  // index: with it in a scalar register every address of the prefetch is a wave-uniform base, advanced by scalar adds,
+  // plus one per-lane byte offset that never changes.
   const int i2 = (tid & 63) * 2;
-  const int kq = tid >> 6;
+  const int kq = __builtin_amdgcn_readfirstlane(tid >> 6);
+  uint32_t lane_off = (uint32_t)i2 * (uint32_t)sizeof(double);
+  // The empty asm keeps the scalar base and the 32-bit offset opaque up to the load, so that the widening of the
+  // offset is selected together with the load and folds into its scalar-base + 32-bit-vector-offset form.  Left to
+  // itself the compiler widens the offset once outside the stage loop or adds part of the base to it, and every load
+  // needs a 64-bit vector add again.  The statement emits no instruction.
+  auto ldg2 = [&](const double* base) __attribute__((always_inline)) {
+    uint64_t b = reinterpret_cast<uint64_t>(base);
+    asm volatile("" : "+s"(b), "+v"(lane_off));
+    return *(const __attribute__((address_space(1))) d2v*)(b + lane_off);
+  };
 
   double qacc[2] = {0.0, 0.0};
   double macc[2] = {0.0, 0.0};  // row N1 of the product: wd . rhs
@@ -285,14 +297,14 @@ __global__ __launch_bounds__(256, 2) void krig_quadform_kernel(
     const int tm_max = (N1 + 1 - i0 + 15) / 16 < 8 ? (N1 + 1 - i0 + 15) / 16 : 8;
     const int t0 = i0 / BK;  // stages in front of the diagonal block
 
-    const double* wp = W + (int64_t)kq * ldw + i0 + i2;
-    const double* rp = R + (int64_t)kq * ldr + p0 + i2;
+    const double* wp = W + (int64_t)kq * ldw + i0;  // wave-uniform; the lane's two doubles lie lane_off bytes on
+    const double* rp = R + (int64_t)kq * ldr + p0;
     if (I == Ibeg) {  // later row blocks find their first stage in LDS: the last stage of the block before fetched it
       d2v ra[4], rb[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        ra[r] = *reinterpret_cast<const d2v*>(wp + (int64_t)(4 * r) * ldw);
-        rb[r] = *reinterpret_cast<const d2v*>(rp + (int64_t)(4 * r) * ldr);
+        ra[r] = ldg2(wp + (int64_t)(4 * r) * ldw);
+        rb[r] = ldg2(rp + (int64_t)(4 * r) * ldr);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -304,16 +316,19 @@ __global__ __launch_bounds__(256, 2) void krig_quadform_kernel(
 
     // The row block with its live-tile count as a constant: t0 full stages, then the TM_MAX stages of the diagonal
     // block, stage s touching row tiles s .. TM_MAX - 1 only (k > i0 + 16 s meets zeros of W' above them).  Every
-    // stage is straight-line MFMA code; the bounds cost neither branches nor dead LDS reads.
-    auto row_block = [&](auto tmx) __attribute__((always_inline)) {
+    // stage is straight-line MFMA code; the bounds cost neither branches nor dead LDS reads.  INTERIOR: all 128 rows
+    // of the block are data rows (< n), so the epilogue is a plain sum of squares.
+    auto row_block = [&](auto tmx, auto interior) __attribute__((always_inline)) {
       constexpr int TM_MAX = decltype(tmx)::value;
-      d4 accw[8][2];   // 1 x 4 wave layout: every wave sees all 128 rows (8 tiles) of 32 columns (2 tiles)
-#pragma unroll
-      for (int tm = 0; tm < TM_MAX; ++tm) accw[tm][0] = accw[tm][1] = d4{0.0, 0.0, 0.0, 0.0};
+      constexpr bool INTERIOR = decltype(interior)::value;
+      // 1 x 4 wave layout: every wave sees all 128 rows (8 tiles) of 32 columns (2 tiles).  Not cleared: the first
+      // stage of the block opens every accumulator with a zero C operand.
+      d4 accw[8][2];
 
-      auto stage = [&](int t, auto tmn, auto is_last) __attribute__((always_inline)) {
+      auto stage = [&](int t, auto tmn, auto is_last, auto is_first) __attribute__((always_inline)) {
         constexpr int TM_MIN = decltype(tmn)::value;
         constexpr bool last = decltype(is_last)::value;
+        constexpr bool first = decltype(is_first)::value;
         const int cur = buf;
         const bool more = !last || (I + 1 < Iend);
         d2v ra[4], rb[4];
@@ -323,11 +338,11 @@ __global__ __launch_bounds__(256, 2) void krig_quadform_kernel(
           const double* rq = last ? rp : rp + (int64_t)(t + 1) * BK * ldr;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            ra[r] = *reinterpret_cast<const d2v*>(wq + (int64_t)(4 * r) * ldw);
-            rb[r] = *reinterpret_cast<const d2v*>(rq + (int64_t)(4 * r) * ldr);
+            ra[r] = ldg2(wq + (int64_t)(4 * r) * ldw);
+            rb[r] = ldg2(rq + (int64_t)(4 * r) * ldr);
           }
         }
-        mma_stage_w14<TM_MIN, TM_MAX>(As + cur * TILE_LDS, Bs + cur * TILE_LDS, accw, wave, lane);
+        mma_stage_w14<TM_MIN, TM_MAX, first>(As + cur * TILE_LDS, Bs + cur * TILE_LDS, accw, wave, lane);
         if (more) {
           double* an = As + (cur ^ 1) * TILE_LDS;
           double* bn = Bs + (cur ^ 1) * TILE_LDS;
@@ -338,12 +353,23 @@ __global__ __launch_bounds__(256, 2) void krig_quadform_kernel(
           }
         }
         __syncthreads();
+        // nothing is scheduled across the end of a stage: left free, the scheduler pulls the LDS reads of several
+        // diagonal stages forward and the kernel no longer fits its 256 registers without scratch
+        __builtin_amdgcn_sched_barrier(0);
         buf ^= 1;
       };
-      for (int t = 0; t < t0; ++t) stage(t, std::integral_constant<int, 0>{}, std::false_type{});
-#define GSS_K3_DIAG_STAGE(S) \
-  if constexpr (S < TM_MAX) stage(t0 + S, std::integral_constant<int, S>{}, std::bool_constant<S + 1 == TM_MAX>{})
-      GSS_K3_DIAG_STAGE(0);
+      constexpr std::integral_constant<int, 0> full{};
+      constexpr bool diag0_last = TM_MAX == 1;
+      if (t0 > 0) {
+        stage(0, full, std::false_type{}, std::true_type{});
+        for (int t = 1; t < t0; ++t) stage(t, full, std::false_type{}, std::false_type{});
+        stage(t0, full, std::bool_constant<diag0_last>{}, std::false_type{});
+      } else {  // the first row block: its diagonal stage 0 is the first stage
+        stage(t0, full, std::bool_constant<diag0_last>{}, std::true_type{});
+      }
+#define GSS_K3_DIAG_STAGE(S)                                                                          \
+  if constexpr (S < TM_MAX)                                                                           \
+  stage(t0 + S, std::integral_constant<int, S>{}, std::bool_constant<S + 1 == TM_MAX>{}, std::false_type{})
       GSS_K3_DIAG_STAGE(1);
       GSS_K3_DIAG_STAGE(2);
       GSS_K3_DIAG_STAGE(3);
@@ -353,33 +379,51 @@ __global__ __launch_bounds__(256, 2) void krig_quadform_kernel(
       GSS_K3_DIAG_STAGE(7);
 #undef GSS_K3_DIAG_STAGE
 
-      // signed squares: rows < n count +, constraint rows n..N1-1 count -, padding rows are zero
+      // signed squares: rows < n count +, constraint rows n..N1-1 count -, padding rows are zero.  The sign, the
+      // padding and the mean row N1 concern only the 16-row tiles that reach row n or beyond: a wave-uniform test per
+      // tile; every other tile is a multiply and an add per element.
+      // The square is rounded before it is added, as it always was: contraction into an fma would change the variance.
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
+#pragma clang fp contract(off)
         double s = 0.0;
 #pragma unroll
-        for (int tm = 0; tm < TM_MAX; ++tm)
+        for (int tm = 0; tm < TM_MAX; ++tm) {
+          if (INTERIOR || i0 + tm * 16 + 16 <= n) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = i0 + tm * 16 + lk + 4 * r;
-            const double v = accw[tm][tn][r];
-            const double vv = v * v;
-            s += (row < n) ? vv : (row < N1 ? -vv : 0.0);
-            if (row == N1) macc[tn] += v;
+            for (int r = 0; r < 4; ++r) {
+              const double v = accw[tm][tn][r];
+              const double vv = v * v;
+              s += vv;
+            }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int row = i0 + tm * 16 + lk + 4 * r;
+              const double v = accw[tm][tn][r];
+              const double vv = v * v;
+              s += (row < n) ? vv : (row < N1 ? -vv : 0.0);
+              if (row == N1) macc[tn] += v;
+            }
           }
+        }
         qacc[tn] += s;
       }
     };
-    // only the last row block can have fewer than 8 live tiles
-    switch (tm_max) {
-      case 1: row_block(std::integral_constant<int, 1>{}); break;
-      case 2: row_block(std::integral_constant<int, 2>{}); break;
-      case 3: row_block(std::integral_constant<int, 3>{}); break;
-      case 4: row_block(std::integral_constant<int, 4>{}); break;
-      case 5: row_block(std::integral_constant<int, 5>{}); break;
-      case 6: row_block(std::integral_constant<int, 6>{}); break;
-      case 7: row_block(std::integral_constant<int, 7>{}); break;
-      default: row_block(std::integral_constant<int, 8>{}); break;
+    // only the last row block can have fewer than 8 live tiles or rows that are not data
+    if (i0 + BM <= n) {
+      row_block(std::integral_constant<int, 8>{}, std::true_type{});
+    } else {
+      switch (tm_max) {
+        case 1: row_block(std::integral_constant<int, 1>{}, std::false_type{}); break;
+        case 2: row_block(std::integral_constant<int, 2>{}, std::false_type{}); break;
+        case 3: row_block(std::integral_constant<int, 3>{}, std::false_type{}); break;
+        case 4: row_block(std::integral_constant<int, 4>{}, std::false_type{}); break;
+        case 5: row_block(std::integral_constant<int, 5>{}, std::false_type{}); break;
+        case 6: row_block(std::integral_constant<int, 6>{}, std::false_type{}); break;
+        case 7: row_block(std::integral_constant<int, 7>{}, std::false_type{}); break;
+        default: row_block(std::integral_constant<int, 8>{}, std::false_type{}); break;
+      }
     }
   }
 

@@ -56,7 +56,9 @@ __device__ __forceinline__ void mma_stage(const double* __restrict__ As, const d
 // issues their MFMAs as straight-line code, without a branch or an exec-mask change between them.  TM_MAX < 8: row
 // tiles tm >= TM_MAX lie entirely in the zero padding below the last row of the operand (last row block).  Every
 // accumulator sees its k in ascending order whatever the bounds, and the products left out are exact zeros.
-template <int TM_MIN, int TM_MAX>
+// FIRST: the stage opens its accumulators.  Their first MFMA (kk = 0) takes the constant zero as its C operand, which
+// the instruction encodes inline, so no register is cleared beforehand and acc need not be initialised.
+template <int TM_MIN, int TM_MAX, bool FIRST = false>
 __device__ __forceinline__ void mma_stage_w14(const double* __restrict__ As, const double* __restrict__ Bs,
                                               d4 (&acc)[8][2], int wave, int lane) {
   static_assert(0 <= TM_MIN && TM_MIN < TM_MAX && TM_MAX <= 8, "live row tiles of a 128-row block");
@@ -72,8 +74,14 @@ __device__ __forceinline__ void mma_stage_w14(const double* __restrict__ As, con
     for (int tm = TM_MIN; tm < TM_MAX; ++tm) a[tm] = ap[tm * 16];
 #pragma unroll
     for (int tm = TM_MIN; tm < TM_MAX; ++tm) {
-      acc[tm][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b0, acc[tm][0], 0, 0, 0);
-      acc[tm][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b1, acc[tm][1], 0, 0, 0);
+      if (FIRST && kk == 0) {
+        const d4 zero = {0.0, 0.0, 0.0, 0.0};
+        acc[tm][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b0, zero, 0, 0, 0);
+        acc[tm][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b1, zero, 0, 0, 0);
+      } else {
+        acc[tm][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b0, acc[tm][0], 0, 0, 0);
+        acc[tm][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b1, acc[tm][1], 0, 0, 0);
+      }
     }
   }
 }
