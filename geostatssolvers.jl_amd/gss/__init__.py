@@ -7,9 +7,9 @@ solver front-ends (`solvers`) that mirror the reference's `solve(problem, solver
 from .geo import (CartesianGrid, Composition, DomainView, Ensemble, GeoTable, PointSet, aitchison, asarray, domain,
                   georef, parent, parentindices, view)
 from .problems import EstimationProblem, SimulationProblem
-from .solvers import (FFTGS, LUGS, SGS, CoKrigingSolver, ExpWeight, IDWSolver, KrigingSolver, LWRSolver, TricubeWeight,
-                      kriging_ui, searcher_ui, simulate_with_generic_loop, solve)
-from .indicator import IndicatorKrigingSolver, postik
+from .solvers import (FFTGS, LUGS, SGS, CoKrigingSolver, CookieCutter, ExpWeight, IDWSolver, KrigingSolver, LWRSolver,
+                      TricubeWeight, kriging_ui, searcher_ui, simulate_with_generic_loop, solve)
+from .indicator import IndicatorKrigingSolver, SISSolver, postik
 from .transforms import InNormalScores, NormalScore
 from .validation import (BlockValidation, CrossValidationResult, KFoldValidation, LeaveBallOut, LeaveOneOut,
                          cross_validate, cverror)

@@ -30,6 +30,7 @@ LUGS_NO_FACTOR = 1
 LUGS_FACT_LU = 2
 SGS_MASK_AFTER_SEARCH = 1
 SGS_METRIC_SHIFT = 4
+SIS_CONTINUOUS, SIS_CATEGORICAL = 0, 1
 NSCORE_FORWARD, NSCORE_INVERSE = 0, 1
 DECLUS_MIN, DECLUS_MAX = 0, 1
 
@@ -127,6 +128,7 @@ SIGNATURES = {
     "gss_sgs_weights": [_p, _p, _p, _p, _p, _i32, _p],
     "gss_sgs_realize": [_p, _u64, _i64, _i64, _p, _p, _i32, _p],
     "gss_sgs_schedule": [_p, _p, _i32],
+    "gss_sis_realize": [_p, _i32, _p, _i32, _p, _f64, _f64, _f64, _f64, _u64, _i64, _i64, _p, _p, _i32, _p],
     "gss_fftgs_create": [C.POINTER(_p), _VG, _i32, _p, _p, _f64, _i32, _p],
     "gss_fftgs_destroy": [_p],
     "gss_fftgs_spectrum": [_p, _p, _i32, _p],

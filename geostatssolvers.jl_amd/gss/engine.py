@@ -570,6 +570,32 @@ class SGSHandle:
                                       st.mem_flag(out), current_stream()))
         return out
 
+    def realize_indicator(self, kind, cutoffs, fstar, zmin=0.0, zmax=0.0, tail_power=(1.0, 1.0), seed=0, first_real=0,
+                          nreals=1, uniforms=None, device=False, out=None):
+        """gss_sis_realize: sequential indicator simulation on this handle, which must have been built with the
+        indicator variogram.  `kind`: "continuous" (`cutoffs`, the global ccdf `fstar`, `zmin` / `zmax` / `tail_power` of
+        the ccdf model) or "categorical" (`cutoffs=None`, `fstar` the global proportions; the handle's zdata and the
+        result are codes 0 .. K-1).  `uniforms`: (nreals, N) instead of the Philox ones."""
+        kinds = {"continuous": _lib.SIS_CONTINUOUS, "categorical": _lib.SIS_CATEGORICAL}
+        if kind not in kinds:
+            raise ValueError(f"kind={kind!r}: 'continuous' or 'categorical'")
+        cut = None if cutoffs is None else np.ascontiguousarray(cutoffs, dtype=np.float64).reshape(-1)
+        fs = np.ascontiguousarray(fstar, dtype=np.float64).reshape(-1)
+        if cut is not None and cut.size != fs.size:
+            raise ValueError(f"fstar has {fs.size} values for {cut.size} cutoffs")
+        uniforms = st.prep(uniforms)
+        if uniforms is not None and tuple(uniforms.shape) != (nreals, self.N):
+            raise ValueError(f"uniforms must have shape ({nreals}, {self.N})")
+        if out is not None:
+            if tuple(out.shape) != (nreals, self.N):
+                raise ValueError(f"out must have shape ({nreals}, {self.N})")
+        else:
+            out = st.empty(bool(device) or is_torch(uniforms), (nreals, self.N))
+        check(self._l.gss_sis_realize(self._h, kinds[kind], ptr(cut), int(fs.size), ptr(fs), float(zmin), float(zmax),
+                                      float(tail_power[0]), float(tail_power[1]), int(seed), int(first_real),
+                                      int(nreals), ptr(uniforms), ptr(out), st.mem_flag(out), current_stream()))
+        return out
+
 
 def _runs(shape, strides):
     """(nblocks, len, stride) of an array with element `strides` if it is `nblocks` contiguous runs of `len` elements

@@ -12,10 +12,12 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import parallel
 from .engine import OK, SK
-from .geo import GeoTable, PointSet, georef
-from .problems import EstimationProblem
-from .solvers import _ball, _distance, _domain_points, _host, _rot_kw, _Solver, searcher_ui
+from .geo import Ensemble, GeoTable, PointSet, georef
+from .problems import EstimationProblem, SimulationProblem
+from .solvers import (_ball, _distance, _domain_points, _host, _initbuff, _next_real, _path_order, _rot_kw, _run_state,
+                      _SGSPlan, _Solver, searcher_ui)
 from .variograms import GaussianVariogram, MetricBall
 
 MAX_CUTOFFS = 16
@@ -154,6 +156,159 @@ class IndicatorKrigingSolver(_Solver):
         # view made from its columns does not carry it, and postik then takes `cutoffs=`.
         sol.cutoffs = cutoffs
         return sol
+
+
+MAX_CATEGORIES = 16
+
+
+def _codes(values, labels, what) -> np.ndarray:
+    """Category codes 0 .. K-1 (as doubles, NaN for a missing value) of `values` among `labels`."""
+    out = np.full(len(values), np.nan)
+    lookup = {lab.item() if hasattr(lab, "item") else lab: i for i, lab in enumerate(labels)}
+    for i, v in enumerate(values):
+        v = v.item() if hasattr(v, "item") else v
+        if v is None or (isinstance(v, float) and np.isnan(v)):
+            continue
+        if v not in lookup:
+            raise ValueError(f"{what}: the value {v!r} is not among the categories")
+        out[i] = lookup[v]
+    return out
+
+
+class SISSolver(_Solver):
+    """Sequential indicator simulation (GSLIB sisim, median form; gss.h, gss_sis_realize): realisations of a categorical
+    variable, or of a continuous one without a Gaussian model.  Per variable, one of `cutoffs` (continuous: 1 .. 16,
+    increasing) or `categories` (categorical: 2 .. 16 labels; the realisations carry these labels, in their dtype), and
+    `variogram`, the one indicator variogram.  `proportions`: the global ccdf at the cutoffs / the global proportions of
+    the categories; default: those of the data (with declustering `weights`, one per data row); required without data.
+    Continuous only: `zmin`, `zmax` (default: the data's range, moved 5 % of the larger of that range and the cutoffs'
+    beyond an end cutoff that it does not enclose strictly; required without data) and `tail_power` of the ccdf model.
+    `path`, `minneighbors`, `maxneighbors`, `neighborhood`, `distance` and the globals `init`, `rng`, `mask` as SGS."""
+    PARAMS = dict(cutoffs=None, categories=None, variogram=None, proportions=None, weights=None, zmin=None, zmax=None,
+                  tail_power=(1.0, 1.0), path="linear", minneighbors=1, maxneighbors=10, neighborhood=None,
+                  distance="euclidean")
+    GLOBALS = dict(init="nearest", rng=None, mask="after")
+
+    def _draw_rule(self, var, p, z, w):
+        """(kind, cutoffs, fstar, zmin, zmax, tail_power) of a variable from its parameters and data values `z`
+        (continuous: the values; categorical: codes; NaN: missing)."""
+        have = ~np.isnan(z)
+        if p["categories"] is not None:
+            K = len(p["categories"])
+            if not 2 <= K <= MAX_CATEGORIES:
+                raise ValueError(f"{K} categories: 2 .. {MAX_CATEGORIES}")
+            if p["proportions"] is not None:
+                fs = np.asarray(p["proportions"], dtype=np.float64).reshape(-1)
+            elif have.any():
+                fs = np.diff(np.concatenate([[0.0], global_proportions(z, np.arange(K, dtype=np.float64), w)]))
+            else:
+                raise ValueError(f"variable {var}: without data the proportions are required")
+            if fs.size != K or np.any(fs < 0.0) or abs(fs.sum() - 1.0) > 1e-9:
+                raise ValueError(f"variable {var}: {K} proportions in [0, 1] that sum to 1 are required")
+            return "categorical", None, fs, 0.0, 0.0, (1.0, 1.0)
+        cut = check_cutoffs(p["cutoffs"])
+        if p["proportions"] is not None:
+            fs = np.asarray(p["proportions"], dtype=np.float64).reshape(-1)
+        elif have.any():
+            fs = global_proportions(z, cut, w)
+        else:
+            raise ValueError(f"variable {var}: without data the proportions are required")
+        if fs.size != cut.size or np.any(fs < 0.0) or np.any(fs > 1.0) or np.any(np.diff(fs) < 0.0):
+            raise ValueError(f"variable {var}: {cut.size} non-decreasing proportions in [0, 1] are required")
+        zmin, zmax = p["zmin"], p["zmax"]
+        if (zmin is None or zmax is None) and not have.any():
+            raise ValueError(f"variable {var}: without data zmin and zmax are required")
+        if have.any():
+            lo, hi = float(np.min(z[have])), float(np.max(z[have]))
+            step = 0.05 * (max(hi - lo, cut[-1] - cut[0]) or 1.0)
+            zmin = (lo if lo < cut[0] else cut[0] - step) if zmin is None else zmin
+            zmax = (hi if hi > cut[-1] else cut[-1] + step) if zmax is None else zmax
+        if not (zmin < cut[0] and zmax > cut[-1]):
+            raise ValueError("zmin / zmax must enclose the cutoffs strictly")
+        wlo, whi = (float(t) for t in p["tail_power"])
+        if not (wlo > 0.0 and whi > 0.0):
+            raise ValueError("tail exponents must be positive")
+        return "continuous", cut, fs, float(zmin), float(zmax), (wlo, whi)
+
+    def preprocess(self, problem):
+        if not isinstance(problem, SimulationProblem):
+            raise TypeError("SISSolver solves SimulationProblems")
+        if not hasattr(self.engine.SGS, "realize_indicator"):
+            raise NotImplementedError(f"engine {getattr(self.engine, 'name', self.engine)!r} has no indicator simulation")
+        pdom = problem.domain
+        cent = pdom.centroids()
+        N = cent.shape[0]
+        mask = self.globals.get("mask", "after")
+        if mask not in ("after", "during"):
+            raise ValueError(f"mask={mask!r}: 'after' or 'during'")
+        pre = {}
+        for var in problem.variables:
+            p = self.params(var)
+            if (p["cutoffs"] is None) == (p["categories"] is None):
+                raise ValueError(f"variable {var}: give `cutoffs` (continuous) or `categories` (categorical)")
+            if p["variogram"] is None:
+                raise ValueError(f"variable {var}: the indicator variogram is required")
+            if getattr(p["variogram"], "kind", None) == "power":
+                raise ValueError("a power variogram has no sill: indicator simulation refuses it")
+            data, z, w = problem.data, np.empty(0), None
+            if data is not None and var in data.table:
+                raw = data[var]
+                z = _codes(raw, p["categories"], f"variable {var}") if p["categories"] is not None else \
+                    np.asarray(raw, dtype=np.float64)
+                if p["weights"] is not None:
+                    w = np.asarray(p["weights"], dtype=np.float64).ravel()
+                    if w.size != z.size:
+                        raise ValueError(f"{w.size} weights for {z.size} data rows")
+                data = GeoTable({var: z}, data.domain)
+            kind, cut, fs, zmin, zmax, tail = self._draw_rule(var, p, z, w)
+            path, order, path_seed = p["path"], None, None
+            if isinstance(path, tuple) and len(path) == 2 and path[0] == "random":
+                path_seed = int(path[1])
+            else:
+                order = _path_order(path, N, pdom)
+            dist = _distance(p)
+            if dist is not None and not isinstance(dist, str) and mask != "after":
+                raise NotImplementedError("the haversine search distance needs mask='after'")
+            dlocs, zd = _initbuff(self.engine, self.globals.get("init", "nearest"), cent, data, var, pdom)
+            _, nmax = searcher_ui(pdom, p["maxneighbors"], p["distance"], p["neighborhood"])
+            radius, radii = _ball(p["neighborhood"])
+
+            def draw(h, seed, first, count, rule=(kind, cut, fs, zmin, zmax, tail)):
+                return h.realize_indicator(*rule, seed, first, count)
+
+            labels = None if p["categories"] is None else np.asarray(p["categories"])
+            pre[var] = dict(labels=labels, plan=_SGSPlan(
+                self.engine, (p["variogram"], cent, dlocs, zd, 0.0, nmax, p["minneighbors"], radius, radii), N, path_seed,
+                order, mask == "after", dist, draw=draw, **_rot_kw(p["neighborhood"])))
+        pre["_run"] = _run_state(self, problem)
+        return pre
+
+    @staticmethod
+    def _labelled(q, y):
+        y = _host(y)
+        return y if q["labels"] is None else q["labels"][y.astype(np.int64)]
+
+    def solvesingle(self, problem, covars, preproc):
+        r = _next_real(preproc, covars)
+        run = preproc["_run"]
+        return {var: self._labelled(preproc[var], preproc[var]["plan"].realize(run["seed"] + run["vindex"][var], r, 1))[0]
+                for var in covars}
+
+    def solve(self, problem, gather: bool = True):
+        pre = self.preprocess(problem)
+        run = pre["_run"]
+        rank, ws = parallel.world()
+        lo, hi = parallel.shard_range(problem.nreals, rank, ws)
+        reals = {}
+        for var in problem.variables:
+            plan = pre[var]["plan"]
+            y = _host(plan.realize(run["seed"] + run["vindex"][var], lo, hi - lo))
+            plan.close()
+            if gather and ws > 1:
+                y = parallel.all_gather_concat(y, problem.nreals)
+            y = self._labelled(pre[var], y)
+            reals[var] = [y[r] for r in range(y.shape[0])]
+        return Ensemble(problem.domain, reals)
 
 
 def postik(solution: GeoTable, var: str, zmin, zmax, tail_power=(1.0, 1.0), thresholds=(), probs=(), cutoffs=None,

@@ -1204,10 +1204,14 @@ class _SGSPlan:
     """What SGS.preprocess hands to solvesingle / solve for one variable.  A shared visiting order (LinearPath, an
     explicit order) is one device handle: stage A once, lanes = realisations.  `path=("random", seed)` is a RandomPath:
     the reference draws a new permutation in every solvesingle (seq.jl:99-102), so realisation r gets the permutation
-    `default_rng([seed, r])` and the handles are built per block of realisations, on demand."""
+    `default_rng([seed, r])` and the handles are built per block of realisations, on demand.
+    `draw(handle, seed, first, count)`: what a handle is asked for; None: its Gaussian `realize` (SISSolver passes the
+    indicator recursion on the same handles)."""
 
-    def __init__(self, engine, make_args, N, path_seed=None, order=None, mask_after=True, distance=None, rotation=None):
+    def __init__(self, engine, make_args, N, path_seed=None, order=None, mask_after=True, distance=None, rotation=None,
+                 draw=None):
         self.engine, self.args, self.N = engine, make_args, N
+        self.draw = draw or (lambda h, seed, first, count: h.realize(seed, first, count))
         self.path_seed, self.order = path_seed, order
         self.kw = dict(mask_after_search=True) if mask_after else {}
         if distance not in (None, "euclidean"):
@@ -1226,14 +1230,14 @@ class _SGSPlan:
         if self.path_seed is None:
             if self.shared is None:
                 self.shared = self.engine.SGS(vg, cent, self.order, dlocs, zd, mean, nmax, nmin, radius, radii, **self.kw)
-            return self.shared.realize(seed, first, count)
+            return self.draw(self.shared, seed, first, count)
         out = []
         for a in range(first, first + count, SGS_PATHS_PER_HANDLE):
             b = min(a + SGS_PATHS_PER_HANDLE, first + count)
             paths = np.stack([self.path_of(r) for r in range(a, b)])
             h = self.engine.SGS(vg, cent, paths, dlocs, zd, mean, nmax, nmin, radius, radii, path_base=a, **self.kw)
             try:
-                out.append(h.realize(seed, a, b - a))
+                out.append(self.draw(h, seed, a, b - a))
             finally:
                 h.close()
         return np.concatenate(out, axis=0)
@@ -1312,6 +1316,66 @@ class SGS(_Solver):
                 y = parallel.all_gather_concat(y, problem.nreals)
             reals[var] = [y[r] for r in range(y.shape[0])]
         return Ensemble(problem.domain, reals)
+
+
+# ------------------------------------------------------------------------------------------
+# CookieCutter
+# ------------------------------------------------------------------------------------------
+def _show(solver) -> str:
+    """`show(io, solver)` of a solver: its own repr where it has one, else the name of its type."""
+    return type(solver).__name__ if type(solver).__repr__ is object.__repr__ else repr(solver)
+
+
+class CookieCutter:
+    """cookie.jl:27-83: `master` simulates one (facies) variable; every other variable of the problem is taken, cell by
+    cell, from the realisation of `others[v]` where the master realisation equals `v`.  Cells whose master value has no
+    entry in `others` are NaN (the reference leaves them undefined).  Host logic only: the masking runs on whatever
+    arrays the sub-solvers return."""
+
+    def __init__(self, master, others):
+        self.master = master
+        self.others = dict(others)
+
+    def __repr__(self):                                                               # cookie.jl:89-91
+        return "CookieCutter"
+
+    def describe(self) -> str:                                                        # cookie.jl:93-99
+        lines = ["CookieCutter", f"  └─{tuple(self.master.vparams)[0]} ⇨ {_show(self.master)}"]
+        lines += [f"    └─{val} ⇨ {_show(s)}" for val, s in self.others.items()]
+        return "\n".join(lines)
+
+    __str__ = describe
+
+    def solve(self, problem: SimulationProblem, **kw):
+        mvars = tuple(self.master.vparams)
+        if len(mvars) != 1:
+            raise ValueError("one single variable must be specified in master solver")
+        mvar = mvars[0]
+        if mvar not in problem.variables:
+            raise ValueError("invalid variable in master solver")
+        ovars = tuple(v for v in problem.variables if v != mvar)
+        if not ovars:
+            raise ValueError("cookie-cutter requires problem with more than one target variable")
+        head = (problem.data, problem.domain) if problem.data is not None else (problem.domain,)
+        mreals = solve(SimulationProblem(*head, mvar, problem.nreals), self.master, **kw)[mvar]
+        oproblem = SimulationProblem(*head, ovars, problem.nreals)
+        reals = {}
+        for mval, osolver in self.others.items():
+            osol = solve(oproblem, osolver, **kw)
+            for var in ovars:
+                for i, vals in enumerate(osol[var]):
+                    if var not in reals:
+                        reals[var] = [None] * len(osol[var])
+                    if reals[var][i] is None:
+                        reals[var][i] = vals.new_full(vals.shape, float("nan")) if hasattr(vals, "new_full") else \
+                            np.full(np.shape(vals), np.nan)
+                    mask = np.asarray(_host(mreals[i])) == mval
+                    if hasattr(vals, "is_cuda"):
+                        import torch
+                        mask = torch.as_tensor(mask, device=vals.device)
+                    reals[var][i][mask] = vals[mask]                                  # cookie.jl:74-75
+        reals[mvar] = mreals
+        return Ensemble(problem.domain, {v: reals[v] for v in problem.variables})
 
 
 def solve(problem, solver, **kw):

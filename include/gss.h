@@ -909,6 +909,40 @@ int32_t gss_sgs_realize(gss_sgs_t* h, uint64_t seed, int64_t first_real, int64_t
 #define GSS_SGS_SCHEDULE_WORDS 7
 int32_t gss_sgs_schedule(gss_sgs_t* h, int32_t* out, int32_t n);
 
+/* ---- SIS: sequential indicator simulation (GSLIB sisim, median form) on an SGS handle -----------------------------
+ * (The reference has no indicator simulator; the conventions are this library's own, those of the indicator-kriging
+ * section below.)  Median indicator kriging has one variogram for all cutoffs, hence one simple-kriging weight vector
+ * per node: a handle of gss_sgs_create / gss_sgs_create_paths built with the INDICATOR variogram holds the whole
+ * realisation-independent part.  Its mean and sigma are not used; its zdata are the values at the conditioning cells
+ * (categorical kind: codes 0 .. K-1 stored as doubles).
+ *
+ * Per node, for each realisation, with the node's list idx[0 .. ncond-1] and weights w taken in list order:
+ *   GSS_SIS_CONTINUOUS   1 <= K <= 16 strictly increasing finite cutoffs, fstar in [0, 1] and non-decreasing,
+ *       zmin < c_0, zmax > c_{K-1}, w_lo, w_hi > 0.  F_q = F*_q + sum_j w_j ((z_j <= c_q) - F*_q), the sum by fma in list
+ *       order (no neighbours: the marginal F*); the order-relation correction of the indicator-kriging section (the same
+ *       doubles); the value is the smallest z with F(z) >= u under the ccdf model of gss_ik_post (linear inside classes,
+ *       power tails to zmin / zmax, a flat segment returns its left end).
+ *   GSS_SIS_CATEGORICAL  2 <= K <= 16 categories, cutoffs NULL, fstar the K global proportions (each in [0, 1], summing
+ *       to 1 within 1e-9).  p_s = p*_s + sum_j w_j ((z_j == s) - p*_s), each clipped to [0, 1]; divided by the clipped sum
+ *       where that is positive, else p*; cumulated in category order; the draw is the first category s with u < cum_s, or,
+ *       if rounding at the top leaves none, the last one with a positive probability.  The output is the code as a double.
+ *       The codes in the handle's zdata are checked in the call, on a host copy: integral and in 0 .. K-1.
+ *   Data cells keep their zdata.
+ * cutoffs, fstar: HOST memory.  uniforms: NULL, or nreals x N in `mem`; NULL: the uniform of (realisation r, cell c) is
+ * element c of gss_philox_uniform(seed, first_real + r, N).  out: nreals x N in `mem`; host output goes through the
+ * output ring in blocks, as gss_sgs_realize, whose realisation-range rule for handles with one visiting order per
+ * realisation holds here too.  GSS_ERR_INVALID before any launch: K out of range, bad cutoffs, proportions or tails, a
+ * NULL out with nreals > 0, an unknown kind, a zdata that is no code.
+ * Sweeps: level by level where the handle has levels (a team schedule is not used: node-major field, a launch per
+ * level), along the path where it has none or where its levels hold fewer than 2 simulated nodes on average (DESIGN.md
+ * section 4; the environment variable GSS_SIS_WALK_BELOW, read at every call, replaces the 2).  Every sweep gives the
+ * same bits.  Not offered: full indicator simulation (one variogram per cutoff needs K sets of weights), ordinary
+ * indicator kriging inside the recursion (stage A is simple kriging).  Profile scopes: "sis_fill", "sis_sweep". */
+enum { GSS_SIS_CONTINUOUS = 0, GSS_SIS_CATEGORICAL = 1 };
+int32_t gss_sis_realize(gss_sgs_t* h, int32_t kind, const double* cutoffs, int32_t K, const double* fstar,
+                        double zmin, double zmax, double w_lo, double w_hi, uint64_t seed, int64_t first_real,
+                        int64_t nreals, const double* uniforms, double* out, int32_t mem, void* stream);
+
 /* ---- normal-score transform: skewed data into Gaussian space and realisations back (GSLIB nscore / backtr, the
  * reversible Quantile() step of a GeoStats pipeline).  Not in the reference's solvers; DESIGN.md section 4.
  *   Fit (host, preprocess): n >= 1 finite values z with optional weights w (finite, > 0; NULL = 1) are sorted stably,
