@@ -568,8 +568,11 @@ __device__ __attribute__((noinline)) static double gss_matern_general(double d, 
   if (d > 700.0) return 0.0;
   const int n = (int)floor(nu + 0.5);
   const double mu = nu - (double)n;
-  // (2 / d)^nu would overflow: the correlation differs from 1 by O(d^2) there (only reachable with nu > 1)
-  if (nu * log(2.0 / d) > 690.0) return 1.0;
+  // K_nu(d) ~ Gamma(nu) / 2 (2 / d)^nu would overflow (ln Gamma(nu) bounded from above by Stirling's series cut after
+  // its 1 / (12 nu)): the correlation is 1 - d^2 / (4 (nu - 1)) + O(d^4) there (only reachable with nu > 1).  Without
+  // the Gamma term the product 0 * inf came out as NaN in a window above the guard from nu ~ 13 on (d up to 2e-5 at
+  // nu = 50), and the plain 1 was 2e-14 off at nu = 50 (tests/test_gpu_cov_probe.py).
+  if (nu * log(2.0 / d) + ((nu - 0.5) * log(nu) - nu + 1.01) > 690.0) return 1.0 - d * d / (4.0 * (nu - 1.0));
   const double t = 8.0 * mu * mu - 1.0;
   const double g1 = gss_clenshaw(GSS_TEMME_G1, t), g2 = gss_clenshaw(GSS_TEMME_G2, t);
   const double gampl = g2 - mu * g1;  // 1 / Gamma(1 + mu)

@@ -136,6 +136,10 @@ def _shape(vg: Variogram, x: np.ndarray) -> np.ndarray:
         from scipy.special import gamma, kv
         with np.errstate(invalid="ignore", over="ignore"):
             val = 1.0 - (2.0 ** (1.0 - nu) / gamma(nu)) * d ** nu * kv(nu, d)
+        if nu > 1.0:
+            # d^nu underflows or K_nu overflows at a tiny d (0 * inf): the series there is 1 - d^2 / (4 (nu - 1)) + ...,
+            # the next terms O(d^4) and O(d^(2 nu)) being far below a rounding where that happens (d < 1e-4 for nu <= 50)
+            val = np.where(np.isfinite(val) | (d >= 1e-3), val, d * d / (4.0 * (nu - 1.0)))
         return np.where(d > 0, val, 0.0)
     raise ValueError(k)
 

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Random hunt over the covariance evaluation on the device (gss_cov_pairwise) against the oracle: every stationary model,
 Matern of any order in (0, 12], nested models of up to four structures, anisotropy, dimensions 1..3, lags from 0 and 1e-9
-to thousands of ranges.  python3 tools/hunt_covariance.py [seed] [cases]"""
+to thousands of ranges.  python3 tools/hunt_covariance.py [seed] [cases]
+
+The deterministic counterpart is tests/test_gpu_cov_probe.py: every evaluation form (not only gss_cov_pairwise) at the
+floating-point neighbours of each switch inside the evaluators, against 50-digit values (tests/cov_probe.py)."""
 import os
 import sys
 
