@@ -915,6 +915,7 @@ int32_t gss_shutdown(void) {
   GSS_ENTRY();
   free_bounce_buffers();
   vario_release();
+  spde_release();
   std::lock_guard<std::mutex> lock(g_pool_mu);
   for (auto& b : g_pool) (void)hipFree(b.p);
   g_pool.clear();

@@ -1119,6 +1119,7 @@ int32_t knn_index_build_device(const double* xdev, int64_t n, int dim, KnnIndex*
 // gss_stat counters "vario_tiles_total" / "vario_tiles_opened" of the last gss_variogram_empirical; -1: not one of them
 int32_t vario_stat(const char* name, int64_t* value);
 void vario_release();   // gss_shutdown: the page-locked counter and its event
+void spde_release();    // gss_shutdown: the page-locked "all columns done" word of gss_spde_realize (spde.hip)
 
 // ---------------------------------------------------------------------------------------------
 // noise (noise.hip)

@@ -4,11 +4,11 @@ The package holds only what the hot path needs: the ctypes binding of the C-ABI 
 array-level engine (`engine`), the minimal geospatial containers the solvers read (`geo`), and the
 solver front-ends (`solvers`) that mirror the reference's `solve(problem, solver)` API.
 """
-from .geo import (CartesianGrid, Composition, DomainView, Ensemble, GeoTable, PointSet, aitchison, asarray, domain,
-                  georef, parent, parentindices, view)
+from .geo import (CartesianGrid, Composition, DomainView, Ensemble, GeoTable, PointSet, SimpleMesh, aitchison, asarray,
+                  domain, georef, parent, parentindices, triangulate, view)
 from .problems import EstimationProblem, SimulationProblem
-from .solvers import (FFTGS, LUGS, SGS, CoKrigingSolver, CookieCutter, ExpWeight, IDWSolver, KrigingSolver, LWRSolver,
-                      TricubeWeight, kriging_ui, searcher_ui, simulate_with_generic_loop, solve)
+from .solvers import (FFTGS, LUGS, SGS, SPDEGS, CoKrigingSolver, CookieCutter, ExpWeight, IDWSolver, KrigingSolver,
+                      LWRSolver, TricubeWeight, kriging_ui, searcher_ui, simulate_with_generic_loop, solve)
 from .indicator import IndicatorKrigingSolver, SISSolver, postik
 from .transforms import InNormalScores, NormalScore
 from .validation import (BlockValidation, CrossValidationResult, KFoldValidation, LeaveBallOut, LeaveOneOut,

@@ -21,13 +21,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSS_LIB_PATH") or os.path.normpath(os.path.join(_HERE, "..", "lib", "libgss_hip.so"))
 
 MEM_HOST, MEM_DEVICE = 0, 1
-OK, ERR_INVALID, ERR_HIP, ERR_NOT_POSDEF, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_ALLOC = range(7)
+OK, ERR_INVALID, ERR_HIP, ERR_NOT_POSDEF, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_ALLOC, ERR_NO_CONVERGENCE = range(8)
 KRIG_NO_FACTOR = 1
 KRIG_ASYNC_FIT = 2
 FFTGS_NO_SPECTRUM = 1
 FFTGS_LMC_NUGGET_SALT = 0x6e75676765744c4d      # gss.h, GSS_FFTGS_LMC_NUGGET_SALT
 LUGS_NO_FACTOR = 1
 LUGS_FACT_LU = 2
+SPDE_NOISE_REFERENCE, SPDE_NOISE_LUMPED = 0, 1
 SGS_MASK_AFTER_SEARCH = 1
 SGS_METRIC_SHIFT = 4
 SIS_CONTINUOUS, SIS_CATEGORICAL = 0, 1
@@ -144,6 +145,12 @@ SIGNATURES = {
     "gss_lugs_state_buffer": [_p, C.POINTER(_p), C.POINTER(_i64)],
     "gss_lugs_adopt_state": [_p],
     "gss_lugs_realize": [_p, _u64, _i64, _i64, _p, _f64, _p, _p, _p, _i32, _p],
+    "gss_spde_create": [C.POINTER(_p), _p, _i64, _i32, _p, _i64, _f64, _f64, _i32, _i32, _p],
+    "gss_spde_destroy": [_p],
+    "gss_spde_info": [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f64)],
+    "gss_spde_operator": [_p, _p, _p, _p, _p, _i32, _p],
+    "gss_spde_realize": [_p, _u64, _i64, _i64, _p, _f64, _i64, _p, _p, _i32, _p],
+    "gss_spde_last_solve": [_p, C.POINTER(_i64), C.POINTER(_f64), C.POINTER(_i64)],
     "gss_nscore_create": [C.POINTER(_p), _p, _p, _i64, _f64, _f64, _f64, _f64, _p],
     "gss_nscore_destroy": [_p],
     "gss_nscore_info": [_p, C.POINTER(_i64)],

@@ -504,6 +504,71 @@ class LUGSHandle(_NativeState):
         return out, wout
 
 
+class SPDEHandle:
+    """gss_spde_t*: the CSR of S = kappa^2 M - B of a triangle mesh in HBM; every realisation is one sparse solve."""
+
+    NOISE = {"reference": _lib.SPDE_NOISE_REFERENCE, "lumped": _lib.SPDE_NOISE_LUMPED}
+
+    def __init__(self, vertices, triangles, sill=1.0, range=1.0, noise="reference"):
+        """`vertices` (nv, 2 or 3) and `triangles` (nt, 3; 0-based) as numpy arrays or CUDA tensors (both in one
+        space).  `noise`: "reference" (spde.jl:98, w ~ N(0, I)) or "lumped" (Lindgren's w ~ N(0, inv(M)))."""
+        if noise not in self.NOISE:
+            raise ValueError(f"noise={noise!r}: 'reference' or 'lumped'")
+        self._l = _lib.lib()
+        dev = st.same_space("vertices and triangles", vertices, triangles)
+        v = st.samples(vertices, dev)
+        t = st.prep(triangles, np.int64)
+        if v.ndim != 2 or t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("vertices (nv, d) and triangles (nt, 3)")
+        h = C.c_void_p()
+        check(self._l.gss_spde_create(C.byref(h), ptr(v), v.shape[0], v.shape[1], ptr(t), t.shape[0], float(sill),
+                                      float(range), self.NOISE[noise], st.mem_flag(v), current_stream()))
+        self._h = h
+        nv, nt, nnz, tau2 = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        check(self._l.gss_spde_info(h, C.byref(nv), C.byref(nt), C.byref(nnz), C.byref(tau2)))
+        self.nv, self.nt, self.nnz, self.tau2 = nv.value, nt.value, nnz.value, tau2.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.gss_spde_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def operator(self):
+        """(rowptr, col, val, mass): the CSR of S (columns ascending within a row) and diag(M), on the host."""
+        rowptr, col = np.empty(self.nv + 1, dtype=np.int64), np.empty(self.nnz, dtype=np.int32)
+        val, mass = np.empty(self.nnz), np.empty(self.nv)
+        check(self._l.gss_spde_operator(self._h, ptr(rowptr), ptr(col), ptr(val), ptr(mass), MEM_HOST,
+                                        current_stream()))
+        return rowptr, col, val, mass
+
+    def realize(self, seed, first_real, nreals, noise=None, rtol=None, maxiter=None, vertices=False, device=False):
+        """Element values (nreals, nt) of realisations first_real .. first_real + nreals - 1; `vertices=True`: the pair
+        (vertex values (nreals, nv), element values).  `noise`: (nreals, nv) normals instead of the Philox stream of
+        `seed`.  A column that does not converge raises GSSError (ERR_NO_CONVERGENCE); `last_solve()` has the counts."""
+        noise = st.prep(noise)
+        dev = bool(device) or st.on_device(noise)
+        if noise is not None:
+            if dev and not st.on_device(noise):
+                raise ValueError("device=True needs the noise as a CUDA tensor")
+            if tuple(noise.shape) != (nreals, self.nv):
+                raise ValueError(f"noise must be (nreals, nv) = ({nreals}, {self.nv}), got {tuple(noise.shape)}")
+        where = noise if st.on_device(noise) else dev
+        eout = st.empty(where, (nreals, self.nt))
+        vout = st.empty(where, (nreals, self.nv)) if vertices else None
+        check(self._l.gss_spde_realize(self._h, int(seed), int(first_real), int(nreals), ptr(noise),
+                                       0.0 if rtol is None else float(rtol), 0 if maxiter is None else int(maxiter),
+                                       ptr(vout), ptr(eout), st.mem_flag(eout), current_stream()))
+        return (vout, eout) if vertices else eout
+
+    def last_solve(self):
+        """(largest iteration count of a column, largest final ||r|| / ||b||, unconverged columns) of the last realize."""
+        it, rel, un = C.c_int64(), C.c_double(), C.c_int64()
+        check(self._l.gss_spde_last_solve(self._h, C.byref(it), C.byref(rel), C.byref(un)))
+        return it.value, rel.value, un.value
+
+
 class SGSHandle:
     """gss_sgs_t*: neighbour lists, simple-kriging weights and sigmas of every path node in HBM.
 
@@ -739,6 +804,7 @@ class HipEngine:
     FFTGS_LMC = FFTGSHandle.lmc
     LUGS = LUGSHandle
     SGS = SGSHandle
+    SPDE = SPDEHandle
 
     @staticmethod
     def nscore(values, weights=None, tails=None, tail_power=(1.0, 1.0)):

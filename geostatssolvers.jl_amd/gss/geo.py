@@ -85,6 +85,53 @@ class CartesianGrid(Domain):
                 and np.array_equal(self.origin, other.origin) and np.array_equal(self.spacing, other.spacing))
 
 
+class SimpleMesh(Domain):
+    """SimpleMesh(vertices, triangles): vertices (nv, 2 or 3), triangles (nt, 3) 0-based vertex indices.  The elements
+    are the triangles (spde.jl:108-109 hands back one value per element); the SPDE operators live on the vertices."""
+
+    def __init__(self, vertices, triangles):
+        v = np.ascontiguousarray(vertices, dtype=np.float64)
+        t = np.ascontiguousarray(triangles, dtype=np.int64)
+        if v.ndim != 2 or t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("SimpleMesh(vertices, triangles): vertices (nv, d) and triangles (nt, 3)")
+        self.vertices, self.triangles = v, t
+
+    @property
+    def nvertices(self):
+        return self.vertices.shape[0]
+
+    def nelements(self):
+        return self.triangles.shape[0]
+
+    def embeddim(self):
+        return self.vertices.shape[1]
+
+    def centroids(self):
+        return np.ascontiguousarray(self.vertices[self.triangles].mean(axis=1))
+
+    def __eq__(self, other):
+        return (isinstance(other, SimpleMesh) and np.array_equal(self.vertices, other.vertices)
+                and np.array_equal(self.triangles, other.triangles))
+
+
+def triangulate(grid: "CartesianGrid") -> SimpleMesh:
+    """The 2-D grid as a triangle mesh: the vertices are the (nx + 1)(ny + 1) grid nodes, x fastest, and every cell
+    (i, j) is split along the diagonal from its node (i, j) to its node (i + 1, j + 1) into two counter-clockwise
+    triangles, the lower right one first."""
+    if not isinstance(grid, CartesianGrid) or len(grid.dims) != 2:
+        raise ValueError("triangulate: a 2-D CartesianGrid")
+    nx, ny = grid.dims
+    xs = grid.origin[0] + np.arange(nx + 1) * grid.spacing[0]
+    ys = grid.origin[1] + np.arange(ny + 1) * grid.spacing[1]
+    X, Y = np.meshgrid(xs, ys, indexing="xy")
+    vertices = np.stack([X.ravel(), Y.ravel()], axis=1)
+    i, j = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
+    n00 = (j * (nx + 1) + i).ravel()
+    n10, n01, n11 = n00 + 1, n00 + nx + 1, n00 + nx + 2
+    tri = np.stack([np.stack([n00, n10, n11], axis=1), np.stack([n00, n11, n01], axis=1)], axis=1).reshape(-1, 3)
+    return SimpleMesh(vertices, tri)
+
+
 class DomainView(Domain):
     """view(domain, inds): subset of a parent domain (fft.jl:66 `parent`, :152 `parentindices`)."""
 

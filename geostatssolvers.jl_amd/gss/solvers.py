@@ -20,9 +20,9 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import parallel
+from . import _lib, parallel
 from .engine import EDK, OK, SK, UK, default_engine
-from .geo import Composition, Ensemble, GeoTable, PointSet, georef, parent, parentindices
+from .geo import Composition, Ensemble, GeoTable, PointSet, SimpleMesh, georef, parent, parentindices
 from .problems import EstimationProblem, SimulationProblem
 from .variograms import GaussianVariogram, MetricBall, VariogramModel
 
@@ -1192,6 +1192,71 @@ class LUGS(_Solver):
                     y = parallel.all_gather_concat(y, problem.nreals)
                 reals[v] = [y[r] for r in range(y.shape[0])]
         return Ensemble(problem.domain, {v: reals[v] for v in problem.variables})
+
+
+# ------------------------------------------------------------------------------------------
+# SPDEGS
+# ------------------------------------------------------------------------------------------
+class SPDEGS(_Solver):
+    """spde.jl:23-115 on a `SimpleMesh`: one sparse solve per realisation instead of the dense factor of the precision
+    (gss.h "SPDEGS").  `noise`: "reference" (spde.jl:98, w ~ N(0, I)) or "lumped" (Lindgren's w ~ N(0, inv(M)))."""
+    PARAMS = dict(sill=1.0, range=1.0)                                                        # spde.jl:24-25
+    GLOBALS = dict(rng=None, noise="reference", rtol=1e-10, maxiter=None)
+
+    def preprocess(self, problem: SimulationProblem):
+        """spde.jl:29-76: one handle per distinct (sill, range); every rank builds its own (assembly is cheap)."""
+        if problem.data is not None:
+            raise NotImplementedError("conditional simulation is not implemented")           # spde.jl:30
+        mesh = problem.domain
+        if not isinstance(mesh, SimpleMesh):
+            raise ValueError(f"SPDEGS needs a SimpleMesh domain, got {type(mesh).__name__}: triangulate(grid) turns a "
+                             f"2-D CartesianGrid into one")
+        handles, pre = {}, {}
+        for conames in self.covariables(problem):
+            for var in conames:
+                p = self.params(var)
+                sill, rng_ = float(p["sill"]), float(p["range"])
+                assert sill > 0, "sill must be positive"                                     # spde.jl:53
+                assert rng_ > 0, "range must be positive"                                    # spde.jl:54
+                if (sill, rng_) not in handles:
+                    handles[sill, rng_] = self.engine.SPDE(mesh.vertices, mesh.triangles, sill=sill, range=rng_,
+                                                           noise=self.globals["noise"])
+                pre[var] = handles[sill, rng_]
+        pre["_handles"] = list(handles.values())
+        pre["_run"] = _run_state(self, problem)
+        return pre
+
+    def _block(self, pre, var, lo, count):
+        """spde.jl:78-115 for realisations lo .. lo+count-1 of one variable -> (count, nelements)."""
+        run = pre["_run"]
+        try:
+            return pre[var].realize(run["seed"] + run["vindex"][var], lo, count, rtol=self.globals["rtol"],
+                                    maxiter=self.globals["maxiter"])
+        except _lib.GSSError as e:
+            if e.code != _lib.ERR_NO_CONVERGENCE:
+                raise
+            raise RuntimeError(str(e)) from None
+
+    def solvesingle(self, problem: SimulationProblem, covars, preproc):
+        """spde.jl:78-115 with the reference's signature: one realisation per call, no index (see _run_state)."""
+        r = _next_real(preproc, covars)
+        return {v: self._block(preproc, v, r, 1)[0] for v in covars}
+
+    def solve(self, problem: SimulationProblem, gather: bool = True):
+        pre = self.preprocess(problem)
+        rank, ws = parallel.world()
+        lo, hi = parallel.shard_range(problem.nreals, rank, ws)
+        reals = {}
+        try:
+            for var in problem.variables:
+                y = self._block(pre, var, lo, hi - lo)
+                if gather and ws > 1:
+                    y = parallel.all_gather_concat(y, problem.nreals)
+                reals[var] = [y[r] for r in range(y.shape[0])]
+        finally:
+            for h in pre["_handles"]:
+                h.close()
+        return Ensemble(problem.domain, reals)
 
 
 # ------------------------------------------------------------------------------------------

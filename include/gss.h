@@ -59,7 +59,8 @@ enum {
   GSS_ERR_NOT_POSDEF = 3,   /* covariance factorisation hit a non-positive pivot                  */
   GSS_ERR_UNSUPPORTED = 4,  /* feature outside the hot-path scope           */
   GSS_ERR_NO_DEVICE = 5,
-  GSS_ERR_ALLOC = 6
+  GSS_ERR_ALLOC = 6,
+  GSS_ERR_NO_CONVERGENCE = 7 /* an iterative solve reached its iteration limit (gss_spde_realize)   */
 };
 
 enum { GSS_MEM_HOST = 0, GSS_MEM_DEVICE = 1 };
@@ -124,6 +125,7 @@ enum { GSS_PT_OK = 0, GSS_PT_MISSING = 1, GSS_PT_SINGULAR = 2 };
 typedef struct gss_krig gss_krig_t;
 typedef struct gss_fftgs gss_fftgs_t;
 typedef struct gss_lugs gss_lugs_t;
+typedef struct gss_spde gss_spde_t;
 typedef struct gss_sgs gss_sgs_t;
 
 /* ---- library ------------------------------------------------------------------------------ */
@@ -852,6 +854,59 @@ int32_t gss_lugs_adopt_state(gss_lugs_t* h);
 int32_t gss_lugs_realize(gss_lugs_t* h, uint64_t seed, int64_t first_real, int64_t nreals,
                          const double* noise, double rho, const double* w1, double* out, double* w_out,
                          int32_t mem, void* stream);
+
+/* ---- SPDEGS (spde.jl:29-115; Lindgren et al. 2011) -------------------------------------------
+ * Gaussian simulation on a triangle mesh.  The reference forms the dense precision Q = A'A / tau^2 with
+ * A = kappa^2 I - inv(M) B, factorises it and draws z = L w with L L' = inv(Q) (spde.jl:60-68, 98-99).  The same
+ * distribution is z = tau inv(A) w, i.e. one sparse symmetric positive definite solve per realisation,
+ *     (kappa^2 M - B) z = tau M w,
+ * which is what this handle does: S = kappa^2 M - B is assembled once in CSR and every block of realisations is one
+ * Jacobi-preconditioned conjugate-gradient run over interleaved columns ("SPDEGS").
+ *
+ * Operators ([DEP] Meshes.jl `laplacematrix` / `measurematrix`, written out).  For a triangle (a, b, c) with area
+ * T > 0 (in 3-D half the norm of the cross product) the angle at c is opposite the edge (a, b) and
+ * cot_c = ((a - c) . (b - c)) / (2 T).  The triangle adds +cot_c / 2 to B[a][b] and B[b][a], -cot_c / 2 to B[a][a] and
+ * B[b][b], and T / 3 to the lumped mass M[a][a]; cyclically for the other two corners.  kappa = 1 / range; with the
+ * parameter dimension d = 2 of a surface and alpha = 2, nu = alpha - d / 2 = 1 and
+ * tau^2 = sill^2 kappa^(2 nu) (4 pi)^(d/2) Gamma(alpha) / Gamma(nu) = 4 pi sill^2 kappa^2.  The reference squares
+ * `sill` (spde.jl:50, 63) and so does the library: the parameter acts as a standard deviation.
+ *
+ * Noise.  GSS_SPDE_NOISE_REFERENCE is the reference's w ~ N(0, I) (right-hand side tau M w), whose vertex variance
+ * scales with the vertex area; GSS_SPDE_NOISE_LUMPED is Lindgren's lumped discretisation Q = A' M A / tau^2, i.e.
+ * w ~ N(0, inv(M)) (right-hand side tau M^(1/2) w with w ~ N(0, I)), whose variance does not.
+ *
+ * Refusals, before any other device work (host arrays are checked on the host, device arrays on the device).
+ * GSS_ERR_INVALID: a coordinate that is not finite, sill <= 0 or range <= 0 (spde.jl:53-54), an index outside
+ * [0, nv), a triangle with a repeated vertex or without area, a vertex that belongs to no triangle (M singular: the
+ * reference's inv(M) fails there too), nv < 3 or nt < 1.  GSS_ERR_UNSUPPORTED: dim outside {2, 3}, nv >= 2^31 - 1,
+ * 12 nt >= 2^31 (the assembly sorts 12 contributions per triangle with 32-bit positions).
+ * The assembly uses no floating-point atomics: the twelve contributions of every triangle are sorted by (row, column)
+ * with a stable radix sort and summed in triangle order, so equal inputs give equal bits.
+ */
+enum { GSS_SPDE_NOISE_REFERENCE = 0,   /* b = tau M w       (spde.jl:98-99, w ~ N(0, I))        */
+       GSS_SPDE_NOISE_LUMPED    = 1 }; /* b = tau M^(1/2) w (Lindgren 2011: Q = A' M A / tau^2) */
+int32_t gss_spde_create(gss_spde_t** out, const double* vertices, int64_t nv, int32_t dim /* 2 or 3 */,
+                        const int64_t* triangles, int64_t nt /* nt x 3, 0-based */,
+                        double sill, double range, int32_t flags, int32_t mem, void* stream);
+int32_t gss_spde_destroy(gss_spde_t* h);
+int32_t gss_spde_info(const gss_spde_t* h, int64_t* nv, int64_t* nt, int64_t* nnz, double* tau2);
+/* parity: CSR of S = kappa^2 M - B (rowptr nv+1, col nnz, val nnz; columns ascending within a row) and diag(M);
+ * any of the four may be NULL */
+int32_t gss_spde_operator(gss_spde_t* h, int64_t* rowptr, int32_t* col, double* val, double* mass,
+                          int32_t mem, void* stream);
+/* realisations first_real .. first_real+nreals-1.  noise == NULL: w = gss_philox_normal(seed, r, nv); else
+ * nreals x nv normals supplied (parity mode).  vout (nreals x nv, may be NULL): vertex values z.  eout (nreals x nt,
+ * may be NULL): element values, the mean of the three vertex values (spde.jl:108-109, `integrate` of the piecewise
+ * linear field divided by the element's area).  At least one of the two outputs.
+ * rtol <= 0: 1e-10; maxiter <= 0: 20 000.  A column stops (and its solution is no longer touched) once its recursive
+ * residual satisfies ||r|| <= rtol ||b||; a column that reaches maxiter makes the call return GSS_ERR_NO_CONVERGENCE
+ * after every output has been written, the message names the first such realisation and its residual.
+ * Realisation r depends on (seed, r) and the mesh only: splitting a call, another first_real or other companions in
+ * the block give the same bits.  Profile scopes: "spde_assemble", "spde_cg". */
+int32_t gss_spde_realize(gss_spde_t* h, uint64_t seed, int64_t first_real, int64_t nreals, const double* noise,
+                         double rtol, int64_t maxiter, double* vout, double* eout, int32_t mem, void* stream);
+/* after a realize: largest iteration count of any column, largest final ||r||/||b||, columns that did not converge */
+int32_t gss_spde_last_solve(const gss_spde_t* h, int64_t* iters, double* relres, int64_t* unconverged);
 
 /* ---- SGS -----------------------------------------------------------
  * gss_sgs_create replaces SGS.preprocess (sgs.jl:56-85: SimpleKriging(variogram, mean) and the marginal
