@@ -21,6 +21,11 @@
 //   spde_update_kernel  alpha = (r.z) / (p.Ap) from the slab, x += alpha p, r -= alpha Ap, partials of r.z and r.r
 // Every column has its own scalars; one that has converged is skipped by both kernels from then on.  The host reads
 // one page-locked word ("all columns done") every SPDE_POLL iterations and nothing else.
+//
+// Data (not in the reference; gss.h, "SPDEGS with data"): conditioning by kriging in the data space.  The same CG loop
+// (spde_cg_block) solves W = inv(S) P' once per data set; a block of realisations is then the unconditional solve, the
+// residuals at the observations, two triangular products with the factor of P Sigma P' + R, the tall-skinny product
+// s^2 . (W lambda) (spde_combine_kernel) and a second solve.
 #include "gss_internal.h"
 
 #include <hipcub/hipcub.hpp>
@@ -324,8 +329,9 @@ __global__ __launch_bounds__(SPDE_THREADS) void spde_finish_kernel(const double*
 
 // r = b = bscale w for the nb columns of the block (zero beyond), one thread per vertex: the normals are read (or
 // drawn) realisation-major, the block is written as one contiguous row per vertex
+// (ldn: doubles between two realisations of `noise`: nv, or nv + nd when the handle carries data)
 template <int NB>
-__global__ __launch_bounds__(256) void spde_rhs_kernel(const double* __restrict__ noise, uint64_t seed,
+__global__ __launch_bounds__(256) void spde_rhs_kernel(const double* __restrict__ noise, int64_t ldn, uint64_t seed,
                                                        int64_t first_real, int nb, const double* __restrict__ bscale,
                                                        int64_t nv, double* __restrict__ r) {
   const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -333,7 +339,7 @@ __global__ __launch_bounds__(256) void spde_rhs_kernel(const double* __restrict_
   const double s = bscale[v];
   for (int c = 0; c < NB; ++c) {
     double w = 0.0;
-    if (c < nb) w = noise ? noise[(int64_t)c * nv + v] : philox_normal(seed, (uint32_t)(first_real + c), (uint64_t)v);
+    if (c < nb) w = noise ? noise[(int64_t)c * ldn + v] : philox_normal(seed, (uint32_t)(first_real + c), (uint64_t)v);
     r[v * NB + c] = c < nb ? s * w : 0.0;
   }
 }
@@ -353,12 +359,287 @@ __global__ __launch_bounds__(256) void spde_epilogue_kernel(const double* __rest
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// data: observation rows, the data-space system and the correction of a block (gss.h, "SPDEGS with data")
+// ---------------------------------------------------------------------------------------------
+constexpr int SPDE_LOC_CHUNK = 128;   // fewest triangles one thread of the locate kernel walks
+constexpr int SPDE_CMB_ROWS = 256;    // vertices per workgroup of the combine kernel, one per thread
+constexpr int SPDE_CMB_JT = 16;       // observations per LDS stage of the combine kernel (34 KiB of W, 2 KiB of lambda)
+
+// Barycentric coordinates l[0..2] of p (of its projection onto the plane when the triangle lies in space) in the
+// triangle with corners P[0..2], by signed area ratios relative to P[0]; returns whether all lie in [-tol, 1 + tol].
+// *dist: distance of p from the plane, 0 when it is at most tol edge lengths (always in 2-D, where z = 0).
+__host__ __device__ __forceinline__ bool tri_locate(const double (*P)[3], const double* p, double tol, double* l,
+                                                    double* dist) {
+#pragma clang fp contract(off)
+  const double u[3] = {P[1][0] - P[0][0], P[1][1] - P[0][1], P[1][2] - P[0][2]};
+  const double v[3] = {P[2][0] - P[0][0], P[2][1] - P[0][1], P[2][2] - P[0][2]};
+  const double w[3] = {p[0] - P[0][0], p[1] - P[0][1], p[2] - P[0][2]};
+  const double n[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+  const double a[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};   // w x v
+  const double b[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};   // u x w
+  const double nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+  l[1] = ((a[0] * n[0] + a[1] * n[1]) + a[2] * n[2]) / nn;
+  l[2] = ((b[0] * n[0] + b[1] * n[1]) + b[2] * n[2]) / nn;
+  l[0] = (1.0 - l[1]) - l[2];
+  const double len = sqrt(sqrt(nn));                                   // sqrt(2 area)
+  const double d = fabs((w[0] * n[0] + w[1] * n[1]) + w[2] * n[2]) / sqrt(nn);
+  *dist = d <= tol * len ? 0.0 : d;
+  const double lo = -tol, hi = 1.0 + tol;
+  return l[0] >= lo && l[0] <= hi && l[1] >= lo && l[1] <= hi && l[2] >= lo && l[2] <= hi;
+}
+
+__device__ __forceinline__ void spde_corners(const double* __restrict__ x, int dim, const int32_t* __restrict__ tri,
+                                             int64_t t, double (*P)[3]) {
+  for (int k = 0; k < 3; ++k)
+    for (int a = 0; a < 3; ++a) P[k][a] = a < dim ? x[(int64_t)tri[3 * t + k] * dim + a] : 0.0;
+}
+
+// thread (point, chunk): the nearest accepting triangle of the chunk, the lowest index among equally near ones
+__global__ __launch_bounds__(256) void spde_locate_kernel(const double* __restrict__ x, int dim,
+                                                          const int32_t* __restrict__ tri, int64_t nt, int64_t chunk,
+                                                          const double* __restrict__ pts, int64_t np, double tol,
+                                                          int64_t* __restrict__ cand_t, double* __restrict__ cand_d) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= np) return;
+  double p[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; a < dim; ++a) p[a] = pts[i * dim + a];
+  const int64_t t0 = (int64_t)blockIdx.y * chunk, t1 = t0 + chunk < nt ? t0 + chunk : nt;
+  int64_t best = -1;
+  double bd = 0.0;
+  for (int64_t t = t0; t < t1; ++t) {
+    double P[3][3], l[3], d;
+    spde_corners(x, dim, tri, t, P);
+    if (tri_locate(P, p, tol, l, &d) && (best < 0 || d < bd)) {
+      best = t;
+      bd = d;
+    }
+  }
+  cand_t[(int64_t)blockIdx.y * np + i] = best;
+  cand_d[(int64_t)blockIdx.y * np + i] = bd;
+}
+
+// thread point: the chunks' candidates in ascending order, then the weights in the winner
+__global__ __launch_bounds__(256) void spde_locate_pick_kernel(const double* __restrict__ x, int dim,
+                                                               const int32_t* __restrict__ tri,
+                                                               const double* __restrict__ pts, int64_t np, double tol,
+                                                               const int64_t* __restrict__ cand_t,
+                                                               const double* __restrict__ cand_d, int nchunks,
+                                                               int64_t* __restrict__ out_t, double* __restrict__ out_w) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= np) return;
+  int64_t best = -1;
+  double bd = 0.0;
+  for (int q = 0; q < nchunks; ++q) {
+    const int64_t t = cand_t[(int64_t)q * np + i];
+    const double d = cand_d[(int64_t)q * np + i];
+    if (t >= 0 && (best < 0 || d < bd)) {
+      best = t;
+      bd = d;
+    }
+  }
+  double l[3] = {0.0, 0.0, 0.0};
+  if (best >= 0) {
+    double p[3] = {0.0, 0.0, 0.0}, P[3][3], d;
+    for (int a = 0; a < dim; ++a) p[a] = pts[i * dim + a];
+    spde_corners(x, dim, tri, best, P);
+    (void)tri_locate(P, p, tol, l, &d);
+  }
+  out_t[i] = best;
+  for (int k = 0; k < 3; ++k) out_w[3 * i + k] = l[k];
+}
+
+// r (zeroed) += P' e_j for the nb observations j0 .. of a block: thread c owns column c and adds its row's three
+// entries in order (a vertex named twice gets both)
+template <int NB>
+__global__ __launch_bounds__(64) void spde_obs_rhs_kernel(const int32_t* __restrict__ obs_v,
+                                                          const double* __restrict__ obs_w, int64_t j0, int nb,
+                                                          double* __restrict__ r) {
+  const int c = threadIdx.x;
+  if (c >= nb) return;
+  for (int k = 0; k < 3; ++k) r[(int64_t)obs_v[3 * (j0 + c) + k] * NB + c] += obs_w[3 * (j0 + c) + k];
+}
+
+// the NB solved columns of a block into columns j0 .. j0 + NB - 1 of the row-major W (nv x ndp)
+template <int NB>
+__global__ __launch_bounds__(256) void spde_w_store_kernel(const double* __restrict__ x, int64_t nv, int64_t ndp,
+                                                           int64_t j0, double* __restrict__ W) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < nv * NB) W[(i / NB) * ndp + j0 + i % NB] = x[i];
+}
+
+__global__ __launch_bounds__(256) void spde_w_scale_kernel(const double* __restrict__ W, const double* __restrict__ s,
+                                                           int64_t nv, int64_t ndp, double* __restrict__ sW) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < nv * ndp) sW[i] = s[i / ndp] * W[i];
+}
+
+// C += diag(r); the diagonal is kept for the pivot test
+__global__ __launch_bounds__(256) void spde_gram_diag_kernel(double* __restrict__ C, int64_t nd,
+                                                             const double* __restrict__ sqrt_r,
+                                                             double* __restrict__ diag) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nd) return;
+  double c = C[i + i * nd];
+  if (sqrt_r) c = c + sqrt_r[i] * sqrt_r[i];
+  C[i + i * nd] = c;
+  diag[i] = c;
+}
+
+// pivot i of the factorisation is 1 / Li[i][i]^2: one that is not above 64 nd eps of its diagonal entry is rounding
+__global__ __launch_bounds__(256) void spde_pivot_kernel(const double* __restrict__ Li, int64_t nd,
+                                                         const double* __restrict__ diag,
+                                                         unsigned long long* __restrict__ err) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nd) return;
+  const double q = Li[i + i * nd], piv = 1.0 / (q * q);
+  if (!(piv > 64.0 * (double)nd * DBL_EPSILON * diag[i]) || !(piv <= DBL_MAX)) atomicMin(err, (unsigned long long)i);
+}
+
+// res[i][c] = y_i - mu - (P x)_i - sqrt(r_i) n_(c,i) for the nb realisations of a block, zero beyond; x == NULL: y - mu
+// alone.  The normal is read (or drawn) only where r_i > 0.
+template <int NB>
+__global__ __launch_bounds__(256) void spde_residual_kernel(const double* __restrict__ x,
+                                                            const int32_t* __restrict__ obs_v,
+                                                            const double* __restrict__ obs_w,
+                                                            const double* __restrict__ y,
+                                                            const double* __restrict__ sqrt_r,
+                                                            const double* __restrict__ noise, int64_t ldn,
+                                                            uint64_t seed, int64_t first_real, int nb, int64_t nv,
+                                                            int64_t nd, double mu, double* __restrict__ res) {
+#pragma clang fp contract(off)
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= nd * NB) return;
+  const int64_t i = idx / NB;
+  const int c = (int)(idx % NB);
+  double v = 0.0;
+  if (c < nb) {
+    v = y[i] - mu;
+    if (x) {
+      double px = obs_w[3 * i] * x[(int64_t)obs_v[3 * i] * NB + c];
+      px = px + obs_w[3 * i + 1] * x[(int64_t)obs_v[3 * i + 1] * NB + c];
+      px = px + obs_w[3 * i + 2] * x[(int64_t)obs_v[3 * i + 2] * NB + c];
+      v = v - px;
+      const double sr = sqrt_r ? sqrt_r[i] : 0.0;
+      if (sr > 0.0) {
+        const double n = noise ? noise[(int64_t)c * ldn + nv + i]
+                               : philox_normal(seed, (uint32_t)(first_real + c), (uint64_t)(nv + i));
+        v = v - sr * n;
+      }
+    }
+  }
+  res[idx] = v;
+}
+
+// Lt = Li' (both nd x nd, column-major), so that the product with inv(L)' reads along columns as well
+__global__ __launch_bounds__(256) void spde_transpose_kernel(const double* __restrict__ Li, int64_t nd,
+                                                             double* __restrict__ Lt) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q < nd * nd) Lt[q] = Li[(q / nd) + (q % nd) * nd];
+}
+
+// out = A in for the NB columns of a block (in, out: nd x NB), A nd x nd column-major and triangular: lower (inv(L)) or
+// UPPER (inv(L)', the transposed copy).  Thread i owns row i with its NB sums in registers: the 64 lanes of a wave read
+// 64 consecutive words of column j of A, every lane the same words of `in`.  j ascends over the entries of the row's
+// triangle and every column has its own sum.
+template <int NB, bool UPPER>
+__global__ __launch_bounds__(64) void spde_factor_apply_kernel(const double* __restrict__ A, int64_t nd,
+                                                               const double* __restrict__ in,
+                                                               double* __restrict__ out) {
+  const int64_t i0 = (int64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
+  const int64_t last = i0 + 63 < nd - 1 ? i0 + 63 : nd - 1;
+  const int64_t jlo = UPPER ? i0 : 0, jhi = UPPER ? nd - 1 : last;   // the columns some row of this workgroup meets
+  double acc[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) acc[c] = 0.0;
+  for (int64_t j = jlo; j <= jhi; ++j) {
+    if (i < nd && (UPPER ? j >= i : j <= i)) {
+      const double a = A[i + j * nd];
+#pragma unroll
+      for (int c = 0; c < NB; ++c) acc[c] = fma(a, in[j * NB + c], acc[c]);
+    }
+  }
+  if (i < nd) {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) out[i * NB + c] = acc[c];
+  }
+}
+
+// t[v][c] = s[v]^2 sum_j W[v][j] lambda[j][c]: the tall-skinny product of a block.  A workgroup takes SPDE_CMB_ROWS
+// vertices, one per thread, which keeps the NB sums of its vertex in registers.  W goes through LDS in stages of
+// SPDE_CMB_JT observations (read once, along its rows; a thread then reads its own row, one word of padding apart) and
+// so does lambda (every lane reads the same words).  j ascends and every column has its own sum: a column's bits do not
+// depend on its companions.  Bytes: 8 nv ndp read, 8 nv NB written; lambda (8 nd NB) comes from the cache.
+template <int NB>
+__global__ __launch_bounds__(SPDE_CMB_ROWS) void spde_combine_kernel(const double* __restrict__ W, int64_t ndp,
+                                                                      int64_t nd, const double* __restrict__ lam,
+                                                                      const double* __restrict__ bscale, int64_t nv,
+                                                                      double* __restrict__ t) {
+  __shared__ double sW[SPDE_CMB_ROWS * (SPDE_CMB_JT + 1)];
+  __shared__ double sL[SPDE_CMB_JT * NB];
+  const int64_t v0 = (int64_t)blockIdx.x * SPDE_CMB_ROWS;
+  double acc[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) acc[c] = 0.0;
+  for (int64_t j0 = 0; j0 < nd; j0 += SPDE_CMB_JT) {
+    for (int q = threadIdx.x; q < SPDE_CMB_ROWS * SPDE_CMB_JT; q += SPDE_CMB_ROWS) {
+      const int row = q / SPDE_CMB_JT, jj = q % SPDE_CMB_JT;
+      const int64_t v = v0 + row, j = j0 + jj;
+      sW[row * (SPDE_CMB_JT + 1) + jj] = (v < nv && j < nd) ? W[v * ndp + j] : 0.0;
+    }
+    for (int q = threadIdx.x; q < SPDE_CMB_JT * NB; q += SPDE_CMB_ROWS)
+      sL[q] = j0 + q / NB < nd ? lam[j0 * NB + q] : 0.0;
+    __syncthreads();
+    const double* mine = sW + threadIdx.x * (SPDE_CMB_JT + 1);
+    for (int jj = 0; jj < SPDE_CMB_JT; ++jj) {
+      const double w = mine[jj];
+#pragma unroll
+      for (int c = 0; c < NB; ++c) acc[c] = fma(w, sL[jj * NB + c], acc[c]);
+    }
+    __syncthreads();
+  }
+  const int64_t v = v0 + threadIdx.x;
+  if (v < nv) {
+    const double s = bscale[v], s2 = s * s;
+#pragma unroll
+    for (int c = 0; c < NB; ++c) t[v * NB + c] = s2 * acc[c];
+  }
+}
+
+// spde_epilogue_kernel for a block with data: the vertex value is (xu + xc) + mu (xu == NULL: xc + mu, the mean)
+template <int NB>
+__global__ __launch_bounds__(256) void spde_epilogue_cond_kernel(const double* __restrict__ xu,
+                                                                 const double* __restrict__ xc, double mu, int nb,
+                                                                 int64_t nv, const int32_t* __restrict__ tri,
+                                                                 int64_t nt, double* __restrict__ vout,
+                                                                 double* __restrict__ eout) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  auto at = [&](int64_t v, int c) {
+    const double a = xu ? xu[v * NB + c] + xc[v * NB + c] : xc[v * NB + c];
+    return a + mu;
+  };
+  if (vout && i < nv)
+    for (int c = 0; c < nb; ++c) vout[(int64_t)c * nv + i] = at(i, c);
+  if (eout && i < nt) {
+    const int64_t a = tri[3 * i], b = tri[3 * i + 1], d = tri[3 * i + 2];
+    for (int c = 0; c < nb; ++c) eout[(int64_t)c * nt + i] = ((at(a, c) + at(b, c)) + at(d, c)) / 3.0;
+  }
+}
+
 // the page-locked word the spmv kernel of workgroup 0 writes and the host reads every SPDE_POLL iterations (one per
 // process: the library's lock admits one call at a time)
 static int* g_spde_done = nullptr;
 void spde_release() {
   if (g_spde_done) (void)hipHostFree(g_spde_done);
   g_spde_done = nullptr;
+}
+
+static int32_t spde_done_word(int** dev) {   // ... and its device address
+  if (!g_spde_done) GSS_HIP(hipHostMalloc(reinterpret_cast<void**>(&g_spde_done), sizeof(int), hipHostMallocDefault));
+  GSS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(dev), g_spde_done, 0));
+  return GSS_OK;
 }
 
 static int spde_block_columns() {   // columns per block: 16; GSS_SPDE_NB = 8 or 32 for measurements
@@ -381,8 +662,23 @@ struct gss_spde {
   DevBuf tri;                      // nt x 3, 32-bit
   DevBuf rowptr, col, val;         // CSR of S
   DevBuf mass, dinv, bscale;       // diag(M), 1 / diag(S), tau m or tau sqrt(m)
+  DevBuf xv;                       // nv x dim vertex coordinates (gss_spde_locate)
   int64_t last_iters = 0, last_unconverged = 0;
   double last_relres = 0.0;
+  // data (nd == 0: none)
+  int64_t nd = 0, ndp = 0;         // observations; the same rounded up to whole blocks (row length of W)
+  double mu = 0.0;
+  bool noisy = false;              // some error variance is positive
+  DevBuf obs_v, obs_w, yobs;       // nd x 3 (32-bit), nd x 3, nd
+  DevBuf sqrt_r;                   // nd
+  DevBuf W;                        // nv x ndp row-major: inv(S) P'
+  DevBuf Li, Lt;                   // nd x nd column-major: inv(L) of P Sigma P' + R = L L', and its transpose
+  void drop_data() {
+    nd = ndp = 0;
+    mu = 0.0;
+    noisy = false;
+    obs_v.release(); obs_w.release(); yobs.release(); sqrt_r.release(); W.release(); Li.release(); Lt.release();
+  }
 };
 
 static const char* spde_what(int code) {
@@ -516,25 +812,38 @@ struct SpdeBlockResult {
   CgCol colstate[SPDE_NB_MAX];
 };
 
-// Realisations first_real .. first_real + nb - 1 (nb <= NB) as one block; every array in HBM.  Returns after the
-// block's column states have reached the host (the one wait besides the polls).
+// The vectors of a block, all nv x NB interleaved, and the dot-product slabs: x, r, two directions, Ap; x2 (handles
+// with data only) holds the second solution of a block.
 template <int NB>
-static int32_t spde_solve_block(gss_spde* h, uint64_t seed, int64_t first_real, int nb, const double* noise,
-                                double tol2, int64_t maxiter, double* vout, double* eout, double* work, CgCol* state,
-                                int* done_dev, SpdeBlockResult* res, hipStream_t s) {
-  const int64_t nv = h->nv, nt = h->nt;
+struct SpdeWork {
+  double *x, *r, *P[2], *Ap, *slab_rz, *slab_rr, *slab_pap, *x2;
+  static size_t doubles(int64_t nv, bool second) {
+    return (size_t)nv * NB * (second ? 6 : 5) + (size_t)3 * SPDE_GROUPS * NB;
+  }
+  SpdeWork(double* w, int64_t nv, bool second) {
+    const size_t vec = (size_t)nv * NB;
+    x = w; r = x + vec; P[0] = r + vec; P[1] = r + 2 * vec; Ap = r + 3 * vec;
+    slab_rz = Ap + vec; slab_rr = slab_rz + SPDE_GROUPS * NB; slab_pap = slab_rr + SPDE_GROUPS * NB;
+    x2 = second ? slab_pap + SPDE_GROUPS * NB : nullptr;
+  }
+};
+
+// S x = b for the NB columns of a block, b already in wk.r (interleaved; a zero column is done at once): the CG loop,
+// then the block's column states on their way to *res.  Everything is queued on s; the caller waits for s before it
+// reads *res (the polls of the loop are the only waits in here).
+template <int NB>
+static int32_t spde_cg_block(gss_spde* h, const SpdeWork<NB>& wk, double* x, double tol2, int64_t maxiter, CgCol* state,
+                             int* done_dev, SpdeBlockResult* res, hipStream_t s) {
+  const int64_t nv = h->nv;
   constexpr int G = SPDE_THREADS / NB;
   int64_t want = (nv + G - 1) / G, wantu = (nv * NB + SPDE_THREADS - 1) / SPDE_THREADS;
   if (wantu > want) want = wantu;
   const unsigned groups = (unsigned)(want < SPDE_GROUPS ? want : SPDE_GROUPS);   // a function of nv alone
   const size_t vec = (size_t)nv * NB;
-  double *x = work, *r = x + vec, *P[2] = {r + vec, r + 2 * vec}, *Ap = r + 3 * vec;
-  double *slab_rz = Ap + vec, *slab_rr = slab_rz + SPDE_GROUPS * NB, *slab_pap = slab_rr + SPDE_GROUPS * NB;
+  double *r = wk.r, *const *P = wk.P, *Ap = wk.Ap;
+  double *slab_rz = wk.slab_rz, *slab_rr = wk.slab_rr, *slab_pap = wk.slab_pap;
   GSS_HIP(hipMemsetAsync(x, 0, sizeof(double) * vec, s));
   GSS_HIP(hipMemsetAsync(P[0], 0, sizeof(double) * vec, s));   // beta = 0 multiplies it in the first iteration
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_rhs_kernel<NB>), dim3(blocks_of(nv)), dim3(256), 0, s, noise, seed,
-                     first_real, nb, h->bscale.as<double>(), nv, r);
-  GSS_HIP(hipGetLastError());
   hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_update_kernel<NB, true>), dim3(groups), dim3(SPDE_THREADS), 0, s,
                      h->dinv.as<double>(), x, r, nullptr, nullptr, nullptr, nullptr, slab_rz, slab_rr, nv);
   GSS_HIP(hipGetLastError());
@@ -564,12 +873,70 @@ static int32_t spde_solve_block(gss_spde* h, uint64_t seed, int64_t first_real, 
                      (int)groups, state + (k & 1) * NB, state + ((k + 1) & 1) * NB, (int)k, tol2);
   GSS_HIP(hipGetLastError());
   GSS_HIP(hipMemcpyAsync(res->colstate, state + ((k + 1) & 1) * NB, sizeof(CgCol) * NB, hipMemcpyDeviceToHost, s));
+  return GSS_OK;
+}
+
+// lambda = inv(L)' inv(L) res for the block in `res` (nd x NB), then wk.r = s^2 . (W lambda); tmp: nd x NB
+template <int NB>
+static int32_t spde_correction_rhs(gss_spde* h, const SpdeWork<NB>& wk, double* res, double* tmp, hipStream_t s) {
+  const int64_t nv = h->nv, nd = h->nd;
+  const unsigned fb = (unsigned)((nd + 63) / 64);
+  {
+    ProfScope ps("spde_lambda", s);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_factor_apply_kernel<NB, false>), dim3(fb), dim3(64), 0, s,
+                       h->Li.as<double>(), nd, res, tmp);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_factor_apply_kernel<NB, true>), dim3(fb), dim3(64), 0, s,
+                       h->Lt.as<double>(), nd, tmp, res);
+    GSS_HIP(hipGetLastError());
+  }
+  ProfScope ps("spde_combine", s);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_combine_kernel<NB>), dim3((unsigned)((nv + SPDE_CMB_ROWS - 1) / SPDE_CMB_ROWS)),
+                     dim3(SPDE_CMB_ROWS), 0, s, h->W.as<double>(), h->ndp, nd, res, h->bscale.as<double>(), nv, wk.r);
+  GSS_HIP(hipGetLastError());
+  return GSS_OK;
+}
+
+// Realisations first_real .. first_real + nb - 1 (nb <= NB) as one block; every array in HBM.  Returns after the
+// block's column states have reached the host (the one wait besides the polls).  With data: the unconditional solve,
+// the residuals at the observations, the data-space solve, the second solve and the sum (res[1]: its column states;
+// dwork: 2 nd NB doubles).
+template <int NB>
+static int32_t spde_solve_block(gss_spde* h, uint64_t seed, int64_t first_real, int nb, const double* noise,
+                                double tol2, int64_t maxiter, double* vout, double* eout, const SpdeWork<NB>& wk,
+                                double* dwork, CgCol* state, int* done_dev, SpdeBlockResult* res, hipStream_t s) {
+  const int64_t nv = h->nv, nt = h->nt, nd = h->nd, ldn = nv + nd;
   const int64_t m = nv > nt ? nv : nt;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_epilogue_kernel<NB>), dim3(blocks_of(m)), dim3(256), 0, s, x, nb, nv,
-                     h->tri.as<int32_t>(), nt, vout, eout);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_rhs_kernel<NB>), dim3(blocks_of(nv)), dim3(256), 0, s, noise, ldn, seed,
+                     first_real, nb, h->bscale.as<double>(), nv, wk.r);
+  GSS_HIP(hipGetLastError());
+  GSS_TRY(spde_cg_block<NB>(h, wk, wk.x, tol2, maxiter, state, done_dev, &res[0], s));
+  if (nd == 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_epilogue_kernel<NB>), dim3(blocks_of(m)), dim3(256), 0, s, wk.x, nb, nv,
+                       h->tri.as<int32_t>(), nt, vout, eout);
+    GSS_HIP(hipGetLastError());
+    GSS_HIP(hipStreamSynchronize(s));
+    return GSS_OK;
+  }
+  double *dres = dwork, *dtmp = dwork + nd * NB;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_residual_kernel<NB>), dim3(blocks_of(nd * NB)), dim3(256), 0, s, wk.x,
+                     h->obs_v.as<int32_t>(), h->obs_w.as<double>(), h->yobs.as<double>(),
+                     h->noisy ? h->sqrt_r.as<double>() : nullptr, noise, ldn, seed, first_real, nb, nv, nd, h->mu, dres);
+  GSS_HIP(hipGetLastError());
+  GSS_TRY(spde_correction_rhs<NB>(h, wk, dres, dtmp, s));
+  GSS_TRY(spde_cg_block<NB>(h, wk, wk.x2, tol2, maxiter, state, done_dev, &res[1], s));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_epilogue_cond_kernel<NB>), dim3(blocks_of(m)), dim3(256), 0, s, wk.x, wk.x2,
+                     h->mu, nb, nv, h->tri.as<int32_t>(), nt, vout, eout);
   GSS_HIP(hipGetLastError());
   GSS_HIP(hipStreamSynchronize(s));
   return GSS_OK;
+}
+
+// a column's state into the handle's record of the call; returns its ||r|| / ||b||
+static double spde_note_column(gss_spde* h, const CgCol& q) {
+  const double rel = q.bn2 > 0.0 ? std::sqrt(q.rr / q.bn2) : (q.rr == 0.0 ? 0.0 : HUGE_VAL);
+  if (q.iters > h->last_iters) h->last_iters = q.iters;
+  if (!(rel <= h->last_relres)) h->last_relres = rel;
+  return rel;
 }
 
 // first unconverged realisation of the call and its residual
@@ -583,26 +950,30 @@ template <int NB>
 static int32_t spde_realize_dev(gss_spde* h, uint64_t seed, int64_t first_real, int64_t nreals, const double* noise,
                                 double tol2, int64_t maxiter, double* vout, double* eout, SpdeFailure* fail,
                                 hipStream_t s) {
-  const int64_t nv = h->nv, nt = h->nt;
-  DevBuf work, state;
-  GSS_TRY(work.alloc(sizeof(double) * ((size_t)nv * NB * 5 + (size_t)3 * SPDE_GROUPS * NB)));
+  const int64_t nv = h->nv, nt = h->nt, nd = h->nd, ldn = nv + nd;
+  DevBuf work, dwork, state;
+  GSS_TRY(work.alloc(sizeof(double) * SpdeWork<NB>::doubles(nv, nd > 0)));
+  if (nd > 0) GSS_TRY(dwork.alloc(sizeof(double) * (size_t)(2 * nd * NB)));
   GSS_TRY(state.alloc(sizeof(CgCol) * 2 * NB));
-  if (!g_spde_done) GSS_HIP(hipHostMalloc(reinterpret_cast<void**>(&g_spde_done), sizeof(int), hipHostMallocDefault));
   int* done_dev = nullptr;
-  GSS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&done_dev), g_spde_done, 0));
+  GSS_TRY(spde_done_word(&done_dev));
+  const SpdeWork<NB> wk(work.as<double>(), nv, nd > 0);
   for (int64_t r0 = 0; r0 < nreals; r0 += NB) {
     const int nb = (int)(nreals - r0 < NB ? nreals - r0 : NB);
-    SpdeBlockResult res;
+    SpdeBlockResult res[2];
     *g_spde_done = 0;
-    GSS_TRY(spde_solve_block<NB>(h, seed, first_real + r0, nb, noise ? noise + r0 * nv : nullptr, tol2, maxiter,
-                                 vout ? vout + r0 * nv : nullptr, eout ? eout + r0 * nt : nullptr, work.as<double>(),
-                                 state.as<CgCol>(), done_dev, &res, s));
-    for (int c = 0; c < nb; ++c) {
-      const CgCol& q = res.colstate[c];
-      const double rel = q.bn2 > 0.0 ? std::sqrt(q.rr / q.bn2) : (q.rr == 0.0 ? 0.0 : HUGE_VAL);
-      if (q.iters > h->last_iters) h->last_iters = q.iters;
-      if (!(rel <= h->last_relres)) h->last_relres = rel;
-      if (!q.done) {
+    GSS_TRY(spde_solve_block<NB>(h, seed, first_real + r0, nb, noise ? noise + r0 * ldn : nullptr, tol2, maxiter,
+                                 vout ? vout + r0 * nv : nullptr, eout ? eout + r0 * nt : nullptr, wk,
+                                 dwork.as<double>(), state.as<CgCol>(), done_dev, res, s));
+    for (int c = 0; c < nb; ++c) {   // with data a realisation is two solves: the worse of the two counts
+      double rel = spde_note_column(h, res[0].colstate[c]);
+      bool done = res[0].colstate[c].done != 0;
+      if (nd > 0) {
+        const double rel2 = spde_note_column(h, res[1].colstate[c]);
+        if (!(rel2 <= rel)) rel = rel2;
+        done = done && res[1].colstate[c].done != 0;
+      }
+      if (!done) {
         ++h->last_unconverged;
         if (fail->real < 0) {
           fail->real = first_real + r0 + c;
@@ -610,6 +981,147 @@ static int32_t spde_realize_dev(gss_spde* h, uint64_t seed, int64_t first_real, 
         }
       }
     }
+  }
+  return GSS_OK;
+}
+
+// W = inv(S) P' block after block, then C = (sW)' (sW) + diag(r) with sW = diag(s) W, its factor and the factor's
+// inverse.  The observation arrays are on the handle already.  *bad_col: first column of W that did not converge.
+template <int NB>
+static int32_t spde_condition_dev(gss_spde* h, double tol2, int64_t maxiter, int64_t* bad_col, double* bad_rel,
+                                  int64_t* pivot, hipStream_t s) {
+  const int64_t nv = h->nv, nd = h->nd, ndp = h->ndp;
+  *bad_col = *pivot = -1;
+  {
+    ProfScope ps("spde_cond_w", s);
+    DevBuf work, state;
+    GSS_TRY(work.alloc(sizeof(double) * SpdeWork<NB>::doubles(nv, false)));
+    GSS_TRY(state.alloc(sizeof(CgCol) * 2 * NB));
+    int* done_dev = nullptr;
+    GSS_TRY(spde_done_word(&done_dev));
+    const SpdeWork<NB> wk(work.as<double>(), nv, false);
+    for (int64_t j0 = 0; j0 < ndp; j0 += NB) {
+      const int nb = (int)(nd - j0 < NB ? nd - j0 : NB);
+      SpdeBlockResult res;
+      *g_spde_done = 0;
+      GSS_HIP(hipMemsetAsync(wk.r, 0, sizeof(double) * (size_t)nv * NB, s));
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_obs_rhs_kernel<NB>), dim3(1), dim3(64), 0, s, h->obs_v.as<int32_t>(),
+                         h->obs_w.as<double>(), j0, nb, wk.r);
+      GSS_HIP(hipGetLastError());
+      GSS_TRY(spde_cg_block<NB>(h, wk, wk.x, tol2, maxiter, state.as<CgCol>(), done_dev, &res, s));
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_w_store_kernel<NB>), dim3(blocks_of(nv * NB)), dim3(256), 0, s, wk.x, nv,
+                         ndp, j0, h->W.as<double>());
+      GSS_HIP(hipGetLastError());
+      GSS_HIP(hipStreamSynchronize(s));
+      for (int c = 0; c < nb; ++c) {
+        const double rel = spde_note_column(h, res.colstate[c]);
+        if (!res.colstate[c].done) {
+          ++h->last_unconverged;
+          if (*bad_col < 0) {
+            *bad_col = j0 + c;
+            *bad_rel = rel;
+          }
+        }
+      }
+    }
+    if (*bad_col >= 0) return GSS_OK;
+  }
+  DevBuf C, diag, scr, info, err;
+  GSS_TRY(C.alloc(sizeof(double) * (size_t)(nd * nd)));
+  GSS_TRY(h->Li.alloc(sizeof(double) * (size_t)(nd * nd)));
+  GSS_TRY(diag.alloc(sizeof(double) * (size_t)nd));
+  GSS_TRY(info.alloc(sizeof(int)));
+  GSS_TRY(err.alloc(sizeof(unsigned long long)));
+  const int64_t ws = potrf_inverse_work_doubles(nd) > nd * nd ? potrf_inverse_work_doubles(nd) : nd * nd;
+  GSS_TRY(scr.alloc(sizeof(double) * (size_t)ws));
+  for (int attempt = 0;; ++attempt) {
+    {
+      ProfScope ps("spde_cond_gram", s);
+      DevBuf sW;
+      if (sW.alloc(sizeof(double) * (size_t)(nv * ndp)) != GSS_OK) {
+        set_error("gss_spde_condition: no room for diag(s) W (%lld x %lld doubles) beside W", (long long)nv, (long long)ndp);
+        return GSS_ERR_ALLOC;
+      }
+      hipLaunchKernelGGL(spde_w_scale_kernel, dim3(blocks_of(nv * ndp)), dim3(256), 0, s, h->W.as<double>(),
+                         h->bscale.as<double>(), nv, ndp, sW.as<double>());
+      GSS_HIP(hipGetLastError());
+      GSS_TRY(gemm_f64(nd, nd, nv, 1.0, sW.as<double>(), 1, ndp, sW.as<double>(), ndp, 1, 0.0, C.as<double>(), 1, nd,
+                       false, s));
+      hipLaunchKernelGGL(spde_gram_diag_kernel, dim3(blocks_of(nd)), dim3(256), 0, s, C.as<double>(), nd,
+                         h->noisy ? h->sqrt_r.as<double>() : nullptr, diag.as<double>());
+      GSS_HIP(hipGetLastError());
+      GSS_HIP(hipStreamSynchronize(s));   // (sW goes back to the pool)
+    }
+    ProfScope ps("spde_cond_factor", s);
+    GSS_HIP(hipMemsetAsync(h->Li.p, 0, sizeof(double) * (size_t)(nd * nd), s));
+    GSS_TRY(potrf_inverse_f64(C.as<double>(), nd, nd, h->Li.as<double>(), nd, scr.as<double>(), info.as<int>(), false,
+                              s));
+    int code = 0;
+    GSS_HIP(hipMemcpyAsync(&code, info.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipStreamSynchronize(s));
+    if (code < 0 && attempt == 0) {   // the single-launch panel gave up at a grid barrier: once more without it
+      potrf_panel_disable();
+      continue;
+    }
+    if (code < 0) {
+      set_error("gss_spde_condition: the factorisation gave up waiting at a grid barrier");
+      return GSS_ERR_HIP;
+    }
+    if (code > 0) {
+      *pivot = code - 1;
+      return GSS_OK;
+    }
+    break;
+  }
+  GSS_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(spde_pivot_kernel, dim3(blocks_of(nd)), dim3(256), 0, s, h->Li.as<double>(), nd, diag.as<double>(),
+                     err.as<unsigned long long>());
+  GSS_HIP(hipGetLastError());
+  unsigned long long word = SPDE_CLEAN;
+  GSS_TRY(spde_read_err(err, s, &word));
+  if (word != SPDE_CLEAN) {
+    *pivot = (int64_t)word;
+    return GSS_OK;
+  }
+  GSS_TRY(h->Lt.alloc(sizeof(double) * (size_t)(nd * nd)));
+  hipLaunchKernelGGL(spde_transpose_kernel, dim3(blocks_of(nd * nd)), dim3(256), 0, s, h->Li.as<double>(), nd,
+                     h->Lt.as<double>());
+  GSS_HIP(hipGetLastError());
+  GSS_HIP(hipStreamSynchronize(s));
+  return GSS_OK;
+}
+
+// the kriging mean: lambda0 = inv(C) (y - mu) in column 0 of a block, one solve, mu added by the epilogue
+template <int NB>
+static int32_t spde_mean_dev(gss_spde* h, double tol2, int64_t maxiter, double* vout, double* eout, SpdeFailure* fail,
+                             hipStream_t s) {
+  const int64_t nv = h->nv, nt = h->nt, nd = h->nd;
+  DevBuf work, dwork, state;
+  GSS_TRY(work.alloc(sizeof(double) * SpdeWork<NB>::doubles(nv, false)));
+  GSS_TRY(dwork.alloc(sizeof(double) * (size_t)(2 * nd * NB)));
+  GSS_TRY(state.alloc(sizeof(CgCol) * 2 * NB));
+  int* done_dev = nullptr;
+  GSS_TRY(spde_done_word(&done_dev));
+  const SpdeWork<NB> wk(work.as<double>(), nv, false);
+  double *dres = dwork.as<double>(), *dtmp = dres + nd * NB;
+  SpdeBlockResult res;
+  *g_spde_done = 0;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_residual_kernel<NB>), dim3(blocks_of(nd * NB)), dim3(256), 0, s, nullptr,
+                     h->obs_v.as<int32_t>(), h->obs_w.as<double>(), h->yobs.as<double>(), nullptr, nullptr, 0, 0, 0, 1,
+                     nv, nd, h->mu, dres);
+  GSS_HIP(hipGetLastError());
+  GSS_TRY(spde_correction_rhs<NB>(h, wk, dres, dtmp, s));
+  GSS_TRY(spde_cg_block<NB>(h, wk, wk.x, tol2, maxiter, state.as<CgCol>(), done_dev, &res, s));
+  const int64_t m = nv > nt ? nv : nt;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(spde_epilogue_cond_kernel<NB>), dim3(blocks_of(m)), dim3(256), 0, s, nullptr, wk.x,
+                     h->mu, 1, nv, h->tri.as<int32_t>(), nt, vout, eout);
+  GSS_HIP(hipGetLastError());
+  GSS_HIP(hipStreamSynchronize(s));
+  const double rel = spde_note_column(h, res.colstate[0]);
+  if (!res.colstate[0].done) {
+    ++h->last_unconverged;
+    fail->real = 0;
+    fail->relres = rel;
   }
   return GSS_OK;
 }
@@ -622,6 +1134,33 @@ static int32_t spde_realize_nb(gss_spde* h, uint64_t seed, int64_t first_real, i
     case 32: return spde_realize_dev<32>(h, seed, first_real, nreals, noise, tol2, maxiter, vout, eout, fail, s);
     default: return spde_realize_dev<16>(h, seed, first_real, nreals, noise, tol2, maxiter, vout, eout, fail, s);
   }
+}
+
+static int32_t spde_condition_nb(gss_spde* h, double tol2, int64_t maxiter, int64_t* bad_col, double* bad_rel,
+                                 int64_t* pivot, hipStream_t s) {
+  switch (spde_block_columns()) {
+    case 8: return spde_condition_dev<8>(h, tol2, maxiter, bad_col, bad_rel, pivot, s);
+    case 32: return spde_condition_dev<32>(h, tol2, maxiter, bad_col, bad_rel, pivot, s);
+    default: return spde_condition_dev<16>(h, tol2, maxiter, bad_col, bad_rel, pivot, s);
+  }
+}
+
+static int32_t spde_mean_nb(gss_spde* h, double tol2, int64_t maxiter, double* vout, double* eout, SpdeFailure* fail,
+                            hipStream_t s) {
+  switch (spde_block_columns()) {
+    case 8: return spde_mean_dev<8>(h, tol2, maxiter, vout, eout, fail, s);
+    case 32: return spde_mean_dev<32>(h, tol2, maxiter, vout, eout, fail, s);
+    default: return spde_mean_dev<16>(h, tol2, maxiter, vout, eout, fail, s);
+  }
+}
+
+// rtol and maxiter as the exports take them -> tol^2 and a positive count
+static int32_t spde_solve_args(const char* who, double* rtol, int64_t* maxiter) {
+  GSS_REQUIRE(*rtol < 1.0, "%s: rtol = %g; it must be below 1 (<= 0 selects 1e-10)", who, *rtol);
+  if (!(*rtol > 0.0)) *rtol = 1e-10;
+  if (*maxiter <= 0) *maxiter = 20000;
+  GSS_REQUIRE(*maxiter <= INT32_MAX, "%s: maxiter = %lld", who, (long long)*maxiter);
+  return GSS_OK;
 }
 
 extern "C" {
@@ -666,6 +1205,9 @@ int32_t gss_spde_create(gss_spde_t** out, const double* vertices, int64_t nv, in
   GSS_TRY(sx.in(vertices, sizeof(double) * (size_t)(nv * dim), mem, s));
   GSS_TRY(st.in(triangles, sizeof(int64_t) * (size_t)(3 * nt), mem, s));
   GSS_TRY(spde_assemble(h, sx.as<double>(), st.as<int64_t>(), std::sqrt(h->tau2), s));
+  GSS_TRY(h->xv.alloc(sizeof(double) * (size_t)(nv * dim)));
+  GSS_HIP(hipMemcpyAsync(h->xv.p, sx.p, sizeof(double) * (size_t)(nv * dim), hipMemcpyDeviceToDevice, s));
+  GSS_HIP(hipStreamSynchronize(s));
   guard.h = nullptr;
   *out = h;
   return GSS_OK;
@@ -717,7 +1259,7 @@ int32_t gss_spde_realize(gss_spde_t* h, uint64_t seed, int64_t first_real, int64
   h->last_relres = 0.0;
   if (nreals == 0) return GSS_OK;
   hipStream_t s = to_stream(stream);
-  const int64_t nv = h->nv, nt = h->nt;
+  const int64_t nv = h->nv, nt = h->nt, ldn = nv + h->nd;   // with data the error normals follow the field's
   const double tol2 = rtol * rtol;
   SpdeFailure fail;
   if (mem == GSS_MEM_DEVICE) {
@@ -732,11 +1274,11 @@ int32_t gss_spde_realize(gss_spde_t* h, uint64_t seed, int64_t first_real, int64
     GSS_TRY(osv.begin(vout, sizeof(double) * (size_t)nv, nreals, mem, s, rb));
     GSS_TRY(ose.begin(eout, sizeof(double) * (size_t)nt, nreals, mem, s, rb));
     DevBuf nbuf;
-    if (noise) GSS_TRY(nbuf.alloc(sizeof(double) * (size_t)((nreals < rb ? nreals : rb) * nv)));
+    if (noise) GSS_TRY(nbuf.alloc(sizeof(double) * (size_t)((nreals < rb ? nreals : rb) * ldn)));
     for (int64_t r0 = 0; r0 < nreals; r0 += rb) {
       const int64_t n = nreals - r0 < rb ? nreals - r0 : rb;
       if (noise)
-        GSS_HIP(hipMemcpyAsync(nbuf.p, noise + r0 * nv, sizeof(double) * (size_t)(n * nv), hipMemcpyHostToDevice, s));
+        GSS_HIP(hipMemcpyAsync(nbuf.p, noise + r0 * ldn, sizeof(double) * (size_t)(n * ldn), hipMemcpyHostToDevice, s));
       double *dv = nullptr, *de = nullptr;
       if (vout) GSS_TRY(osv.slot(r0, s, &dv));
       if (eout) GSS_TRY(ose.slot(r0, s, &de));
@@ -763,6 +1305,194 @@ int32_t gss_spde_last_solve(const gss_spde_t* h, int64_t* iters, double* relres,
   if (iters) *iters = h->last_iters;
   if (relres) *relres = h->last_relres;
   if (unconverged) *unconverged = h->last_unconverged;
+  return GSS_OK;
+}
+
+int32_t gss_spde_locate(gss_spde_t* h, const double* points, int64_t np, double tol, int64_t* triangle,
+                        double* weight, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(mem == GSS_MEM_HOST || mem == GSS_MEM_DEVICE, "gss_spde_locate: mem = %d", mem);
+  GSS_REQUIRE(np >= 0 && np <= INT32_MAX, "gss_spde_locate: np = %lld", (long long)np);
+  GSS_REQUIRE(tol < 0.5, "gss_spde_locate: tol = %g; it must be below 1/2 (<= 0 selects 1e-9)", tol);
+  if (np == 0) return GSS_OK;
+  GSS_REQUIRE(points != nullptr && triangle != nullptr && weight != nullptr, "gss_spde_locate: NULL array");
+  if (!(tol > 0.0)) tol = 1e-9;
+  hipStream_t s = to_stream(stream);
+  Staged sp, st, sw;
+  GSS_TRY(sp.in(points, sizeof(double) * (size_t)(np * h->dim), mem, s));
+  GSS_TRY(st.out(triangle, sizeof(int64_t) * (size_t)np, mem));
+  GSS_TRY(sw.out(weight, sizeof(double) * (size_t)(3 * np), mem));
+  // a thread walks at least SPDE_LOC_CHUNK triangles and there are at most 1 024 chunks
+  int64_t chunk = (h->nt + 1023) / 1024;
+  if (chunk < SPDE_LOC_CHUNK) chunk = SPDE_LOC_CHUNK;
+  const int nchunks = (int)((h->nt + chunk - 1) / chunk);
+  DevBuf ct, cd;
+  GSS_TRY(ct.alloc(sizeof(int64_t) * (size_t)(np * nchunks)));
+  GSS_TRY(cd.alloc(sizeof(double) * (size_t)(np * nchunks)));
+  hipLaunchKernelGGL(spde_locate_kernel, dim3(blocks_of(np), (unsigned)nchunks), dim3(256), 0, s, h->xv.as<double>(),
+                     h->dim, h->tri.as<int32_t>(), h->nt, chunk, sp.as<double>(), np, tol, ct.as<int64_t>(),
+                     cd.as<double>());
+  hipLaunchKernelGGL(spde_locate_pick_kernel, dim3(blocks_of(np)), dim3(256), 0, s, h->xv.as<double>(), h->dim,
+                     h->tri.as<int32_t>(), sp.as<double>(), np, tol, ct.as<int64_t>(), cd.as<double>(), nchunks,
+                     st.as<int64_t>(), sw.as<double>());
+  GSS_HIP(hipGetLastError());
+  GSS_TRY(st.back(s));
+  GSS_TRY(sw.back(s));
+  GSS_HIP(hipStreamSynchronize(s));
+  return GSS_OK;
+}
+
+int32_t gss_spde_condition_clear(gss_spde_t* h) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_HIP(hipDeviceSynchronize());   // nothing queued reads the data any more
+  h->drop_data();
+  return GSS_OK;
+}
+
+int32_t gss_spde_condition(gss_spde_t* h, int64_t nd, const int64_t* obs_vertex, const double* obs_weight,
+                           const double* value, const double* error_var, double mean, double rtol, int64_t maxiter,
+                           int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  // The earlier data go first: whatever this call is refused for, the handle has none afterwards.
+  if (h->nd > 0) {
+    GSS_HIP(hipDeviceSynchronize());   // nothing queued reads them any more
+    h->drop_data();
+  }
+  GSS_REQUIRE(mem == GSS_MEM_HOST || mem == GSS_MEM_DEVICE, "gss_spde_condition: mem = %d", mem);
+  GSS_REQUIRE(nd >= 1, "gss_spde_condition: nd = %lld; at least one observation", (long long)nd);
+  GSS_REQUIRE(obs_vertex != nullptr && obs_weight != nullptr && value != nullptr, "gss_spde_condition: NULL array");
+  GSS_REQUIRE(std::fabs(mean) <= DBL_MAX, "gss_spde_condition: the mean is not finite");
+  GSS_TRY(spde_solve_args("gss_spde_condition", &rtol, &maxiter));
+  if (nd > INT32_MAX / 64) {
+    set_error("gss_spde_condition: nd = %lld; the limit is 2^25", (long long)nd);
+    return GSS_ERR_UNSUPPORTED;
+  }
+  hipStream_t s = to_stream(stream);
+  // the observation table is small: it is checked on the host wherever it lives
+  std::vector<int64_t> hv((size_t)(3 * nd));
+  std::vector<double> hw((size_t)(3 * nd)), hy((size_t)nd), hr(error_var ? (size_t)nd : 0);
+  if (mem == GSS_MEM_DEVICE) {
+    GSS_HIP(hipMemcpyAsync(hv.data(), obs_vertex, sizeof(int64_t) * hv.size(), hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(hw.data(), obs_weight, sizeof(double) * hw.size(), hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipMemcpyAsync(hy.data(), value, sizeof(double) * hy.size(), hipMemcpyDeviceToHost, s));
+    if (error_var) GSS_HIP(hipMemcpyAsync(hr.data(), error_var, sizeof(double) * hr.size(), hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipStreamSynchronize(s));
+  } else {
+    hv.assign(obs_vertex, obs_vertex + 3 * nd);
+    hw.assign(obs_weight, obs_weight + 3 * nd);
+    hy.assign(value, value + nd);
+    if (error_var) hr.assign(error_var, error_var + nd);
+  }
+  std::vector<int32_t> v32((size_t)(3 * nd));
+  bool noisy = false;
+  for (int64_t i = 0; i < nd; ++i) {
+    for (int k = 0; k < 3; ++k) {
+      const int64_t v = hv[(size_t)(3 * i + k)];
+      GSS_REQUIRE(v >= 0 && v < h->nv, "gss_spde_condition: observation %lld has a vertex index outside [0, nv)",
+                  (long long)i);
+      GSS_REQUIRE(std::fabs(hw[(size_t)(3 * i + k)]) <= DBL_MAX,
+                  "gss_spde_condition: observation %lld has a weight that is not finite", (long long)i);
+      v32[(size_t)(3 * i + k)] = (int32_t)v;
+    }
+    GSS_REQUIRE(std::fabs(hy[(size_t)i]) <= DBL_MAX, "gss_spde_condition: observation %lld has a value that is not finite",
+                (long long)i);
+    if (error_var) {
+      const double r = hr[(size_t)i];
+      GSS_REQUIRE(std::fabs(r) <= DBL_MAX, "gss_spde_condition: observation %lld has an error variance that is not finite",
+                  (long long)i);
+      GSS_REQUIRE(r >= 0.0, "gss_spde_condition: observation %lld has a negative error variance (%g)", (long long)i, r);
+      noisy = noisy || r > 0.0;
+      hr[(size_t)i] = std::sqrt(r);
+    }
+  }
+  struct Guard {
+    gss_spde* h;
+    ~Guard() { if (h) h->drop_data(); }
+  } guard{h};
+  const int64_t NB = spde_block_columns();
+  h->nd = nd;
+  h->ndp = round_up(nd, NB);
+  h->mu = mean;
+  h->noisy = noisy;
+  h->last_iters = h->last_unconverged = 0;
+  h->last_relres = 0.0;
+  GSS_TRY(h->obs_v.alloc(sizeof(int32_t) * v32.size()));
+  GSS_TRY(h->obs_w.alloc(sizeof(double) * hw.size()));
+  GSS_TRY(h->yobs.alloc(sizeof(double) * hy.size()));
+  GSS_HIP(hipMemcpyAsync(h->obs_v.p, v32.data(), sizeof(int32_t) * v32.size(), hipMemcpyHostToDevice, s));
+  GSS_HIP(hipMemcpyAsync(h->obs_w.p, hw.data(), sizeof(double) * hw.size(), hipMemcpyHostToDevice, s));
+  GSS_HIP(hipMemcpyAsync(h->yobs.p, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice, s));
+  if (noisy) {
+    GSS_TRY(h->sqrt_r.alloc(sizeof(double) * hr.size()));
+    GSS_HIP(hipMemcpyAsync(h->sqrt_r.p, hr.data(), sizeof(double) * hr.size(), hipMemcpyHostToDevice, s));
+  }
+  GSS_HIP(hipStreamSynchronize(s));   // the vectors above may go
+  if (h->W.alloc(sizeof(double) * (size_t)h->nv * (size_t)h->ndp) != GSS_OK) {
+    set_error("gss_spde_condition: W = inv(S) P' does not fit: %lld x %lld doubles (8 nv nd bytes)", (long long)h->nv,
+              (long long)h->ndp);
+    return GSS_ERR_ALLOC;
+  }
+  ProfScope ps("spde_condition", s);
+  int64_t bad_col = -1, pivot = -1;
+  double bad_rel = 0.0;
+  GSS_TRY(spde_condition_nb(h, rtol * rtol, maxiter, &bad_col, &bad_rel, &pivot, s));
+  if (bad_col >= 0) {
+    set_error("gss_spde_condition: the solve for observation %lld did not reach rtol = %g in %lld iterations (||r|| / ||b|| "
+              "= %.3g; %lld of the %lld columns did not converge)", (long long)bad_col, rtol, (long long)maxiter, bad_rel,
+              (long long)h->last_unconverged, (long long)nd);
+    return GSS_ERR_NO_CONVERGENCE;
+  }
+  if (pivot >= 0) {
+    set_error("gss_spde_condition: the data covariance P Sigma P' + R is not positive definite (pivot %lld): two exact "
+              "observations of the same quantity, or an observation with zero weights", (long long)pivot);
+    return GSS_ERR_NOT_POSDEF;
+  }
+  guard.h = nullptr;
+  return GSS_OK;
+}
+
+int32_t gss_spde_condition_info(gss_spde_t* h, int64_t* nd, double* mean, double* W, int32_t mem, void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(mem == GSS_MEM_HOST || mem == GSS_MEM_DEVICE, "gss_spde_condition_info: mem = %d", mem);
+  if (nd) *nd = h->nd;
+  if (mean) *mean = h->mu;
+  if (W && h->nd > 0) {
+    hipStream_t s = to_stream(stream);
+    GSS_HIP(hipMemcpy2DAsync(W, sizeof(double) * (size_t)h->nd, h->W.p, sizeof(double) * (size_t)h->ndp,
+                             sizeof(double) * (size_t)h->nd, (size_t)h->nv,
+                             mem == GSS_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    GSS_HIP(hipStreamSynchronize(s));
+  }
+  return GSS_OK;
+}
+
+int32_t gss_spde_mean(gss_spde_t* h, double rtol, int64_t maxiter, double* vout, double* eout, int32_t mem,
+                      void* stream) {
+  GSS_ENTRY();
+  GSS_REQUIRE(h != nullptr, "NULL handle");
+  GSS_REQUIRE(h->nd > 0, "gss_spde_mean: the handle carries no data (gss_spde_condition)");
+  GSS_REQUIRE(vout != nullptr || eout != nullptr, "gss_spde_mean: neither vout nor eout");
+  GSS_REQUIRE(mem == GSS_MEM_HOST || mem == GSS_MEM_DEVICE, "gss_spde_mean: mem = %d", mem);
+  GSS_TRY(spde_solve_args("gss_spde_mean", &rtol, &maxiter));
+  h->last_iters = h->last_unconverged = 0;
+  h->last_relres = 0.0;
+  hipStream_t s = to_stream(stream);
+  Staged sv, se;
+  GSS_TRY(sv.out(vout, sizeof(double) * (size_t)h->nv, mem));
+  GSS_TRY(se.out(eout, sizeof(double) * (size_t)h->nt, mem));
+  SpdeFailure fail;
+  GSS_TRY(spde_mean_nb(h, rtol * rtol, maxiter, sv.as<double>(), se.as<double>(), &fail, s));
+  GSS_TRY(sv.back(s));
+  GSS_TRY(se.back(s));
+  if (fail.real >= 0) {
+    set_error("gss_spde_mean: the solve did not reach rtol = %g in %lld iterations (||r|| / ||b|| = %.3g)", rtol,
+              (long long)maxiter, fail.relres);
+    return GSS_ERR_NO_CONVERGENCE;
+  }
   return GSS_OK;
 }
 

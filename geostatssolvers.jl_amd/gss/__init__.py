@@ -8,7 +8,7 @@ from .geo import (CartesianGrid, Composition, DomainView, Ensemble, GeoTable, Po
                   domain, georef, parent, parentindices, triangulate, view)
 from .problems import EstimationProblem, SimulationProblem
 from .solvers import (FFTGS, LUGS, SGS, SPDEGS, CoKrigingSolver, CookieCutter, ExpWeight, IDWSolver, KrigingSolver,
-                      LWRSolver, TricubeWeight, kriging_ui, searcher_ui, simulate_with_generic_loop, solve)
+                      LWRSolver, SPDEKriging, TricubeWeight, kriging_ui, searcher_ui, simulate_with_generic_loop, solve)
 from .indicator import IndicatorKrigingSolver, SISSolver, postik
 from .transforms import InNormalScores, NormalScore
 from .validation import (BlockValidation, CrossValidationResult, KFoldValidation, LeaveBallOut, LeaveOneOut,

@@ -151,6 +151,11 @@ SIGNATURES = {
     "gss_spde_operator": [_p, _p, _p, _p, _p, _i32, _p],
     "gss_spde_realize": [_p, _u64, _i64, _i64, _p, _f64, _i64, _p, _p, _i32, _p],
     "gss_spde_last_solve": [_p, C.POINTER(_i64), C.POINTER(_f64), C.POINTER(_i64)],
+    "gss_spde_locate": [_p, _p, _i64, _f64, _p, _p, _i32, _p],
+    "gss_spde_condition": [_p, _i64, _p, _p, _p, _p, _f64, _f64, _i64, _i32, _p],
+    "gss_spde_condition_clear": [_p],
+    "gss_spde_condition_info": [_p, C.POINTER(_i64), C.POINTER(_f64), _p, _i32, _p],
+    "gss_spde_mean": [_p, _f64, _i64, _p, _p, _i32, _p],
     "gss_nscore_create": [C.POINTER(_p), _p, _p, _i64, _f64, _f64, _f64, _f64, _p],
     "gss_nscore_destroy": [_p],
     "gss_nscore_info": [_p, C.POINTER(_i64)],

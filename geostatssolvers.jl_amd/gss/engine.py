@@ -527,6 +527,7 @@ class SPDEHandle:
         nv, nt, nnz, tau2 = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
         check(self._l.gss_spde_info(h, C.byref(nv), C.byref(nt), C.byref(nnz), C.byref(tau2)))
         self.nv, self.nt, self.nnz, self.tau2 = nv.value, nt.value, nnz.value, tau2.value
+        self.nd = 0                                                    # observations attached by condition()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -543,16 +544,74 @@ class SPDEHandle:
                                         current_stream()))
         return rowptr, col, val, mass
 
+    def locate(self, points, tol=None):
+        """(triangle (np,) int64, weights (np, 3)) of `points` (np, dim): the triangle that contains each point (the
+        nearest one whose plane projection contains it in 3-D; the lowest index on an edge or a vertex; -1 for none) and
+        the barycentric weights in the order of its vertices.  Numpy in, numpy out; CUDA tensor in, CUDA tensors out."""
+        p = st.prep(points)
+        if p.ndim != 2:
+            raise ValueError("points (np, dim)")
+        tri, w = st.empty(p, (p.shape[0],), np.int64), st.empty(p, (p.shape[0], 3))
+        check(self._l.gss_spde_locate(self._h, ptr(p), p.shape[0], 0.0 if tol is None else float(tol), ptr(tri), ptr(w),
+                                      st.mem_flag(p), current_stream()))
+        return tri, w
+
+    def condition(self, obs_vertex, obs_weight, value, error_variance=None, mean=0.0, rtol=None, maxiter=None):
+        """Attach observations: row i of `obs_vertex` (nd, 3) and `obs_weight` (nd, 3) is a sparse row of P, `value`
+        (nd) what it observed, `error_variance` None (exact data) or (nd) values >= 0, `mean` the known field mean.
+        Replaces earlier data; `realize` then returns conditional realisations and `mean()` the kriging mean."""
+        v = st.prep(obs_vertex, np.int64)
+        dev = st.same_space("the observation arrays", v, obs_weight, value,
+                            *([] if error_variance is None else [error_variance]))
+        w, y, r = st.prep(obs_weight), st.prep(value), st.prep(error_variance)
+        nd = y.shape[0]
+        if tuple(v.shape) != (nd, 3) or tuple(w.shape) != (nd, 3) or (r is not None and tuple(r.shape) != (nd,)):
+            raise ValueError("obs_vertex (nd, 3), obs_weight (nd, 3), value (nd,) and error_variance (nd,)")
+        self.nd = 0
+        check(self._l.gss_spde_condition(self._h, nd, ptr(v), ptr(w), ptr(y), ptr(r), float(mean),
+                                         0.0 if rtol is None else float(rtol), 0 if maxiter is None else int(maxiter),
+                                         st.mem_flag(dev), current_stream()))
+        self.nd = nd
+
+    def condition_clear(self):
+        check(self._l.gss_spde_condition_clear(self._h))
+        self.nd = 0
+
+    def attached(self):
+        """(nd, mean) of the data the library holds for this handle; nd = 0: none."""
+        nd, mean = C.c_int64(), C.c_double()
+        check(self._l.gss_spde_condition_info(self._h, C.byref(nd), C.byref(mean), None, MEM_HOST, current_stream()))
+        return nd.value, mean.value
+
+    def weights(self):
+        """W = inv(S) P' (nv, nd) of the attached data, on the host (parity)."""
+        W = np.empty((self.nv, self.nd))
+        check(self._l.gss_spde_condition_info(self._h, None, None, ptr(W), MEM_HOST, current_stream()))
+        return W
+
+    def mean(self, rtol=None, maxiter=None, vertices=False, device=False):
+        """The kriging mean of the attached data per element (nt,); `vertices=True`: the pair (vertices (nv,), elements)."""
+        eout = st.empty(bool(device), (self.nt,))
+        vout = st.empty(bool(device), (self.nv,)) if vertices else None
+        check(self._l.gss_spde_mean(self._h, 0.0 if rtol is None else float(rtol), 0 if maxiter is None else int(maxiter),
+                                    ptr(vout), ptr(eout), st.mem_flag(eout), current_stream()))
+        return (vout, eout) if vertices else eout
+
     def realize(self, seed, first_real, nreals, noise=None, rtol=None, maxiter=None, vertices=False, device=False):
         """Element values (nreals, nt) of realisations first_real .. first_real + nreals - 1; `vertices=True`: the pair
         (vertex values (nreals, nv), element values).  `noise`: (nreals, nv) normals instead of the Philox stream of
-        `seed`.  A column that does not converge raises GSSError (ERR_NO_CONVERGENCE); `last_solve()` has the counts."""
+        `seed`; with data attached (nreals, nv + nd), the field normals followed by the error normals.  A column that
+        does not converge raises GSSError (ERR_NO_CONVERGENCE); `last_solve()` has the counts."""
         noise = st.prep(noise)
         dev = bool(device) or st.on_device(noise)
         if noise is not None:
             if dev and not st.on_device(noise):
                 raise ValueError("device=True needs the noise as a CUDA tensor")
-            if tuple(noise.shape) != (nreals, self.nv):
+            if self.nd:
+                if tuple(noise.shape) != (nreals, self.nv + self.nd):
+                    raise ValueError(f"noise must be (nreals, nv + nd) = ({nreals}, {self.nv + self.nd}), got "
+                                     f"{tuple(noise.shape)}")
+            elif tuple(noise.shape) != (nreals, self.nv):
                 raise ValueError(f"noise must be (nreals, nv) = ({nreals}, {self.nv}), got {tuple(noise.shape)}")
         where = noise if st.on_device(noise) else dev
         eout = st.empty(where, (nreals, self.nt))

@@ -109,6 +109,18 @@ class SimpleMesh(Domain):
     def centroids(self):
         return np.ascontiguousarray(self.vertices[self.triangles].mean(axis=1))
 
+    def locate(self, points, tol=None, engine=None):
+        """(triangle (np,), weights (np, 3)) of `points` (np, d) on the device: the triangle that contains each point
+        (-1: none; the lowest index on a shared edge or vertex) and its barycentric weights (gss.h, gss_spde_locate)."""
+        if engine is None:
+            from .engine import default_engine
+            engine = default_engine()
+        h = engine.SPDE(self.vertices, self.triangles)
+        try:
+            return h.locate(points, tol=tol)
+        finally:
+            h.close()
+
     def __eq__(self, other):
         return (isinstance(other, SimpleMesh) and np.array_equal(self.vertices, other.vertices)
                 and np.array_equal(self.triangles, other.triangles))

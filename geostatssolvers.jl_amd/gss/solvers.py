@@ -1197,31 +1197,119 @@ class LUGS(_Solver):
 # ------------------------------------------------------------------------------------------
 # SPDEGS
 # ------------------------------------------------------------------------------------------
+SPDE_CONDITION_MODES = ("element", "point")
+
+
+def _per_variable(value, var, what):
+    """A global that is a scalar or a {var: value} dictionary -> the float of `var` (absent: 0)."""
+    v = value.get(var, 0.0) if isinstance(value, dict) else value
+    v = float(v)
+    if not np.isfinite(v):
+        raise ValueError(f"{what} of {var} must be finite, got {v}")
+    return v
+
+
+def _spde_check_globals(solver, variables):
+    """condition / error_variance / mean of SPDEGS and SPDEKriging, checked before any device work."""
+    mode = solver.globals["condition"]
+    if mode is not None and mode not in SPDE_CONDITION_MODES:
+        raise ValueError(f"condition={mode!r}: None, 'element' or 'point'")
+    for var in variables:
+        r = _per_variable(solver.globals["error_variance"], var, "error_variance")
+        if r < 0:
+            raise ValueError(f"error_variance of {var} must not be negative, got {r}")
+        _per_variable(solver.globals["mean"], var, "mean")
+    return mode
+
+
+def _spde_attach(solver, handle, mesh, data, var):
+    """Locate the data of `var` on the mesh and attach them to the handle.  "element": every datum constrains the value
+    of the triangle that contains it (weights 1/3), the quantity the solvers hand back; "point": the piecewise linear
+    field at the datum's location (barycentric weights).  Rows whose value is NaN are skipped."""
+    mode = solver.globals["condition"]
+    z = np.asarray(data[var], dtype=np.float64)
+    keep = np.flatnonzero(~np.isnan(z))
+    if keep.size == 0:
+        raise ValueError(f"all data of {var} are missing")
+    pts = np.ascontiguousarray(data.domain.centroids()[keep], dtype=np.float64)
+    if pts.shape[1] != mesh.embeddim():
+        raise ValueError(f"data of dimension {pts.shape[1]} on a mesh of dimension {mesh.embeddim()}")
+    tri, w = handle.locate(pts)
+    out = np.flatnonzero(tri < 0)
+    if out.size:
+        i = int(out[0])
+        raise ValueError(f"datum {int(keep[i])} of {var} at {tuple(float(c) for c in pts[i])} lies outside the mesh")
+    r = _per_variable(solver.globals["error_variance"], var, "error_variance")
+    if mode == "element":
+        w = np.full((keep.size, 3), 1.0 / 3.0)
+        uniq, count = np.unique(tri, return_counts=True)
+        if r == 0.0 and (count > 1).any():
+            t = int(uniq[count > 1][0])
+            rows = keep[tri == t]
+            raise ValueError(f"data {rows.tolist()} of {var} lie in triangle {t}: two exact values of one element; give "
+                             f"an error_variance or use condition='point'")
+    handle.condition(mesh.triangles[tri], w, z[keep], None if r == 0.0 else np.full(keep.size, r),
+                     mean=_per_variable(solver.globals["mean"], var, "mean"), rtol=solver.globals["rtol"],
+                     maxiter=solver.globals["maxiter"])
+    return tri
+
+
+def _spde_mesh(solver, problem):
+    mesh = problem.domain
+    if not isinstance(mesh, SimpleMesh):
+        raise ValueError(f"{type(solver).__name__} needs a SimpleMesh domain, got {type(mesh).__name__}: "
+                         f"triangulate(grid) turns a 2-D CartesianGrid into one")
+    return mesh
+
+
+def _spde_no_convergence(e):
+    if e.code != _lib.ERR_NO_CONVERGENCE:
+        raise e
+    raise RuntimeError(str(e)) from None
+
+
 class SPDEGS(_Solver):
     """spde.jl:23-115 on a `SimpleMesh`: one sparse solve per realisation instead of the dense factor of the precision
-    (gss.h "SPDEGS").  `noise`: "reference" (spde.jl:98, w ~ N(0, I)) or "lumped" (Lindgren's w ~ N(0, inv(M)))."""
+    (gss.h "SPDEGS").  `noise`: "reference" (spde.jl:98, w ~ N(0, I)) or "lumped" (Lindgren's w ~ N(0, inv(M))).
+
+    Data (not in the reference, which refuses them): `condition="element"` makes every realisation's value of the
+    triangle that contains a datum equal to it, `condition="point"` the piecewise linear field at the datum's location;
+    `error_variance` (a scalar or {var: value}) loosens that to a noisy observation, `mean` (likewise) is the known
+    mean of the field.  With `condition=None` data are refused in the reference's words."""
     PARAMS = dict(sill=1.0, range=1.0)                                                        # spde.jl:24-25
-    GLOBALS = dict(rng=None, noise="reference", rtol=1e-10, maxiter=None)
+    GLOBALS = dict(rng=None, noise="reference", rtol=1e-10, maxiter=None, condition=None, error_variance=0.0, mean=0.0)
 
     def preprocess(self, problem: SimulationProblem):
-        """spde.jl:29-76: one handle per distinct (sill, range); every rank builds its own (assembly is cheap)."""
-        if problem.data is not None:
+        """spde.jl:29-76: one handle per distinct (sill, range); every rank builds its own (assembly is cheap).  A
+        variable with data gets a handle of its own, which carries them."""
+        mode = _spde_check_globals(self, problem.variables)
+        if problem.data is not None and mode is None:
             raise NotImplementedError("conditional simulation is not implemented")           # spde.jl:30
-        mesh = problem.domain
-        if not isinstance(mesh, SimpleMesh):
-            raise ValueError(f"SPDEGS needs a SimpleMesh domain, got {type(mesh).__name__}: triangulate(grid) turns a "
-                             f"2-D CartesianGrid into one")
+        mesh = _spde_mesh(self, problem)
         handles, pre = {}, {}
-        for conames in self.covariables(problem):
-            for var in conames:
-                p = self.params(var)
-                sill, rng_ = float(p["sill"]), float(p["range"])
-                assert sill > 0, "sill must be positive"                                     # spde.jl:53
-                assert rng_ > 0, "range must be positive"                                    # spde.jl:54
-                if (sill, rng_) not in handles:
-                    handles[sill, rng_] = self.engine.SPDE(mesh.vertices, mesh.triangles, sill=sill, range=rng_,
-                                                           noise=self.globals["noise"])
-                pre[var] = handles[sill, rng_]
+        try:
+            for conames in self.covariables(problem):
+                for var in conames:
+                    p = self.params(var)
+                    sill, rng_ = float(p["sill"]), float(p["range"])
+                    assert sill > 0, "sill must be positive"                                     # spde.jl:53
+                    assert rng_ > 0, "range must be positive"                                    # spde.jl:54
+                    has_data = problem.data is not None and var in problem.data.table
+                    key = (sill, rng_, var) if has_data else (sill, rng_)
+                    if key not in handles:
+                        handles[key] = self.engine.SPDE(mesh.vertices, mesh.triangles, sill=sill, range=rng_,
+                                                        noise=self.globals["noise"])
+                        if has_data:
+                            _spde_attach(self, handles[key], mesh, problem.data, var)
+                    pre[var] = handles[key]
+        except _lib.GSSError as e:
+            for h in handles.values():
+                h.close()
+            _spde_no_convergence(e)
+        except Exception:
+            for h in handles.values():
+                h.close()
+            raise
         pre["_handles"] = list(handles.values())
         pre["_run"] = _run_state(self, problem)
         return pre
@@ -1257,6 +1345,36 @@ class SPDEGS(_Solver):
             for h in pre["_handles"]:
                 h.close()
         return Ensemble(problem.domain, reals)
+
+
+class SPDEKriging(_Solver):
+    """Simple kriging on a `SimpleMesh` under the SPDE model of SPDEGS: the mean of the field given the data, per
+    element (gss.h, gss_spde_mean).  `condition` ("element", the default here, or "point"), `error_variance` and `mean`
+    as SPDEGS.  It returns no variance column: the diagonal of the posterior covariance needs a solve per vertex or a
+    selected inversion, which the library does not have."""
+    PARAMS = dict(sill=1.0, range=1.0)
+    GLOBALS = dict(noise="reference", rtol=1e-10, maxiter=None, condition="element", error_variance=0.0, mean=0.0)
+
+    def solve(self, problem: EstimationProblem, gather: bool = True):
+        mode = _spde_check_globals(self, problem.variables)
+        if mode is None:
+            raise ValueError("condition=None: SPDEKriging needs 'element' or 'point'")
+        mesh = _spde_mesh(self, problem)
+        cols = {}
+        for var in problem.variables:
+            p = self.params(var)
+            sill, rng_ = float(p["sill"]), float(p["range"])
+            assert sill > 0, "sill must be positive"
+            assert rng_ > 0, "range must be positive"
+            h = self.engine.SPDE(mesh.vertices, mesh.triangles, sill=sill, range=rng_, noise=self.globals["noise"])
+            try:
+                _spde_attach(self, h, mesh, problem.data, var)
+                cols[var] = h.mean(rtol=self.globals["rtol"], maxiter=self.globals["maxiter"])
+            except _lib.GSSError as e:
+                _spde_no_convergence(e)
+            finally:
+                h.close()
+        return georef(cols, mesh)
 
 
 # ------------------------------------------------------------------------------------------

@@ -908,6 +908,54 @@ int32_t gss_spde_realize(gss_spde_t* h, uint64_t seed, int64_t first_real, int64
 /* after a realize: largest iteration count of any column, largest final ||r||/||b||, columns that did not converge */
 int32_t gss_spde_last_solve(const gss_spde_t* h, int64_t* iters, double* relres, int64_t* unconverged);
 
+/* ---- SPDEGS with data: conditioning by kriging in the data space ("SPDEGS") ----
+ * Not in the reference (spde.jl:30 refuses data).  With s = the right-hand-side scale of the handle (tau m or
+ * tau sqrt(m)) the vertex field has the covariance Sigma = inv(S) diag(s^2) inv(S).  An observation i is a sparse row
+ * of P (three vertices, three weights), a value y_i, an error variance r_i >= 0 and the known field mean mu.
+ *   set-up      W = inv(S) P' (nd columns through the block CG), C = W' diag(s^2) W + diag(r) = P Sigma P' + R,
+ *               C = L L' and inv(L)
+ *   mean        mu + inv(S) (s^2 . (W inv(C) (y - mu)))                                      one solve
+ *   realisation x_u = inv(S) (s . w_r), today's unconditional realisation of (seed, r), same bits;
+ *               e_i = sqrt(r_i) n_(r,i);  lambda = inv(C) (y - mu - P x_u - e);
+ *               x_c = (x_u + inv(S) (s^2 . (W lambda))) + mu                                 two solves
+ * Only solves with S occur; r = 0 (exact data) is allowed and then P x_c = y up to the CG tolerance.
+ *
+ * gss_spde_locate: for np points (np x dim of the mesh) the triangle that contains each and its barycentric weights
+ *   (np x 3, in the order of the triangle's vertices).  Brute force: every point against every triangle.  A triangle
+ *   accepts a point whose barycentric coordinates (of its projection onto the triangle's plane when dim = 3) all lie in
+ *   [-tol, 1 + tol]; among the accepting triangles the one nearest to the point wins (distance to the plane; a distance
+ *   of at most tol edge lengths counts as zero, in 2-D every distance is zero), and among equally near ones the lowest
+ *   index: a point on an edge or a vertex goes to the lowest triangle that shares it.  No triangle: index -1, weights 0.
+ *   tol <= 0 selects 1e-9.
+ * gss_spde_condition: attaches nd observations to the handle (replacing earlier ones).  obs_vertex nd x 3 (0-based),
+ *   obs_weight nd x 3, value nd, error_var NULL (all zero) or nd values.  rtol / maxiter as gss_spde_realize, for the
+ *   nd solves of W.  Refusals.  GSS_ERR_INVALID: nd < 1, an index outside [0, nv), a value, weight or variance that is
+ *   not finite, a negative variance, a mean that is not finite.  GSS_ERR_NOT_POSDEF: C is singular to working precision
+ *   (e.g. two exact observations with the same row); the message names the pivot.  GSS_ERR_NO_CONVERGENCE: a column of
+ *   W did not reach rtol.  GSS_ERR_ALLOC: W does not fit; it takes 8 nv ceil16(nd) bytes for the life of the data, and
+ *   the set-up the same again for diag(s) W.  After a refusal the handle has no data: earlier data are dropped before
+ *   anything else is looked at (only a NULL handle leaves them).
+ * gss_spde_condition_clear: back to unconditional realisations (the same bits as before the data).
+ * gss_spde_condition_info: nd (0 without data), the mean, and (parity) W as nv x nd row-major; any may be NULL.
+ * gss_spde_mean: the kriging mean at the vertices (vout, nv) and elements (eout, nt; the mean of the three vertex
+ *   values); at least one of the two.  GSS_ERR_INVALID without data.
+ * gss_spde_realize with data attached returns conditional realisations: `noise` is then nreals x (nv + nd), the field
+ *   normals followed by the error normals (read only where r_i > 0), and the seeded error normal of observation i in
+ *   realisation r is gss_philox_normal(seed, r, nv + i).  Realisation r depends on (seed, r), the mesh and the data
+ *   only.  gss_spde_last_solve reports the worse of the two solves.  Profile scopes: "spde_condition" and inside it
+ *   "spde_cond_w", "spde_cond_gram", "spde_cond_factor"; per block "spde_lambda" (the two triangular products) and
+ *   "spde_combine" (the combine kernel).
+ */
+int32_t gss_spde_locate(gss_spde_t* h, const double* points, int64_t np, double tol, int64_t* triangle,
+                        double* weight, int32_t mem, void* stream);
+int32_t gss_spde_condition(gss_spde_t* h, int64_t nd, const int64_t* obs_vertex, const double* obs_weight,
+                           const double* value, const double* error_var, double mean, double rtol, int64_t maxiter,
+                           int32_t mem, void* stream);
+int32_t gss_spde_condition_clear(gss_spde_t* h);
+int32_t gss_spde_condition_info(gss_spde_t* h, int64_t* nd, double* mean, double* W, int32_t mem, void* stream);
+int32_t gss_spde_mean(gss_spde_t* h, double rtol, int64_t maxiter, double* vout, double* eout, int32_t mem,
+                      void* stream);
+
 /* ---- SGS -----------------------------------------------------------
  * gss_sgs_create replaces SGS.preprocess (sgs.jl:56-85: SimpleKriging(variogram, mean) and the marginal
  *   Normal(mean, sqrt(sill))) and the realisation-independent part of the SeqSim path loop: for every

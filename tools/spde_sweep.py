@@ -170,15 +170,101 @@ def worker(a):
         h.close()
 
 
+def conditional(a):
+    """--conditional: gss_spde_condition and conditional realisations on grid_1e5 (range 10) and sphere_7 with 100 and
+    1 000 observations at random points (barycentric rows, error variance 0.01), NB = 16.  One JSON line per case:
+      locate_ms                gss_spde_locate of the observation points (brute force)
+      setup_ms, w_ms, gram_ms, factor_ms   gss_spde_condition and its profile scopes "spde_cond_w" (the nd solves),
+                               "spde_cond_gram" (diag(s) W and the product), "spde_cond_factor"
+      uncond_ms, cond_ms, ratio   16 realisations without and with the data in the same session (floor: 2, two solves)
+      combine_us, copy_us      the combine kernel of a block (profile scope "spde_combine") beside a device copy of
+                               W's bytes (8 nv nd, nd rounded up to 16)
+      lambda_us                the two triangular products with inv(L) of a block (profile scope "spde_lambda")
+      mean_ms                  gss_spde_mean
+    profiles/spde_cond_sweep.jsonl."""
+    import numpy as np
+    import torch
+
+    import gss
+    import spde_ref as R
+    from gss import _lib
+    from gss.engine import SPDEHandle
+
+    def event_ms(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        t = [event_ms(fn) for _ in range(a.reps)]
+        return statistics.median(t), min(t), max(t)
+
+    def scope(name):
+        ms, n = _lib.profile_read(name)
+        return ms / max(n, 1)
+
+    k = 10 if a.small else 1
+    g = gss.triangulate(gss.CartesianGrid(316 // k - 1, 316 // k - 1))
+    cases = [("grid_1e5", (g.vertices, g.triangles), 10.0), ("sphere_7", R.icosphere(3 if a.small else 7), 0.05)]
+    lines = []
+    for name, (V, T), rng in cases:
+        h = SPDEHandle(V, T, sill=1.0, range=rng)
+        for nd in (100 // k, 1000 // k):
+            gen = np.random.default_rng(nd)
+            tri = gen.choice(len(T), size=nd, replace=False)
+            pts = np.einsum("ik,ikd->id", gen.dirichlet(np.ones(3), size=nd), V[T[tri]])
+            row = dict(mesh=name, nv=h.nv, nt=h.nt, range=rng, nd=nd, NB=16)
+            row["locate_ms"] = timed(lambda: h.locate(pts))
+            where, w = h.locate(pts)
+            assert np.array_equal(where, tri)
+            y, r = gen.normal(size=nd), np.full(nd, 0.01)
+            h.condition_clear()
+            row["uncond_ms"] = timed(lambda: h.realize(1, 0, 16, device=True))
+            row["uncond_iters"] = h.last_solve()[0]
+            _lib.profile_enable(True)
+            _lib.profile_reset()
+            row["setup_ms"] = timed(lambda: h.condition(T[where], w, y, r))
+            row["w_ms"], row["gram_ms"], row["factor_ms"] = (scope(s) for s in ("spde_cond_w", "spde_cond_gram",
+                                                                                "spde_cond_factor"))
+            row["w_iters"] = h.last_solve()[0]
+            _lib.profile_reset()
+            row["cond_ms"] = timed(lambda: h.realize(1, 0, 16, device=True))
+            row["cond_iters"] = h.last_solve()[0]
+            row["combine_us"], row["lambda_us"] = 1e3 * scope("spde_combine"), 1e3 * scope("spde_lambda")
+            _lib.profile_enable(False)
+            row["ratio"] = row["cond_ms"][0] / row["uncond_ms"][0]
+            row["mean_ms"] = timed(lambda: h.mean(device=True))
+            nbytes = 8 * h.nv * ((nd + 15) // 16 * 16)
+            row["w_bytes"] = nbytes
+            src = torch.empty(nbytes // 8, dtype=torch.float64, device="cuda")
+            dst = torch.empty_like(src)
+            row["copy_us"] = 1e3 * timed(lambda: [dst.copy_(src) for _ in range(10)])[0] / 10
+            del src, dst
+            print(json.dumps(row), flush=True)
+            lines.append(json.dumps(row))
+        h.close()
+    if not a.small:
+        with open(os.path.join(ROOT, "profiles", "spde_cond_sweep.jsonl"), "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--small", action="store_true", help="a tenth of every size (a quick check of the tool itself)")
+    ap.add_argument("--conditional", action="store_true", help="the conditioning path (profiles/spde_cond_sweep.jsonl)")
     ap.add_argument("--worker", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.worker:
         return worker(a)
+    if a.conditional:
+        return conditional(a)
     lines = []
     for nb in (16, 8, 32):
         cmd = [sys.executable, os.path.abspath(__file__), "--worker", str(nb), "--reps", str(a.reps), "--warmup",
